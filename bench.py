@@ -1,8 +1,12 @@
 #!/usr/bin/env python3
 """bench.py — rendered rays/s of the HIP conditional-NeRF renderer on synthetic BASELINE.json configs.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2] [--precision bf16x3]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2] [--precision bf16x3] [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps, writes the last timed step's outputs if --dump-outputs is given, and prints the result
+line.  Everything else (the dominant-kernel pass of `roofline.dominant_kernel`, `other_precisions`, `sustained`, `gradient_step`,
+`cpu_baseline` with the `parity` gate, and for N > 1 the weak-scaling pass and the `allgather` latency) runs only with --full.
 
 A "step" = one `render_rays` pass (rows a2-a18 of SURVEY.md §8; for a hierarchical config also row a20: the coarse NeuRay
 pass + inverse-CDF resampling) over one batch of R rays whose inputs are already resident in HBM; per-frame setup (weight
@@ -11,7 +15,7 @@ packing, KNN grid, map repack) is outside the timed region, like the reference's
   --scaling strong (the default for every config since round 4: BASELINE's "rays/sec at 1/2/4/8 GPUs" asks how much faster ONE batch gets):
                    ONE R-ray batch, rank r renders shard_range(R, r, N); value = R / step;
   --scaling weak   every rank renders its own R-ray batch of the same frame; value = N * R / step (true by construction up to the all-gather).
-With --scaling auto (default) an N>1 run times BOTH: `value` / `ms_per_step` / `scaling` are the STRONG numbers, `weak_scaling` carries the weak
+With --scaling auto (default) an N>1 --full run times BOTH: `value` / `ms_per_step` / `scaling` are the STRONG numbers, `weak_scaling` carries the weak
 ones in the same line (`scaling_modes: "both"`), and `allgather` the measured latency of the step's one collective on its own.
 Rank 0 prints one JSON line.
 
@@ -93,7 +97,12 @@ def main():
                     help="after the headline: this many seconds of back-to-back steps of the same workload -> `sustained` (0 = skip; N = 1 only)")
     ap.add_argument("--no-parity-gate", action="store_true", help="report `parity` but do not fail the run (rc 3) when it is above 1e-4")
     ap.add_argument("--scaling", default="auto", choices=["auto", "weak", "strong"],
-                    help="N>1: weak = R rays per rank, strong = one R-ray batch sharded over the ranks (auto: BOTH are timed, value = strong)")
+                    help="N>1: weak = R rays per rank, strong = one R-ray batch sharded over the ranks (auto: strong; with --full BOTH are timed, value = strong)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also measure and check everything else: dominant-kernel pass, other precisions, sustained, gradient step, "
+                         "cpu_baseline + parity gate, N>1 weak-scaling pass and all-gather latency (the --no-* / --also / --sustained-seconds options act here)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the per-ray outputs of the last timed step as DIR/<name>.npy (float32, a seeded sample of rays above 60 MB in all)")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -146,7 +155,7 @@ def main():
     cfg = CONFIGS[args.config]
     R = args.rays or cfg.R            # weak: rays per rank; strong: rays of the one batch
     S = cfg.S_total
-    both = args.scaling == "auto" and world > 1          # N > 1 by default: the strong pass is the headline, the weak pass rides in the same line
+    both = args.scaling == "auto" and world > 1 and args.full   # N > 1 --full: the strong pass is the headline, the weak pass rides in the same line
     scaling = args.scaling if args.scaling != "auto" else "strong"
     frame = make_frame(cfg)
 
@@ -188,6 +197,7 @@ def main():
     # batch i overlaps the kernels of batch i + 1; drain() collects the last one inside the timed region, so K timed steps = K renders + K completed gathers.
     loop = [None]
     last_out = [None]
+    gathered = [None]   # N > 1 / --force-gather: the all-gathered outputs of the last timed step (what a caller of the sharded step receives)
 
     def render_local(out_buffers=None):
         zz = B["z"]
@@ -233,7 +243,7 @@ def main():
         ev0.record()
         for _ in range(steps):
             step()
-        drain()
+        gathered[0] = drain()
         ev1.record()
         torch.cuda.synchronize()
         if world > 1:
@@ -249,20 +259,24 @@ def main():
 
     wall, dev_ms = timed(args.steps, args.warmup)
     ms_per_step = wall * 1e3 / args.steps
-    # the outputs of the LAST timed step of this rank (the batch is the same every step): what `parity` below compares with the CPU oracle
-    headline_out = {k: v.clone() for k, v in last_out[0].items()}
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, gathered[0] if gather else last_out[0])
 
-    # dominant kernel (fused neural-point kernel): HIP events around each of its launches, on the
-    # stream it is launched on, over a second pass of the same steps (the events themselves are outside `value`)
     import ctypes as ct
-    from nerf_loc_amd import _lib
-    lib = _lib.load()
-    lib.nl_profile_begin()
-    for _ in range(args.steps):
-        step()
-    drain()
     fused_ms, launches = ct.c_float(0), ct.c_int(0)
-    _lib.check(lib.nl_profile_end(ct.byref(fused_ms), ct.byref(launches)), "nl_profile_end")
+    if args.full:
+        # the outputs of the LAST timed step of this rank (the batch is the same every step): what `parity` below compares with the CPU oracle
+        headline_out = {k: v.clone() for k, v in last_out[0].items()}
+
+        # dominant kernel (fused neural-point kernel): HIP events around each of its launches, on the
+        # stream it is launched on, over a second pass of the same steps (the events themselves are outside `value`)
+        from nerf_loc_amd import _lib
+        lib = _lib.load()
+        lib.nl_profile_begin()
+        for _ in range(args.steps):
+            step()
+        drain()
+        _lib.check(lib.nl_profile_end(ct.byref(fused_ms), ct.byref(launches)), "nl_profile_end")
     total_rays = R if (scaling == "strong" and world > 1) else world * R     # rays all ranks rendered per step
     value = total_rays * args.steps / wall
     # algorithmic flops of what THIS rank computes per step (+ the coarse pass of a hierarchical config: 64 x V x 8384 MAC per ray)
@@ -315,7 +329,7 @@ def main():
                                     * samples_per_launch / sec / 1e12,   # (f16mx, layer 1: 10 matrix instructions of 8 passes for 6 k-steps)
         }
 
-    if gather:
+    if gather and args.full:
         # the step's one collective on its own: K blocking all-gathers of the last step's packed per-ray outputs (pack + RCCL + unpack), nothing else running —
         # the latency a step would pay if it could not overlap it with the next batch's kernels (it can: gather_ray_outputs_async)
         out_l = last_out[0]
@@ -346,7 +360,7 @@ def main():
                                   "note": "every rank renders its own R-ray batch of the same frame + the all-gather: N x the one-GPU rate up to the collective"}
         result["scaling_modes"] = "both"
 
-    if args.also and world == 1:
+    if args.full and args.also and world == 1:
         extra = {}
         for p in [x for x in args.also.split(",") if x and x != args.precision]:
             rnd.set_precision(p)
@@ -358,15 +372,15 @@ def main():
         rnd.set_precision(args.precision)
         result["other_precisions"] = extra
 
-    if world == 1 and args.sustained_seconds > 0:
+    if args.full and world == 1 and args.sustained_seconds > 0:
         result["sustained"] = sustained(step, drain, rnd, R, args.sustained_seconds, ms_per_step)
 
-    if rank == 0 and world == 1 and not args.no_gradient_step and not hier and args.precision != "fp32":
+    if args.full and rank == 0 and world == 1 and not args.no_gradient_step and not hier and args.precision != "fp32":
         try:   # (an extra next to the headline: whatever happens here must not cost the line)
             result["gradient_step"] = gradient_step(rnd, cfg, frame, rays, weights, torch.device(f"cuda:{local_rank}"))
         except Exception as e:   # noqa: BLE001
             result["gradient_step"] = {"error": f"{type(e).__name__}: {e}"[:300]}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         result["cpu_baseline"], result["parity"] = cpu_baseline(cfg, frame, rays, weights, u_all, thread_sweep=args.cpu_thread_sweep, gpu_out=headline_out,
                                                                 precision=args.precision)
     # RCCL prints its version banner (NCCL_DEBUG=VERSION) through C stdio, which a pipe flushes only at exit: every rank pushes it out
@@ -386,6 +400,23 @@ def main():
         if par is not None and not par["ok"] and not args.no_parity_gate:
             print(f"bench.py: parity of the timed batch against the CPU oracle is above {par['bar']:g}: {par['max_rel']}", file=sys.stderr)
             raise SystemExit(3)
+
+
+DUMP_MAX_BYTES = 60 * 10**6   # (the .npy files of one dump stay below 64 MB in all)
+
+
+def dump_outputs(path, out):
+    """--dump-outputs: the per-ray outputs of the last timed step as <path>/<name>.npy in float32 (the mask as 0 / 1).  Above DUMP_MAX_BYTES in all, the same
+    seeded sample of rays (rows in ascending order) is kept of every output, so that two builds run with the same arguments write the same rows."""
+    os.makedirs(path, exist_ok=True)
+    arrs = {k: v.detach().float().cpu().numpy() for k, v in out.items()}
+    total = sum(a.nbytes for a in arrs.values())
+    if total > DUMP_MAX_BYTES:
+        R = next(iter(arrs.values())).shape[0]
+        rows = np.sort(np.random.default_rng(0).choice(R, R * DUMP_MAX_BYTES // total, replace=False))
+        arrs = {k: a[rows] for k, a in arrs.items()}
+    for k, a in arrs.items():
+        np.save(os.path.join(path, f"{k}.npy"), a)
 
 
 def gradient_step(rnd, cfg, frame, rays, weights, dev):

@@ -64,6 +64,26 @@ SETUP_CASES = {
 }
 
 
+# KNN cases (n queries, m points, K, lattice ties): the reference's knn_cpu.cpp outputs (idx + ascending sort of its python wrapper, knn_utils.py:60-74)
+# are stored in tests/golden/knn_ref.npz under knn_key(...)
+KNN_CASES = [(300, 500, 8, False), (200, 300, 8, True), (100, 5, 8, False), (64, 200, 1, False)]
+
+
+def knn_clouds(seed, n, m, dup=False):
+    rng = np.random.default_rng(seed)
+    q = rng.standard_normal((n, 3)).astype(np.float32)
+    p = rng.standard_normal((m, 3)).astype(np.float32)
+    if dup and m > 4:
+        p[1::3] = p[0:-1:3][: len(p[1::3])]
+        p = np.round(p * 4) / 4  # lattice -> many exact ties
+        q = np.round(q * 4) / 4
+    return q, p
+
+
+def knn_key(n, m, K, dup):
+    return f"n{n}_m{m}_K{K}_dup{int(dup)}"
+
+
 def build_setup_case(name: str):
     """-> dict(cfg, frame, rays, weights) for per-frame setup case `name`."""
     cfg = SETUP_CASES[name]

@@ -451,7 +451,25 @@ def run_setup_case(model_mod, name="setup"):
           f"conf range=({float(sp['fine']['confidence'].min()):.3f},{float(sp['fine']['confidence'].max()):.3f})")
 
 
+def run_knn_cases():
+    """tests/golden/knn_ref.npz: the reference's knn_cpu.cpp (oracle/_ref/libref_knn.so) on the seeded clouds of tests/test_knn_oracle.py."""
+    from tests.golden_cases import KNN_CASES, knn_clouds, knn_key
+    lib = ctypes.CDLL(os.path.join(ROOT, "oracle", "_ref", "libref_knn.so"))
+    lib.ref_knn_cpu.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
+    save = {}
+    for n, m, K, dup in KNN_CASES:
+        q, p = knn_clouds(7 * n + m, n, m, dup)
+        idx, d2 = np.zeros((n, K), np.int64), np.zeros((n, K), np.float32)
+        lib.ref_knn_cpu(q.ctypes.data, n, p.ctypes.data, m, K, d2.ctypes.data, idx.ctypes.data)
+        save[knn_key(n, m, K, dup) + "_d2"], save[knn_key(n, m, K, dup) + "_idx"] = d2, idx
+    path = os.path.join(ROOT, "tests", "golden", "knn_ref.npz")
+    np.savez_compressed(path, **save)
+    print(f"knn: wrote {path} ({os.path.getsize(path)/1024:.0f} KiB)")
+
+
 def main():
+    if len(sys.argv) > 1 and sys.argv[1] == "knn":
+        return run_knn_cases()
     model_mod, ku = install_shims()
     if len(sys.argv) > 1 and sys.argv[1] == "setup":
         run_setup_case(model_mod, "setup")
