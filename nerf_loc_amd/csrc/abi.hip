@@ -63,7 +63,7 @@ bool nl_point_fused_supported(int W, int precision);
 int nl_launch_point_fused(const NlPointFusedArgs& a, int W, int precision, hipStream_t st);
 size_t nl_point_stream2_bytes(int W);
 int nl_pack_point_stream2(const float* w1, const float* w2, const float* w3, const float* wk, const float* wv, const float* b2, const float* b3,
-                          const float* rd_w, void* out, int W, int F, hipStream_t st, int mx = 0, int* mx_scratch = nullptr);
+                          const float* rd_w, void* out, int W, int F, hipStream_t st, int mx = 0);
 bool nl_point_fused2_supported(int W, int precision);
 int nl_launch_sample_chain(const float* O, const float* T64, const float* wscale, const float* gamma, const float* beta, float eps, const void* wbase,
                            size_t off_g2, const float* bias_g2, size_t off_fc, size_t off_f0, size_t off_ba, const float* bias_f0, float* FA, float* fth,
@@ -71,7 +71,7 @@ int nl_launch_sample_chain(const float* O, const float* T64, const float* wscale
 int nl_launch_query_chain(const float* T64, const void* wbase, size_t off_g2, const float* bias_g2, size_t off_q, float* Q, int64_t M, int precision,
                           hipStream_t st);
 int nl_launch_point_fused2(const NlPointFusedArgs& a, int W, int precision, hipStream_t st, bool mx = false, float* keep_kv = nullptr, unsigned* const* keep_mk = nullptr,
-                           const float* tmax = nullptr, unsigned* logit_amax = nullptr, unsigned long long* clk = nullptr);
+                           unsigned* logit_amax = nullptr, unsigned long long* clk = nullptr);
 int nl_table_absmax(const float* x, size_t n, float* out, hipStream_t st);
 bool nl_point_bwd_chain_supported(int W);
 size_t nl_point_bwd_stream_bytes(int W);
@@ -142,14 +142,6 @@ int nl_persistent_cus() {
 
 namespace {
 
-// A/B switches used while developing the kernels (NERFLOC_POINT_V1, NERFLOC_NO_TMERGE, NERFLOC_NO_CHAIN) exist only in a build
-// with -DNERFLOC_DEBUG_SWITCHES; the shipped library reads no environment variable on the render path.
-#ifdef NERFLOC_DEBUG_SWITCHES
-inline bool dbg_switch(const char* name) { return getenv(name) != nullptr; }
-#else
-inline bool dbg_switch(const char*) { return false; }
-#endif
-
 // ------------------------------------------------------------------------------------------ weight table
 const char* kWeightNames[] = {
     "ray_diff_fc.0.weight", "ray_diff_fc.0.bias", "ray_diff_fc.2.weight", "ray_diff_fc.2.bias",
@@ -202,7 +194,7 @@ struct Layout {
   GemmDim g[G_COUNT];
   size_t b32[G_COUNT], bhi[G_COUNT], blo[G_COUNT], bst[G_COUNT], bsh[G_COUNT], bias[G_COUNT];   // bsh: the weight stream in fp16 hi / lo (split-FP16 arithmetic)
   size_t rd_w, dec_w, sig_w, sig_b, bl2_w, bl2_b, bl4_w, bl4_b, ln_g, ln_b;
-  size_t pt_stream, pt_stream2, pt_stream2_mx, pt_stream2_f16, pt_bwd_stream, pt_mx_sc, mvf_pack, pt_bias, blw, dec_mfma, zeros;   // blw: [32][8] rgb/vis/angle columns of rgb_blending_mlp.0 + bias[32]  // fused point-branch weight stream (W in {64,128,256}) and its 3 bias rows
+  size_t pt_stream, pt_stream2, pt_stream2_mx, pt_stream2_f16, pt_bwd_stream, mvf_pack, pt_bias, blw, dec_mfma, zeros;   // blw: [32][8] rgb/vis/angle columns of rgb_blending_mlp.0 + bias[32]  // fused point-branch weight stream (W in {64,128,256}) and its 3 bias rows
   size_t mx_convout;   // NL_PREC_F16MX (round 6): fp6 images + block scales of G_CONVOUTF for tgemm_mx_kernel (W = 256)
   size_t mx_feat0;     // ... and of G_FEAT0P for feat_comp_mx_kernel (feat_mlp.0 + compositing in one kernel)
   size_t un_g[U_COUNT], un_b[U_COUNT];     // LayerNorm([C, L]) affine tables, position-major (L, C)
@@ -320,11 +312,10 @@ Layout make_layout(const nl_config* c) {
   L.pt_bias = take(4 * 3 * (size_t)W);
   L.pt_stream = take((W == 64 || W == 128 || W == 256) ? nl_point_stream_bytes(W) : 256);
   L.pt_stream2 = take((W == 128 || W == 256) ? nl_point_stream2_bytes(W) : 256);
-  L.pt_stream2_mx = take((W == 128 || W == 256) ? nl_point_stream2_bytes(W) : 256);   // NL_PREC_F16MX: f16 fragments + fp8 images of layers 2, 3, k / v
+  L.pt_stream2_mx = take((W == 128 || W == 256) ? nl_point_stream2_bytes(W) : 256);   // NL_PREC_F16MX: f16 fragments + MX-FP6 images of every layer
   L.pt_stream2_f16 = take((W == 128 || W == 128 * 2) ? nl_point_stream2_bytes(W) : 256);  // split-FP16 stream: the gradient path's fused forward (pt_forward_keep_fused)
   L.pt_bwd_stream = take(nl_point_bwd_chain_supported(W) ? nl_point_bwd_stream_bytes(W) : 256);   // transposed weights of the branch's rows: the frozen-weight way back (point_bwd.hip)
-  L.pt_mx_sc = take(4 * 64);
-  L.mvf_pack = take(nl_mv_front_pack_bytes());                                          // out_fc.0 as register-resident A fragments of mv_front_kernel (C = 192)                                                            // their per-chunk scale bytes while packing
+  L.mvf_pack = take(nl_mv_front_pack_bytes());                                          // out_fc.0 as register-resident A fragments of mv_front_kernel (C = 192)
   L.zeros = take(4096);
   L.mx_convout = take(W == 256 ? nl_tgemm_mx_image_bytes(L.g[G_CONVOUTF].Kpad) : 0);
   L.mx_feat0 = take(W == 256 ? nl_tgemm_mx_image_bytes(L.g[G_FEAT0P].Kpad) : 0);
@@ -566,10 +557,6 @@ struct nl_frame {
   // never lazily inside a render call (stream / event creation is illegal during graph capture) and never shared between frames, so two
   // renderers on two caller streams do not record into each other's events.  side_ok == false: everything runs on the caller's stream.
   hipStream_t side; hipEvent_t ev_fork, ev_join; bool side_ok;
-  // round 6: the search in parts (do_point: part p + 1 of the exact KNN is released onto the side stream when the neural-point kernel of part p starts) —
-  // ev_go[p]: recorded on the caller's stream in front of part p - 1's neural-point launch; ev_done[p]: part p's neighbours and aggregation scales are written
-  static constexpr int kMaxParts = 4;
-  hipEvent_t ev_go[kMaxParts], ev_done[kMaxParts]; bool parts_ok;
   // precision guard (NL_RENDER_PRECISION_GUARD): the mode guarded calls render this frame in once one of them found the conditioning indicator beyond the
   // configured mode's validated range (-1: none yet), how often that happened, and the mode the last guarded call's outputs were produced in.  Host-side
   // state of a frame that is documented as not re-entrant; mutable because render calls take the frame as const.
@@ -640,7 +627,7 @@ void carve_hd(Bump& b, const nl_config* c, int V, int64_t R, HdBufs& h) {
 // whether the fused render path runs statistics + out_fc.0 in mv_front_kernel and recomputes the blend taps (round 4): a function of the configuration alone,
 // so that workspace sizing and the render call agree
 inline bool front_path(const nl_config* c, int V) {
-  return !dbg_switch("NERFLOC_NO_FRONT") && c->precision != NL_PREC_F32 && nl_mv_front_supported(c->C, V, 1);
+  return c->precision != NL_PREC_F32 && nl_mv_front_supported(c->C, V, 1);
 }
 
 struct RenderBufs {
@@ -651,7 +638,7 @@ void carve_render(Bump& b, const nl_config* c, int V, int64_t R, RenderBufs& rb)
   const size_t N = (size_t)R * c->S;
   rb.xyz = b.take<float>(N * 3); rb.z = b.take<float>(N);
   rb.G = b.take<float>(N * c->W);
-  // the blend layer's per-(sample, view) rows exist only where mv_front_kernel + blend_taps_kernel do not apply (other feature widths, fp32 mode, debug switch):
+  // the blend layer's per-(sample, view) rows exist only where mv_front_kernel + blend_taps_mfma_kernel do not apply (other feature widths, fp32 mode):
   // at config 2 that is 0.67 GB of the chunk's workspace
   rb.bl1 = front_path(c, V) ? nullptr : b.take<float>(N * V * 32);
   rb.rgbv = b.take<float>(N * V * 4);
@@ -665,7 +652,7 @@ void carve_render(Bump& b, const nl_config* c, int V, int64_t R, RenderBufs& rb)
 struct Ctx {
   const nl_config* c; Layout L; const char* pk; hipStream_t st;
   uint64_t has_bst = ~0ull, has_bsh = ~0ull;   // layers whose streaming-kernel images exist in pk (pack_info)
-  bool mx = false;                             // NL_PREC_F16MX: the fused neural-point kernel multiplies as fp16 hi.hi + two MX-FP8 cross terms (everything else: BF16X3)
+  bool mx = false;                             // NL_PREC_F16MX: the fused neural-point kernel multiplies as fp16 hi.hi + two MX-FP6 cross terms (everything else: BF16X3)
   template <class T> const T* p(size_t off) const { return (const T*)(pk + off); }
 };
 
@@ -709,7 +696,7 @@ int run_gemm(const Ctx& x, int g, const SegSpec* segs, int nseg, int64_t M, floa
   if (prec == NL_PREC_F32) a.B = x.pk + x.L.b32[g];
   else if (prec != NL_PREC_F16X3_INTERNAL) { a.B = x.pk + x.L.bhi[g]; a.Blo = x.pk + x.L.blo[g]; a.Bst = ((x.has_bst >> g) & 1) ? x.pk + x.L.bst[g] : nullptr; }
   // NL_PREC_F16MX: conv_out multiplies as fp16 hi.hi + two MX-FP6 cross terms too (tgemm_mx_kernel) when its images exist
-  if (x.mx && g == G_CONVOUTF && prec == NL_PREC_BF16X3 && x.c->W == 256 && ((x.has_bsh >> g) & 1) && !dbg_switch("NERFLOC_NO_TGEMM_MX")) {
+  if (x.mx && g == G_CONVOUTF && prec == NL_PREC_BF16X3 && x.c->W == 256 && ((x.has_bsh >> g) & 1)) {
     a.Bsh_mx = x.pk + x.L.bsh[g]; a.Bmx = x.pk + x.L.mx_convout;
   }
   for (int i = 0; i < nseg; ++i) if (segs[i].frag == 3 && ((x.has_bsh >> g) & 1)) a.Bsh16 = x.pk + x.L.bsh[g];   // split-FP16 fragments: the layer's fp16 stream (conv1)
@@ -822,8 +809,6 @@ int ensure_ptt(const Ctx& x, const nl_frame* fc) {
 // side stream first, so no kernel is left writing the caller's workspace behind its back and an active capture stays well-formed.
 struct SideJoin {
   hipStream_t main = nullptr, side = nullptr; hipEvent_t ev = nullptr; bool armed = false;
-  int parts = 1;            // > 1: only part 0 of the search has been issued (rows [0, part_rows)); do_point issues the others, each when the part before it starts
-  int64_t part_rays = 0;    // rays per part (parts are cut at ray boundaries: the per-sample direction is the ray's)
   void arm(hipStream_t m, hipStream_t s_, hipEvent_t e) { main = m; side = s_; ev = e; armed = true; }
   int join() {
     if (!armed) return NL_OK;
@@ -892,9 +877,8 @@ int do_point(const Ctx& x, const nl_frame* f, const float* xyz, const float* dir
     SegSpec sg{G, W, W, 0, 1};
     NL_TRY(run_gemm(x, G_Q, &sg, 1, N, p.Q, 128, NL_ACT_NONE));
   }
-  const int parts = knn_done ? knn_done->parts : 1;
-  if (knn_done && parts == 1) NL_TRY(knn_done->join());
-  if (parts > 1 && (!fused_path || dir_div <= 0)) return NL_ERR_UNSUPPORTED;   // (render_rays_impl plans parts for the fused kernels only)
+  // (Issuing the search in parts, each under the neural-point launch of the part before it, was measured slower: profiles/r6_knn_parts_*_timeline.txt.)
+  if (knn_done) NL_TRY(knn_done->join());
   if (fused_path) {
     NL_TRY(ensure_ptt(x, f));
     if (!knn_done) NL_TRY(nl_launch_wscale(p.idx, p.d2, f->sp_conf, N, K, f->M, p.wscale, x.st));
@@ -907,40 +891,12 @@ int do_point(const Ctx& x, const nl_frame* f, const float* xyz, const float* dir
     a.N = (int)N; a.M = (int)(f->M > 0x7fffffff ? 0x7fffffff : f->M); a.inv_span = 1.f / (f->views.far_ - f->views.near_);
     hipEvent_t pe0 = nullptr, pe1 = nullptr;
     if (prof_arm(&pe0, &pe1)) NL_CHECK_HIP(hipEventRecord(pe0, x.st));
-    const bool use_v1 = dbg_switch("NERFLOC_POINT_V1");
     a.logit_amax = reinterpret_cast<unsigned*>(f->views_dev + 249);   // (read by the v1 kernel; the v2 launcher takes it as a parameter)
-    // The search in parts (round 6; VERDICT r5 item 1c: "KNN of chunk k + 1 under point_fused2 of chunk k — build it, keep the timeline whichever way it falls").
-    // Only part 0 of the search is issued up front; part p + 1 is released onto the side stream when the neural-point launch of part p starts (rows of different
-    // samples are independent: the kernel runs once per part).  BUILT, MEASURED, OFF (NL_KNN_PARTS = 1): beside the persistent matrix kernel the search finds room
-    // for ONE of its workgroups per CU (88 of the 512 registers per lane are left) and runs at 130 queries / us instead of 700; the front end does end 0.30 / 0.40 ms
-    // earlier with 2 / 4 parts, but the neural-point launches take 0.34 ms longer per 262 144 queries searched beside them (+17-20 %: the search's vector instructions
-    // issue from the same SIMDs) and wait for their part — 7.70 (1 part) / 7.89 (2) / 8.05 ms (4) per config-2 step, same box (profiles/r6_knn_parts_*_timeline.txt).
-    const int64_t rows_pp = parts > 1 ? knn_done->part_rays * a.dir_div : N;
-    for (int pt = 0; pt < parts; ++pt) {
-      const int64_t n0 = pt * rows_pp, n1 = n0 + rows_pp < N ? n0 + rows_pp : N;
-      if (n0 >= N) break;
-      if (parts > 1) {
-        const int64_t m0 = n1, m1 = m0 + rows_pp < N ? m0 + rows_pp : N;
-        if (pt + 1 < parts && m0 < N) {
-          NL_CHECK_HIP(hipEventRecord(f->ev_go[pt + 1], x.st));
-          NL_CHECK_HIP(hipStreamWaitEvent(f->side, f->ev_go[pt + 1], 0));
-          NL_TRY(nl_knn_search(&f->grid, xyz + 3 * m0, m1 - m0, K, p.idx + (size_t)K * m0, p.d2 + (size_t)K * m0, f->side));
-          NL_TRY(nl_launch_wscale(p.idx + (size_t)K * m0, p.d2 + (size_t)K * m0, f->sp_conf, m1 - m0, K, f->M, p.wscale + m0, f->side));
-          NL_CHECK_HIP(hipEventRecord(f->ev_done[pt + 1], f->side));
-        }
-        NL_CHECK_HIP(hipStreamWaitEvent(x.st, f->ev_done[pt], 0));
-      }
-      NlPointFusedArgs b = a;
-      b.xyz = xyz + 3 * n0; b.dir = dir + (size_t)dir_stride * (n0 / a.dir_div); b.idx = p.idx + (size_t)K * n0; b.Q = p.Q + (size_t)128 * n0; b.O = p.O + (size_t)128 * n0;
-      b.N = (int)(n1 - n0);
-      int rc2 = NL_ERR_UNSUPPORTED;
-      if (!use_v1 && nl_point_fused2_supported(W, x.c->precision)) rc2 = nl_launch_point_fused2(b, W, x.c->precision, x.st, mx, nullptr, nullptr, f->views_dev + 248,
-                                                                                                        reinterpret_cast<unsigned*>(f->views_dev + 249),
-                                                                                                        reinterpret_cast<unsigned long long*>(f->views_dev + 250));
-      if (rc2 == NL_ERR_UNSUPPORTED) rc2 = nl_launch_point_fused(b, W, x.c->precision, x.st);   // (e.g. more rows than 32-bit buffer offsets reach)
-      NL_TRY(rc2);
-    }
-    if (knn_done && parts > 1) NL_TRY(knn_done->join());   // (the last part's event was waited for above: this only disarms the guard)
+    int rc2 = NL_ERR_UNSUPPORTED;
+    if (nl_point_fused2_supported(W, x.c->precision)) rc2 = nl_launch_point_fused2(a, W, x.c->precision, x.st, mx, nullptr, nullptr, reinterpret_cast<unsigned*>(f->views_dev + 249),
+                                                                                   reinterpret_cast<unsigned long long*>(f->views_dev + 250));
+    if (rc2 == NL_ERR_UNSUPPORTED) rc2 = nl_launch_point_fused(a, W, x.c->precision, x.st);   // (e.g. more rows than 32-bit buffer offsets reach)
+    NL_TRY(rc2);
     if (pe1) NL_CHECK_HIP(hipEventRecord(pe1, x.st));
   } else {
     if (!p.X) return NL_ERR_UNSUPPORTED;
@@ -1072,7 +1028,7 @@ int pt_forward_staged(const Ctx& x, const nl_frame* f, const float* xyz, const f
 // fused neural-point kernel in split-FP16 (point_fused2_kernel<NRT, true, false, F16, KEEP>) that also leaves the k / v rows and the three layers' sign bits — what
 // pt_backward_only reads — instead of an encode kernel, four (N x 8)-row GEMMs through HBM and an attention kernel (round 4: 1.7 -> 0.6 ms of a 512-ray step).
 bool pt_keep_fused_ok(const Ctx& x, const nl_frame* f, int64_t N, int K) {
-  return !dbg_switch("NERFLOC_NO_KEEP_FUSED") && K == 8 && x.c->precision == NL_PREC_F16X3_INTERNAL && nl_point_fused2_supported(x.c->W, NL_PREC_BF16X3) && f->M >= 1 &&
+  return K == 8 && x.c->precision == NL_PREC_F16X3_INTERNAL && nl_point_fused2_supported(x.c->W, NL_PREC_BF16X3) && f->M >= 1 &&
          N * 8 * 1024 <= 0x7fffffffll && ((int64_t)f->M + 1) * x.c->W * 4 <= 0x7fffffffll;
 }
 int pt_forward_keep_fused(const Ctx& x, const nl_frame* f, const float* xyz, const float* dir, int dir_stride, int dir_div, const float* G, int64_t N,
@@ -1120,15 +1076,10 @@ int pt_backward_only(const Ctx& xb, const Ctx& x, const nl_frame* f, const float
   NL_TRY(run_gemm(xb, G_FC_T, &sp, 1, N, p.gO, 128, NL_ACT_NONE));
   // frozen weights, W = 128 / 256, K = 8: the attention's way back, the four (N x 8)-row products and the LeakyReLU masks in between as ONE launch that keeps the rows
   // in registers (point_bwd.hip); d query comes back from it
-  const bool chain = !tg && K == 8 && pt_mask_bits(x) && pt_table(x) && !dbg_switch("NERFLOC_NO_BWD_CHAIN") && nl_point_bwd_chain_supported(W) && NK * 1024 <= 0x7fffffffll;
-  const bool chain_att = chain && !dbg_switch("NERFLOC_NO_BWD_ATT");
+  const bool chain = !tg && K == 8 && pt_mask_bits(x) && pt_table(x) && nl_point_bwd_chain_supported(W) && NK * 1024 <= 0x7fffffffll;
   if (chain) {
     const unsigned* mk[3] = {p.mk[0], p.mk[1], p.mk[2]};
-    if (chain_att) NL_TRY(nl_launch_point_bwd_chain(nullptr, mk, x.p<char>(x.L.pt_bwd_stream), p.gX, NK, W, x.st, p.Q, p.KV, p.gO, p.gQ));
-    else {
-      NL_TRY(nl_launch_attn_backward(p.Q, p.KV, p.gO, N, K, p.gQ, p.gKV, x.st));
-      NL_TRY(nl_launch_point_bwd_chain(p.gKV, mk, x.p<char>(x.L.pt_bwd_stream), p.gX, NK, W, x.st));
-    }
+    NL_TRY(nl_launch_point_bwd_chain(nullptr, mk, x.p<char>(x.L.pt_bwd_stream), p.gX, NK, W, x.st, p.Q, p.KV, p.gO, p.gQ));
     if (g_G) {   // residual path + query projection
       NL_TRY(run_gemm(xb, G_Q_T, &sgq, 1, N, p.FCo, W, NL_ACT_NONE));   // (FCo is free from here on)
       NL_TRY(nl_launch_add(p.gpre, p.FCo, g_G, (size_t)N * W, x.st));
@@ -1349,8 +1300,7 @@ int do_unet(const Ctx& x, const float* in, int64_t R, float* geo, const UnBufs& 
             bool need_geo = true, int in_frag = 0, bool fuse_inner = false) {   // in_frag: NlGemmSeg::frag of `in` (0: fp32 rows, 1: fragment image, 3: its split-FP16 form)
   const int W = x.c->W, S = x.c->S;
   // the two phases of every transposed convolution as one launch (bf16 modes; the fp32 kernels keep the separate phases)
-  static const bool no_merge = dbg_switch("NERFLOC_NO_TMERGE");
-  const bool merged = x.c->precision != NL_PREC_F32 && !no_merge;
+  const bool merged = x.c->precision != NL_PREC_F32;
   auto g = [&](int i) { return x.p<float>(x.L.un_g[i]); };
   auto b = [&](int i) { return x.p<float>(x.L.un_b[i]); };
   auto gl = [&](int i) { return x.p<float>(x.L.un_gl[i]); };   // accumulator-lane order: what the GEMM's fused LayerNorm reads
@@ -1358,7 +1308,7 @@ int do_unet(const Ctx& x, const float* in, int64_t R, float* geo, const UnBufs& 
   const float eps = 1e-5f;
   // feature_agg's two consumers take their weights with the channels of every 32-block in accumulator order in the bf16 modes (G_CONV1F / G_CONVOUTF, streaming
   // kernel): from the chain kernel's fragment image (in_frag) or from fp32 rows read in that order — the same products in the same order either way
-  const bool korder = in_frag || ((x.c->precision == NL_PREC_BF16X3 || x.c->precision == NL_PREC_BF16) && !dbg_switch("NERFLOC_NO_FRAG") && (((size_t)in) & 15) == 0 &&
+  const bool korder = in_frag || ((x.c->precision == NL_PREC_BF16X3 || x.c->precision == NL_PREC_BF16) && (((size_t)in) & 15) == 0 &&
                                   ((x.has_bst >> G_CONV1F) & 1) && ((x.has_bst >> G_CONVOUTF) & 1));
   const int fa_mode = in_frag ? in_frag : (korder ? 2 : 0);
   {  // conv1: W -> 64 over S
@@ -1369,9 +1319,8 @@ int do_unet(const Ctx& x, const float* in, int64_t R, float* geo, const UnBufs& 
     if (!fused) NL_TRY(nl_launch_ln_slab_elu(u.r1, R, S, 64, g(U_CONV1), b(U_CONV1), eps, nullptr, u.c1, x.st));
   }
   // conv2 ... trans_conv1 as one kernel (unet_inner.hip: a pair of rays per workgroup, every slab in LDS): S = 128, the streaming kernels' weight images
-  static const bool no_inner = dbg_switch("NERFLOC_NO_UNET_INNER");
   const uint64_t inner_bits = (1ull << G_CONV2) | (1ull << G_CONV3) | (1ull << G_T3M) | (1ull << G_T2M) | (1ull << G_T1M);
-  if (fuse_inner && merged && !no_inner && nl_unet_inner_supported(S, x.c->precision) && (x.has_bst & inner_bits) == inner_bits) {
+  if (fuse_inner && merged && nl_unet_inner_supported(S, x.c->precision) && (x.has_bst & inner_bits) == inner_bits) {
     NlUnetInnerArgs ia;
     ia.c1 = u.c1; ia.c2 = u.c2; ia.x2 = u.x2; ia.R = (int)R; ia.eps = eps;
     const int gs[5] = {G_CONV2, G_CONV3, G_T3M, G_T2M, G_T1M}, us[5] = {U_CONV2, U_CONV3, U_T3, U_T2, U_T1};
@@ -1603,7 +1552,7 @@ int do_heads(const Ctx& x, int V, const float* z, const float* FA, const float* 
     float* wts = out->weights ? out->weights + ray0 * S : h.fth;
     NL_TRY(nl_launch_composite(z, h.sigma, h.rgb_s, nullptr, valid_s, R, S, W, white, out, ray0, nullptr, h.wsum, x.st, nullptr, out->weights ? nullptr : h.fth));
     // ... and applies feat_mlp.2 to the rows it has summed (the per-ray GEMM below: 33 us whatever the batch, 3 % of a 512-ray shard's step)
-    const bool f2 = x.L.g[G_FEAT2].Npad <= 192 && !dbg_switch("NERFLOC_NO_FEAT2_FUSED");
+    const bool f2 = x.L.g[G_FEAT2].Npad <= 192;
     NL_TRY(nl_launch_feat_comp_mx(FA, wts, N, S, x.pk + x.L.bsh[G_FEAT0P], x.pk + x.L.mx_feat0, x.p<float>(x.L.bias[G_FEAT0P]), h.hc, x.st,
                                   f2 ? x.p<float>(x.L.b32[G_FEAT2]) : nullptr, x.L.g[G_FEAT2].Npad, C, h.wsum, out->feat + ray0 * C, fa_f16));
     feat_done = f2;
@@ -1988,10 +1937,10 @@ int nl_pack_weights(const nl_config* cfg, const float* const* t, int n, void* pa
                                    (char*)packed + L.pt_stream2, W, F, st);
     if (rc != NL_OK) return rc;
     rc = nl_pack_point_stream2(t[T_B0W], t[T_B2W], t[T_B4W], t[T_WK], t[T_WV], t[T_B2B], t[T_B4B], (const float*)((char*)packed + L.rd_w),
-                               (char*)packed + L.pt_stream2_mx, W, F, st, 1, (int*)((char*)packed + L.pt_mx_sc));
+                               (char*)packed + L.pt_stream2_mx, W, F, st, 1);
     if (rc != NL_OK) return rc;
     rc = nl_pack_point_stream2(t[T_B0W], t[T_B2W], t[T_B4W], t[T_WK], t[T_WV], t[T_B2B], t[T_B4B], (const float*)((char*)packed + L.rd_w),
-                               (char*)packed + L.pt_stream2_f16, W, F, st, 2, nullptr);
+                               (char*)packed + L.pt_stream2_f16, W, F, st, 2);
     if (rc != NL_OK) return rc;
     rc = nl_pack_point_bwd_stream(t[T_B0W], t[T_B2W], t[T_B4W], t[T_WK], t[T_WV], (char*)packed + L.pt_bwd_stream, W, F, st);
     if (rc != NL_OK) return rc;
@@ -2065,11 +2014,6 @@ int nl_frame_create(const nl_config* cfg, const nl_frame_desc* d, void* mem, siz
                hipEventCreateWithFlags(&f->ev_fork, hipEventDisableTiming) == hipSuccess &&
                hipEventCreateWithFlags(&f->ev_join, hipEventDisableTiming) == hipSuccess;
   if (!f->side_ok) (void)hipGetLastError();
-  f->parts_ok = f->side_ok;
-  for (int i = 0; i < nl_frame::kMaxParts; ++i) { f->ev_go[i] = f->ev_done[i] = nullptr; }
-  for (int i = 0; i < nl_frame::kMaxParts && f->parts_ok; ++i)
-    f->parts_ok = hipEventCreateWithFlags(&f->ev_go[i], hipEventDisableTiming) == hipSuccess && hipEventCreateWithFlags(&f->ev_done[i], hipEventDisableTiming) == hipSuccess;
-  if (!f->parts_ok) (void)hipGetLastError();
   *out = f;
   return NL_OK;
 }
@@ -2079,7 +2023,6 @@ int nl_frame_destroy(nl_frame* f) {
   if (f->side) { (void)hipStreamSynchronize(f->side); (void)hipStreamDestroy(f->side); }
   if (f->ev_fork) (void)hipEventDestroy(f->ev_fork);
   if (f->ev_join) (void)hipEventDestroy(f->ev_join);
-  for (int i = 0; i < nl_frame::kMaxParts; ++i) { if (f->ev_go[i]) (void)hipEventDestroy(f->ev_go[i]); if (f->ev_done[i]) (void)hipEventDestroy(f->ev_done[i]); }
   delete f;
   return NL_OK;
 }
@@ -2598,23 +2541,12 @@ int render_rays_impl(const nl_config* cfg, const void* packed, const nl_frame* f
       NL_CHECK_HIP(hipEventRecord(f->ev_fork, x.st));
       NL_CHECK_HIP(hipStreamWaitEvent(f->side, f->ev_fork, 0));
       knn.arm(x.st, f->side, f->ev_join);
-#ifndef NL_KNN_PARTS
-#define NL_KNN_PARTS 1   // measured (profiles/r6_knn_parts_{1,2,4}_timeline.txt): 2 / 4 parts shorten the front end by 0.3 / 0.4 ms and lengthen the neural-point span by 0.41 / 0.92 ms — off
-#endif
-#ifndef NL_KNN_PARTS_MIN_ROWS
-#define NL_KNN_PARTS_MIN_ROWS (1 << 18)
-#endif
-      // the search in parts (do_point): part 0 now, the others as the neural-point launches of the parts before them start
-      const int parts = (f->parts_ok && NL_KNN_PARTS > 1 && N >= NL_KNN_PARTS_MIN_ROWS && rc >= NL_KNN_PARTS && !dbg_switch("NERFLOC_NO_KNN_PARTS")) ? NL_KNN_PARTS : 1;
-      static_assert(NL_KNN_PARTS <= nl_frame::kMaxParts, "events per frame");
-      const int64_t part_rays = (rc + parts - 1) / parts, n_first = parts > 1 ? part_rays * S : N;
-      NL_TRY(nl_knn_search(&f->grid, rb.xyz, n_first, 8, rb.pt.idx, rb.pt.d2, f->side));
-      NL_TRY(nl_launch_wscale(rb.pt.idx, rb.pt.d2, f->sp_conf, n_first, 8, f->M, rb.pt.wscale, f->side));
-      if (parts > 1) { NL_CHECK_HIP(hipEventRecord(f->ev_done[0], f->side)); knn.parts = parts; knn.part_rays = part_rays; }
+      NL_TRY(nl_knn_search(&f->grid, rb.xyz, N, 8, rb.pt.idx, rb.pt.d2, f->side));
+      NL_TRY(nl_launch_wscale(rb.pt.idx, rb.pt.d2, f->sp_conf, N, 8, f->M, rb.pt.wscale, f->side));
     }
     // the chain kernels recompute the multiview feature rows G (N x W) from out_fc's 64-wide hidden rows: G is only materialised for
     // the stage output or when the separate launches run instead
-    const bool use_chain = !dbg_switch("NERFLOC_NO_CHAIN") && W == 256 && cfg->precision != NL_PREC_F32 && N * 1024 <= 0x7fffffffll &&
+    const bool use_chain = W == 256 && cfg->precision != NL_PREC_F32 && N * 1024 <= 0x7fffffffll &&
                            nl_point_fused_supported(W, cfg->precision);
     const bool front = front_path(cfg, V) && f->C == cfg->C && nl_mv_front_supported(f->C, V, N) && rb.bl1 == nullptr;
     NL_TRY(do_mv(x, f, qc, rb.xyz, N, rb.G, nullptr, nullptr, rb.valid_s, front ? nullptr : rb.bl1, rb.rgbv, rb.mv, use_chain && !out->mv_feature_agg,
@@ -2626,15 +2558,15 @@ int render_rays_impl(const nl_config* cfg, const void* packed, const nl_frame* f
     const bool want_feat = out->feat != nullptr;
     // feature_agg has two consumers left on this path — conv1 and conv_out, three taps each: the chain kernel hands it over as the split-bf16 fragments it
     // holds anyway (same bytes in the same buffer) unless someone wants the fp32 rows: the stage output, or feat_mlp.0 over the live tiles of an early-terminated batch
-    const bool fa_frag = use_chain && !dbg_switch("NERFLOC_NO_FRAG") && (N & 31) == 0 && !out->feature_agg && !(want_feat && term_eps > 0.f);
+    const bool fa_frag = use_chain && (N & 31) == 0 && !out->feature_agg && !(want_feat && term_eps > 0.f);
     // f16mx: feat_mlp.0 leaves the chain kernel — it runs after the density, fused with the compositing of its rows (do_heads: feat_late)
     // (the kernel reads the samples' weights as 16-byte rows: a caller's `weights` buffer that is not 16-byte aligned keeps the old path — no alignment was ever asked of it)
     const bool feat_late = want_feat && term_eps == 0.f && fa_frag && x.mx && ((x.has_bsh >> G_FEAT0P) & 1) && nl_feat_comp_mx_supported(W, S, N) &&
-                           (((size_t)out->weights) & 15) == 0 && !dbg_switch("NERFLOC_NO_FEAT_COMP");
+                           (((size_t)out->weights) & 15) == 0;
     // split-FP16 fragments where EVERY consumer of the image multiplies in fp16-based arithmetic: conv1 -> tgemm_conv1_kernel<true, true>, conv_out -> tgemm_mx_kernel,
     // feat_mlp.0 -> feat_comp_mx_kernel (or nobody), the blend projection inside the chain kernel on its fp16 stream (W = 256, S = 128, f16mx)
     const bool fa_f16 = fa_frag && x.mx && W == 256 && S == 128 && (!want_feat || feat_late) && ((x.has_bsh >> G_CONV1F) & 1) && ((x.has_bsh >> G_CONVOUTF) & 1) &&
-                        ((x.has_bsh >> G_BLENDAP) & 1) && !dbg_switch("NERFLOC_NO_TGEMM_MX") && !dbg_switch("NERFLOC_NO_F16FRAG");
+                        ((x.has_bsh >> G_BLENDAP) & 1);
     const ChainOut chain{(want_feat && term_eps == 0.f && !feat_late) ? rb.hd.fth : nullptr, rb.hd.blA, &chain_done, use_chain ? rb.mv.t64 : nullptr, fa_frag, fa_f16};
     NL_TRY(do_point(x, f, rb.xyz, rays_d + 3 * r0, 3, S, rb.G, N, 8, rb.FA, rb.pt, fork ? &knn : nullptr, &chain));
     const int chain_parts = chain_done ? ((want_feat && term_eps == 0.f && !feat_late ? 1 : 0) | 2) : 0;

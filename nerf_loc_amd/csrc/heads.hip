@@ -88,105 +88,6 @@ __global__ __launch_bounds__(256) void blend_kernel(const float* __restrict__ hA
   rgb_s[3 * (size_t)n] = r; rgb_s[3 * (size_t)n + 1] = g; rgb_s[3 * (size_t)n + 2] = b;
 }
 
-// The same tail with the per-(sample, view) part of layer 1 RECOMPUTED instead of read back (round 4: mv_front_kernel no longer writes the N x V x 32 rows,
-// 0.7 GB out and in per config-2 batch): IBRNet projection of the sample into view v (ibrnet.py:169-192), the bilinear (zeros, align_corners = True) tap of
-// the per-frame projected feature map pfeat = W[:, feat] . featmap (32 channels: a linear layer commutes with the tap), the view-angle features
-// (ibrnet.py:144-167) and the [rgb | vis | angle] columns + bias (blw).  One lane per sample; views the sample is invisible in (vis == 0: logit masked to
-// -1e9, model.py:536) are skipped by the lane.  rgbv (N*V, 4) = tapped colours + visibility from mv_front_kernel.
-__global__ __launch_bounds__(256) void blend_taps_kernel(const NlViews vw, const float* __restrict__ viewsdev, const float* __restrict__ pfeat /*(V,h,w,32)*/,
-                                                         const float* __restrict__ blw /*[32][8], bias[32]*/, const float* __restrict__ xyz,
-                                                         const float* __restrict__ hA, const float* __restrict__ rgbv, int N,
-                                                         const float* __restrict__ w2 /*[16][32]*/, const float* __restrict__ b2,
-                                                         const float* __restrict__ w4 /*[16]*/, const float* __restrict__ b4,
-                                                         float* __restrict__ rgb_s, const int* __restrict__ n_alive, int S) {
-  using namespace nlmv;
-  const int n = blockIdx.x * blockDim.x + threadIdx.x;
-  if (n >= N) return;
-  if (n_alive) {
-    const int r = n / S;
-    if (n - r * S >= n_alive[r]) { rgb_s[3 * (size_t)n] = 0.f; rgb_s[3 * (size_t)n + 1] = 0.f; rgb_s[3 * (size_t)n + 2] = 0.f; return; }
-  }
-  const int V = vw.V;
-  const float X = xyz[3 * (size_t)n], Y = xyz[3 * (size_t)n + 1], Z = xyz[3 * (size_t)n + 2];
-  float qc0 = vw.qcam[0], qc1 = vw.qcam[1], qc2 = vw.qcam[2];
-  if (vw.qrows) { const float* qr = vw.qrows + 3 * (size_t)(n / vw.qS); qc0 = qr[0]; qc1 = qr[1]; qc2 = qr[2]; }
-  float tq[3] = {qc0 - X, qc1 - Y, qc2 - Z};
-  const float rq = 1.f / (sqrtf(tq[0] * tq[0] + tq[1] * tq[1] + tq[2] * tq[2]) + 1e-6f);
-  tq[0] *= rq; tq[1] *= rq; tq[2] *= rq;
-  float xa[32];   // per-sample part of layer 1 (feature_agg columns of rgb_blending_mlp.0)
-#pragma unroll
-  for (int i4 = 0; i4 < 8; ++i4) {
-    const float4 t = *(const float4*)(hA + (size_t)n * 32 + 4 * i4);
-    xa[4 * i4] = t.x; xa[4 * i4 + 1] = t.y; xa[4 * i4 + 2] = t.z; xa[4 * i4 + 3] = t.w;
-  }
-  const size_t fmap = (size_t)vw.h * vw.w;
-  float lg[NL_MAX_VIEWS];
-  float mx = -3.4e38f;
-  for (int v = 0; v < V; ++v) {
-    const float4 cv = *(const float4*)(rgbv + ((size_t)n * V + v) * 4);
-    float o = -1e9f;
-    if (cv.w != 0.f) {
-      const float4 p0 = *(const float4*)(viewsdev + 12 * v), p1 = *(const float4*)(viewsdev + 12 * v + 4), p2 = *(const float4*)(viewsdev + 12 * v + 8);
-      const float cx = fmaf(p0.z, Z, fmaf(p0.y, Y, p0.x * X)) + p0.w;
-      const float cy = fmaf(p1.z, Z, fmaf(p1.y, Y, p1.x * X)) + p1.w;
-      const float cz = fmaf(p2.z, Z, fmaf(p2.y, Y, p2.x * X)) + p2.w;
-      const float zc = fmaxf(cz, 1e-8f);
-      float px = cx / zc, py = cy / zc;
-      px = fminf(fmaxf(px, -1e6f), 1e6f);
-      py = fminf(fmaxf(py, -1e6f), 1e6f);
-      const float xn = 2.f * px / (float)(vw.Wimg - 1) - 1.f;
-      const float yn = 2.f * py / (float)(vw.H - 1) - 1.f;
-      const Taps tf = make_taps<true, false>(xn, yn, vw.w, vw.h);
-      int of[4];
-      unpack_taps(pack_taps(tf, vw.w, vw.h), vw.w, of);
-      const float w0 = (tf.mn && tf.mw) ? tf.nw : 0.f, w1 = (tf.mn && tf.me) ? tf.ne : 0.f, w2t = (tf.ms && tf.mw) ? tf.sw : 0.f, w3 = (tf.ms && tf.me) ? tf.se : 0.f;
-      float tt[3] = {viewsdev[192 + 3 * v] - X, viewsdev[192 + 3 * v + 1] - Y, viewsdev[192 + 3 * v + 2] - Z};
-      const float rt = 1.f / (sqrtf(tt[0] * tt[0] + tt[1] * tt[1] + tt[2] * tt[2]) + 1e-6f);
-      tt[0] *= rt; tt[1] *= rt; tt[2] *= rt;
-      const float df[3] = {tq[0] - tt[0], tq[1] - tt[1], tq[2] - tt[2]};
-      const float rd = 1.f / fmaxf(sqrtf(df[0] * df[0] + df[1] * df[1] + df[2] * df[2]), 1e-6f);
-      const float in8[8] = {cv.x, cv.y, cv.z, cv.w, df[0] * rd, df[1] * rd, df[2] * rd, tq[0] * tt[0] + tq[1] * tt[1] + tq[2] * tt[2]};
-      const float* pb = pfeat + (size_t)v * fmap * 32;
-      float x[32];
-#pragma unroll
-      for (int c4 = 0; c4 < 8; ++c4) {
-        const float4 a = *(const float4*)(pb + (size_t)of[0] * 32 + 4 * c4), b = *(const float4*)(pb + (size_t)of[1] * 32 + 4 * c4);
-        const float4 c = *(const float4*)(pb + (size_t)of[2] * 32 + 4 * c4), d = *(const float4*)(pb + (size_t)of[3] * 32 + 4 * c4);
-        x[4 * c4] = fmaf(d.x, w3, fmaf(c.x, w2t, fmaf(b.x, w1, a.x * w0)));
-        x[4 * c4 + 1] = fmaf(d.y, w3, fmaf(c.y, w2t, fmaf(b.y, w1, a.y * w0)));
-        x[4 * c4 + 2] = fmaf(d.z, w3, fmaf(c.z, w2t, fmaf(b.z, w1, a.z * w0)));
-        x[4 * c4 + 3] = fmaf(d.w, w3, fmaf(c.w, w2t, fmaf(b.w, w1, a.w * w0)));
-      }
-#pragma unroll
-      for (int i = 0; i < 32; ++i) {
-        float a = x[i] + blw[256 + i];
-#pragma unroll
-        for (int jj = 0; jj < 8; ++jj) a = fmaf(blw[i * 8 + jj], in8[jj], a);
-        x[i] = nl_lrelu(xa[i] + a);
-      }
-      o = b4[0];
-#pragma unroll
-      for (int j = 0; j < 16; ++j) {
-        float a = b2[j];
-#pragma unroll
-        for (int i = 0; i < 32; ++i) a = fmaf(w2[j * 32 + i], x[i], a);
-        o = fmaf(w4[j], nl_lrelu(a), o);
-      }
-    }
-    lg[v] = o;
-    mx = fmaxf(mx, o);
-  }
-  float den = 0.f;
-  for (int v = 0; v < V; ++v) { lg[v] = expf(lg[v] - mx); den += lg[v]; }
-  float r = 0.f, g = 0.f, b = 0.f;
-  for (int v = 0; v < V; ++v) {
-    const float wv = lg[v] / den;
-    const float* c = rgbv + ((size_t)n * V + v) * 4;
-    r += c[0] * wv; g += c[1] * wv; b += c[2] * wv;
-  }
-  rgb_s[3 * (size_t)n] = r; rgb_s[3 * (size_t)n + 1] = g; rgb_s[3 * (size_t)n + 2] = b;
-}
-
 // Front-to-back compositing (model.py:541-560,597) + valid-ray mask (:572-575).  One wave per ray.
 // Each lane owns CH = ceil(S/64) consecutive samples; transmittance = exclusive product scan
 // (lane-local serial product, then a wave-level multiplicative scan of the lane totals).
@@ -396,7 +297,12 @@ int nl_launch_blend(const float* hA, const float* h1, const float* rgbv, int64_t
   return NL_OK;
 }
 
-// Round 5: the same function with lanes = (sample row r, channel octet g) instead of lane = sample.  What bound the lane-per-sample kernel was not its ~900 vector
+// The same tail with the per-(sample, view) part of layer 1 RECOMPUTED instead of read back (round 4: mv_front_kernel no longer writes the N x V x 32 rows,
+// 0.7 GB out and in per config-2 batch): IBRNet projection of the sample into view v (ibrnet.py:169-192), the bilinear (zeros, align_corners = True) tap of
+// the per-frame projected feature map pfeat = W[:, feat] . featmap (32 channels: a linear layer commutes with the tap), the view-angle features
+// (ibrnet.py:144-167) and the [rgb | vis | angle] columns + bias (blw).  Views the sample is invisible in (vis == 0: logit masked to
+// -1e9, model.py:536) are skipped by the lane.  rgbv (N*V, 4) = tapped colours + visibility from mv_front_kernel.
+// Round 5: lanes = (sample row r, channel octet g) instead of the round-4 lane = sample.  What bound the lane-per-sample kernel was not its ~900 vector
 // instructions per (sample, view) but its taps: 32 sixteen-byte loads per lane and view, every lane on its own 128-byte texel row — the CU's address unit takes ~64
 // cycles per such instruction (tools/ubench/vmem_issue.hip; `r5_pmc_sq*.csv`: 2.7e6 load instructions per launch, waves waiting 63 % of their cycles).  Here a wave walks
 // 16 consecutive samples; the four lanes of a row own 8 of the projected map's 32 channels each: a tap is TWO loads per lane, and one instruction touches 16 texel rows
@@ -568,12 +474,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 8))) voi
 int nl_launch_blend_taps(const NlViews& vw, const float* viewsdev, const float* pfeat, const float* blw, const float* xyz, const float* hA, const float* rgbv, int64_t N,
                          const float* w2, const float* b2, const float* w4, const float* b4, float* rgb_s, hipStream_t st, const int* n_alive, int S) {
   if (N <= 0) return NL_OK;
-#ifdef NL_BLEND_TAPS_V1   // (A/B builds: the lane-per-sample kernel of round 4)
-  hipLaunchKernelGGL(blend_taps_kernel, dim3((unsigned)nl_cdiv(N, 256)), dim3(256), 0, st, vw, viewsdev, pfeat, blw, xyz, hA, rgbv, (int)N, w2, b2, w4, b4, rgb_s, n_alive, S);
-#else
   const size_t lds = (288 + (size_t)4 * 16 * vw.V * BT_SLOT) * sizeof(float);   // <= 38 KB at 16 views
   hipLaunchKernelGGL(blend_taps_mfma_kernel, dim3((unsigned)nl_cdiv(N, 64)), dim3(256), lds, st, vw, viewsdev, pfeat, blw, xyz, hA, rgbv, (int)N, w2, b2, w4, b4, rgb_s, n_alive, S);
-#endif
   NL_LAUNCH_CHECK();
   return NL_OK;
 }

@@ -189,9 +189,6 @@ struct BestK {
 };
 
 // Merge one candidate per lane (kd = bits(dist2), ki = idx; 0xffffffff/0xffffffff = none) into the best list.
-#ifndef KNN_KO
-#define KNN_KO 0   // knock-out bits for timing experiments (results are garbage): 1 no selection loop, 2 no leaf candidates, 4 no breadth-first descent
-#endif
 #ifdef KNN_STATS   // debug build: step counts over one search, printed by nl_knn_search (tools/build_variant.sh stats knn.hip -DKNN_STATS)
 __device__ unsigned long long knn_stats[16];
 #define KNN_CNT(i, v) do { if (__lane_id() == 0) atomicAdd(&knn_stats[i], (unsigned long long)(v)); } while (0)
@@ -200,7 +197,6 @@ __device__ unsigned long long knn_stats[16];
 #endif
 template <int K>
 __device__ __forceinline__ void select_into(BestK<K>& best, unsigned kd, unsigned ki, unsigned kp) {
-  if (KNN_KO & 1) { best.d ^= kd & 1u; return; }
   while (true) {
     const bool cont = kd < best.td || (kd == best.td && ki < best.ti);
     if (__ballot(cont) == 0ull) break;
@@ -273,10 +269,9 @@ __device__ __forceinline__ void scan_range(const QueryCtx& c, const float4* __re
   }
 }
 
-#ifndef KNN_FRONT_CAP
-#define KNN_FRONT_CAP 128   // (256 -> 128 in round 5: 15 KB of LDS per workgroup instead of 23.5 = 8 waves per SIMD instead of 6: 0.80 -> 0.70 ms at config 2; a fuller frontier spills into coarse leaves, exact either way)
-#endif
-constexpr int FRONT_CAP = KNN_FRONT_CAP;   // frontier entries per wave (nodes kept as leaves beyond that)
+// frontier entries per wave (nodes kept as leaves beyond that).  256 -> 128 in round 5: 15 KB of LDS per workgroup instead of 23.5 = 8 waves per SIMD
+// instead of 6: 0.80 -> 0.70 ms at config 2; a fuller frontier spills into coarse leaves, exact either way
+constexpr int FRONT_CAP = 128;
 constexpr int LEAF_CAP = 128;
 constexpr int LEAF_COUNT_MAX = 8;   // nodes with <= this many points are scanned instead of expanded; also the slot width
 
@@ -393,7 +388,6 @@ __global__ __launch_bounds__(256) void knn_wave_kernel(const float* __restrict__
   // <= 8 nodes — the frontier starts there instead of at the root (near a surface: level 1-2 of 6; every skipped level is a 60-instruction batch of this wave).
   // (Wave-uniform arithmetic; the box is widened by the rounding slack and one cell, and every child still passes the exact box test below.)
   int Lstart = GRID_BITS;
-#ifndef NL_KNN_NO_START_LEVEL
   if (U < 3.0e38f) {
     const float r = sqrtf(U * 1.000001f) + c.slack;
     const int lo0 = min(max((int)floorf((c.qx - r - c.org0) * inv_cell) - 1, 0), GRID_N - 1), hi0 = min(max((int)floorf((c.qx + r - c.org0) * inv_cell) + 1, 0), GRID_N - 1);
@@ -411,13 +405,11 @@ __global__ __launch_bounds__(256) void knn_wave_kernel(const float* __restrict__
       nfront = __popcll(mk);
     }
   }
-#endif
   if (Lstart == GRID_BITS && lane == 0) { front[0] = 0u; fxyz[0] = 0u; }
   KNN_CNT(4, Lstart); KNN_CNT(5, prev_full ? 0 : 1); KNN_CNT(6 + Lstart, 1);
 
   // leaves hold <= 16 points each: four leaves per 64-lane batch, one per 16-lane slot (no prefix sums, no index search)
   auto flush_leaves = [&]() {
-    if (KNN_KO & 2) { nleaf = 0; return; }
     constexpr int SL = LEAF_COUNT_MAX;   // lanes per slot
     for (int b = 0; b < nleaf; b += 64 / SL) {
       KNN_CNT(1, 1);
@@ -432,7 +424,7 @@ __global__ __launch_bounds__(256) void knn_wave_kernel(const float* __restrict__
     if (best.full()) U = fminf(U, __uint_as_float(best.td));   // (never full while the query is deferred)
   };
 
-  for (int L = (KNN_KO & 4) ? 0 : Lstart; L > 0; --L) {
+  for (int L = Lstart; L > 0; --L) {
     int nnext = 0;
     const int sh = 3 * (L - 1);
     for (int base = 0; base < nfront; base += 8) {
@@ -569,18 +561,13 @@ int nl_knn_search(const NlKnnGrid* g, const float* xyz, int64_t N, int K, int* i
   if (K < 1 || K > 8) return NL_ERR_UNSUPPORTED;
   // consecutive queries per wave (each takes its bound from the one before): 16 for render-sized batches (-7 % against 4), 4 where the
   // batch would not fill the chip otherwise (descriptor queries: 1024 points)
-#ifndef NL_KNN_BIG_LOG2
-#define NL_KNN_BIG_LOG2 18
-#endif
-#ifndef NL_KNN_SPW_SMALL
-#define NL_KNN_SPW_SMALL 4
-#endif
-  const bool big = N >= (1 << NL_KNN_BIG_LOG2);
-  const int spw = big ? 16 : NL_KNN_SPW_SMALL;
+  constexpr int spw_small = 4;
+  const bool big = N >= (1 << 18);
+  const int spw = big ? 16 : spw_small;
   dim3 grid(nl_xcd_grid(nl_cdiv(N, 4 * spw)));
 #define NL_KNN(KK, SPW) hipLaunchKernelGGL((knn_wave_kernel<KK, SPW>), grid, dim3(256), 0, st, xyz, (int)N, g->params, g->starts, g->sorted, K, idx, d2)
-  if (K == 1) { if (big) NL_KNN(1, 16); else NL_KNN(1, NL_KNN_SPW_SMALL); }
-  else { if (big) NL_KNN(8, 16); else NL_KNN(8, NL_KNN_SPW_SMALL); }
+  if (K == 1) { if (big) NL_KNN(1, 16); else NL_KNN(1, spw_small); }
+  else { if (big) NL_KNN(8, 16); else NL_KNN(8, spw_small); }
 #undef NL_KNN
   NL_LAUNCH_CHECK();
 #ifdef KNN_STATS

@@ -671,10 +671,8 @@ int nl_launch_mv_vis_mfma(const NlViews& vw, const float* visf_hwc, const void* 
                           float* dd_out, bool x3, hipStream_t st) {
   if (N <= 0) return NL_OK;
   const int tpv = (int)nl_cdiv(N, 32), total = tpv * vw.V;
-#ifndef MV_VIS_MAX_BLOCKS
-#define MV_VIS_MAX_BLOCKS 2048
-#endif
-  const int blocks = (int)(nl_cdiv(total, 4) < MV_VIS_MAX_BLOCKS ? nl_cdiv(total, 4) : MV_VIS_MAX_BLOCKS);
+  constexpr int64_t max_blocks = 2048;
+  const int blocks = (int)(nl_cdiv(total, 4) < max_blocks ? nl_cdiv(total, 4) : max_blocks);
   if (x3) hipLaunchKernelGGL(mv_vis_mfma_kernel<true>, dim3(blocks), dim3(256), 0, st, vw, visf_hwc, (const uint4*)dpack, xyz, (int)N, tpv, total, vis_out, dd_out);
   else hipLaunchKernelGGL(mv_vis_mfma_kernel<false>, dim3(blocks), dim3(256), 0, st, vw, visf_hwc, (const uint4*)dpack, xyz, (int)N, tpv, total, vis_out, dd_out);
   NL_LAUNCH_CHECK();
@@ -687,12 +685,7 @@ int nl_launch_mv_stats(const NlViews& vw, const float* viewsdev, const float* im
   if (N <= 0) return NL_OK;
   if (C > 192) return NL_ERR_UNSUPPORTED;
   const bool v4 = (C % 4 == 0) && ((((size_t)feat) & 15) == 0);   // 16-B channel groups
-#ifdef NERFLOC_DEBUG_SWITCHES
-  static const bool force_wave = getenv("NERFLOC_MVSTATS_WAVE") != nullptr;   // A/B switch (debug builds only): one sample per wave everywhere
-#else
-  const bool force_wave = false;
-#endif
-  if (v4 && !rgb_feat && !vis_ang && !force_wave) {   // everything but the stage API: eight samples per wave
+  if (v4 && !rgb_feat && !vis_ang) {   // everything but the stage API: eight samples per wave
     dim3 grid8(nl_xcd_grid(nl_cdiv(N, 32)));
 #define NL_MS8(VT) hipLaunchKernelGGL((mv_stats8_kernel<VT>), grid8, dim3(256), sizeof(float) * 4 * 8 * VT * MS8_SLOT, st, vw, viewsdev, images, feat, C, \
                                       xyz, (int)N, vis_in, dd_in, g393, ldg, valid_s, pfeat, blw, bl1, rgbv)

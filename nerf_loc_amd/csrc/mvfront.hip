@@ -16,7 +16,7 @@
 //     vector unit (lane = output unit) and enter the MFMA as the accumulator's initial value;
 //   * the per-(sample, view) scalar work (projection, tap weights, colour taps, weight normalisation) runs with lane = (sample, view), 64 pairs per wave.
 // Output: the 64-wide hidden rows t64 (N x 64), the valid flags and the tapped colours + visibility (N x V x 4) for the blend kernel — the statistics row
-// and the blend layer's per-(sample, view) rows (bl1: 0.7 GB written and read back per batch) no longer exist on this path: blend_taps_kernel (heads.hip)
+// and the blend layer's per-(sample, view) rows (bl1: 0.7 GB written and read back per batch) no longer exist on this path: blend_taps_mfma_kernel (heads.hip)
 // recomputes its taps.
 #include "mvdec.h"
 
@@ -28,28 +28,12 @@ typedef float mf_f32x4 __attribute__((ext_vector_type(4)));
 typedef float mf_f32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned mf_u32x4 __attribute__((ext_vector_type(4)));
 
-#ifndef MF_KO
-#define MF_KO 0   // knock-out bits for timing experiments (results are garbage): 1 no texel loads in phase B, 2 no phase B, 4 no colour taps in phase A, 8 no MFMA phase, 16 no staging writes, 64 every texel fetch from texel 0 (all cache hits), 128 phase A's inputs computed instead of loaded (what fetching them a round ahead could return at most)
-#endif
-#ifndef MF_PK
-#define MF_PK 1   // phase B's channel pairs on the packed-fp32 instructions (round 6); 0 = one scalar FMA per channel
-#endif
-#ifndef MF_AHEAD
-#define MF_AHEAD 0   // 1 = phase A's inputs fetched across the previous round's matrix phase: measured 870 -> 920 us (the five registers spill loop invariants to scratch, whose reloads drain vmcnt: round 6); 0 = loaded where they are used
-#endif
-#ifndef MF_CPL
-#define MF_CPL 3
-#endif
-constexpr int MF_CPL_ = MF_CPL;    // channels per lane in phase B: 3 = all 64 lanes, 12-byte loads; 4 = lanes 0..47, 16-byte loads
-constexpr int MF_C = 192;          // feature channels (3 per lane)
+constexpr int MF_C = 192;          // feature channels (3 per lane in phase B: all 64 lanes, 12-byte loads)
 constexpr int MF_KS = 12;          // k-steps of 32: [mean 192 | variance 192]
 constexpr int MF_LD = 400;         // staging row stride in halves (384 + pad): 200 dwords = 8 (mod 64) — the MFMA phase's ds_read_b128 (lane = (row, k-quarter), 16-lane
                                    // groups {0-3, 12-15, 20-27} ...) then start on 16 distinct 4-bank slots; 392 (= 4 mod 64) put rows c and c - 1 of neighbouring quarters on one slot:
                                    // a 2-way conflict in every group (SQ_LDS_BANK_CONFLICT 2.2e8 per launch in round 4; no measurable time: the phase hides behind the tap loads)
-#ifndef MF_NW
-#define MF_NW 8
-#endif
-constexpr int MF_NWAVES = MF_NW;   // waves per workgroup: 8 (two per SIMD) or 4 (one per SIMD: leaves half of the register file to co-resident kernels — the exact KNN on the side stream)
+constexpr int MF_NWAVES = 8;       // waves per workgroup (two per SIMD)
 constexpr int MF_NS = 4 * MF_NWAVES;   // samples per round (4 per wave)
 constexpr int MF_SLOT = 8;         // dwords per (sample, view): packed cell, 4 tap weights, view weight, 2 unused
 constexpr int MF_LDS_BYTES = 2 * MF_NS * MF_LD * 2 + MF_NS * 64 * 4 + MF_NWAVES * 4 * 16 * MF_SLOT * 4 + MF_NS * 4;
@@ -105,7 +89,7 @@ __global__ __launch_bounds__(64 * MF_NWAVES, 1) void mv_front_kernel(const NlVie
   const size_t fmap = (size_t)vw.h * vw.w;
 
   // ---- resident: this wave's slice of out_fc.0 (n-tile nt) as A fragments, the small columns' row of output unit `lane`
-  const int nt = wave & 3, half = wave >> 2;   // (4 waves: every wave one n-tile, one half of 16 samples)
+  const int nt = wave & 3, half = wave >> 2;
   mf_u32x4 wa[MF_KS][2];
 #pragma unroll
   for (int ks = 0; ks < MF_KS; ++ks) {
@@ -120,8 +104,7 @@ __global__ __launch_bounds__(64 * MF_NWAVES, 1) void mv_front_kernel(const NlVie
   const int r_begin = lb * rounds_per_block, r_end = min(nrounds, r_begin + rounds_per_block);
   float* myslots = slots + (size_t)wave * 4 * 16 * MF_SLOT;
 
-  // the round's per-(sample, view) inputs (position, visibility, depth difference) are fetched while the PREVIOUS round's out_fc.0 phase runs (round 6): phase A otherwise
-  // starts with a global-memory latency at two waves per SIMD, and in that phase the accumulators and texel rows of phase B are dead, so five registers cost nothing
+  // the round's per-(sample, view) inputs: position, visibility, depth difference
   auto load_in = [&](int round, float& X, float& Y, float& Z, float& vis, float& dd) __attribute__((always_inline)) {
     const int s = lane >> 4, v = lane & 15;
     const int n = round * MF_NS + wave * 4 + s;
@@ -131,8 +114,6 @@ __global__ __launch_bounds__(64 * MF_NWAVES, 1) void mv_front_kernel(const NlVie
     const unsigned vo = (unsigned)vl * (unsigned)N + (unsigned)nn;   // V N < 2^31 (nl_mv_front_supported): a 32-bit offset from the scalar base, no hoisted 64-bit lane pointer
     vis = vis_in[vo]; dd = dd_in[vo];
   };
-  float nX = 0.f, nY = 0.f, nZ = 0.f, nvis = 0.f, ndd = 0.f;
-  if (MF_AHEAD && r_begin < r_end) load_in(r_begin, nX, nY, nZ, nvis, ndd);
   for (int round = r_begin; round < r_end; ++round) {
     const int n0 = round * MF_NS + wave * 4;
     // ---------------------------------------------------------------- phase A: lane = (sample s, view v)
@@ -141,13 +122,10 @@ __global__ __launch_bounds__(64 * MF_NWAVES, 1) void mv_front_kernel(const NlVie
       const int s = lane >> 4, v = lane & 15;
       const int n = n0 + s;
       const bool live = n < N;
-      const int nn = live ? n : N - 1;
       const bool vact = v < V;
       const int vl = vact ? v : 0;
-      float X, Y, Z, vis_l = 0.f, dd_l = 0.f;
-      if (MF_KO & 128) { X = 0.25f + 1e-6f * (float)nn; Y = 0.5f - 1e-6f * (float)nn; Z = 1.f + 2e-6f * (float)nn; }   // (knock-out 128: phase A's position / visibility / depth-difference inputs without memory)
-      else if (MF_AHEAD) { X = nX; Y = nY; Z = nZ; vis_l = nvis; dd_l = ndd; }
-      else load_in(round, X, Y, Z, vis_l, dd_l);
+      float X, Y, Z, vis_l, dd_l;
+      load_in(round, X, Y, Z, vis_l, dd_l);
       const float4 p0 = *(const float4*)(viewsdev + 12 * vl), p1 = *(const float4*)(viewsdev + 12 * vl + 4), p2 = *(const float4*)(viewsdev + 12 * vl + 8);
       const float cx = fmaf(p0.z, Z, fmaf(p0.y, Y, p0.x * X)) + p0.w;
       const float cy = fmaf(p1.z, Z, fmaf(p1.y, Y, p1.x * X)) + p1.w;
@@ -174,14 +152,13 @@ __global__ __launch_bounds__(64 * MF_NWAVES, 1) void mv_front_kernel(const NlVie
         const float i0 = (ti.mn && ti.mw) ? ti.nw : 0.f, i1 = (ti.mn && ti.me) ? ti.ne : 0.f, i2 = (ti.ms && ti.mw) ? ti.sw : 0.f, i3 = (ti.ms && ti.me) ? ti.se : 0.f;
         const float* ib = images + (size_t)vl * 3 * HW;
 #pragma unroll
-        for (int c = 0; c < ((MF_KO & 4) ? 0 : 3); ++c) {
+        for (int c = 0; c < 3; ++c) {
           const float* pl = ib + (size_t)c * HW;
           rgb[c] = fmaf(pl[oi[3]], i3, fmaf(pl[oi[2]], i2, fmaf(pl[oi[1]], i1, pl[oi[0]] * i0)));
         }
       }
-      const unsigned vo = (unsigned)vl * (unsigned)N + (unsigned)nn;   // V N < 2^31 (nl_mv_front_supported): a 32-bit offset from the scalar base, no hoisted 64-bit lane pointer
-      const float vis = (MF_KO & 128) ? (vact ? 0.125f + 1e-7f * (float)vo : 0.f) : (vact ? vis_l : 0.f);
-      const float dd = (MF_KO & 128) ? 0.01f : (vact ? dd_l : 0.f);
+      const float vis = vact ? vis_l : 0.f;
+      const float dd = vact ? dd_l : 0.f;
       const float vsum = mf_sum16(vis);
       const float wgt = vis / (vsum + 1e-8f);
       vmask = 0;
@@ -223,7 +200,7 @@ __global__ __launch_bounds__(64 * MF_NWAVES, 1) void mv_front_kernel(const NlVie
     __builtin_amdgcn_wave_barrier();   // the slots are wave-private: LDS ordering within the wave is all phase B needs
 
     // ---------------------------------------------------------------- phase B: lane = channels 3 lane .. 3 lane + 2, view by view over the four samples
-    constexpr int CPL = MF_CPL_;
+    constexpr int CPL = 3;
     float a1[4][CPL], a2[4][CPL];
 #pragma unroll
     for (int s = 0; s < 4; ++s)
@@ -235,7 +212,7 @@ __global__ __launch_bounds__(64 * MF_NWAVES, 1) void mv_front_kernel(const NlVie
     // (eight requests to L2 per row, all waiting for the slowest).  Every wave starts its view loop at a different view — a function of the wave's position in
     // its RAY, so that a sample's summation order does not depend on how the batch was chunked — and finds most rows already fetched by a neighbour.
     const int rot = (int)(((unsigned)n0 % (unsigned)(vw.qS > 0 ? vw.qS : 1)) >> 2) % V;
-    for (int vi = 0; vi < ((MF_KO & 2) ? 0 : V); ++vi) {
+    for (int vi = 0; vi < V; ++vi) {
       int v = vi + rot;
       v = v >= V ? v - V : v;
       if (!((vmask >> v) & 1u)) continue;   // weight exactly 0 for all four samples: nothing of this view reaches a statistic (wave-uniform)
@@ -252,47 +229,35 @@ __global__ __launch_bounds__(64 * MF_NWAVES, 1) void mv_front_kernel(const NlVie
         const float4 c4 = *(const float4*)sl;      // (every lane reads the same address: an LDS broadcast)
         const float2 c2 = *(const float2*)(sl + 4);
         const unsigned cell = (unsigned)__builtin_amdgcn_readfirstlane((int)__float_as_uint(c4.x));
-        if (cell != cur && !(MF_KO & 1)) {   // wave-uniform: the four texel rows of the new cell
+        if (cell != cur) {   // wave-uniform: the four texel rows of the new cell
           cur = cell;
           int o[4];
-          unpack_taps((MF_KO & 64) ? (cell & 0xc0000000u) : cell, vw.w, o);   // (knock-out 64: every fetch from texel 0 of the view — all hits)
+          unpack_taps(cell, vw.w, o);
 #pragma unroll
           for (int k = 0; k < 4; ++k) {
             const float* p = fb + ((unsigned)o[k] * (unsigned)MF_C + lch);
-            if constexpr (CPL == 4) { const float4 t4 = *(const float4*)p; T[k][0] = t4.x; T[k][1] = t4.y; T[k][2] = t4.z; T[k][3] = t4.w; }
-            else { T[k][0] = p[0]; T[k][1] = p[1]; T[k][2] = p[2]; }
+            T[k][0] = p[0]; T[k][1] = p[1]; T[k][2] = p[2];
           }
         }
         const float w0 = c4.y, w1 = c4.z, w2 = c4.w, w3 = c2.x, wg = c2.y;
-        if constexpr (CPL == 3 && MF_PK) {
-          // channels 0, 1 as one packed operation each (v_pk_mul_f32 / v_pk_fma_f32 / v_pk_add_f32: the same roundings in the same order, two thirds of the instructions)
-          const mf_f32x2 t0 = {T[0][0], T[0][1]}, t1 = {T[1][0], T[1][1]}, t2 = {T[2][0], T[2][1]}, t3 = {T[3][0], T[3][1]};
-          const mf_f32x2 W0 = {w0, w0}, W1 = {w1, w1}, W2 = {w2, w2}, W3 = {w3, w3}, WG = {wg, wg};
-          const mf_f32x2 x = __builtin_elementwise_fma(t3, W3, __builtin_elementwise_fma(t2, W2, __builtin_elementwise_fma(t1, W1, t0 * W0)));
-          const mf_f32x2 t = WG * x;
-          mf_f32x2 A1 = {a1[s][0], a1[s][1]}, A2 = {a2[s][0], a2[s][1]};
-          A1 += t;
-          A2 = __builtin_elementwise_fma(t, x, A2);
-          a1[s][0] = A1[0]; a1[s][1] = A1[1]; a2[s][0] = A2[0]; a2[s][1] = A2[1];
-          const float xs = fmaf(T[3][2], w3, fmaf(T[2][2], w2, fmaf(T[1][2], w1, T[0][2] * w0)));
-          const float ts = wg * xs;
-          a1[s][2] += ts;
-          a2[s][2] = fmaf(ts, xs, a2[s][2]);
-        } else {
-#pragma unroll
-        for (int j = 0; j < CPL; ++j) {
-          const float x = fmaf(T[3][j], w3, fmaf(T[2][j], w2, fmaf(T[1][j], w1, T[0][j] * w0)));
-          const float t = wg * x;
-          a1[s][j] += t;
-          a2[s][j] = fmaf(t, x, a2[s][j]);
-        }
-        }
+        // channels 0, 1 as one packed operation each (v_pk_mul_f32 / v_pk_fma_f32 / v_pk_add_f32: the same roundings in the same order, two thirds of the instructions)
+        const mf_f32x2 t0 = {T[0][0], T[0][1]}, t1 = {T[1][0], T[1][1]}, t2 = {T[2][0], T[2][1]}, t3 = {T[3][0], T[3][1]};
+        const mf_f32x2 W0 = {w0, w0}, W1 = {w1, w1}, W2 = {w2, w2}, W3 = {w3, w3}, WG = {wg, wg};
+        const mf_f32x2 x = __builtin_elementwise_fma(t3, W3, __builtin_elementwise_fma(t2, W2, __builtin_elementwise_fma(t1, W1, t0 * W0)));
+        const mf_f32x2 t = WG * x;
+        mf_f32x2 A1 = {a1[s][0], a1[s][1]}, A2 = {a2[s][0], a2[s][1]};
+        A1 += t;
+        A2 = __builtin_elementwise_fma(t, x, A2);
+        a1[s][0] = A1[0]; a1[s][1] = A1[1]; a2[s][0] = A2[0]; a2[s][1] = A2[1];
+        const float xs = fmaf(T[3][2], w3, fmaf(T[2][2], w2, fmaf(T[1][2], w1, T[0][2] * w0)));
+        const float ts = wg * xs;
+        a1[s][2] += ts;
+        a2[s][2] = fmaf(ts, xs, a2[s][2]);
       }
     }
-    if (MF_AHEAD && round + 1 < r_end) load_in(round + 1, nX, nY, nZ, nvis, ndd);   // (in flight across the staging writes, both barriers and the matrix phase)
     // every wave is through with the previous round's staging tile (its MFMA phase ended at a barrier) — this round's rows may be written
 #pragma unroll
-    for (int s = 0; s < ((MF_KO & 16) ? 0 : 4); ++s) {
+    for (int s = 0; s < 4; ++s) {
       const float Ws = wsumS[wave * 4 + s];
       const int row = wave * 4 + s;
 #pragma unroll
@@ -320,7 +285,7 @@ __global__ __launch_bounds__(64 * MF_NWAVES, 1) void mv_front_kernel(const NlVie
       const int srow = 16 * half + col;
       mf_f32x4 acc = *(const mf_f32x4*)(partial + srow * 64 + 16 * nt + 4 * kq);
 #pragma unroll
-      for (int ks = 0; ks < ((MF_KO & 8) ? 0 : MF_KS); ++ks) {
+      for (int ks = 0; ks < MF_KS; ++ks) {
         const mf_u32x4 bh = *(const mf_u32x4*)(st_hi + srow * MF_LD + 32 * ks + 8 * kq);
         const mf_u32x4 bl = *(const mf_u32x4*)(st_lo + srow * MF_LD + 32 * ks + 8 * kq);
         acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(mf_bf16x8, wa[ks][1]), __builtin_bit_cast(mf_bf16x8, bh), acc, 0, 0, 0);

@@ -41,22 +41,6 @@ typedef _Float16 f16x32 __attribute__((ext_vector_type(32)));
 
 namespace {
 
-#ifndef PF2_KO
-#define PF2_KO 0   // knock-out bits for timing experiments (results are garbage): 1 no in-loop prologue, 2 no layer epilogues, 4 no LDS-DMA in the loop, 8 no attention, 256 no barriers in the tile loop (what the waves' skew costs), 512 the barrier of every odd region only (what a ring with one slot of slack could return at most), 16 the second cross-term matrix instruction of every slab skipped (its reads and fills stay): the matrix-pipe time fp6 cross terms would take
-#endif
-constexpr int KO = PF2_KO;
-#ifndef PF2_MX_FP6
-#define PF2_MX_FP6 1   // the cross terms of NL_PREC_F16MX: 1 = MX-FP6 (e2m3, 8 passes per K = 64: 1.5 matrix-instruction equivalents per product), 0 = MX-FP8 (e4m3, 16 passes: 2.0)
-#endif
-#ifndef PF2_L1_MX
-#define PF2_L1_MX 1   // MX-FP6: layer 1 (K = 96: positional encoding + ray_diff_fc outputs) also as fp16 hi.hi + two fp6 cross terms (6 + 4 matrix instructions of 8 passes instead of 18)
-#endif
-constexpr bool L1MX = PF2_L1_MX;
-constexpr int MXK = PF2_MX_FP6 ? 2 : 1;   // the one MX instance this library carries (pack and launch agree by construction)
-#ifndef PF2_PE_F32
-#define PF2_PE_F32 1   // the positional encoding's sin / cos recurrence of the f16mx instance in fp32 (round 6): 4.5e-6 on the encoding against the 3e-5 of its fp6
-                       // cross-term image; 0 = fp64 like the other precisions (whose operands carry 1e-7)
-#endif
 #ifdef PF2_TRACE
 __device__ unsigned long long pf2_trace[256];   // debug: cycle counter at every region start of one tile (block 0, wave 0)
 #endif
@@ -92,10 +76,10 @@ struct Geo {
   static constexpr int RES_RD = NBUF * SLOT;                 // resident: ray_diff_fc A fragments [layer][part][64] uint4
   static constexpr int RES_BIAS = RES_RD + 2 * PARTS * 64;   // resident: biases in accumulator order, floats [rd1 32 | rd2 32 | L2 W | L3 W]
   static constexpr int RES_ATT = RES_BIAS + (64 + 2 * W) / 4;   // attention weights [wave][head][32 rows] floats (wave-private)
-  static constexpr int RES_SC = RES_ATT + 4 * 4 * 32 / 4;   // MX mode: E8M0 scale bytes of the chunks' fp8 weight images, ints [NC][2] = {w_hi8, w_lo8}
-  static constexpr int RES_BND = RES_SC + (2 * NC + 3) / 4;   // MX mode: 8 floats — the bounds the activation block scales are derived from (pf2_mx_bounds_kernel)
-  static constexpr int RES_SC6 = RES_BND + 2;   // MX-FP6: the wide chunks' weight-scale dwords [chunk 2 NRT + 8][lane 64] x {w_hi6, w_lo6} (pack_point_mx6_kernel)
-  static constexpr int LDS_U4 = RES_SC6 + (MX6 ? (L1MX ? NC : 2 * NRT + 8) * 32 : 0);
+  // MX-FP6: the chunks' weight-scale dwords [chunk NC][lane 64] x {w_hi6, w_lo6} (pack_point_mx6_kernel), at their offset in the packed stream's resident block
+  // (behind (2 NC + 3) / 4 + 2 unused uint4)
+  static constexpr int RES_SC6 = RES_ATT + 4 * 4 * 32 / 4 + (2 * NC + 3) / 4 + 2;
+  static constexpr int LDS_U4 = RES_SC6 + (MX6 ? NC * 32 : 0);
   // micro-steps of a finished chunk's epilogue: layers: 8 pairs x (LeakyReLU + hi | lo); k head: 9; v head: 4 x (4 sums + store)
   // (KEEP: + 4 row stores of a k head / 4 x 4 dword stores of a v head: the rows nl_attn_backward reads)
   static constexpr int epi_steps(int c) { return layer(c) < 3 ? 8 * (X3 ? 2 : 1) + (MX6 && (rt(c) & 1) ? 2 : 0) : (rt(c) < 4 ? 10 : 10) + (KEEP ? 4 : 0); }
@@ -147,38 +131,19 @@ __device__ __forceinline__ unsigned lo2(float v0, float v1, unsigned hi) {
       : "=&v"(lo), "=&v"(t0), "=&v"(t1) : "v"(v0), "v"(v1), "v"(hi));
   return lo;
 }
-// ---- "fp16 hi.hi + two MX-FP8 cross terms" (MX mode): hi = f16(v) (v_cvt_pk_f16_f32, saturating under MODE.FP16_OVFL),
-// lo = v - hi exactly (v_fma_mix_f32 reads the f16 half directly), fp8 images hi8 = e4m3(hi), lo8 = e4m3(lo * 2^11) (the matrix instruction's
-// block scale 2^-11 undoes the factor); two bytes land in the low (HALF = 0) or high (HALF = 1) half of their dword.
+// LeakyReLU of a pair + its f16 hi word (v_cvt_pk_f16_f32, saturating under MODE.FP16_OVFL)
 __device__ __forceinline__ unsigned lrelu_hi2_f16(float& v0, float& v1) {
   unsigned hi; float t0, t1;
   asm("v_mul_f32 %3, 0x3c23d70a, %1\n\tv_mul_f32 %4, 0x3c23d70a, %2\n\tv_max_f32 %1, %1, %3\n\tv_max_f32 %2, %2, %4\n\tv_cvt_pk_f16_f32 %0, %1, %2"
       : "=&v"(hi), "+v"(v0), "+v"(v1), "=&v"(t0), "=&v"(t1));
   return hi;
 }
-// sc_hi / sc_lo: the lane's (= the row's) power-of-two block scales of the two images (both conversions DIVIDE by their scale operand)
 // ... + the running row maximum of |value| in the same statement (an asm boundary costs a compiler-inserted s_nop: 120 per tile as a separate v_max3)
 __device__ __forceinline__ unsigned lrelu_hi2_f16_amax(float& v0, float& v1, float& m) {
   unsigned hi; float t0, t1;
   asm("v_mul_f32 %3, 0x3c23d70a, %1\n\tv_mul_f32 %4, 0x3c23d70a, %2\n\tv_max_f32 %1, %1, %3\n\tv_max_f32 %2, %2, %4\n\tv_max3_f32 %5, |%1|, |%2|, %5\n\tv_cvt_pk_f16_f32 %0, %1, %2"
       : "=&v"(hi), "+v"(v0), "+v"(v1), "=&v"(t0), "=&v"(t1), "+v"(m));
   return hi;
-}
-template <int HALF>
-__device__ __forceinline__ void mx_bytes2(float v0, float v1, unsigned hi, unsigned& h8, unsigned& l8, float sc_hi, float sc_lo) {
-  float t0, t1;
-  if (HALF == 0)
-    asm("v_fma_mix_f32 %2, %6, -1.0, %4 op_sel_hi:[1,0,0]\n\tv_fma_mix_f32 %3, %6, -1.0, %5 op_sel:[1,0,0] op_sel_hi:[1,0,0]\n\t"
-        "v_cvt_scalef32_pk_fp8_f16 %0, %6, %8\n\tv_cvt_scalef32_pk_fp8_f32 %1, %2, %3, %7"
-        : "+v"(h8), "+v"(l8), "=&v"(t0), "=&v"(t1) : "v"(v0), "v"(v1), "v"(hi), "v"(sc_lo), "v"(sc_hi));
-  else
-    asm("v_fma_mix_f32 %2, %6, -1.0, %4 op_sel_hi:[1,0,0]\n\tv_fma_mix_f32 %3, %6, -1.0, %5 op_sel:[1,0,0] op_sel_hi:[1,0,0]\n\t"
-        "v_cvt_scalef32_pk_fp8_f16 %0, %6, %8 op_sel:[0,0,1]\n\tv_cvt_scalef32_pk_fp8_f32 %1, %2, %3, %7 op_sel:[0,0,0,1]"
-        : "+v"(h8), "+v"(l8), "=&v"(t0), "=&v"(t1) : "v"(v0), "v"(v1), "v"(hi), "v"(sc_lo), "v"(sc_hi));
-}
-// running row maximum of |activation| (MX mode: what the next layer's block scale is bounded from)
-__device__ __forceinline__ void amax2(float& m, float v0, float v1) {
-  asm("v_max3_f32 %0, |%1|, |%2|, %0" : "+v"(m) : "v"(v0), "v"(v1));
 }
 
 // hi/lo split of a pair: hi = bf16(v), lo = bf16(v - float(hi))
@@ -246,14 +211,12 @@ __device__ __forceinline__ void sincos_d(double x, double& s, double& c) {
 }
 
 struct Pf2Scalars { int dir_stride, dir_div; unsigned dir_magic; int dir_shift; unsigned dir_one; int N, M; float inv_span; int ntiles; unsigned t_bytes;
-                    const float* tmax;      // MX mode: max |T| over the frame's table (one float, written by nl_table_absmax), or null (= 0)
+                    const float* tmax;      // (read by no instance)
                     unsigned* logit_amax;
                     unsigned long long* clk; };   // optional: [shader cycles, 100-MHz reference ticks] workgroup 0 spent in this launch (bench.py: the clock under load)   // optional: running maximum of |attention logit| (q.k / sqrt d_k) as float bits, atomicMax'ed once per wave (nl_frame_diagnostics)
 
-// MX (with X3) = 1, round 4: layer 1 stays three-term split-bf16 (K = 96, issue-bound anyway); layers 2, 3 and the k / v projections multiply as
-// fp16 hi.hi + fp8(lo).fp8(hi) + fp8(hi).fp8(lo): per K = 64 slab 4 x v_mfma_f32_32x32x16_f16 + 2 x v_mfma_scale_f32_32x32x64_f8f6f4 instead of 12 bf16 MFMAs.
-// MX = 2, round 5 (the instance the library carries, PF2_MX_FP6): the same two cross terms on fp6 (e2m3) operands — 8 passes instead of 16 — with a power-of-two scale per
-// 32-value block taken from the values themselves; every layer, layer 1 included (PF2_L1_MX).  DESIGN.md 2.4.
+// MX (with X3) = 2, round 5: every layer, layer 1 included, multiplies as fp16 hi.hi + fp6(lo).fp6(hi) + fp6(hi).fp6(lo) (e2m3 operands, 8 passes per K = 64),
+// with a power-of-two scale per 32-value block taken from the values themselves.  (MX = 1 was the round-4 MX-FP8 instance, since removed.)  DESIGN.md 2.4.
 // F16 (with X3, without MX): every layer in three-term split-FP16 (2^-22 products: what the gradient path's forward needs so that its LeakyReLU sign decisions are the
 // fp32 function's).  KEEP: the kernel also leaves what the frozen-weight way back reads — the k / v rows (N x 8, 256) and the SIGN of the three
 // layers' outputs as bits in the streaming GEMM's ep_maskin layout ([32-row tile][lane][4 dwords]) — so that the staged forward of the branch (an encode kernel,
@@ -264,13 +227,14 @@ __global__ __launch_bounds__(256, 1) void point_fused2_kernel(
     const float* __restrict__ p_xyz, const float* __restrict__ p_dir, const int* __restrict__ p_idx, const float* __restrict__ p_Q,
     float* __restrict__ p_O, const float* __restrict__ p_ptt, const float* __restrict__ p_sp_xyz,
     const float* __restrict__ p_sp_dir, const uint4* __restrict__ p_wstream, const Pf2Scalars sc, const Pf2Keep keep) {
+  static_assert(MX == 0 || MX == 2, "MX = 2: the MX-FP6 instance");
   static_assert(!MX || X3, "the MX mode extends the three-term mode");
   static_assert(!F16 || (X3 && !MX), "split-FP16 is a three-term mode");
   static_assert(!KEEP || F16, "the kept masks must come from the split-FP16 forward");
-  constexpr bool MX6 = MX == 2, MX8 = MX == 1;   // cross terms on MX-FP6 (e2m3) / MX-FP8 (e4m3)
+  constexpr bool MX6 = MX == 2;   // cross terms on MX-FP6 (e2m3)
   using GG = Geo<NRT, X3, KEEP, MX6>;
   constexpr int W = GG::W, PARTS = GG::PARTS, MPK = GG::MPK, NC = GG::NC, SLOT = GG::SLOT;
-  if (MX || F16) __builtin_amdgcn_s_setreg(1473, 1);   // hwreg(HW_REG_MODE, 23, 1) = FP16_OVFL: f16 / fp8 conversions saturate instead of producing inf / NaN
+  if (MX || F16) __builtin_amdgcn_s_setreg(1473, 1);   // hwreg(HW_REG_MODE, 23, 1) = FP16_OVFL: f16 conversions saturate instead of producing inf / NaN
   // ONE __shared__ object, read through ONE native vector type with compile-time slot indices: hipcc then keeps the alias
   // information that lets SIInsertWaitcnts leave LDS reads alone while LDS-DMA writes are in flight
   __shared__ uint4 lds_all[GG::LDS_U4];
@@ -298,8 +262,7 @@ __global__ __launch_bounds__(256, 1) void point_fused2_kernel(
     const uint4* src = p_wstream + (size_t)GG::STREAM_KB * 64;
     for (int i = tid; i < 2 * PARTS * 64; i += 256) lds_all[GG::RES_RD + i] = src[(i / (PARTS * 64)) * 128 + i % (PARTS * 64)];
     for (int i = tid; i < (64 + 2 * W) / 4; i += 256) lds_all[GG::RES_BIAS + i] = src[256 + i];
-    if (MX8) for (int i = tid; i < (2 * NC + 3) / 4 + 2; i += 256) lds_all[GG::RES_SC + i] = src[256 + (64 + 2 * W) / 4 + i];   // + the bounds block
-    if (MX6) for (int i = tid; i < (L1MX ? NC : 2 * NRT + 8) * 32; i += 256) lds_all[GG::RES_SC6 + i] = src[256 + (64 + 2 * W) / 4 + (2 * NC + 3) / 4 + 2 + i];
+    if (MX6) for (int i = tid; i < NC * 32; i += 256) lds_all[GG::RES_SC6 + i] = src[256 + (64 + 2 * W) / 4 + (2 * NC + 3) / 4 + 2 + i];
   }
   __syncthreads();
 
@@ -354,11 +317,7 @@ __global__ __launch_bounds__(256, 1) void point_fused2_kernel(
   // storage every such insert keeps the whole old vector alive in the compiler's eyes — both ping-pong halves then stay live
   // around the tile loop (512 registers + 290 spills instead of ~400)
   unsigned Xh[2][2 * NRT][4], Xl[2][2 * NRT][4];
-  // MX mode: Xh holds f16 pairs; the fp8 images of a slab (4 k-steps) as the matrix instruction wants them: [buffer][slab][0 = hi8, 1 = lo8][8 dwords], byte
-  // u = 8 s + t of a lane <-> element t of k-step 4 q + s (the weight images use the same map: any bijection works as long as both operands share it)
-  unsigned X8[2][NRT / 2][2][8];
-  u32x4 w8[2][4];   // fp8 A operands of a slab, double-buffered by slab parity: [0..1] = w_hi8 (32 bytes per lane), [2..3] = w_lo8
-  // ---- MX-FP6 (MX == 2, round 5): the two cross terms on e2m3 elements, 8 passes per K = 64 instead of 16 (profiles/ubench_mx6_rowtile.txt: conversions, layouts, timing).
+  // ---- MX-FP6 (MX == 2, round 5): the two cross terms on e2m3 elements, 8 passes per K = 64 instead of the 16 of fp8 (profiles/ubench_mx6_rowtile.txt: conversions, layouts, timing).
   // A lane's 32 values of a slab are ONE MX block with its own power-of-two scale — 2^(floor(log2 max) - 2), from the values themselves: the largest lands in [4, 8) of e2m3's
   // 7.5 — for the activations (per row, slab and image; the residual image takes the hi image's scale x 2^-11) and for the weights (per output row and half-slab, from the
   // packing kernel: byte q of the chunk's two scale dwords).  The f16 B fragments of a slab live in ONE 16-register vector (Xh16): v_cvt_scalef32_pk32_fp6_f16 packs the hi
@@ -372,7 +331,7 @@ __global__ __launch_bounds__(256, 1) void point_fused2_kernel(
   unsigned hp6[2][8];                   // f16 pairs of the two row tiles a slab is made of (until the slab is complete)
   float lo6t[2][16];                    // their residuals
   float scf6 = 1.f;
-  // layer 1 in the same arithmetic (L1MX): its B operands of the tile — slab 0 = k-steps 0-3 (positional encoding + raw offsets), slab 1 = k-steps 4, 5 (ray_diff_fc outputs) + two
+  // layer 1 in the same arithmetic: its B operands of the tile — slab 0 = k-steps 0-3 (positional encoding + raw offsets), slab 1 = k-steps 4, 5 (ray_diff_fc outputs) + two
   // empty k-steps — as f16 fragments (P16), fp6 images (P6[slab][0 = hi, 1 = residual]) and the two scale-byte registers; pp* / plo*: pairs and residuals until a slab is complete
   u32x16 P16[2];
   unsigned P6[2][2][6];
@@ -380,38 +339,9 @@ __global__ __launch_bounds__(256, 1) void point_fused2_kernel(
   unsigned pp0[16], pp1[8];
   float plo0[32], plo1[16];
   float pam0 = 0.f, pam1 = 0.f;
-  const int* ssc = reinterpret_cast<const int*>(lds_all + GG::RES_SC);
-  // MX mode, round 5: the activations' fp8 images carry a block scale PER ROW AND LAYER instead of the constants 1 / 2^-11 (whose window was |a| = 2^-6 ... 448:
-  // beyond it the cross terms saturated and the product fell back to single-fp16 accuracy — tools/scale_sweep.py found it with the feature maps x 8).  The scale of
-  // layer L's output rows is fixed BEFORE the layer runs, from a bound that cannot be exceeded: |out| <= max_c ||w_c||_1 . max|in| + max|b| with max|in| the row's
-  // running maximum over the previous layer's outputs (one v_max3 per finished pair), layer 1 from max|T| over the frame's table + the L1 norms of its
-  // positional-encoding / ray-difference columns.  The bound is ~50x loose, which e4m3's 15 binades absorb (values land at <= 256 of 448; what falls below
-  // the normal range is < 0.4 % of the row's largest value).  xs_hi / xs_lo: the floats the conversions divide by, xs_e8h / xs_e8l: the E8M0 bytes the matrix
-  // instruction reads for the lane's row (both halves of a row hold the same values), indexed by the ping-pong buffer the rows live in.
-  float xs_hi[2] = {1.f, 1.f}, xs_lo[2] = {0.00048828125f, 0.00048828125f};
-  int xs_e8h[2] = {127, 127}, xs_e8l[2] = {116, 116};
-  float amax = 0.f, cur_b1 = 0.f, pn_b1 = 0.f;
+  float amax = 0.f;
   float lmax = 0.f;   // largest |attention logit| this lane has scored: the softmax over nearly tied neighbours turns a logit error e into a weight error ~e, and the
                       // logit error is (relative product error) x |logit| — the conditioning indicator nl_frame_diagnostics reports
-  float bnd_c1a = 0.f, bnd_c1x = 0.f, bnd_B2 = 0.f, bnd_bm2 = 0.f, bnd_B3 = 0.f, bnd_bm3 = 0.f, bnd_t = 0.f;
-  if constexpr (MX8) {
-    const float* bf = reinterpret_cast<const float*>(lds_all + GG::RES_BND);
-    auto uni = [](float v) __attribute__((always_inline)) { return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v))); };
-    bnd_c1a = uni(bf[0]); bnd_c1x = uni(bf[1]); bnd_B2 = uni(bf[2]); bnd_bm2 = uni(bf[3]); bnd_B3 = uni(bf[4]); bnd_bm3 = uni(bf[5]);
-    bnd_t = sc.tmax ? uni(*sc.tmax) : 0.f;
-  }
-  // bound (>= the largest |value| of the lane's row) -> the scales of buffer `buf`: 2^(e - 8) with bound < 2^e, i.e. bound / scale < 256
-  auto set_scale = [&](auto Bc, float bound) __attribute__((always_inline)) {
-    constexpr int buf = decltype(Bc)::value;
-    int eb = __builtin_amdgcn_frexp_expf(bound) + 119;
-    eb = eb < 12 ? 12 : (eb > 254 ? 254 : eb);
-    xs_hi[buf] = __builtin_bit_cast(float, eb << 23); xs_lo[buf] = __builtin_bit_cast(float, (eb - 11) << 23);
-    xs_e8h[buf] = eb; xs_e8l[buf] = eb - 11;
-  };
-  auto row_amax = [&]() __attribute__((always_inline)) {   // both halves of a row: lane ^ 32 holds the other 16 channels of every row tile
-    const float o = __shfl_xor(amax, 32, 64);
-    return fmaxf(amax, o);
-  };
   unsigned Ph[GG::KS1][4], Pl[GG::KS1][4];
   u32x4 frh[GG::RL], frl[GG::RL];         // A-fragment ring, position = (running k-step) % RL
   // accumulator of chunk c = acc[c & 3].  Four, because the accumulator is INITIALISED by loads that must be in flight early:
@@ -436,16 +366,6 @@ __global__ __launch_bounds__(256, 1) void point_fused2_kernel(
   };
   auto mfma_h = [](const u32x4& a, const u32x4& b, const f32x16& c) __attribute__((always_inline)) {
     return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-  };
-  // fp8 (e4m3) x fp8, K = 64; sa / sb: E8M0 exponent of the operand's block scale (one value for every block here)
-  auto mfma_8 = [](const i32x8& a, const i32x8& b, const f32x16& c, int sa, int sb) __attribute__((always_inline)) {
-    return __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a, b, c, 0, 0, 0, sa, 0, sb);
-  };
-  auto cat8 = [](const u32x4& a, const u32x4& b) __attribute__((always_inline)) {
-    return i32x8{(int)a[0], (int)a[1], (int)a[2], (int)a[3], (int)b[0], (int)b[1], (int)b[2], (int)b[3]};
-  };
-  auto frag8 = [](const unsigned (&d)[8]) __attribute__((always_inline)) {
-    return i32x8{(int)d[0], (int)d[1], (int)d[2], (int)d[3], (int)d[4], (int)d[5], (int)d[6], (int)d[7]};
   };
 
   // LeakyReLU + split of a finished pair -> dword `d` of the destination fragments
@@ -474,12 +394,14 @@ __global__ __launch_bounds__(256, 1) void point_fused2_kernel(
   unsigned rdbh[2] = {0, 0}, rdbl[2] = {0, 0}, hidh[4] = {0, 0, 0, 0}, hidl[4] = {0, 0, 0, 0};
   f32x16 pa = zero16;
   f32x4 pb[4];
-  using pe_t = std::conditional_t<(MX6 && L1MX && PF2_PE_F32), float, double>;   // fp64 FMAs issue at the fp32 rate on this part: what fp32 returns is registers (24 instead of 48)
+  // the positional encoding's sin / cos recurrence of the MX-FP6 instance in fp32 (round 6): 4.5e-6 on the encoding against the 3e-5 of its fp6 cross-term image;
+  // fp64 in the other precisions, whose operands carry 1e-7 (fp64 FMAs issue at the fp32 rate on this part: what fp32 returns is registers, 24 instead of 48)
+  using pe_t = std::conditional_t<MX6, float, double>;
   constexpr pe_t PE_PIO2_HI = sizeof(pe_t) == 4 ? (pe_t)1.57079637050628662 : (pe_t)1.5707963267948966;
   constexpr pe_t PE_PIO2_LO = sizeof(pe_t) == 4 ? (pe_t)-4.37113882867379e-8 : (pe_t)6.123233995736766e-17;
   pe_t sx[3], skd[3], sr[3], sr2[3], su[3], sw[3], ss[3], scs[3];
   int skq[3];
-  constexpr int NPL = 2, NPC = (MX6 && L1MX) ? 57 : 55, NPRO = NPL + NPC;   // load steps, compute steps (L1MX: + the two slabs' packing conversions)
+  constexpr int NPL = 2, NPC = MX6 ? 57 : 55, NPRO = NPL + NPC;   // load steps, compute steps (MX-FP6: + the two slabs' packing conversions)
   auto pro_step = [&](auto Ic) __attribute__((always_inline)) {
     constexpr int I = decltype(Ic)::value;
     if constexpr (I == 0) {   // ---- loads that depend on the tile number only
@@ -519,11 +441,6 @@ __global__ __launch_bounds__(256, 1) void point_fused2_kernel(
         poff[0] = (pq[0] - pp[0]) * sc.inv_span; poff[1] = (pq[1] - pp[1]) * sc.inv_span; poff[2] = (pq[2] - pp[2]) * sc.inv_span;
         prd[0] = pdv[0] - pnd[0]; prd[1] = pdv[1] - pnd[1]; prd[2] = pdv[2] - pnd[2];
         prd[3] = pdv[0] * pnd[0] + pdv[1] * pnd[1] + pdv[2] * pnd[2];
-        if constexpr (MX8) {   // |base_mlp.0 row| <= max|T| + sum |w| over the sin / cos / ray-difference columns + sum |w| over the raw-offset columns x max |offset|
-          float mo = fabsf(poff[0]);
-          amax2(mo, poff[1], poff[2]);
-          pn_b1 = fmaf(bnd_c1x, mo, bnd_t + bnd_c1a);
-        }
       } else if constexpr (C == 1) {
         pq[0] = sqrtf(prd[0] * prd[0] + prd[1] * prd[1] + prd[2] * prd[2]) + 1e-8f;   // pq[0] is free now: the norm
       } else if constexpr (C == 2) { prd[0] /= pq[0]; prd[1] /= pq[0]; }
@@ -554,7 +471,7 @@ __global__ __launch_bounds__(256, 1) void point_fused2_kernel(
         finish_pair(pa[4 * g + 2] + pb[g][2], pa[4 * g + 3] + pb[g][3], hidh[2 * g + 1], hidl[2 * g + 1]);
       } else if constexpr (C >= 8 && C <= 11) {   // output layer -> k-steps 4, 5
         constexpr int g = C - 8;
-        if constexpr (MX6 && L1MX) {   // k-steps 4, 5 = dwords 2 g, 2 g + 1 of slab 1
+        if constexpr (MX6) {   // k-steps 4, 5 = dwords 2 g, 2 g + 1 of slab 1
           if constexpr (g == 0) pam1 = 0.f;
           float v0 = pa[4 * g] + pb[g][0], v1 = pa[4 * g + 1] + pb[g][1], v2 = pa[4 * g + 2] + pb[g][2], v3 = pa[4 * g + 3] + pb[g][3];
           v0 = vmax(v0, v0 * 0.01f); v1 = vmax(v1, v1 * 0.01f); v2 = vmax(v2, v2 * 0.01f); v3 = vmax(v3, v3 * 0.01f);
@@ -586,7 +503,7 @@ __global__ __launch_bounds__(256, 1) void point_fused2_kernel(
         }
       } else if constexpr (C >= 39 && C < 54) {
         constexpr int f = (C - 39) / 3, a = (C - 39) % 3, p = 5 * a + f;
-        if constexpr (MX6 && L1MX) {   // pair p = dword p of slab 0
+        if constexpr (MX6) {   // pair p = dword p of slab 0
           if constexpr (C == 39) pam0 = 0.f;
           const float v0 = (float)ss[a], v1 = (float)scs[a];
           pp0[p] = hi2_f16_amax(v0, v1, pam0);
@@ -603,7 +520,7 @@ __global__ __launch_bounds__(256, 1) void point_fused2_kernel(
           ss[a] = s2;
         }
       } else if constexpr (C == 54) {
-        if constexpr (MX6 && L1MX) {
+        if constexpr (MX6) {
           const float v0 = hh ? poff[2] : poff[0], v1 = hh ? 0.f : poff[1];
           pp0[15] = hi2_f16_amax(v0, v1, pam0);
           lo2_f32(v0, v1, pp0[15], plo0[30], plo0[31]);
@@ -613,7 +530,7 @@ __global__ __launch_bounds__(256, 1) void point_fused2_kernel(
         Ph[3][3] = h;
         if (X3) Pl[3][3] = l;
         }
-      } else {   // L1MX: a slab of the layer-1 operands is complete — block scale, the f16 fragments as one vector, the two fp6 images (as in the layers' epilogues)
+      } else {   // MX-FP6: a slab of the layer-1 operands is complete — block scale, the f16 fragments as one vector, the two fp6 images (as in the layers' epilogues)
         constexpr int q = C - 55;
         int eb = __builtin_amdgcn_frexp_expf(q == 0 ? pam0 : pam1) + 124;
         eb = eb < 12 ? 12 : (eb > 254 ? 254 : eb);
@@ -671,14 +588,6 @@ __global__ __launch_bounds__(256, 1) void point_fused2_kernel(
     if (part == 0) frh[pos] = v; else frl[pos] = v;
   };
 
-  // MX mode: 16 of the 32 fp8 bytes per lane of slab q of chunk c (part 1 of the slot: [slab][w_hi8 lo16 | w_hi8 hi16 | w_lo8 lo16 | w_lo8 hi16][lane]) -> w8[parity][i]
-  auto read_w8 = [&](auto Cc, auto Qc, auto Ic) __attribute__((always_inline)) {
-    constexpr int c = GG::cm(decltype(Cc)::value), q = decltype(Qc)::value, i = decltype(Ic)::value;
-    constexpr int li = (c % NBUF) * SLOT + (GG::ksi(c) + 4 * q + i) * 64;
-    if constexpr (li >= 4096 && li < 8192) w8[q & 1][i] = __builtin_bit_cast(u32x4, lds_hi[li - 4096]);
-    else w8[q & 1][i] = __builtin_bit_cast(u32x4, lds_all[li + lane]);
-  };
-
   // MX-FP6: the images of slab q of chunk c: part 1 of the slot = per slab [w_hi6 dwords 0-3 | w_hi6 dwords 4-5 | w_lo6 dwords 0-3 | w_lo6 dwords 4-5][lane] = 1 K + 512 + 1 K + 512 bytes
   auto read_w6 = [&](auto Cc, auto Qc, auto Ic) __attribute__((always_inline)) {
     constexpr int c = GG::cm(decltype(Cc)::value), q = decltype(Qc)::value, i = decltype(Ic)::value;
@@ -696,7 +605,7 @@ __global__ __launch_bounds__(256, 1) void point_fused2_kernel(
   // ... and the chunk's two scale dwords: resident (8 bytes per lane and wide chunk)
   auto read_wsc6 = [&](auto Cc) __attribute__((always_inline)) {
     constexpr int c = GG::cm(decltype(Cc)::value);
-    wsc6 = lds_res8[(GG::RES_SC6 - NBUF * SLOT) * 2 + (L1MX ? c : c - NRT) * 64];
+    wsc6 = lds_res8[(GG::RES_SC6 - NBUF * SLOT) * 2 + c * 64];
   };
 
   // ---------------------------------------------------------------- epilogue micro-steps of chunk C, run inside region C+1
@@ -737,18 +646,6 @@ __global__ __launch_bounds__(256, 1) void point_fused2_kernel(
           const u32x6 r = cvt_2xpk16_fp6_f32(l0, l1, scf6 * 0.00048828125f);
           X6[out][q][1][0] = r[0]; X6[out][q][1][1] = r[1]; X6[out][q][1][2] = r[2]; X6[out][q][1][3] = r[3]; X6[out][q][1][4] = r[4]; X6[out][q][1][5] = r[5];
         }
-      } else if constexpr (MX) {
-        if constexpr (sub == 0) {
-          if constexpr (RT == 0 && p == 0) {   // the scales of this layer's output rows (see xs_hi): fixed before its first row tile is converted
-            if constexpr (L == 0) set_scale(std::integral_constant<int, 0>{}, cur_b1);
-            else if constexpr (L == 1) set_scale(std::integral_constant<int, 1>{}, fmaf(bnd_B2, row_amax(), bnd_bm2));
-            else set_scale(std::integral_constant<int, 0>{}, fmaf(bnd_B3, row_amax(), bnd_bm3));
-            amax = 0.f;
-          }
-          ev0 = acc[AB][2 * p]; ev1 = acc[AB][2 * p + 1];
-          if constexpr (L < 2) ehi = lrelu_hi2_f16_amax(ev0, ev1, amax); else ehi = lrelu_hi2_f16(ev0, ev1);
-          Xh[out][fo][d] = ehi;
-        } else mx_bytes2<d & 1>(ev0, ev1, ehi, X8[out][fo >> 2][0][2 * (fo & 3) + (d >> 1)], X8[out][fo >> 2][1][2 * (fo & 3) + (d >> 1)], xs_hi[out], xs_lo[out]);
       } else if constexpr (sub == 0) {
         ev0 = acc[AB][2 * p]; ev1 = acc[AB][2 * p + 1];
         ehi = F16 ? lrelu_hi2_f16(ev0, ev1) : lrelu_hi2(ev0, ev1);
@@ -823,16 +720,15 @@ __global__ __launch_bounds__(256, 1) void point_fused2_kernel(
   // everything that is issued in the shadow of MFMA slot K of region G
   auto fill = [&](auto Gc, auto Kc) __attribute__((always_inline)) {
     constexpr int G = decltype(Gc)::value, K = decltype(Kc)::value;
-    // slots of a region: one per MFMA (3 per k-step); an MX region has 8 units per slab (f16 MFMA = 1, fp8 MFMA = 2: its issue shadow is twice as long),
-    // its barrier sits in front of unit 8 (NSL - 1) + 3 (every LDS-DMA piece is issued before it), and a layer epilogue must be through before the last slab
+    // slots of a region: one per MFMA (3 per k-step); an MX region's cross-term instructions take 8 passes like the f16 ones: 6 units per slab, its barrier in front
+    // of unit 6 (NSL - 1) + 3 (every LDS-DMA piece is issued before it), and a layer epilogue must be through before the last slab
     constexpr int NKS = GG::nks(G);
-    constexpr bool L1R = MX6 && L1MX && GG::layer(G) == 0;   // a layer-1 region in the MX-FP6 arithmetic: 10 units, the barrier in front of unit 7
+    constexpr bool L1R = MX6 && GG::layer(G) == 0;   // a layer-1 region in the MX-FP6 arithmetic: 10 units, the barrier in front of unit 7
     constexpr bool MXR = MX && GG::layer(G) > 0;
-    // (MX-FP6: its cross-term instructions take 8 passes like the f16 ones — 6 units per slab, the barrier in front of unit 6 (NSL - 1) + 3)
-    constexpr int NS = L1R ? 10 : MXR ? (MX6 ? 6 * (NKS / 4) : 2 * NKS) : MPK * NKS, NSD = L1R ? 7 : MXR ? (MX6 ? 6 * (NKS / 4) - 3 : 2 * NKS - 5) : MPK * (NKS - 1),
-                  NSEL = L1R ? 8 : MXR ? (MX6 ? 6 * (NKS / 4) - 6 : 2 * NKS - 8) : NSD;
+    constexpr int NS = L1R ? 10 : MXR ? 6 * (NKS / 4) : MPK * NKS, NSD = L1R ? 7 : MXR ? 6 * (NKS / 4) - 3 : MPK * (NKS - 1),
+                  NSEL = L1R ? 8 : MXR ? 6 * (NKS / 4) - 6 : NSD;
     // LDS-DMA pieces of chunk G+3 (its slot held chunk G-1, which every wave left behind at the previous barrier)
-    if constexpr (K < NSD && !(KO & 4)) {
+    if constexpr (K < NSD) {
       constexpr int ND = GG::ppw(G + 3), d0 = K * ND / NSD, d1 = (K + 1) * ND / NSD;
       static_for<d1 - d0>([&](auto Ic) __attribute__((always_inline)) { dma_piece(std::integral_constant<int, G + 3>{}, std::integral_constant<int, d0 + decltype(Ic)::value>{}); });
     }
@@ -843,13 +739,11 @@ __global__ __launch_bounds__(256, 1) void point_fused2_kernel(
       else load_Tg(std::integral_constant<int, G + 2 - NC>{}, std::integral_constant<int, g>{}, pn_toff);   // the next tile's first two row tiles
     }
     // the next tile's prologue: tile-number loads at the start of layer 3, neighbour gathers half a layer later, arithmetic under k / v
-    if constexpr (!(KO & 1)) {
-      if constexpr (K == 0 && G == 2 * NRT) pro_step(std::integral_constant<int, 0>{});
-      if constexpr (K == 0 && G == 2 * NRT + NRT / 2) pro_step(std::integral_constant<int, 1>{});
-      if constexpr (G >= 3 * NRT && G < 3 * NRT + 6) {
-        constexpr int lo = pro_lo(G), cnt = pro_lo(G + 1) - lo, c0 = K * cnt / NS, c1 = (K + 1) * cnt / NS;
-        static_for<c1 - c0>([&](auto Ic) __attribute__((always_inline)) { pro_step(std::integral_constant<int, NPL + lo + c0 + decltype(Ic)::value>{}); });
-      }
+    if constexpr (K == 0 && G == 2 * NRT) pro_step(std::integral_constant<int, 0>{});
+    if constexpr (K == 0 && G == 2 * NRT + NRT / 2) pro_step(std::integral_constant<int, 1>{});
+    if constexpr (G >= 3 * NRT && G < 3 * NRT + 6) {
+      constexpr int lo = pro_lo(G), cnt = pro_lo(G + 1) - lo, c0 = K * cnt / NS, c1 = (K + 1) * cnt / NS;
+      static_for<c1 - c0>([&](auto Ic) __attribute__((always_inline)) { pro_step(std::integral_constant<int, NPL + lo + c0 + decltype(Ic)::value>{}); });
     }
     if constexpr (K == NS / 2 && (GG::layer(G + 1) == 1 || GG::layer(G + 1) == 2)) load_bias(std::integral_constant<int, G + 1>{});
     // query slice of the head whose k projection this region computes (scored in the next region)
@@ -862,7 +756,7 @@ __global__ __launch_bounds__(256, 1) void point_fused2_kernel(
       // A layer's last row tile is finished inside the first region of the NEXT layer, which consumes the fragments it produces
       // in its last two k-step groups (operands are assembled at the start of a group): layer epilogues end one group early
       constexpr int NE = GG::epi_steps(G - 1), NSE = GG::layer(G - 1) < 3 ? NSEL : NS;
-      if constexpr (K < NSE && !((KO & 2) && GG::layer(G - 1) < 3) && !((KO & 8) && GG::layer(G - 1) == 3)) {
+      if constexpr (K < NSE) {
         constexpr int e0 = K * NE / NSE, e1 = (K + 1) * NE / NSE;
         static_for<e1 - e0>([&](auto Ec) __attribute__((always_inline)) {
           epi_step(std::integral_constant<int, G - 1>{}, std::integral_constant<int, e0 + decltype(Ec)::value>{}, std::integral_constant<bool, G == 0>{});
@@ -884,8 +778,7 @@ __global__ __launch_bounds__(256, 1) void point_fused2_kernel(
 #endif
     constexpr int L = GG::layer(G), NKS = GG::nks(G), AB = G & 3, CK = GG::cumks(G);
     constexpr bool ZI = L == 3;   // k / v projections have no bias: the first MFMA takes C = 0
-    constexpr bool NEXT_MX = MX && (GG::layer(G + 1) > 0 || (MX6 && L1MX));   // the next chunk's part 1 holds fp8 / fp6 images (its part 0: f16 fragments)
-    if constexpr (MX6 && L1MX && L == 0) {
+    if constexpr (MX6 && L == 0) {
       // layer 1 on the same arithmetic: slab 0 = k-steps 0-3, slab 1 = k-steps 4, 5 (+ two empty ones: zero positions in both operands' images); 6 + 4 matrix instructions of
       // 8 passes; units: 0-3 | 4, 5 | 6, 7 | 8, 9, the barrier in front of unit 7
       read_wsc6(Gc);
@@ -894,9 +787,9 @@ __global__ __launch_bounds__(256, 1) void point_fused2_kernel(
         static_for<NKQ>([&](auto Sc) __attribute__((always_inline)) {
           constexpr int sI = decltype(Sc)::value, ks = 4 * q + sI, pos = GG::rpos(CK + ks);
           if constexpr (ks == NKS - 1) {
-            if constexpr (!(KO & 4)) wait_vmcnt<GG::ppw(G + 2) + GG::ppw(G + 3)>();
+            wait_vmcnt<GG::ppw(G + 2) + GG::ppw(G + 3)>();
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            if constexpr (!(KO & 256) && !((KO & 512) && (G & 1))) __builtin_amdgcn_s_barrier();
+            __builtin_amdgcn_s_barrier();
           }
           const u32x4 bh = __builtin_shufflevector(P16[q], P16[q], 4 * sI, 4 * sI + 1, 4 * sI + 2, 4 * sI + 3);
           if constexpr (ks + 2 < NKS) read_frag(Gc, std::integral_constant<int, ks + 2>{}, std::integral_constant<int, 0>{});
@@ -935,19 +828,15 @@ __global__ __launch_bounds__(256, 1) void point_fused2_kernel(
         static_for<4>([&](auto Sc) __attribute__((always_inline)) {
           constexpr int sI = decltype(Sc)::value, ks = 4 * q + sI, pos = GG::rpos(CK + ks);
           if constexpr (ks == NKS - 1) {
-            if constexpr (!(KO & 4)) wait_vmcnt<GG::ppw(G + 2) + GG::ppw(G + 3)>();
+            wait_vmcnt<GG::ppw(G + 2) + GG::ppw(G + 3)>();
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            if constexpr (!(KO & 256) && !((KO & 512) && (G & 1))) __builtin_amdgcn_s_barrier();
+            __builtin_amdgcn_s_barrier();
           }
           const u32x4 bh = __builtin_shufflevector(Xh16[IN][q], Xh16[IN][q], 4 * sI, 4 * sI + 1, 4 * sI + 2, 4 * sI + 3);
           if constexpr (ks + 2 < NKS) read_frag(Gc, std::integral_constant<int, ks + 2>{}, std::integral_constant<int, 0>{});
           else if constexpr (ks == NKS - 1) {
             read_frag(Gc, std::integral_constant<int, NKS>{}, std::integral_constant<int, 0>{});
             read_frag(Gc, std::integral_constant<int, NKS + 1>{}, std::integral_constant<int, 0>{});
-            if constexpr (!NEXT_MX) {   // the next tile's first layer-1 chunk: split-bf16 parts
-              read_frag(Gc, std::integral_constant<int, NKS>{}, std::integral_constant<int, 1>{});
-              read_frag(Gc, std::integral_constant<int, NKS + 1>{}, std::integral_constant<int, 1>{});
-            }
           }
           const f32x16 c0 = (ZI && ks == 0) ? zero16 : acc[AB];
           acc[AB] = TR ? mfma_h(bh, frh[pos], c0) : mfma_h(frh[pos], bh, c0);
@@ -961,14 +850,12 @@ __global__ __launch_bounds__(256, 1) void point_fused2_kernel(
           const unsigned(&xd)[6] = X6[IN][q][1 - im];
           const i32x8 xb = {(int)xd[0], (int)xd[1], (int)xd[2], (int)xd[3], (int)xd[4], (int)xd[5], 0, 0};
           const int sw = (int)wsc6[im], sx = (int)(im == 0 ? xs6l[IN] : xs6h[IN]);
-          if constexpr (!((KO & 16) && im == 1) && !((KO & 32) && im == 0) && !((KO & 64) && q >= 2) && !((KO & 128) && q < 2)) {   // (32 / 64 / 128: debugging knock-outs of single cross terms)
-            if constexpr (TR) acc[AB] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(xb, wa, acc[AB], 2, 2, q, sx, q, sw);
-            else acc[AB] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(wa, xb, acc[AB], 2, 2, q, sw, q, sx);
-          }
+          if constexpr (TR) acc[AB] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(xb, wa, acc[AB], 2, 2, q, sx, q, sw);
+          else acc[AB] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(wa, xb, acc[AB], 2, 2, q, sw, q, sx);
           if constexpr (q + 1 < NSL) {
             read_w6(Gc, std::integral_constant<int, q + 1>{}, std::integral_constant<int, 2 * im>{});
             read_w6(Gc, std::integral_constant<int, q + 1>{}, std::integral_constant<int, 2 * im + 1>{});
-          } else if constexpr (NEXT_MX) {
+          } else {   // the next chunk's slab 0
             read_w6(std::integral_constant<int, G + 1>{}, std::integral_constant<int, 0>{}, std::integral_constant<int, 2 * im>{});
             read_w6(std::integral_constant<int, G + 1>{}, std::integral_constant<int, 0>{}, std::integral_constant<int, 2 * im + 1>{});
           }
@@ -976,74 +863,15 @@ __global__ __launch_bounds__(256, 1) void point_fused2_kernel(
           __builtin_amdgcn_sched_barrier(0);
         });
       });
-    } else if constexpr (MX && L > 0) {
-      constexpr int NSL = NKS / 4, IN = (L + 1) & 1;
-      constexpr bool TR = L == 3 && GG::rt(G) >= 4;   // v heads: D = X . Wv^T (rows = neighbour rows) instead of D^T
-      const int swh = ssc[2 * GG::cm(G)], swl = ssc[2 * GG::cm(G) + 1];
-      static_for<NSL>([&](auto Qc) __attribute__((always_inline)) {
-        constexpr int q = decltype(Qc)::value;
-        static_for<4>([&](auto Sc) __attribute__((always_inline)) {
-          constexpr int ks = 4 * q + decltype(Sc)::value, pos = GG::rpos(CK + ks);
-          if constexpr (ks == NKS - 1) {
-            if constexpr (!(KO & 4)) wait_vmcnt<GG::ppw(G + 2) + GG::ppw(G + 3)>();
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            if constexpr (!(KO & 256) && !((KO & 512) && (G & 1))) __builtin_amdgcn_s_barrier();
-          }
-          const u32x4 bh = frag4(Xh[IN][ks]);
-          if constexpr (ks + 2 < NKS) read_frag(Gc, std::integral_constant<int, ks + 2>{}, std::integral_constant<int, 0>{});
-          else if constexpr (ks == NKS - 1) {
-            read_frag(Gc, std::integral_constant<int, NKS>{}, std::integral_constant<int, 0>{});
-            read_frag(Gc, std::integral_constant<int, NKS + 1>{}, std::integral_constant<int, 0>{});
-            if constexpr (!NEXT_MX) {   // the next tile's first layer-1 chunk: split-bf16 parts
-              read_frag(Gc, std::integral_constant<int, NKS>{}, std::integral_constant<int, 1>{});
-              read_frag(Gc, std::integral_constant<int, NKS + 1>{}, std::integral_constant<int, 1>{});
-            }
-          }
-          const f32x16 c0 = (ZI && ks == 0) ? zero16 : acc[AB];
-          acc[AB] = TR ? mfma_h(bh, frh[pos], c0) : mfma_h(frh[pos], bh, c0);
-          fill(Gc, std::integral_constant<int, 8 * q + decltype(Sc)::value>{});
-          __builtin_amdgcn_sched_barrier(0);
-        });
-        // the two cross terms: w_hi8 x a_lo8 (block scale 2^-11 on the activations' side), w_lo8 x a_hi8 (the weights' lo image carries its own scale)
-        {
-          const i32x8 wa = cat8(w8[q & 1][0], w8[q & 1][1]), xb = frag8(X8[IN][q][1]);
-          acc[AB] = TR ? mfma_8(xb, wa, acc[AB], xs_e8l[IN], swh) : mfma_8(wa, xb, acc[AB], swh, xs_e8l[IN]);
-          if constexpr (q + 1 < NSL) {
-            read_w8(Gc, std::integral_constant<int, q + 1>{}, std::integral_constant<int, 0>{});
-            read_w8(Gc, std::integral_constant<int, q + 1>{}, std::integral_constant<int, 1>{});
-          } else if constexpr (NEXT_MX) {
-            read_w8(std::integral_constant<int, G + 1>{}, std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{});
-            read_w8(std::integral_constant<int, G + 1>{}, std::integral_constant<int, 0>{}, std::integral_constant<int, 1>{});
-          }
-          fill(Gc, std::integral_constant<int, 8 * q + 4>{});
-          fill(Gc, std::integral_constant<int, 8 * q + 5>{});
-          __builtin_amdgcn_sched_barrier(0);
-        }
-        {
-          const i32x8 wa = cat8(w8[q & 1][2], w8[q & 1][3]), xb = frag8(X8[IN][q][0]);
-          if constexpr (!(KO & 16)) acc[AB] = TR ? mfma_8(xb, wa, acc[AB], xs_e8h[IN], swl) : mfma_8(wa, xb, acc[AB], swl, xs_e8h[IN]);
-          else asm volatile("" :: "v"(wa), "v"(xb));
-          if constexpr (q + 1 < NSL) {
-            read_w8(Gc, std::integral_constant<int, q + 1>{}, std::integral_constant<int, 2>{});
-            read_w8(Gc, std::integral_constant<int, q + 1>{}, std::integral_constant<int, 3>{});
-          } else if constexpr (NEXT_MX) {
-            read_w8(std::integral_constant<int, G + 1>{}, std::integral_constant<int, 0>{}, std::integral_constant<int, 2>{});
-            read_w8(std::integral_constant<int, G + 1>{}, std::integral_constant<int, 0>{}, std::integral_constant<int, 3>{});
-          }
-          fill(Gc, std::integral_constant<int, 8 * q + 6>{});
-          fill(Gc, std::integral_constant<int, 8 * q + 7>{});
-          __builtin_amdgcn_sched_barrier(0);
-        }
-      });
     } else
     static_for<NKS>([&](auto Kc) __attribute__((always_inline)) {
       constexpr int ks = decltype(Kc)::value, pos = GG::rpos(CK + ks);
       if constexpr (ks == NKS - 1) {
         // chunk G+1 must have landed (only the pieces of G+2, G+3 may still fly) and every wave must be through with chunk G's
         // slot reads; its last fragments are in registers already
-        if constexpr (!(KO & 4)) wait_vmcnt<GG::ppw(G + 2) + GG::ppw(G + 3)>();
+        wait_vmcnt<GG::ppw(G + 2) + GG::ppw(G + 3)>();
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        if constexpr (!(KO & 256) && !((KO & 512) && (G & 1))) __builtin_amdgcn_s_barrier();
+        __builtin_amdgcn_s_barrier();
       }
       auto bsel = [&](auto Hi) __attribute__((always_inline)) {
         if constexpr (L == 0) { if constexpr (decltype(Hi)::value) return frag4(Ph[ks]); else return frag4(Pl[ks]); }
@@ -1058,17 +886,6 @@ __global__ __launch_bounds__(256, 1) void point_fused2_kernel(
         if constexpr (ks + 2 < NKS) {
           if constexpr (m == 0) read_frag(Gc, std::integral_constant<int, ks + 2>{}, std::integral_constant<int, 0>{});
           if constexpr (X3 && m == 1) read_frag(Gc, std::integral_constant<int, ks + 2>{}, std::integral_constant<int, 1>{});
-        } else if constexpr (ks == NKS - 1 && NEXT_MX) {   // a layer-1 region hands over to an MX region: f16 fragments of its k-steps 0, 1 + the fp8 images of its slab 0
-          if constexpr (m == 0) {
-            read_frag(Gc, std::integral_constant<int, NKS>{}, std::integral_constant<int, 0>{});
-            read_frag(Gc, std::integral_constant<int, NKS + 1>{}, std::integral_constant<int, 0>{});
-          } else if constexpr (MX6) {
-            read_w6(std::integral_constant<int, G + 1>{}, std::integral_constant<int, 0>{}, std::integral_constant<int, 2 * (m - 1)>{});
-            read_w6(std::integral_constant<int, G + 1>{}, std::integral_constant<int, 0>{}, std::integral_constant<int, 2 * (m - 1) + 1>{});
-          } else {
-            read_w8(std::integral_constant<int, G + 1>{}, std::integral_constant<int, 0>{}, std::integral_constant<int, 2 * (m - 1)>{});
-            read_w8(std::integral_constant<int, G + 1>{}, std::integral_constant<int, 0>{}, std::integral_constant<int, 2 * (m - 1) + 1>{});
-          }
         } else if constexpr (ks == NKS - 1) {
           if constexpr (m == 0) {
             read_frag(Gc, std::integral_constant<int, NKS>{}, std::integral_constant<int, 0>{});
@@ -1099,14 +916,14 @@ __global__ __launch_bounds__(256, 1) void point_fused2_kernel(
     static_for<GG::ppw(decltype(Cc)::value)>([&](auto Ic) __attribute__((always_inline)) { dma_piece(Cc, Ic); });
   });
   static_for<NPRO>(pro_step);   // the first tile's prologue, back to back
-  toff = pn_toff; qoff = pn_qoff; ooff_cur = pn_ooff; cur_b1 = pn_b1;
+  toff = pn_toff; qoff = pn_qoff; ooff_cur = pn_ooff;
   kvtile = ((unsigned)tile * 128u + (unsigned)wave * 32u) * 1024u; kvrow = kvtile + (unsigned)j * 1024u;
   load_T(std::integral_constant<int, 0>{}, toff); load_T(std::integral_constant<int, 1>{}, toff);
   wait_vmcnt<GG::ppw(1) + GG::ppw(2)>();   // conservative: the prologue's own loads are younger than every piece
   __builtin_amdgcn_s_barrier();
   read_frag(std::integral_constant<int, NC - 1>{}, std::integral_constant<int, GG::nks(NC - 1)>{}, std::integral_constant<int, 0>{});
   read_frag(std::integral_constant<int, NC - 1>{}, std::integral_constant<int, GG::nks(NC - 1) + 1>{}, std::integral_constant<int, 0>{});
-  if constexpr (MX6 && L1MX) {   // chunk 0's slab-0 images instead of its lo fragments
+  if constexpr (MX6) {   // chunk 0's slab-0 images instead of its lo fragments
     static_for<4>([&](auto Ic) __attribute__((always_inline)) { read_w6(std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{}, Ic); });
   } else if constexpr (X3) {
     read_frag(std::integral_constant<int, NC - 1>{}, std::integral_constant<int, GG::nks(NC - 1)>{}, std::integral_constant<int, 1>{});
@@ -1123,7 +940,7 @@ __global__ __launch_bounds__(256, 1) void point_fused2_kernel(
     }
     ++trace_it;
 #endif
-    ooff_prev = ooff_cur; ooff_cur = pn_ooff; toff = pn_toff; qoff = pn_qoff; cur_b1 = pn_b1;
+    ooff_prev = ooff_cur; ooff_cur = pn_ooff; toff = pn_toff; qoff = pn_qoff;
     tile_prev = tile; kvtile_prev = kvtile;
     tile = pn_tile;
     kvtile = ((unsigned)tile * 128u + (unsigned)wave * 32u) * 1024u; kvrow = kvtile + (unsigned)j * 1024u;
@@ -1149,24 +966,6 @@ __device__ __forceinline__ int pf2_m(int r, int hh) { return (r & 3) + 8 * (r >>
 
 // Stream: chunk (layer, rt) = [part hi/lo][k-step][lane][8 bf16] in A-fragment order (lane: out row 32 rt + (lane & 31), k-slots
 // 8 (lane >> 5) + t); then the resident block: ray_diff_fc fragments [layer][part][lane][8] (4 KB) and the bias tables (floats).
-// f32 (already divided by the block scale) -> OCP e4m3 byte, round to nearest even, saturating at +-448 (what v_cvt_scalef32_pk_fp8_f32 does under FP16_OVFL)
-__device__ __forceinline__ unsigned char pf2_e4m3(float x) {
-  const unsigned char sg = x < 0.f ? 0x80 : 0;
-  const float a = fabsf(x);
-  if (!(a == a)) return sg | 0x7f;
-  if (a >= 448.f) return sg | 0x7e;
-  int e;
-  (void)frexpf(a, &e);            // a = m 2^e, m in [0.5, 1)
-  int E = e - 1;                  // a = 1.xxx 2^E
-  if (a == 0.f || E < -6) {       // subnormal grid: multiples of 2^-9
-    const int qn = (int)rintf(a * 512.f);
-    return sg | (unsigned char)qn;   // qn == 8 is the smallest normal (0x08): the encodings are contiguous
-  }
-  int qn = (int)rintf(ldexpf(a, 3 - E));   // 8 .. 16
-  if (qn == 16) { qn = 8; ++E; }
-  const int b = ((E + 7) << 3) | (qn - 8);
-  return sg | (unsigned char)(b > 0x7e ? 0x7e : b);
-}
 __device__ __forceinline__ unsigned short pf2_f2h(float x) { return __builtin_bit_cast(unsigned short, (_Float16)x); }
 __device__ __forceinline__ float pf2_h2f(unsigned short b) { return (float)__builtin_bit_cast(_Float16, b); }
 
@@ -1175,82 +974,6 @@ __device__ __forceinline__ float pf2_weight(const float* w2, const float* w3, co
   if (layer == 1) return w2[(size_t)orow * W + fin];
   if (layer == 2) return w3[(size_t)orow * W + fin];
   return orow < 128 ? wk[(size_t)orow * W + fin] : wv[(size_t)(orow - 128) * W + fin];
-}
-
-// MX mode: E8M0 scale bytes of every chunk's fp8 images.  One block per chunk c of layers 1..3 (c = NRT .. NC-1): the largest |f16(w)| and the largest
-// |w - f16(w)| over the chunk's 32 rows x K, scale = the power of two that puts it at or below e4m3's 448.  sc[2 c] = w_hi8, sc[2 c + 1] = w_lo8.
-__global__ void pf2_mx_scale_kernel(const float* __restrict__ w2, const float* __restrict__ w3, const float* __restrict__ wk, const float* __restrict__ wv,
-                                    int* __restrict__ sc, int NRT) {
-  const int W = 32 * NRT, c = blockIdx.x;
-  __shared__ float smh[256], sml[256];
-  float mh = 0.f, ml = 0.f;
-  if (c >= NRT) {
-    const int layer = c < 2 * NRT ? 1 : c < 3 * NRT ? 2 : 3, rt = c < 3 * NRT ? c % NRT : c - 3 * NRT;
-    for (int i = threadIdx.x; i < 32 * W; i += blockDim.x) {
-      const float v = pf2_weight(w2, w3, wk, wv, layer, 32 * rt + i / W, i % W, W);
-      const float h = pf2_h2f(pf2_f2h(v));
-      mh = fmaxf(mh, fabsf(h)); ml = fmaxf(ml, fabsf(v - h));
-    }
-  }
-  smh[threadIdx.x] = mh; sml[threadIdx.x] = ml;
-  __syncthreads();
-  for (int st = 128; st > 0; st >>= 1) {
-    if ((int)threadIdx.x < st) { smh[threadIdx.x] = fmaxf(smh[threadIdx.x], smh[threadIdx.x + st]); sml[threadIdx.x] = fmaxf(sml[threadIdx.x], sml[threadIdx.x + st]); }
-    __syncthreads();
-  }
-  if (threadIdx.x < 2) {
-    const float m = threadIdx.x == 0 ? smh[0] : sml[0];
-    int e = -40;
-    if (m > 0.f) { int ex; const float fr = frexpf(m / 448.f, &ex); e = fr == 0.5f ? ex - 1 : ex; }   // ceil(log2(m / 448))
-    e = e < -100 ? -100 : (e > 100 ? 100 : e);
-    sc[2 * c + threadIdx.x] = 127 + e;
-  }
-}
-
-// MX mode: the constants the activation block scales are bounded from (point_fused2_kernel: xs_hi), 8 floats behind the chunks' scale bytes:
-//   [0] c1a = max_c (sum |W1[c, sin / cos columns]| + r1 . sum |W1[c, ray-difference columns]|),  r1 >= |ray_diff_fc output| (its inputs are unit-vector
-//       components and a cosine: |.| <= 1; LeakyReLU does not increase a magnitude)
-//   [1] c1x = max_c sum |W1[c, the three raw-offset columns]|      [2] B2 = max_c ||W2[c, :]||_1   [3] max |b2|   [4] B3   [5] max |b3|
-__global__ void pf2_mx_bounds_kernel(const float* __restrict__ w1, const float* __restrict__ w2, const float* __restrict__ w3, const float* __restrict__ b2,
-                                     const float* __restrict__ b3, const float* __restrict__ rd_w, float* __restrict__ out, int W, int F) {
-  __shared__ float red[6][256];
-  __shared__ float s_r1;
-  const int t = threadIdx.x;
-  if (t == 0) {
-    float hmax = 0.f;
-    for (int i = 0; i < 16; ++i) {
-      float a = fabsf(rd_w[64 + i]);
-      for (int jj = 0; jj < 4; ++jj) a += fabsf(rd_w[i * 4 + jj]);
-      hmax = fmaxf(hmax, a);
-    }
-    float r1 = 0.f;
-    for (int o = 0; o < 27; ++o) {
-      float a = 0.f;
-      for (int i = 0; i < 16; ++i) a += fabsf(rd_w[80 + o * 16 + i]);
-      r1 = fmaxf(r1, a * hmax + fabsf(rd_w[80 + 432 + o]));
-    }
-    s_r1 = r1 * 1.01f;
-  }
-  __syncthreads();
-  float m[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  for (int c = t; c < W; c += 256) {
-    const float* r = w1 + (size_t)c * (F + 90);
-    float a = 0.f, x = 0.f, e = 0.f;
-    for (int jj = 0; jj < 3; ++jj) x += fabsf(r[F + jj]);
-    for (int jj = 3; jj < 63; ++jj) a += fabsf(r[F + jj]);
-    for (int jj = 63; jj < 90; ++jj) e += fabsf(r[F + jj]);
-    m[0] = fmaxf(m[0], a + e * s_r1); m[1] = fmaxf(m[1], x);
-    float n2 = 0.f, n3 = 0.f;
-    for (int k = 0; k < W; ++k) { n2 += fabsf(w2[(size_t)c * W + k]); n3 += fabsf(w3[(size_t)c * W + k]); }
-    m[2] = fmaxf(m[2], n2); m[3] = fmaxf(m[3], fabsf(b2[c])); m[4] = fmaxf(m[4], n3); m[5] = fmaxf(m[5], fabsf(b3[c]));
-  }
-  for (int i = 0; i < 6; ++i) red[i][t] = m[i];
-  __syncthreads();
-  for (int st = 128; st > 0; st >>= 1) {
-    if (t < st) for (int i = 0; i < 6; ++i) red[i][t] = fmaxf(red[i][t], red[i][t + st]);
-    __syncthreads();
-  }
-  if (t < 8) out[t] = t < 6 ? red[t][0] * 1.0001f : 0.f;
 }
 
 // max |x| over n floats -> *out (as a float; *out must be zeroed first: non-negative floats order like their bit patterns)
@@ -1264,7 +987,7 @@ __global__ void pf2_absmax_kernel(const float* __restrict__ x, size_t n, unsigne
 __global__ void pack_point_stream2_kernel(const float* __restrict__ w1, const float* __restrict__ w2, const float* __restrict__ w3,
                                           const float* __restrict__ wk, const float* __restrict__ wv, const float* __restrict__ b2,
                                           const float* __restrict__ b3, const float* __restrict__ rd_w, unsigned short* __restrict__ out,
-                                          int NRT, int F, int mx, const int* __restrict__ mxsc) {
+                                          int NRT, int F, int mx) {
   const int W = 32 * NRT, KSL = 2 * NRT;
   const long long n_l1 = (long long)NRT * 6 * 512, n_lw = (long long)NRT * KSL * 512, n_kv = (long long)8 * KSL * 512;
   const long long total = n_l1 + 2 * n_lw + n_kv;   // (chunk, k-step, lane, t) elements of one part
@@ -1297,21 +1020,8 @@ __global__ void pack_point_stream2_kernel(const float* __restrict__ w1, const fl
     if (layer == 0) base = (long long)rt * 2 * 6 * 512;
     else base = (long long)NRT * 2 * 6 * 512 + ((long long)(layer - 1) * NRT + rt) * 2 * KSL * 512;
     const long long in_part = ((long long)ks * 64 + lane) * 8 + t;
-    if (mx == 3 && (layer > 0 || L1MX)) out[base + in_part] = pf2_f2h(v);   // MX-FP6: the f16 fragments; pack_point_mx6_kernel writes the images and their scales
-    else if (mx == 1 && layer > 0) {
-      // MX chunk: part 0 = f16(w) in the same fragment order; part 1 = per slab q of 4 k-steps [w_hi8 bytes 0-15 | 16-31 | w_lo8 bytes 0-15 | 16-31][lane][16], byte
-      // u = 8 (ks & 3) + t of a lane <-> this element; hi8 = e4m3(f16(w) / s_hi), lo8 = e4m3((w - f16(w)) / s_lo), scales per chunk (pf2_mx_scale_kernel)
-      const int c = (layer - 1) * NRT + NRT + rt;   // chunk index (k / v heads: rt = 0..7 behind layer 3's base)
-      const unsigned short hb = pf2_f2h(v);
-      const float hf = pf2_h2f(hb);
-      out[base + in_part] = hb;
-      unsigned char* ob = reinterpret_cast<unsigned char*>(out + base + (long long)nks * 512);
-      const int q = ks >> 2, sI = ks & 3;
-      const float s_hi = ldexpf(1.f, mxsc[2 * c] - 127), s_lo = ldexpf(1.f, mxsc[2 * c + 1] - 127);
-      const long long bo = (((long long)(4 * q + (sI >> 1)) * 64 + lane) * 16) + 8 * (sI & 1) + t;
-      ob[bo] = pf2_e4m3(hf / s_hi);
-      ob[bo + 2 * 64 * 16] = pf2_e4m3((v - hf) / s_lo);
-    } else if (mx == 2) {   // split-FP16 stream (F16 mode): hi = f16(w), lo = f16(w - hi), every layer
+    if (mx == 3) out[base + in_part] = pf2_f2h(v);   // MX-FP6: the f16 fragments; pack_point_mx6_kernel writes the images and their scales
+    else if (mx == 2) {   // split-FP16 stream (F16 mode): hi = f16(w), lo = f16(w - hi), every layer
       const unsigned short h = pf2_f2h(v);
       out[base + in_part] = h;
       out[base + (long long)nks * 512 + in_part] = pf2_f2h(v - pf2_h2f(h));
@@ -1346,10 +1056,6 @@ __global__ void pack_point_stream2_kernel(const float* __restrict__ w1, const fl
     else { const int q = i - 64, l = q / W, c = q - l * W, rt = c >> 5, hh = (c >> 4) & 1, f = 32 * rt + pf2_m(c & 15, hh); v = l == 0 ? b2[f] : b3[f]; }
     bt[i] = v;
   }
-  if (mx == 1 && e < 2 * (3 * NRT + 8)) {   // the chunks' scale bytes behind the bias tables
-    int* st = reinterpret_cast<int*>(out + res + 2048) + 64 + 2 * W;
-    st[e] = mxsc[e];
-  }
 }
 
 // MX-FP6 images of the wide chunks (layers 2, 3, k / v heads): one thread = one MX block = (chunk, slab q, lane, image).  The 32 weights of output row 32 rt + (lane & 31)
@@ -1367,15 +1073,14 @@ __device__ __forceinline__ unsigned pf2_e2m3(float a) {   // a >= 0, already div
   unsigned c = ((unsigned)(e + 1) << 3) + (m - 8u);    // m == 16 carries into the exponent
   return c > 31u ? 31u : c;
 }
-// (L1MX: the layer-1 chunks too — chunk index c = 0 .. NC - 1, layer-1 chunks hold 6 k-steps = slab 0 + half of slab 1, the k-slots of k-steps 6, 7 are zero)
+// The layer-1 chunks too: chunk index c = 0 .. NC - 1, layer-1 chunks hold 6 k-steps = slab 0 + half of slab 1, the k-slots of k-steps 6, 7 are zero.
 __global__ void pack_point_mx6_kernel(const float* __restrict__ w1, const float* __restrict__ w2, const float* __restrict__ w3, const float* __restrict__ wk,
                                       const float* __restrict__ wv, unsigned char* __restrict__ out, int NRT, int F) {
   const int W = 32 * NRT, KSL = 2 * NRT, NSL = NRT / 2;
   const int e = blockIdx.x * blockDim.x + threadIdx.x;
-  const int nwide = 2 * NRT + 8, nch = L1MX ? NRT + nwide : nwide;
+  const int nwide = 2 * NRT + 8, nch = NRT + nwide;
   if (e >= nch * NSL * 64 * 2) return;
-  const int im = e & 1, lane = (e >> 1) & 63, q = (e >> 7) % NSL, ci = (e >> 7) / NSL;
-  const int c = L1MX ? ci : ci + NRT;              // chunk index 0 .. NC - 1
+  const int im = e & 1, lane = (e >> 1) & 63, q = (e >> 7) % NSL, c = (e >> 7) / NSL;   // c: chunk index 0 .. NC - 1
   const int cw = c - NRT;                          // wide chunk 0 .. 2 NRT + 7 (negative: a layer-1 chunk)
   if (c < NRT && q >= 2) return;                   // layer 1: two slabs
   const int layer = c < NRT ? 0 : cw < NRT ? 1 : cw < 2 * NRT ? 2 : 3, rt = c < NRT ? c : cw < 2 * NRT ? cw % NRT : cw - 2 * NRT;
@@ -1421,10 +1126,10 @@ __global__ void pack_point_mx6_kernel(const float* __restrict__ w1, const float*
   a[0] = d[0]; a[1] = d[1]; a[2] = d[2]; a[3] = d[3];
   unsigned* b2 = reinterpret_cast<unsigned*>(cb + f16b + (size_t)q * 3072 + (size_t)im * 1536 + 1024 + (size_t)lane * 8);
   b2[0] = d[4]; b2[1] = d[5];
-  // the scale byte: resident table behind the stream's bias tables, scale ints and bounds block
+  // the scale byte: resident table behind the stream's bias tables (and (2 NC + 3) / 4 + 2 unused 16-byte units)
   const int NC = 3 * NRT + 8;
   unsigned char* tab = out + ((size_t)NRT * 12 + (size_t)(2 * NRT + 8) * 2 * KSL) * 1024 + 4096 + (size_t)(64 + 2 * W) * 4 + (size_t)((2 * NC + 3) / 4 + 2) * 16;
-  tab[((size_t)(L1MX ? c : cw) * 64 + lane) * 8 + im * 4 + q] = (unsigned char)sb;
+  tab[((size_t)c * 64 + lane) * 8 + im * 4 + q] = (unsigned char)sb;
 }
 
 }  // namespace
@@ -1435,39 +1140,25 @@ size_t nl_point_stream2_bytes(int W) {
          + (size_t)(3 * NRT + 8) * 512;                                                                      // + MX-FP6: the weight-scale table (every chunk)
 }
 
-// mx = 1: the stream of the MX mode (layer 1 split-bf16 as ever; layers 2, 3, k / v: f16 fragments + fp8 images + their scales); mx_scratch: >= 2 (3 W / 32 + 8) ints
+// mx = 0: the split-bf16 stream
+// mx = 1: the stream of the MX-FP6 mode (NL_PREC_F16MX): every layer as f16 fragments + fp6 images + their scales (W = 256 has 28.5 of a chunk's 32 KB in use, W = 128 less)
 // mx = 2: the split-FP16 stream (every layer hi / lo in fp16: the gradient path's forward)
 int nl_pack_point_stream2(const float* w1, const float* w2, const float* w3, const float* wk, const float* wv, const float* b2, const float* b3,
-                          const float* rd_w, void* out, int W, int F, hipStream_t st, int mx, int* mx_scratch) {
+                          const float* rd_w, void* out, int W, int F, hipStream_t st, int mx) {
   const int NRT = W / 32;
   const long long total = ((long long)NRT * 6 + (2LL * NRT + 8) * 2 * NRT) * 512;
-  const bool mx6 = mx == 1 && MXK == 2;   // NL_PREC_F16MX with fp6 cross terms (W = 256 has 28.5 of a chunk's 32 KB in use, W = 128 less)
-  if (mx6) {
-    if (W != 128 && W != 256) return NL_ERR_UNSUPPORTED;
-    hipLaunchKernelGGL(pack_point_stream2_kernel, dim3((unsigned)nl_cdiv(total, 256)), dim3(256), 0, st, w1, w2, w3, wk, wv, b2, b3, rd_w, (unsigned short*)out, NRT, F, 3, nullptr);
-    NL_LAUNCH_CHECK();
-    hipLaunchKernelGGL(pack_point_mx6_kernel, dim3((unsigned)nl_cdiv((long long)(3 * NRT + 8) * (NRT / 2) * 128, 256)), dim3(256), 0, st, w1, w2, w3, wk, wv, (unsigned char*)out, NRT, F);
-    NL_LAUNCH_CHECK();
-    return NL_OK;
-  }
-  if (mx == 1) {
-    if (!mx_scratch) return NL_ERR_BAD_ARG;
-    hipLaunchKernelGGL(pf2_mx_scale_kernel, dim3(3 * NRT + 8), dim3(256), 0, st, w2, w3, wk, wv, mx_scratch, NRT);
-    NL_LAUNCH_CHECK();
-  }
+  if (mx == 1 && W != 128 && W != 256) return NL_ERR_UNSUPPORTED;
   hipLaunchKernelGGL(pack_point_stream2_kernel, dim3((unsigned)nl_cdiv(total, 256)), dim3(256), 0, st, w1, w2, w3, wk, wv, b2, b3, rd_w,
-                     (unsigned short*)out, NRT, F, mx, mx_scratch);
+                     (unsigned short*)out, NRT, F, mx == 1 ? 3 : mx);
   NL_LAUNCH_CHECK();
-  if (mx == 1) {   // the bounds block: behind the resident block's ray_diff_fc fragments (4 KB), bias tables and scale bytes (padded to 16 B)
-    const int NC = 3 * NRT + 8;
-    float* bnd = reinterpret_cast<float*>((char*)out + (size_t)2 * total * 2 + 4096 + (size_t)(64 + 2 * W) * 4 + (size_t)((2 * NC + 3) / 4) * 16);
-    hipLaunchKernelGGL(pf2_mx_bounds_kernel, dim3(1), dim3(256), 0, st, w1, w2, w3, b2, b3, rd_w, bnd, W, F);
+  if (mx == 1) {
+    hipLaunchKernelGGL(pack_point_mx6_kernel, dim3((unsigned)nl_cdiv((long long)(3 * NRT + 8) * (NRT / 2) * 128, 256)), dim3(256), 0, st, w1, w2, w3, wk, wv, (unsigned char*)out, NRT, F);
     NL_LAUNCH_CHECK();
   }
   return NL_OK;
 }
 
-// max |T| over a frame's table (the MX mode's bound on base_mlp.0's outputs): *out <- max |x[0 .. n)|
+// max |T| over a frame's table (reported by nl_frame_diagnostics): *out <- max |x[0 .. n)|
 int nl_table_absmax(const float* x, size_t n, float* out, hipStream_t st) {
   NL_CHECK_HIP(hipMemsetAsync(out, 0, 4, st));
   if (n == 0) return NL_OK;
@@ -1486,7 +1177,7 @@ extern "C" __attribute__((visibility("default"))) int nl_debug_pf2_trace(unsigne
 bool nl_point_fused2_supported(int W, int precision) { return precision != NL_PREC_F32 && (W == 128 || W == 256); }
 
 // keep_kv != null (with the split-FP16 stream in a.wstream2): the F16 + KEEP instance — also writes the k / v rows (N x 8, 256) and the three layers' sign bits
-int nl_launch_point_fused2(const NlPointFusedArgs& a, int W, int precision, hipStream_t st, bool mx, float* keep_kv, unsigned* const* keep_mk, const float* tmax,
+int nl_launch_point_fused2(const NlPointFusedArgs& a, int W, int precision, hipStream_t st, bool mx, float* keep_kv, unsigned* const* keep_mk,
                            unsigned* logit_amax, unsigned long long* clk) {
   if (a.N <= 0) return NL_OK;
   const int g_num_cu = nl_persistent_cus();
@@ -1502,8 +1193,7 @@ int nl_launch_point_fused2(const NlPointFusedArgs& a, int W, int precision, hipS
   sc.N = a.N; sc.M = a.M; sc.inv_span = a.inv_span; sc.ntiles = (int)nl_cdiv(a.N, 16);
   if ((int64_t)a.N * 512 > 0x7fffffffll || ((int64_t)a.M + 1) * W * 4 > 0x7fffffffll) return NL_ERR_UNSUPPORTED;   // 32-bit buffer offsets
   sc.t_bytes = (unsigned)(((int64_t)a.M + 1) * W * 4);
-  sc.tmax = tmax; sc.logit_amax = logit_amax; sc.clk = clk;
-  if (mx && !tmax) return NL_ERR_BAD_ARG;   // (the MX kernel bounds layer 1's outputs with it)
+  sc.tmax = nullptr; sc.logit_amax = logit_amax; sc.clk = clk;
   const int nwg = sc.ntiles < g_num_cu ? (int)nl_xcd_grid(sc.ntiles) : g_num_cu;
   dim3 grid(nwg);
   const bool x3 = precision == NL_PREC_BF16X3;
@@ -1520,7 +1210,7 @@ int nl_launch_point_fused2(const NlPointFusedArgs& a, int W, int precision, hipS
   do {                                                                                                                                               \
     if (keep_kv) hipLaunchKernelGGL((point_fused2_kernel<NRT, true, 0, true, true>), grid, dim3(256), 0, st, a.xyz, a.dir, a.idx, a.Q, a.O, a.ptt, \
                                     a.sp_xyz, a.sp_dir, a.wstream2, sc, kp);                                                                         \
-    else if (mx) hipLaunchKernelGGL((point_fused2_kernel<NRT, true, MXK>), grid, dim3(256), 0, st, a.xyz, a.dir, a.idx, a.Q, a.O, a.ptt, a.sp_xyz,   \
+    else if (mx) hipLaunchKernelGGL((point_fused2_kernel<NRT, true, 2>), grid, dim3(256), 0, st, a.xyz, a.dir, a.idx, a.Q, a.O, a.ptt, a.sp_xyz,   \
                                     a.sp_dir, a.wstream2, sc, kp);                                                                                   \
     else if (x3) hipLaunchKernelGGL((point_fused2_kernel<NRT, true, 0>), grid, dim3(256), 0, st, a.xyz, a.dir, a.idx, a.Q, a.O, a.ptt, a.sp_xyz, \
                                     a.sp_dir, a.wstream2, sc, kp);                                                                                   \
@@ -1528,9 +1218,7 @@ int nl_launch_point_fused2(const NlPointFusedArgs& a, int W, int precision, hipS
                             a.sp_dir, a.wstream2, sc, kp);                                                                                           \
   } while (0)
   if (W == 256) NL_PF2(8);
-#if PF2_KO == 0
   else if (W == 128) NL_PF2(4);
-#endif
   else return NL_ERR_UNSUPPORTED;
 #undef NL_PF2
   NL_LAUNCH_CHECK();

@@ -644,10 +644,7 @@ __global__ __launch_bounds__(64 * TGMX_NW, 1) void tgemm_mx_kernel(const NlGemmA
   auto load_chunk = [&](auto Cc, auto CIc, auto PCc_) __attribute__((always_inline)) {   // PCc: the one 16-byte piece to load (-1: all four)
     constexpr int c = decltype(Cc)::value, ci = decltype(CIc)::value, PCc = decltype(PCc_)::value;
     const float* p; int fr;
-#ifndef TGMX_KO
-#define TGMX_KO 0   // timing experiment (results wrong): 1 = every tap of feature_agg reads the centre row
-#endif
-    if constexpr (c < 24) { constexpr int tp = TGMX_KO ? 1 : c % 3, cb = c / 3; p = P0[tp] + okm[tp] * (cb * cstride0); fr = fr0; }
+    if constexpr (c < 24) { constexpr int tp = c % 3, cb = c / 3; p = P0[tp] + okm[tp] * (cb * cstride0); fr = fr0; }
     else if constexpr (c < 27) { p = P1[c - 24]; fr = 0; }
     else { p = p_zeros; fr = 0; }
     rfr[ci] = fr;
@@ -757,10 +754,8 @@ __global__ __launch_bounds__(64 * TGMX_NW, 1) void tgemm_mx_kernel(const NlGemmA
     const tg_u32x4* Lf = reinterpret_cast<const tg_u32x4*>(lds_all + (SL * TGMX_SLOT) / 16);
     const tg_u32x4* La = reinterpret_cast<const tg_u32x4*>(lds_all + (SL * TGMX_SLOT + TGMX_F16B) / 16);
     const tg_u32x4* Lb = reinterpret_cast<const tg_u32x4*>(lds_all + (SL * TGMX_SLOT + TGMX_F16B + TGMX_IMA) / 16);
-#ifndef TGMX_RD
-#define TGMX_RD 4   // measured 2 / 3 / 4 units ahead: 481-483 / 475 / 472-473 us (241 / 245 registers at 3 / 4, no scratch)
-#endif
-    constexpr int RD = TGMX_RD, RR = RD + 1;   // weight fragments read RD units ahead (RR rotating register sets)
+    // weight fragments read RD units ahead (RR rotating register sets); measured 2 / 3 / 4 units ahead: 481-483 / 475 / 472-473 us (241 / 245 registers at 3 / 4, no scratch)
+    constexpr int RD = 4, RR = RD + 1;
     TGMX_T(2);
     tg_u32x4 ra[RR], rb[RR];
     auto rdA = [&](auto Uc) __attribute__((always_inline)) {
@@ -1121,9 +1116,6 @@ __global__ __launch_bounds__(64 * NW, 1) void feat_comp_mx_kernel(const float* _
 // fp32 rows) is a compile-time chunk table as in tgemm_mx_kernel; the product is the same three-term split-bf16 in the same order as tgemm_kernel's (bit-identical
 // accumulators), the epilogue its NL_EPI_LNSLAB with MaxPool.
 constexpr int TGC1_NRT = 2, TGC1_NW = 4, TGC1_D = 3, TGC1_NB = TGC1_D + 1, TGC1_NCH = 24;
-#ifndef TGC1_KO   // knock-outs for timing experiments (results wrong): 1 = no cross terms (one matrix instruction per product instead of three), 2 = every tap reads the centre row, 4 = the side taps are not loaded at all
-#define TGC1_KO 0
-#endif
 template <bool X3, bool F16 = false>   // F16: split-FP16 fragments (NlGemmSeg::frag == 3) against the layer's fp16 hi / lo weight stream (p_bst then points at it): three-term split-FP16
 __global__ __launch_bounds__(64 * TGC1_NW, 4) void tgemm_conv1_kernel(const NlGemmArgs a, const char* __restrict__ p_bst, float* __restrict__ p_c, const float* __restrict__ p_zeros,
                                                                       const float* __restrict__ p_bias) {
@@ -1175,13 +1167,13 @@ __global__ __launch_bounds__(64 * TGC1_NW, 4) void tgemm_conv1_kernel(const NlGe
   auto act_off = [](int fr, int pc) __attribute__((always_inline)) { return fr == 1 ? 256 * pc : 16 * (pc >> 1) + (fr == 2 ? 8 : 4) * (pc & 1); };
   float4 raw[D][4];   // the raw words of the chunks in flight (ring: chunk c in raw[c % D])
   auto load_act = [&](auto Cc) __attribute__((always_inline)) {
-    constexpr int c = decltype(Cc)::value, tp = (TGC1_KO & 2) ? 1 : c % 3, cb = c / 3;   // (TGC1_KO & 2: every tap reads the centre row — timing experiment, results wrong)
+    constexpr int c = decltype(Cc)::value, tp = c % 3, cb = c / 3;
     const float* p = P0[tp] + okm[tp] * (cb * cstride0);
 #pragma unroll
     for (int pc = 0; pc < 4; ++pc) raw[c % D][pc] = *(const float4*)(p + act_off(fr0, pc));
   };
   auto load_act_piece = [&](auto Cc, auto Pc) __attribute__((always_inline)) {
-    constexpr int c = decltype(Cc)::value, tp = (TGC1_KO & 2) ? 1 : c % 3, cb = c / 3, pc = decltype(Pc)::value;
+    constexpr int c = decltype(Cc)::value, tp = c % 3, cb = c / 3, pc = decltype(Pc)::value;
     const float* p = P0[tp] + okm[tp] * (cb * cstride0);
     raw[c % D][pc] = *(const float4*)(p + act_off(fr0, pc));
   };
@@ -1205,15 +1197,14 @@ __global__ __launch_bounds__(64 * TGC1_NW, 4) void tgemm_conv1_kernel(const NlGe
     TGC1_T(0);
     // chunk g has landed when at most the later chunks' operations are in flight (each chunk: PPW DMA pieces + 4 row loads per wave; vmcnt retires in order)
     constexpr int nlater = (g + D - 1 < NCH ? D - 1 : NCH - 1 - g);
-    // (TGC1_KO & 4, timing only: the side taps are not loaded — the centre chunk's words stand in for them: a third of the row-load instructions)
-    constexpr int later = (TGC1_KO & 4) ? nlater * PPW + 4 * ((g + 1 < NCH && g + 1 <= g + nlater && (g + 1) % 3 == 1) + (g + 2 <= g + nlater && (g + 2) % 3 == 1)) : nlater * (PPW + 4);
+    constexpr int later = nlater * (PPW + 4);
     tg_wait_vmcnt<later>();
     TGC1_T(1);
     __syncthreads();   // every wave's pieces of chunk g are in LDS; every wave has left slot (g + D) % NB = (g - 1) % NB
     TGC1_T(2);
     tg_bf16x8 bh[2], bl[2];
     {
-      const float4 (&rw4)[4] = raw[(TGC1_KO & 4) ? 1 : g % D];
+      const float4 (&rw4)[4] = raw[g % D];
       if (fr0 == 1) {   // fragment image: [k-step 0: hi | lo | k-step 1: hi | lo] (wave-uniform branch around vector moves only)
         bh[0] = __builtin_bit_cast(tg_bf16x8, rw4[0]); bl[0] = __builtin_bit_cast(tg_bf16x8, rw4[1]);
         bh[1] = __builtin_bit_cast(tg_bf16x8, rw4[2]); bl[1] = __builtin_bit_cast(tg_bf16x8, rw4[3]);
@@ -1231,7 +1222,7 @@ __global__ __launch_bounds__(64 * TGC1_NW, 4) void tgemm_conv1_kernel(const NlGe
       constexpr int m = decltype(Mc)::value;
       if constexpr (g + D < NCH) {
         if constexpr (m < PPW) stage_piece(std::integral_constant<int, g + D>{}, Mc);
-        else if constexpr (m < PPW + 4 && (!(TGC1_KO & 4) || (g + D) % 3 == 1)) load_act_piece(std::integral_constant<int, g + D>{}, std::integral_constant<int, m - PPW>{});
+        else if constexpr (m < PPW + 4) load_act_piece(std::integral_constant<int, g + D>{}, std::integral_constant<int, m - PPW>{});
       }
     };
     TGC1_T(3);
@@ -1239,7 +1230,7 @@ __global__ __launch_bounds__(64 * TGC1_NW, 4) void tgemm_conv1_kernel(const NlGe
     tg_static_for<2 * NRT>([&](auto Tc) __attribute__((always_inline)) {
         constexpr int tt = decltype(Tc)::value, ks = tt / NRT, rt = tt % NRT;
         const tg_bf16x8 ah = L[((0 * 2 + ks) * NRT + rt) * 64 + lane];
-        if (X3 && !(TGC1_KO & 1)) {
+        if (X3) {
           const tg_bf16x8 al = L[((1 * 2 + ks) * NRT + rt) * 64 + lane];
           acc[rt] = tg_mfma<F16>(al, bh[ks], acc[rt]);
           acc[rt] = tg_mfma<F16>(ah, bl[ks], acc[rt]);
@@ -1576,11 +1567,7 @@ __global__ __launch_bounds__(256, 1) void sample_chain_kernel(const NlChainArgs 
       // chunk c must have landed: younger operations are the pieces of chunks c+1, c+2 and the other traffic issued since chunk c-3
       constexpr int younger = ppw(c + 1) + ppw(c + 2) + Geo::post(c - 3, FEAT) + Geo::post(c - 2, FEAT) + Geo::post(c - 1, FEAT);
       CHAIN_T(0);
-#ifdef CHAIN_WAIT0
-      tg_wait_vmcnt<0>();
-#else
       tg_wait_vmcnt<(younger < 63 ? younger : 63)>();
-#endif
       __builtin_amdgcn_s_barrier();
       CHAIN_T(1);
       dma_chunk(std::integral_constant<int, c + 3>{});   // its slot held chunk c-1, which every wave has left
@@ -1813,7 +1800,6 @@ bool nl_tgemm_conv1_supported(const NlGemmArgs& a, int precision) {
 int nl_tgemm_launch(const NlGemmArgs& a, int precision, hipStream_t st) {
   const bool x3 = precision == NL_PREC_BF16X3;
   const int nrt = nl_tgemm_nrt(a.N);
-#ifndef NL_NO_TGEMM_CONV1
   if (nl_tgemm_conv1_supported(a, precision)) {
     const dim3 grid((unsigned)nl_cdiv(a.M, 32 * TGC1_NW));
     if (a.seg[0].frag == 3) {
@@ -1823,7 +1809,6 @@ int nl_tgemm_launch(const NlGemmArgs& a, int precision, hipStream_t st) {
     else hipLaunchKernelGGL(tgemm_conv1_kernel<false>, grid, dim3(64 * TGC1_NW), 0, st, a, (const char*)a.Bst, a.C, a.zeros, a.bias);
     return hipPeekAtLastError() == hipSuccess ? NL_OK : NL_ERR_HIP;
   }
-#endif
   if (nl_tgemm_mx_supported(a, precision)) {
     hipLaunchKernelGGL(tgemm_mx_kernel, dim3((unsigned)nl_cdiv(a.M, 32 * TGMX_NW)), dim3(64 * TGMX_NW), 0, st, a, (const char*)a.Bsh_mx, (const char*)a.Bmx, a.C, a.zeros, a.bias);
     return hipPeekAtLastError() == hipSuccess ? NL_OK : NL_ERR_HIP;

@@ -26,9 +26,7 @@ typedef __bf16 ui_bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 ui_bf16x4 __attribute__((ext_vector_type(4)));
 typedef float ui_f32x16 __attribute__((ext_vector_type(16)));
 typedef float ui_f32x2 __attribute__((ext_vector_type(2)));
-#ifndef UI_PK
-#define UI_PK 1   // the epilogue's element-wise arithmetic on pairs (v_pk_add_f32 / v_pk_mul_f32: the same operations in the same order per element, half the instructions); 0 = scalar
-#endif
+// The epilogue's element-wise arithmetic runs on pairs (v_pk_add_f32 / v_pk_mul_f32: the same operations in the same order per element, half the instructions).
 // ELU of a pair (nl_elu_fast per element; the scale by log2(e) and the -1 packed)
 __device__ __forceinline__ ui_f32x2 ui_elu2(ui_f32x2 x) {
   const ui_f32x2 y = x * ui_f32x2{1.4426950408889634f, 1.4426950408889634f};
@@ -97,16 +95,7 @@ template <> struct Lyr<4> {   // trans_conv1 on cat[c1, x1]: K = [c1[m] | x1[m] 
   static constexpr int ioff(int c) { return c / 4; }
 };
 
-#ifndef UI_DEPTH
-#define UI_DEPTH 4
-#endif
-#ifndef UI_BPIPE
-#define UI_BPIPE 1      // the B fragments (LDS) of chunk c + 1 are read before the matrix instructions of chunk c
-#endif
-#ifndef UI_LNPRE
-#define UI_LNPRE 1      // bias and LayerNorm tables of the layer are fetched before its product, not in its epilogue
-#endif
-constexpr int DEPTH = UI_DEPTH;   // weight chunks in flight per wave (16 registers each)
+constexpr int DEPTH = 4;   // weight chunks in flight per wave (16 registers each)
 // ring slot of chunk c of layer ID: the chunks of all five layers form ONE sequence through the ring (a layer's last chunks refill their slots with the next
 // layer's first chunks), so a layer starts at the phase the chunk counts before it leave
 __host__ __device__ constexpr int nch_of(int id) { return id == 0 ? Lyr<0>::NCH : id == 1 ? Lyr<1>::NCH : id == 2 ? Lyr<2>::NCH : id == 3 ? Lyr<3>::NCH : Lyr<4>::NCH; }
@@ -166,11 +155,7 @@ __global__ __launch_bounds__(512, 1) void unet_inner_kernel(const NlUnetInnerArg
     const ui_bf16x8* src = reinterpret_cast<const ui_bf16x8*>(a.w[decltype(LT)::value]) + (size_t)c * (4 * L::NRT * 64) + ct * 64 + lane;
     w[0] = src[(0 * 2 + 0) * L::NRT * 64];
     w[1] = src[(0 * 2 + 1) * L::NRT * 64];
-#ifdef UI_KO_LO      // knock-out (timing only, wrong results): half of the weight bytes are not fetched
-    if (X3) { w[2] = w[0]; w[3] = w[1]; }
-#else
     if (X3) { w[2] = src[(1 * 2 + 0) * L::NRT * 64]; w[3] = src[(1 * 2 + 1) * L::NRT * 64]; }
-#endif
   };
   {   // the first layer's first chunks are on their way while c1 is staged
     const int ct0 = wave % Lyr<0>::NRT;
@@ -205,17 +190,15 @@ __global__ __launch_bounds__(512, 1) void unet_inner_kernel(const NlUnetInnerArg
 
     // bias and LayerNorm tables of this wave's tiles: on their way before the product starts (L2 latency hides behind it)
     float4 bias4[4], gpre[TPW][4], bpre[TPW][4];
-    if (UI_LNPRE) {
 #pragma unroll
-      for (int gq = 0; gq < 4; ++gq) bias4[gq] = *reinterpret_cast<const float4*>(a.bias[ID] + 32 * ct + 8 * gq + 4 * hh);
+    for (int gq = 0; gq < 4; ++gq) bias4[gq] = *reinterpret_cast<const float4*>(a.bias[ID] + 32 * ct + 8 * gq + 4 * hh);
 #pragma unroll
-      for (int ti = 0; ti < TPW; ++ti) {
-        const int wq = ((32 * (rt0 + ti)) % L::LI) / 32;
-        const float* gp = a.gl[ID] + ((size_t)((wq * L::NRT + ct) * 4) * 64 + lane) * 4;
-        const float* bp = a.bl[ID] + ((size_t)((wq * L::NRT + ct) * 4) * 64 + lane) * 4;
+    for (int ti = 0; ti < TPW; ++ti) {
+      const int wq = ((32 * (rt0 + ti)) % L::LI) / 32;   // row tile inside the ray (the lane-major tables' first index)
+      const float* gp = a.gl[ID] + ((size_t)((wq * L::NRT + ct) * 4) * 64 + lane) * 4;
+      const float* bp = a.bl[ID] + ((size_t)((wq * L::NRT + ct) * 4) * 64 + lane) * 4;
 #pragma unroll
-        for (int gq = 0; gq < 4; ++gq) { gpre[ti][gq] = *reinterpret_cast<const float4*>(gp + gq * 256); bpre[ti][gq] = *reinterpret_cast<const float4*>(bp + gq * 256); }
-      }
+      for (int gq = 0; gq < 4; ++gq) { gpre[ti][gq] = *reinterpret_cast<const float4*>(gp + gq * 256); bpre[ti][gq] = *reinterpret_cast<const float4*>(bp + gq * 256); }
     }
     // ---- the product: chunk by chunk, the weight ring DEPTH chunks ahead, the B fragments one chunk ahead
     ui_bf16x8 bfr[2][2][TPW][2];   // [buffer][k-step][tile][hi | lo]
@@ -233,24 +216,21 @@ __global__ __launch_bounds__(512, 1) void unet_inner_kernel(const NlUnetInnerArg
           if (X3) dst[ks][ti][1] = *reinterpret_cast<const ui_bf16x8*>(bp + slab_pl(s));
         }
     };
-    if (UI_BPIPE) load_b(std::integral_constant<int, 0>{}, bfr[0]);
+    load_b(std::integral_constant<int, 0>{}, bfr[0]);
     ui_static_for<L::NCH>([&](auto C) __attribute__((always_inline)) {
       constexpr int c = decltype(C)::value;
       constexpr int slot = (c + ring_phase(ID)) % DEPTH;
       const ui_bf16x8 (&w)[4] = wreg[slot];
-      if constexpr (UI_BPIPE) { if constexpr (c + 1 < L::NCH) load_b(std::integral_constant<int, c + 1>{}, bfr[(c + 1) & 1]); }
-      else load_b(C, bfr[c & 1]);
+      if constexpr (c + 1 < L::NCH) load_b(std::integral_constant<int, c + 1>{}, bfr[(c + 1) & 1]);
       const ui_bf16x8 (&b)[2][TPW][2] = bfr[c & 1];
 #pragma unroll
       for (int ks = 0; ks < 2; ++ks) {
 #pragma unroll
         for (int ti = 0; ti < TPW; ++ti) {
-#ifndef UI_KO_MFMA   // knock-out (timing only): two of the three matrix instructions are not issued
           if (X3) {
             acc[ti] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w[2 + ks], b[ks][ti][0], acc[ti], 0, 0, 0);
             acc[ti] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w[ks], b[ks][ti][1], acc[ti], 0, 0, 0);
           }
-#endif
           acc[ti] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w[ks], b[ks][ti][0], acc[ti], 0, 0, 0);
         }
       }
@@ -273,17 +253,12 @@ __global__ __launch_bounds__(512, 1) void unet_inner_kernel(const NlUnetInnerArg
       float s = 0.f;
 #pragma unroll
       for (int gq = 0; gq < 4; ++gq) {
-        const float4 b4 = UI_LNPRE ? bias4[gq] : *reinterpret_cast<const float4*>(a.bias[ID] + 32 * ct + 8 * gq + 4 * hh);
-        if constexpr (UI_PK) {
-          const ui_f32x2 p0 = ui_f32x2{acc[ti][4 * gq + 0], acc[ti][4 * gq + 1]} + ui_f32x2{b4.x, b4.y};
-          const ui_f32x2 p1 = ui_f32x2{acc[ti][4 * gq + 2], acc[ti][4 * gq + 3]} + ui_f32x2{b4.z, b4.w};
-          acc[ti][4 * gq + 0] = p0[0]; acc[ti][4 * gq + 1] = p0[1]; acc[ti][4 * gq + 2] = p1[0]; acc[ti][4 * gq + 3] = p1[1];
-          const ui_f32x2 q = p0 + p1;
-          s += q[0] + q[1];
-        } else {
-        acc[ti][4 * gq + 0] += b4.x; acc[ti][4 * gq + 1] += b4.y; acc[ti][4 * gq + 2] += b4.z; acc[ti][4 * gq + 3] += b4.w;
-        s += (acc[ti][4 * gq + 0] + acc[ti][4 * gq + 1]) + (acc[ti][4 * gq + 2] + acc[ti][4 * gq + 3]);
-        }
+        const float4 b4 = bias4[gq];
+        const ui_f32x2 p0 = ui_f32x2{acc[ti][4 * gq + 0], acc[ti][4 * gq + 1]} + ui_f32x2{b4.x, b4.y};
+        const ui_f32x2 p1 = ui_f32x2{acc[ti][4 * gq + 2], acc[ti][4 * gq + 3]} + ui_f32x2{b4.z, b4.w};
+        acc[ti][4 * gq + 0] = p0[0]; acc[ti][4 * gq + 1] = p0[1]; acc[ti][4 * gq + 2] = p1[0]; acc[ti][4 * gq + 3] = p1[1];
+        const ui_f32x2 q = p0 + p1;
+        s += q[0] + q[1];
       }
       s1[0] += rayl[ti] == 0 ? s : 0.f;
       s1[1] += rayl[ti] == 0 ? 0.f : s;
@@ -301,17 +276,11 @@ __global__ __launch_bounds__(512, 1) void unet_inner_kernel(const NlUnetInnerArg
 #pragma unroll
     for (int ti = 0; ti < TPW; ++ti) {
       const float m = rayl[ti] == 0 ? mean[0] : mean[1];
-      float s = 0.f;
-      if constexpr (UI_PK) {
-        ui_f32x2 sp = {0.f, 0.f};
-        const ui_f32x2 mm = {m, m};
+      ui_f32x2 sp = {0.f, 0.f};
+      const ui_f32x2 mm = {m, m};
 #pragma unroll
-        for (int r = 0; r < 16; r += 2) { const ui_f32x2 d = ui_f32x2{acc[ti][r], acc[ti][r + 1]} - mm; sp += d * d; }
-        s = sp[0] + sp[1];
-      } else {
-#pragma unroll
-      for (int r = 0; r < 16; ++r) { const float d = acc[ti][r] - m; s += d * d; }
-      }
+      for (int r = 0; r < 16; r += 2) { const ui_f32x2 d = ui_f32x2{acc[ti][r], acc[ti][r + 1]} - mm; sp += d * d; }
+      const float s = sp[0] + sp[1];
       s2[0] += rayl[ti] == 0 ? s : 0.f;
       s2[1] += rayl[ti] == 0 ? 0.f : s;
     }
@@ -333,25 +302,13 @@ __global__ __launch_bounds__(512, 1) void unet_inner_kernel(const NlUnetInnerArg
 #pragma unroll
     for (int ti = 0; ti < TPW; ++ti) {
       const float m = rayl[ti] == 0 ? mean[0] : mean[1], rs = rayl[ti] == 0 ? rstd0 : rstd1;
-      const int wq = ((32 * (rt0 + ti)) % L::LI) / 32;   // row tile inside the ray (the lane-major tables' first index)
-      const float* gp = a.gl[ID] + ((size_t)((wq * L::NRT + ct) * 4) * 64 + lane) * 4;
-      const float* bp = a.bl[ID] + ((size_t)((wq * L::NRT + ct) * 4) * 64 + lane) * 4;
 #pragma unroll
       for (int gq = 0; gq < 4; ++gq) {
-        const float4 g4 = UI_LNPRE ? gpre[ti][gq] : *reinterpret_cast<const float4*>(gp + gq * 256);
-        const float4 be4 = UI_LNPRE ? bpre[ti][gq] : *reinterpret_cast<const float4*>(bp + gq * 256);
-        float v[4];
-        if constexpr (UI_PK) {
-          const ui_f32x2 mm = {m, m}, rr = {rs, rs};
-          const ui_f32x2 p0 = ui_elu2((ui_f32x2{acc[ti][4 * gq + 0], acc[ti][4 * gq + 1]} - mm) * rr * ui_f32x2{g4.x, g4.y} + ui_f32x2{be4.x, be4.y});
-          const ui_f32x2 p1 = ui_elu2((ui_f32x2{acc[ti][4 * gq + 2], acc[ti][4 * gq + 3]} - mm) * rr * ui_f32x2{g4.z, g4.w} + ui_f32x2{be4.z, be4.w});
-          v[0] = p0[0]; v[1] = p0[1]; v[2] = p1[0]; v[3] = p1[1];
-        } else {
-        v[0] = nl_elu_fast((acc[ti][4 * gq + 0] - m) * rs * g4.x + be4.x);
-        v[1] = nl_elu_fast((acc[ti][4 * gq + 1] - m) * rs * g4.y + be4.y);
-        v[2] = nl_elu_fast((acc[ti][4 * gq + 2] - m) * rs * g4.z + be4.z);
-        v[3] = nl_elu_fast((acc[ti][4 * gq + 3] - m) * rs * g4.w + be4.w);
-        }
+        const float4 g4 = gpre[ti][gq], be4 = bpre[ti][gq];
+        const ui_f32x2 mm = {m, m}, rr = {rs, rs};
+        const ui_f32x2 p0 = ui_elu2((ui_f32x2{acc[ti][4 * gq + 0], acc[ti][4 * gq + 1]} - mm) * rr * ui_f32x2{g4.x, g4.y} + ui_f32x2{be4.x, be4.y});
+        const ui_f32x2 p1 = ui_elu2((ui_f32x2{acc[ti][4 * gq + 2], acc[ti][4 * gq + 3]} - mm) * rr * ui_f32x2{g4.z, g4.w} + ui_f32x2{be4.z, be4.w});
+        float v[4] = {p0[0], p0[1], p1[0], p1[1]};
         if constexpr (L::POOL) {   // positions 2 p, 2 p + 1 are neighbouring lanes
 #pragma unroll
           for (int e = 0; e < 4; ++e) v[e] = nl_max_lane_xor1(v[e]);
