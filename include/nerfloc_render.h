@@ -203,13 +203,16 @@ int nl_frame_destroy(nl_frame* frame);
  *                           it sits 2e-5 at |logit| ~ 1 — and the reference's own fp32 arithmetic moves from 1e-6 to 1e-5.  The host mirror uses it to fall back to
  *                           a more exact mode (nerf_loc_amd.conditional_nerf: precision_guard).
  *   [NL_DIAG_POINT_KERNEL_GHZ]  the clock the chip ran the last fused neural-point launch at (the roofline's peak assumes 2.4 GHz; under matrix load it is ~1.7)
+ *   [NL_DIAG_DENSITY_MAX]  the largest density (sigma) among the samples of the batches rendered with NL_RENDER_PRECISION_GUARD (unguarded calls do not pay for the
+ *                           reduction and leave it alone): the guard's second indicator, see NL_GUARD_DENSITY_LIMIT_*
  * n: how many of the NL_DIAG_COUNT values to write. */
 #define NL_DIAG_TABLE_ABSMAX 0
 #define NL_DIAG_LOGIT_ABSMAX 1
 #define NL_DIAG_POINT_KERNEL_GHZ 2   /* shader clock of the last fused neural-point launch (workgroup 0: s_memtime cycles / s_memrealtime): DVFS under matrix load */
 #define NL_DIAG_GUARD_PRECISION 3    /* the nl_precision the last NL_RENDER_PRECISION_GUARD call against this frame produced its outputs in (-1: no guarded call yet) */
 #define NL_DIAG_GUARD_ESCALATIONS 4  /* how many times a guarded call moved this frame to a more exact mode (0, 1 or 2 over a frame's life) */
-#define NL_DIAG_COUNT 5
+#define NL_DIAG_DENSITY_MAX 5        /* largest density (sigma) of the batches rendered with NL_RENDER_PRECISION_GUARD against this frame (0 before the first; a NaN stays a NaN) */
+#define NL_DIAG_COUNT 6
 int nl_frame_diagnostics(const nl_frame* frame, float* host_out, int32_t n, void* stream);
 
 /* ---- stages (each is also reachable through nl_render_rays) -------------------------------------- */
@@ -242,7 +245,8 @@ int nl_ray_unet(const nl_config* cfg, const void* packed, const float* x, int64_
                 void* ws, size_t ws_bytes, void* stream);
 
 size_t nl_heads_composite_workspace_bytes(const nl_config* cfg, int V, int64_t R);
-/* a14-a18 */
+/* a14-a18.  blend1 (N*V,32) / rgbv (N*V,4) / valid_s (N) as nl_mv_aggregate writes them (valid_s may be NULL: the mask is then 0);  out: rgb, depth, weights, mask,
+ * depth_uncertainty, feat, sigma — each may be NULL.  A configuration that is valid but for S > 256: NL_ERR_UNSUPPORTED (a ray is composited by one wave, four samples per lane). */
 int nl_heads_composite(const nl_config* cfg, const void* packed, int V, const float* z_vals, const float* feature_agg,
                        const float* geo, const float* blend1, const float* rgbv, const int32_t* valid_s,
                        int64_t R, int white_bkgd, const nl_render_out* out, void* ws, size_t ws_bytes, void* stream);
@@ -281,8 +285,8 @@ typedef struct nl_render_opts {
                                        * (results are bit-identical either way; for profiling one kernel at a time and for callers that
                                        * must not see a second stream) */
 #define NL_RENDER_PRECISION_GUARD 2u  /* round 6 (ABI 7) — the precision guard AT the boundary: after the batch the library reads the frame's conditioning indicator
-                                       * (NL_DIAG_LOGIT_ABSMAX: one 4-byte device-to-host copy; the call SYNCHRONISES `stream`) and, while it lies beyond the range the
-                                       * mode of the outputs was validated to — NL_GUARD_LOGIT_LIMIT_* below, DESIGN.md 2.3 — renders THIS batch again in the next more
+                                       * (NL_DIAG_LOGIT_ABSMAX and NL_DIAG_DENSITY_MAX: one small device-to-host copy; the call SYNCHRONISES `stream`; both are running maxima over the frame's guarded batches) and, while one lies beyond the range the
+                                       * mode of the outputs was validated to — NL_GUARD_LOGIT_LIMIT_* / NL_GUARD_DENSITY_LIMIT_* below, DESIGN.md 2.3 — renders THIS batch again in the next more
                                        * exact mode (NL_PREC_F16MX -> NL_PREC_BF16X3 -> NL_PREC_F32; NL_PREC_BF16 is a throughput mode and is left alone).  The frame
                                        * then stays in that mode for every later guarded call (until nl_frame_create), so the second pass is paid once per frame;
                                        * NL_DIAG_GUARD_PRECISION / NL_DIAG_GUARD_ESCALATIONS say what happened.  A NaN logit counts as beyond every range.  Every batch
@@ -291,6 +295,13 @@ typedef struct nl_render_opts {
 #define NL_RENDER_FLAGS_ALL 3u
 #define NL_GUARD_LOGIT_LIMIT_F16MX 50.0f    /* tools/scale_sweep.py (profiles/r5_scale_sweep.txt): f16mx <= 5.1e-5 of the CPU oracle up to |logit| 64, 7.2e-5 at 95, 9.3e-5 at 142 */
 #define NL_GUARD_LOGIT_LIMIT_BF16X3 500.0f  /* bf16x3 <= 4.2e-5 up to |logit| 475, 0.3-1.7e-4 at ~1000 */
+/* The guard's second indicator, NL_DIAG_DENSITY_MAX (like the logit indicator a running maximum over the guarded batches of the frame): the density head multiplies
+ * whatever error `geo` carries (f16mx 1.8-2.6e-5, bf16x3 0.9-1.2e-5 of max |geo|) by its gain, and behind a surface one or two samples carry a ray, so nothing averages
+ * that error out.  Scenes with surfaces of tests/test_gpu_surfaces.py, worst output against the CPU oracle: f16mx 2.9-5.2e-5 at densities 17.6-21.9,
+ * 2.8-6.0e-5 at 28.6-35.9, 4.9e-5 at 52.0, 1.05e-4 / 1.02e-4 (depth_uncertainty) at 48.9 / 59.8; nothing was measured between 36 and 48.9.  The worst measured error per
+ * unit of density is 2.8e-6 (5.2e-5 at 18.8), which reaches 1e-4 at 36: the limit is 32, 1.5 x below the first measured miss.  bf16x3 met the bar on every one of
+ * these scenes (<= 7.8e-5, densities up to 61.3) and has no density limit. */
+#define NL_GUARD_DENSITY_LIMIT_F16MX 32.0f
 
 /* rays_o, rays_d (R,3); z_vals (R,S) or NULL to generate linspace(near,far,S) (model.py:451-458,483-484). */
 int nl_render_rays(const nl_config* cfg, const void* packed, const nl_frame* frame, const float* query_center,

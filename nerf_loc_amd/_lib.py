@@ -27,7 +27,8 @@ RENDER_NO_SIDE_STREAM = 1   # nl_render_opts.flags
 RENDER_PRECISION_GUARD = 2  # nl_render_opts.flags (ABI 7): the library checks the conditioning indicator after the batch and re-renders it in a more exact mode if needed
 GUARD_LOGIT_LIMIT = {"f16mx": 50.0, "bf16x3": 500.0}   # include/nerfloc_render.h: NL_GUARD_LOGIT_LIMIT_* (tests/test_abi_symbols.py holds the two in step)
 PRECISION_NAMES = {PREC_F32: "fp32", PREC_BF16X3: "bf16x3", PREC_BF16: "bf16", PREC_F16MX: "f16mx"}
-DIAG_COUNT = 5
+GUARD_DENSITY_LIMIT = {"f16mx": 32.0}  # include/nerfloc_render.h: NL_GUARD_DENSITY_LIMIT_F16MX (the guard's second indicator: the largest density of the frame's guarded batches; bf16x3 has no such limit)
+DIAG_COUNT = 6
 ABI_VERSION = 7   # include/nerfloc_render.h: NL_ABI_VERSION
 
 

@@ -34,6 +34,7 @@ from .frame_setup import backproject_support
 from .frame_setup import get_rays as _hip_get_rays
 from . import diff_render
 from ._lib import GUARD_LOGIT_LIMIT as _GUARD_LOGIT_LIMIT
+from ._lib import GUARD_DENSITY_LIMIT as _GUARD_DENSITY_LIMIT
 from .renderer import HipRenderer
 
 
@@ -186,8 +187,13 @@ class ConditionalNeRF(nn.Module):
     # of W = 32 / 64 report the indicator too.  Limits (NL_GUARD_LOGIT_LIMIT_*): the |logit| up to which the mode stayed within 1e-4 of the CPU oracle on every
     # scene of the sweep with margin (profiles/r5_scale_sweep.txt, MX-FP6 build: f16mx 5.1e-5 at |logit| 64, 7.2e-5 at 95, 9.3e-5 at 142, 1.7e-4 at 462 — the
     # limit is 50 since round 6, it was 100; bf16x3 4.2e-5 at 475 and 0.9-1.7e-4 at ~1000; the synthetic BASELINE scenes sit at 4-6).
+    # The guard's second indicator is the largest density of the frame's batches (NL_GUARD_DENSITY_LIMIT_F16MX = 32; bf16x3 met the bar at every density measured and
+    # has no such limit): behind a surface one or two samples carry a ray and the density head multiplies geo's error by its gain (DESIGN.md 2.3,
+    # tests/test_gpu_surfaces.py).  nl_render_rays_multi does not take the flag (its lanes must not synchronise), so render_rays_frames over several data dicts
+    # applies the same two limits on the host after the call: the logit from the frame's diagnostics, the density from the per-sample densities it asks for.
     # precision_guard=False switches it off; `guard_events` lists what it did.
     LOGIT_LIMIT = dict(_GUARD_LOGIT_LIMIT)
+    DENSITY_LIMIT = dict(_GUARD_DENSITY_LIMIT)
     _SAFER = {"f16mx": "bf16x3", "bf16x3": "fp32", "bf16": "bf16x3"}
 
     def __init__(self, args, activation_func=None, precision: str = "f16mx", device: Optional[str] = None, precision_guard: bool = True):
@@ -308,7 +314,7 @@ class ConditionalNeRF(nn.Module):
         d = r.diagnostics()
         mode = d["guard_precision"]
         if mode is not None and mode != r.precision:
-            self.guard_events.append({"logit_absmax": d["logit_absmax"], "from": r.precision, "to": mode})
+            self.guard_events.append({"logit_absmax": d["logit_absmax"], "density_max": d["density_max"], "from": r.precision, "to": mode})
             del self.guard_events[:-64]
             r.set_precision(mode)
         return out
@@ -684,22 +690,24 @@ class ConditionalNeRF(nn.Module):
                 dcs.append(dc)
             # the query centre is data['pose'] like render_rays' (model.py:472-480 reads the pose of `data`; `rays['pose']` only feeds the hierarchical branch)
             jobs.append((r, o, d, data["pose"][:3, 3].detach(), {"z_vals": z, "white_bkgd": bool(data.get("white_bkgd", self.args.render.white_bkgd)),
-                                                                  "want_feat": bool(self.args.render.render_feature)}))
+                                                                  "want_feat": bool(self.args.render.render_feature), "want_sigma": bool(self.precision_guard)}))
         self._frame_token = {}   # (the single-frame renderers' tables no longer describe the module's caches)
         outs = render_rays_multi(jobs)
         if self.precision_guard:   # the conditioning check of `_guarded`, per frame: a frame beyond its mode's validated range is rendered again in the safer mode
             for i, job in enumerate(jobs):
                 r = job[0]
                 amax = r.diagnostics()["logit_absmax"]
+                dmax = float(outs[i].pop("sigma").max())   # (the library's own indicator needs the flag nl_render_rays_multi refuses; NaN propagates through max)
                 mode = r.precision
-                while mode in self.LOGIT_LIMIT and amax > self.LOGIT_LIMIT[mode]:
+                # (written so that a NaN is beyond every limit, as in the library)
+                while (mode in self.LOGIT_LIMIT and not amax <= self.LOGIT_LIMIT[mode]) or (mode in self.DENSITY_LIMIT and not dmax <= self.DENSITY_LIMIT[mode]):
                     mode = self._SAFER[mode]
                 if mode != r.precision:
-                    self.guard_events.append({"logit_absmax": amax, "from": r.precision, "to": mode, "frame": i})
+                    self.guard_events.append({"logit_absmax": amax, "density_max": dmax, "from": r.precision, "to": mode, "frame": i})
                     del self.guard_events[:-64]
                     r.set_precision(mode)
                     dc = outs[i].get("depth_coarse")
-                    outs[i] = r.render_rays(job[1], job[2], job[3], **job[4])
+                    outs[i] = r.render_rays(job[1], job[2], job[3], **{k: v for k, v in job[4].items() if k != "want_sigma"})
                     if dc is not None:
                         outs[i]["depth_coarse"] = dc
         for o_, dc in zip(outs, dcs):

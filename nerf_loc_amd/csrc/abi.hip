@@ -36,6 +36,7 @@ int nl_launch_unet_inner(const NlUnetInnerArgs& a, int precision, hipStream_t st
 size_t nl_tgemm_mx_image_bytes(int Kpad);
 int nl_launch_sample_points(const float* rays_o, const float* rays_d, int64_t R, int S, float near_, float far_, const float* z_in, float* z_out, float* xyz, hipStream_t st);
 int nl_launch_sigma(const float* geo, int64_t N, int W, const float* w, const float* b, float* sigma, hipStream_t st);
+int nl_launch_sigma_max(const float* sigma, int64_t N, unsigned* slot, hipStream_t st);
 int nl_launch_blend(const float* hA, const float* h1, const float* rgbv, int64_t N, int V, const float* w2, const float* b2, const float* w4, const float* b4, float* rgb_s, hipStream_t st,
                     const int* n_alive = nullptr, int S = 1);
 int nl_launch_blend_taps(const NlViews& vw, const float* viewsdev, const float* pfeat, const float* blw, const float* xyz, const float* hA, const float* rgbv, int64_t N,
@@ -1536,10 +1537,12 @@ int do_heads_pre(const Ctx& x, int V, const float* FA, const float* bl1, const f
 
 int do_heads(const Ctx& x, int V, const float* z, const float* FA, const float* geo, const float* bl1, const float* rgbv,
              const int* valid_s, int64_t R, int white, const nl_render_out* out, int64_t ray0, const HdBufs& h, bool have_sigma = false,
-             bool pre_done = false, float term_eps = 0.f, int chain_parts = 0, const BlendTaps* bt = nullptr, bool feat_late = false, bool fa_f16 = false) {
+             bool pre_done = false, float term_eps = 0.f, int chain_parts = 0, const BlendTaps* bt = nullptr, bool feat_late = false, bool fa_f16 = false,
+             unsigned* density_max = nullptr) {   // density_max: the frame's NL_DIAG_DENSITY_MAX slot (guarded calls only: one small reduction over the batch's densities)
   const int W = x.c->W, S = x.c->S, C = x.c->C;
   const int64_t N = R * S;
   if (!have_sigma) NL_TRY(nl_launch_sigma(geo, N, W, x.p<float>(x.L.sig_w), x.p<float>(x.L.sig_b), h.sigma, x.st));
+  if (density_max) NL_TRY(nl_launch_sigma_max(h.sigma, N, density_max, x.st));
   const bool want_feat = out->feat != nullptr;
   const bool term = term_eps > 0.f && !pre_done;
   if (term) NL_TRY(nl_launch_termination(z, h.sigma, R, S, term_eps, h.n_alive, h.tile_list, h.tile_count, x.st));
@@ -2004,7 +2007,8 @@ int nl_frame_create(const nl_config* cfg, const nl_frame_desc* d, void* mem, siz
       memcpy(f->views_host + 192 + 3 * v, d->cam_centers + 3 * v, 12);
     }
     if (rc == NL_OK && hipMemcpyAsync(f->views_dev, f->views_host, sizeof(f->views_host), hipMemcpyHostToDevice, st) != hipSuccess) rc = NL_ERR_HIP;
-    // the 16 floats of slack behind the matrices hold the frame's diagnostics (nl_frame_diagnostics): [248] max |T|, [249] max |attention logit|
+    // the 16 floats of slack behind the matrices hold the frame's diagnostics (nl_frame_diagnostics): [248] max |T|, [249] max |attention logit|, [250 .. 253] two
+    // clock counters, [254] max density of the guarded batches
     if (rc == NL_OK && hipMemsetAsync(f->views_dev + 240, 0, 64, st) != hipSuccess) rc = NL_ERR_HIP;
   }
   if (rc != NL_OK) { delete f; return rc; }
@@ -2029,12 +2033,12 @@ int nl_frame_destroy(nl_frame* f) {
 
 int nl_frame_diagnostics(const nl_frame* f, float* host_out, int32_t n, void* stream) {
   if (!f || !host_out || n < 1) return NL_ERR_BAD_ARG;
-  struct { float tmax, lmax; unsigned long long cyc, ref; } tmp = {0.f, 0.f, 0ull, 0ull};   // floats 248, 249; two 64-bit counters at floats 250 .. 253
-  static_assert(sizeof(tmp) == 24, "diagnostics block");
+  struct { float tmax, lmax; unsigned long long cyc, ref; float dmax, pad; } tmp = {0.f, 0.f, 0ull, 0ull, 0.f, 0.f};   // floats 248, 249; two 64-bit counters at floats 250 .. 253; 254
+  static_assert(sizeof(tmp) == 32, "diagnostics block");
   NL_CHECK_HIP(hipMemcpyAsync(&tmp, f->views_dev + 248, sizeof(tmp), hipMemcpyDeviceToHost, (hipStream_t)stream));
   NL_CHECK_HIP(hipStreamSynchronize((hipStream_t)stream));
   const float vals[NL_DIAG_COUNT] = {tmp.tmax, tmp.lmax, tmp.ref ? (float)((double)tmp.cyc / ((double)tmp.ref * 10.0)) : 0.f,   // cycles per ns = GHz
-                                     (float)f->guard_last_prec, (float)f->guard_escalations};
+                                     (float)f->guard_last_prec, (float)f->guard_escalations, tmp.dmax};
   for (int i = 0; i < n; ++i) host_out[i] = i < NL_DIAG_COUNT ? vals[i] : 0.f;
   return NL_OK;
 }
@@ -2425,6 +2429,7 @@ int nl_heads_composite(const nl_config* cfg, const void* packed, int V, const fl
                        const nl_render_out* out, void* ws, size_t ws_bytes, void* stream) {
   NL_EFF_CFG(cfg);
   if (R == 0) return NL_OK;   // empty batch: nothing to do, data pointers may be null
+  if (cfg && cfg->S > 256 && cfg->S % 8 == 0) return NL_ERR_UNSUPPORTED;   // composite_kernel holds a ray in one wave, four samples per lane at the most: nothing is launched beyond that
   if (!cfg_ok(cfg) || !packed || !z || !FA || !geo || !blend1 || !rgbv || !out || !ws || R < 0 || V < 1 || V > NL_MAX_VIEWS) return NL_ERR_BAD_ARG;
   if (ws_bytes < nl_heads_composite_workspace_bytes(cfg, V, R)) return NL_ERR_WORKSPACE;
   Bump b{(char*)ws, 0}; HdBufs h; carve_hd(b, cfg, V, R, h);
@@ -2463,6 +2468,10 @@ namespace {
 int prec_rank(int p) { return p == NL_PREC_BF16 ? 0 : p == NL_PREC_F16MX ? 1 : p == NL_PREC_BF16X3 ? 2 : 3; }
 // the |attention logit| up to which a mode stayed within 1e-4 of the CPU oracle on every scene of tools/scale_sweep.py; <= 0: no limit known
 float guard_limit(int p) { return p == NL_PREC_F16MX ? NL_GUARD_LOGIT_LIMIT_F16MX : p == NL_PREC_BF16X3 ? NL_GUARD_LOGIT_LIMIT_BF16X3 : 0.f; }
+// the density up to which a mode stayed within 1e-4 of the CPU oracle on the scenes with surfaces of tests/test_gpu_surfaces.py: the density head
+// multiplies the error geo carries by its gain
+// (bf16x3 met the bar on every one of those scenes, densities up to 61: it has no density limit.)  <= 0: no limit
+float guard_density_limit(int p) { return p == NL_PREC_F16MX ? NL_GUARD_DENSITY_LIMIT_F16MX : 0.f; }
 int guard_safer(int p) { return p == NL_PREC_F16MX ? NL_PREC_BF16X3 : NL_PREC_F32; }
 int render_rays_impl(const nl_config* cfg, const void* packed, const nl_frame* f, const float* qc, const float* rays_o, const float* rays_d, const float* z_vals,
                      int64_t R, int white, const nl_render_out* out, void* ws, size_t ws_bytes, void* stream, const nl_render_opts* opts);
@@ -2474,9 +2483,10 @@ int nl_render_rays_ex(const nl_config* cfg, const void* packed, const nl_frame* 
                       size_t ws_bytes, void* stream, const nl_render_opts* opts) {
   if (!opts || !(opts->flags & NL_RENDER_PRECISION_GUARD) || !cfg || !f || R <= 0)
     return render_rays_impl(cfg, packed, f, qc, rays_o, rays_d, z_vals, R, white, out, ws, ws_bytes, stream, opts);
-  // ---- NL_RENDER_PRECISION_GUARD: render, read the frame's conditioning indicator (one 4-byte copy + a stream synchronisation), and while it is beyond the
-  // validated range of the mode the outputs were produced in, render THIS batch again in the next more exact mode.  The frame stays in that mode for every
-  // later guarded call (a frame whose attention logits are large once has them large in every batch), so the extra pass is paid once per frame.
+  // ---- NL_RENDER_PRECISION_GUARD: render, read the frame's two conditioning indicators (largest |attention logit|, largest density: one 24-byte copy + a stream
+  // synchronisation), and while one is beyond the validated range of the mode the outputs were produced in, render THIS batch again in the next more exact mode.
+  // Both are running maxima over the frame's life, and the frame stays in that mode for every later guarded call (a frame whose attention logits or densities are
+  // large once has them large in every batch), so the extra pass is paid once per frame.
   nl_config c = *cfg;
   if (f->guard_prec >= 0 && prec_rank(f->guard_prec) > prec_rank(c.precision)) c.precision = f->guard_prec;
   for (;;) {
@@ -2485,10 +2495,11 @@ int nl_render_rays_ex(const nl_config* cfg, const void* packed, const nl_frame* 
     f->guard_last_prec = c.precision;
     const float limit = guard_limit(c.precision);
     if (limit <= 0.f) return NL_OK;
-    float amax = 0.f;
-    NL_CHECK_HIP(hipMemcpyAsync(&amax, f->views_dev + 249, sizeof(float), hipMemcpyDeviceToHost, (hipStream_t)stream));
+    float diag[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};   // floats 249 .. 254: [0] max |attention logit|, [5] max density
+    NL_CHECK_HIP(hipMemcpyAsync(diag, f->views_dev + 249, sizeof(diag), hipMemcpyDeviceToHost, (hipStream_t)stream));
     NL_CHECK_HIP(hipStreamSynchronize((hipStream_t)stream));
-    if (amax <= limit) return NL_OK;   // (the kernels record a NaN logit as +inf: it escalates)
+    const float dlimit = guard_density_limit(c.precision);
+    if (diag[0] <= limit && (dlimit <= 0.f ? diag[5] == diag[5] : diag[5] <= dlimit)) return NL_OK;   // (a NaN logit is recorded as +inf, a NaN density as itself: both escalate)
     c.precision = guard_safer(c.precision);
     f->guard_prec = c.precision;
     ++f->guard_escalations;
@@ -2576,7 +2587,7 @@ int render_rays_impl(const nl_config* cfg, const void* packed, const nl_frame* f
     // traced: conv1 stretches by what the taps take (conv1 399 us with the taps' 369 us inside it = a 403-us span against 192 + 222 us one after the other;
     // profiles/r6_blend_side_stream.txt).  Not kept.)
     NL_TRY(do_heads(x, V, rb.z, rb.FA, rb.geo, front ? nullptr : rb.bl1, rb.rgbv, rb.valid_s, rc, white, out, r0, rb.hd, have_sigma, false, term_eps, chain_parts, &bt,
-                    feat_late && chain_done, fa_f16));
+                    feat_late && chain_done, fa_f16, (flags & NL_RENDER_PRECISION_GUARD) ? reinterpret_cast<unsigned*>(f->views_dev + 254) : nullptr));
     if (out->feature_agg) NL_CHECK_HIP(hipMemcpyAsync(out->feature_agg + r0 * S * W, rb.FA, sizeof(float) * N * W, hipMemcpyDeviceToDevice, x.st));
     if (out->mv_feature_agg) NL_CHECK_HIP(hipMemcpyAsync(out->mv_feature_agg + r0 * S * W, rb.G, sizeof(float) * N * W, hipMemcpyDeviceToDevice, x.st));
     if (out->geo) NL_CHECK_HIP(hipMemcpyAsync(out->geo + r0 * S * W, rb.geo, sizeof(float) * N * W, hipMemcpyDeviceToDevice, x.st));

@@ -282,6 +282,30 @@ int nl_launch_sample_points(const float* rays_o, const float* rays_d, int64_t R,
   return NL_OK;
 }
 
+// max over a batch's densities into the frame's diagnostics slot (NL_DIAG_DENSITY_MAX; the precision guard's second conditioning indicator).  sigma >= 0, so the
+// values order like their bit patterns; a NaN (either sign) has a larger pattern than +inf and wins: the guard reads it as beyond every range.
+__global__ __launch_bounds__(256) void sigma_max_kernel(const float* __restrict__ sigma, int N, unsigned* __restrict__ slot) {
+  unsigned m = 0u;
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < N; i += gridDim.x * 256) {
+    const unsigned u = __float_as_uint(sigma[i]);
+    m = u > m ? u : m;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const unsigned t = (unsigned)__shfl_xor((int)m, o, 64);
+    m = t > m ? t : m;
+  }
+  if ((threadIdx.x & 63) == 0 && m != 0u) atomicMax(slot, m);
+}
+
+int nl_launch_sigma_max(const float* sigma, int64_t N, unsigned* slot, hipStream_t st) {
+  if (N <= 0) return NL_OK;
+  const int64_t nb = nl_cdiv(N, 256);
+  hipLaunchKernelGGL(sigma_max_kernel, dim3((unsigned)(nb < 256 ? nb : 256)), dim3(256), 0, st, sigma, (int)N, slot);
+  NL_LAUNCH_CHECK();
+  return NL_OK;
+}
+
 int nl_launch_sigma(const float* geo, int64_t N, int W, const float* w, const float* b, float* sigma, hipStream_t st) {
   if (N <= 0) return NL_OK;
   hipLaunchKernelGGL(sigma_kernel, dim3((unsigned)nl_cdiv(N, 4)), dim3(256), 0, st, geo, (int)N, W, w, b, sigma);

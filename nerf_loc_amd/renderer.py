@@ -326,12 +326,12 @@ class HipRenderer:
 
     def diagnostics(self) -> Dict[str, float]:
         """nl_frame_diagnostics: {'table_absmax': max |T| of the per-frame table, 'logit_absmax': the largest |attention logit| the fused neural-point kernel has
-        scored against this frame so far}.  Synchronises the current stream (a device-to-host copy of two floats)."""
+        scored against this frame so far, 'density_max': the largest density over all batches rendered with precision_guard=True against it (a running maximum, like the logit)}.  Synchronises the current stream (a 32-byte device-to-host copy)."""
         self._ready()
         buf = (ct.c_float * L.DIAG_COUNT)()
         L.check(self.lib.nl_frame_diagnostics(self._frame, buf, L.DIAG_COUNT, self._stream()), "nl_frame_diagnostics")
         return {"table_absmax": float(buf[0]), "logit_absmax": float(buf[1]), "point_kernel_GHz": float(buf[2]),
-                "guard_precision": L.PRECISION_NAMES.get(int(buf[3])), "guard_escalations": int(buf[4])}
+                "guard_precision": L.PRECISION_NAMES.get(int(buf[3])), "guard_escalations": int(buf[4]), "density_max": float(buf[5])}
 
     def clear_frame(self) -> None:
         if self._frame:
@@ -426,14 +426,17 @@ class HipRenderer:
         return ent
 
     def render_rays(self, rays_o, rays_d, query_center, z_vals=None, white_bkgd: bool = False,
-                    intermediates: bool = False, want_feat: bool = True, early_term_eps: float = 0.0,
+                    intermediates=False, want_feat: bool = True, early_term_eps: float = 0.0,
                     side_stream: bool = True, want_knn: bool = False, graph: bool = False, precision_guard: bool = False,
                     out_buffers: Optional[Dict[str, torch.Tensor]] = None, want_weights: bool = True) -> Dict[str, torch.Tensor]:
-        """want_weights=False: the per-sample compositing weights (R, S) are not returned (nl_render_out.weights = null; every other output is unchanged).
+        """intermediates: True = every per-stage output (sigma, feature_agg, mv_feature_agg, geo, knn_idx, knn_d2: the library then materialises the fp32 rows
+        between the stages, i.e. it leaves the fused kernels), or a tuple of names for those alone — ("sigma",) returns the per-sample density of the fused
+        path itself (nl_render_out.sigma with feature_agg left null: same kernels, bit-identical outputs).
+        want_weights=False: the per-sample compositing weights (R, S) are not returned (nl_render_out.weights = null; every other output is unchanged).
         out_buffers: preallocated, contiguous destination tensors for the per-ray outputs (rgb (R,3), depth (R), weights (R,S), mask (R) uint8, depth_uncertainty (R),
         feat (R,C); fp32 but for the mask) — the kernels write straight into them (sharding.py hands in views of ONE buffer per rank, so the all-gather needs no pack step).
         precision_guard=True (nl_render_opts.flags = NL_RENDER_PRECISION_GUARD, ABI 7): the LIBRARY checks the frame's conditioning indicator after the batch
-        (max |attention logit|; one 4-byte copy + a stream synchronisation) and renders the batch again in the next more exact mode (f16mx -> bf16x3 -> fp32) while
+        (max |attention logit| and the largest density, both running maxima over the frame's guarded batches; one small copy + a stream synchronisation) and renders the batch again in the next more exact mode (f16mx -> bf16x3 -> fp32) while
         it lies beyond the validated range of the mode the outputs were produced in; the frame then stays in that mode for later guarded calls
         (`diagnostics()['guard_precision']`).  Off by default: the synchronisation keeps the host from running ahead of the device.
         side_stream=False (nl_render_opts.flags = NL_RENDER_NO_SIDE_STREAM): every kernel on the current stream (bit-identical results;
@@ -481,13 +484,17 @@ class HipRenderer:
                 out["feat"] = torch.empty(R, self.C, device=dev)
             if not want_weights:
                 del out["weights"]
-        if want_knn and not intermediates:   # the neighbours alone (the gradient path hands them to nl_render_rays_backward)
+        if want_knn and intermediates is not True:   # the neighbours alone (the gradient path hands them to nl_render_rays_backward)
             out.update({"knn_idx": torch.empty(R * S, 8, dtype=torch.int32, device=dev), "knn_d2": torch.empty(R * S, 8, device=dev)})
         if intermediates:
             N = R * S
-            out.update({"sigma": torch.empty(N, device=dev), "feature_agg": torch.empty(N, W, device=dev),
-                        "mv_feature_agg": torch.empty(N, W, device=dev), "geo": torch.empty(N, W, device=dev),
-                        "knn_idx": torch.empty(N, 8, dtype=torch.int32, device=dev), "knn_d2": torch.empty(N, 8, device=dev)})
+            stage = {"sigma": lambda: torch.empty(N, device=dev), "feature_agg": lambda: torch.empty(N, W, device=dev),
+                     "mv_feature_agg": lambda: torch.empty(N, W, device=dev), "geo": lambda: torch.empty(N, W, device=dev),
+                     "knn_idx": lambda: torch.empty(N, 8, dtype=torch.int32, device=dev), "knn_d2": lambda: torch.empty(N, 8, device=dev)}
+            names = tuple(stage) if intermediates is True else tuple(intermediates)
+            if not set(names) <= set(stage):
+                raise ValueError(f"intermediates: unknown stage output in {names}; known: {tuple(stage)}")
+            out.update({k: stage[k]() for k in names if k not in out})
         ro = L.NlRenderOut()
         for k, t in out.items():
             setattr(ro, k, t.data_ptr())
@@ -505,7 +512,7 @@ class HipRenderer:
                                            d.data_ptr(), _ptr(z), R, int(bool(white_bkgd)), ct.byref(ro), ws.data_ptr(), ws.numel(), self._stream(),
                                            ct.byref(opts) if (early_term_eps > 0 or per_ray or not side_stream or precision_guard) else None), "nl_render_rays")
         out["mask"] = out["mask"].view(torch.bool)   # 0 / 1 bytes reinterpreted: no conversion kernel
-        if intermediates:
+        if "sigma" in out:
             out["sigma"] = out["sigma"].view(R, S)
         return out
 
@@ -528,15 +535,22 @@ class HipRenderer:
         L.check(self.lib.nl_sample_points(o.data_ptr(), d.data_ptr(), R, self.S, self.near, self.far, _ptr(z), zo.data_ptr(), xyz.data_ptr(), self._stream()), "nl_sample_points")
         return zo, xyz
 
-    def mv_aggregate(self, xyz, query_center, want_raw: bool = True):
+    def mv_aggregate(self, xyz, query_center, want_raw: bool = True, want_blend: bool = False):
         """nl_mv_aggregate.  want_raw=False skips the raw per-view tensors (rgb_feat, vis_ang come back as None) — the form the
-        fused render path uses, which selects the eight-samples-per-wave gather kernel."""
+        fused render path uses, which selects the eight-samples-per-wave gather kernel.
+        want_blend=True: -> (mv_feat, valid_s, blend1 (N, V, 32), rgbv (N, V, 4)), what heads_composite consumes beside feature_agg and geo."""
         self._ready()
         x = _dev_f32(xyz, self.device)
         N, V = x.shape[0], self.V
         qc = torch.as_tensor(query_center).detach().float().cpu().contiguous()
         mv = torch.empty(N, self.W, device=self.device)
         valid = torch.empty(N, dtype=torch.int32, device=self.device)
+        if want_blend:
+            bl1, rgbv = torch.empty(N, V, 32, device=self.device), torch.empty(N, V, 4, device=self.device)
+            ws = self._workspace(self.lib.nl_mv_aggregate_workspace_bytes(ct.byref(self.cfg), V, N))
+            L.check(self.lib.nl_mv_aggregate(ct.byref(self.cfg), self.packed.data_ptr(), self._frame, qc.data_ptr(), x.data_ptr(), N, mv.data_ptr(),
+                                             None, None, valid.data_ptr(), bl1.data_ptr(), rgbv.data_ptr(), ws.data_ptr(), ws.numel(), self._stream()), "nl_mv_aggregate")
+            return mv, valid, bl1, rgbv
         if not want_raw:
             ws = self._workspace(self.lib.nl_mv_aggregate_workspace_bytes(ct.byref(self.cfg), V, N))
             L.check(self.lib.nl_mv_aggregate(ct.byref(self.cfg), self.packed.data_ptr(), self._frame, qc.data_ptr(), x.data_ptr(), N, mv.data_ptr(),
@@ -865,10 +879,43 @@ class HipRenderer:
         L.check(self.lib.nl_ray_unet(ct.byref(self.cfg), self.packed.data_ptr(), xin.data_ptr(), R, geo.data_ptr(), ws.data_ptr(), ws.numel(), self._stream()), "nl_ray_unet")
         return geo
 
+    def heads_composite(self, z_vals, feature_agg, geo, blend1, rgbv, valid_s, white_bkgd: bool = False, want_weights: bool = True, want_feat: bool = True,
+                        want_sigma: bool = False):
+        """Rows a14-a18 as a stage (nl_heads_composite): density head, colour-blend tail, feat_mlp, front-to-back compositing and the valid-ray mask.
+        z_vals (R, S); feature_agg, geo (R*S, W); blend1 (R*S, V, 32) = the per-(sample, view) part of rgb_blending_mlp.0 (pre-activation, bias included);
+        rgbv (R*S, V, 4) = [r, g, b, visibility]; valid_s (R*S) int32 = the sample is seen by more than one view (None: the mask comes back all False).
+        -> dict like render_rays' (weights / feat left out on request, sigma (R, S) added on request)."""
+        if not self._weights_loaded:
+            raise RuntimeError("load_weights() first")
+        dev = self.device
+        z, fa, g, b1, rv = (_dev_f32(t, dev) for t in (z_vals, feature_agg, geo, blend1, rgbv))
+        R, S, W = z.shape[0], self.S, self.W
+        N = R * S
+        V = b1.numel() // (N * 32) if N else 1
+        if tuple(z.shape) != (R, S) or fa.numel() != N * W or g.numel() != N * W or b1.numel() != N * V * 32 or rv.numel() != N * V * 4:
+            raise ValueError(f"heads_composite: shapes do not fit R={R} S={S} W={W} V={V}")
+        vs = None if valid_s is None else torch.as_tensor(valid_s).to(device=dev, dtype=torch.int32).contiguous()
+        out = {"rgb": torch.empty(R, 3, device=dev), "depth": torch.empty(R, device=dev), "mask": torch.empty(R, dtype=torch.uint8, device=dev),
+               "depth_uncertainty": torch.empty(R, device=dev)}
+        if want_weights:
+            out["weights"] = torch.empty(R, S, device=dev)
+        if want_feat:
+            out["feat"] = torch.empty(R, self.C, device=dev)
+        if want_sigma:
+            out["sigma"] = torch.empty(R, S, device=dev)
+        ro = L.NlRenderOut()
+        for k, t in out.items():
+            setattr(ro, k, t.data_ptr())
+        ws = self._workspace(self.lib.nl_heads_composite_workspace_bytes(ct.byref(self.cfg), V, R))
+        L.check(self.lib.nl_heads_composite(ct.byref(self.cfg), self.packed.data_ptr(), V, z.data_ptr(), fa.data_ptr(), g.data_ptr(), b1.data_ptr(), rv.data_ptr(),
+                                            _ptr(vs), R, int(bool(white_bkgd)), ct.byref(ro), ws.data_ptr(), ws.numel(), self._stream()), "nl_heads_composite")
+        out["mask"] = out["mask"].view(torch.bool)
+        return out
+
 
 def render_rays_multi(jobs):
     """Several frames — each a HipRenderer holding its own support set — in ONE library call (nl_render_rays_multi): job =
-    (renderer, rays_o, rays_d, query_center (3,) or (R, 3)[, kwargs: z_vals, white_bkgd, want_feat, early_term_eps]).  The renderers must be of one
+    (renderer, rays_o, rays_d, query_center (3,) or (R, 3)[, kwargs: z_vals, white_bkgd, want_feat, early_term_eps, want_sigma (adds `sigma` (R, S), the per-sample density)]).  The renderers must be of one
     configuration and hold the same weights (the first one's packed blob serves all).  Outputs are bit-identical to `renderer.render_rays(...)` per job;
     the launch chains of the jobs run on library-owned streams forked from / joined into the current stream."""
     jobs = list(jobs)
@@ -904,6 +951,8 @@ def render_rays_multi(jobs):
                "mask": torch.empty(R, dtype=torch.uint8, device=dev), "depth_uncertainty": torch.empty(R, device=dev)}
         if kw.get("want_feat", True):
             out["feat"] = torch.empty(R, r.C, device=dev)
+        if kw.get("want_sigma", False):   # the per-sample density of the fused path (nl_render_out.sigma alone: same kernels, same outputs)
+            out["sigma"] = torch.empty(R, r.S, device=dev)
         ro = L.NlRenderOut()
         for k, t in out.items():
             setattr(ro, k, t.data_ptr())

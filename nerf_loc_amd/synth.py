@@ -287,6 +287,33 @@ def make_weights(cfg: SceneConfig, seed: int | None = None) -> Dict[str, np.ndar
     return out
 
 
+# Density-head rungs (scenes with surfaces).  make_weights gives a density head whose pre-activation (sigma_mlp.0 . geo + b) has mean -0.7 and standard
+# deviation 0.56: a thin medium in which no ray is opaque before its last sample.  A rung rescales that ONE layer so that the pre-activation has a target
+# (std, mean) on the scene at hand; rung A is the recipe `bias + 8, gain 1` (every ray opaque after a few dozen samples).
+SURFACE_RUNGS: Dict[str, Tuple[float, float] | None] = {"A": None, "B": (6.0, -2.0), "C": (10.0, -4.0), "D": (15.0, 0.0)}
+
+
+def surface_gain_offset(rung: str, pre: np.ndarray | None = None) -> Tuple[float, float]:
+    """-> (g, c) of density-head rung `rung`: the head becomes `g * (w . geo + b) + c`.  `pre` = the pre-activation `w . geo + b` of the UNSCALED head on the
+    scene the rung is wanted for, taken from a reference evaluation (the CPU oracle's `geo`), never from the code under test; rung A needs none."""
+    target = SURFACE_RUNGS[rung]
+    if target is None:
+        return 1.0, 8.0
+    if pre is None:
+        raise ValueError(f"rung {rung} is calibrated from the reference's pre-activation")
+    pre = np.asarray(pre, np.float64)
+    g = target[0] / float(pre.std())
+    return g, target[1] - g * float(pre.mean())
+
+
+def with_density_head(weights: Dict[str, np.ndarray], g: float, c: float) -> Dict[str, np.ndarray]:
+    """A copy of `weights` whose density head is `sigma_mlp.0.weight * g`, `sigma_mlp.0.bias * g + c` (every other tensor shared)."""
+    out = dict(weights)
+    out["sigma_mlp.0.weight"] = (weights["sigma_mlp.0.weight"].astype(np.float64) * g).astype(F32)
+    out["sigma_mlp.0.bias"] = (weights["sigma_mlp.0.bias"].astype(np.float64) * g + c).astype(F32)
+    return out
+
+
 def make_coord_desc_weights(cfg: "SceneConfig", seed: int = 0, matcher_dim: int = 192) -> Dict[str, np.ndarray]:
     """Seeded weights of `coord_desc_mlp_{coarse,fine}` (model.py:115-131: 63 -> W -> W -> matcher_hidden_dim, the per-scene fine-tuning heads that
     `use_scene_coord_memorization` adds — every shipped per-scene config turns it on)."""

@@ -42,6 +42,8 @@ def test_guard_limits_of_the_binding_equal_the_header():
     assert re.search(r"#define\s+NL_RENDER_PRECISION_GUARD\s+(\d+)u", hdr).group(1) == str(_lib.RENDER_PRECISION_GUARD)
     assert float(re.search(r"#define\s+NL_GUARD_LOGIT_LIMIT_F16MX\s+([0-9.]+)f", hdr).group(1)) == _lib.GUARD_LOGIT_LIMIT["f16mx"]
     assert float(re.search(r"#define\s+NL_GUARD_LOGIT_LIMIT_BF16X3\s+([0-9.]+)f", hdr).group(1)) == _lib.GUARD_LOGIT_LIMIT["bf16x3"]
+    assert float(re.search(r"#define\s+NL_GUARD_DENSITY_LIMIT_F16MX\s+([0-9.]+)f", hdr).group(1)) == _lib.GUARD_DENSITY_LIMIT["f16mx"]
+    assert set(re.findall(r"#define\s+NL_GUARD_DENSITY_LIMIT_(\w+)", hdr)) == {k.upper() for k in _lib.GUARD_DENSITY_LIMIT}
     assert int(re.search(r"#define\s+NL_DIAG_COUNT\s+(\d+)", hdr).group(1)) == _lib.DIAG_COUNT
     flags_all = int(re.search(r"#define\s+NL_RENDER_FLAGS_ALL\s+(\d+)u", hdr).group(1))
     assert flags_all == (_lib.RENDER_NO_SIDE_STREAM | _lib.RENDER_PRECISION_GUARD)

@@ -525,3 +525,66 @@ def test_precision_guard_escalates_on_ill_conditioned_frames_and_only_there():
     net.precision_guard = False
     net.render_rays(fresh(8.0), rd)
     assert net._renderers["fine"].precision == "f16mx" and len(net.guard_events) == 1
+
+
+@pytest.mark.gpu
+def test_precision_guard_escalates_on_dense_scenes_in_the_single_and_the_multi_frame_path():
+    """The guard's second indicator through the module: with a density head that renders surfaces (density ~ 40, beyond NL_GUARD_DENSITY_LIMIT_F16MX) an f16mx
+    module moves the frame to bf16x3 — in render_rays (the library's guard) AND in render_rays_frames over several data dicts (nl_render_rays_multi refuses
+    the flag, so the module applies the same limit to the per-sample densities it asks for) — and returns what a bf16x3 module returns; with the thin density
+    head of make_weights neither path escalates; the outputs of the multi-frame path carry no extra key."""
+    from nerf_loc_amd.conditional_nerf import ConditionalNeRF
+    from nerf_loc_amd.synth import make_rays, with_density_head
+    dev = torch.device("cuda:0")
+    cfg = SceneConfig("dense", R=24, S=32, W=128, V=4, H=48, Wimg=64, seed=31)
+    thin = dict(make_weights(cfg)); thin.update(make_depth_fusion_weights(cfg.seed))
+    limit = ConditionalNeRF.DENSITY_LIMIT["f16mx"]
+
+    def frames(weights, precision):
+        net, datas, rays_l = None, [], []
+        for seed in (31, 77):
+            cfg_i = cfg.replace(seed=seed)
+            frame = add_setup_inputs(cfg_i, make_frame(cfg_i))
+            case = {"cfg": cfg_i, "frame": frame, "rays": make_rays(cfg_i, frame), "weights": weights}
+            n, data, rd = _module_and_data(case, dev, precision=precision)
+            net = net or n
+            rd["depth_range"] = data["depth_range"][0]
+            datas.append(data); rays_l.append(rd)
+        return net, datas, rays_l
+
+    def reset(net):
+        net.support_neural_points = None
+        net.multiview_aggregator.vis_featmaps = None
+
+    for weights, dense in ((with_density_head(thin, 1.0, 40.0), True), (thin, False)):
+        net, datas, rays_l = frames(weights, "f16mx")
+        ref, _, _ = frames(weights, "bf16x3" if dense else "f16mx")
+        ref.precision_guard = False
+        want = []
+        for d, rd in zip(datas, rays_l):
+            reset(ref)
+            want.append({k: v.clone() for k, v in ref.render_rays(d, rd).items()})
+        # several data dicts in one call: the host-side mirror of the guard
+        outs = net.render_rays_frames(datas, rays_l)
+        assert all(set(o) == set(w) for o, w in zip(outs, want)), [sorted(o) for o in outs]
+        if dense:
+            assert [(e["frame"], e["from"], e["to"]) for e in net.guard_events] == [(0, "f16mx", "bf16x3"), (1, "f16mx", "bf16x3")], net.guard_events
+            assert all(e["density_max"] > limit and e["logit_absmax"] <= ConditionalNeRF.LOGIT_LIMIT["f16mx"] for e in net.guard_events), net.guard_events
+        else:
+            assert net.guard_events == []
+        for o, w in zip(outs, want):
+            assert torch.equal(o["mask"], w["mask"])
+            for k in ("rgb", "depth", "weights", "feat", "depth_uncertainty"):
+                assert rel_err(o[k].cpu().numpy(), w[k].cpu().numpy()) < 1e-5, (dense, k)
+        # one frame through render_rays: the library's guard
+        net.guard_events.clear()
+        reset(net)
+        out = net.render_rays(datas[0], rays_l[0])
+        dg = net._renderers["fine"].diagnostics()
+        if dense:
+            assert len(net.guard_events) == 1 and net.guard_events[0]["to"] == "bf16x3" and net.guard_events[0]["density_max"] > limit, net.guard_events
+            assert dg["guard_precision"] == "bf16x3" and dg["density_max"] > limit
+        else:
+            assert net.guard_events == [] and dg["guard_precision"] == "f16mx" and 0 < dg["density_max"] < limit
+        for k in ("rgb", "depth", "weights", "feat", "depth_uncertainty"):
+            assert rel_err(out[k].cpu().numpy(), want[0][k].cpu().numpy()) < 1e-5, (dense, k)

@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 import torch
 
-from tests.util import l2_rel, rel_err
+from tests.util import l2_rel, rel_err, surface_weights
 
 pytestmark = pytest.mark.gpu
 KEYS = ("rgb", "depth", "weights", "depth_uncertainty", "feat")
@@ -117,9 +117,9 @@ def test_early_termination_keeps_parity_and_skips_work(name):
     sc = _scene(name)
     cfg = sc["cfg"]
     # random-init weights give a thin medium (alpha ~ 0.03 per sample: no ray ever gets opaque before its last sample), so the
-    # density head's bias is raised to make surfaces: sigma ~ 8 -> transmittance below 1e-5 after a few dozen samples
-    sc["weights"] = dict(sc["weights"])
-    sc["weights"]["sigma_mlp.0.bias"] = sc["weights"]["sigma_mlp.0.bias"] + 8.0
+    # density head's bias is raised to make surfaces (rung A of nerf_loc_amd.synth.SURFACE_RUNGS): sigma ~ 8 -> transmittance below 1e-5 after a few dozen samples
+    sc["weights"], gain, offset = surface_weights(sc, "A")
+    assert (gain, offset) == (1.0, 8.0)
     r = _renderer(sc, "bf16x3")
     sel = np.arange(0, cfg.R, 4)
     o, d = sc["rays"]["rays_o"][sel], sc["rays"]["rays_d"][sel]
