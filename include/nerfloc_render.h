@@ -43,9 +43,9 @@ extern "C" {
 #pragma GCC visibility push(default)
 #endif
 
-#define NL_ABI_VERSION 7   /* 2: nl_render_rays_ex / nl_render_opts (early termination, per-ray query centres); 3: nl_render_opts.flags,
+#define NL_ABI_VERSION 8   /* 2: nl_render_rays_ex / nl_render_opts (early termination, per-ray query centres); 3: nl_render_opts.flags,
                             * reserved fields validated, side stream owned by the nl_frame; 5: NL_PREC_F16MX; 6: nl_frame_diagnostics;
-                            * 7: NL_RENDER_PRECISION_GUARD (the precision guard at the boundary), NL_DIAG_GUARD_* */
+                            * 7: NL_RENDER_PRECISION_GUARD (the precision guard at the boundary), NL_DIAG_GUARD_*; 8: nl_s2d_* (the coarse matcher) */
 #define NL_MAX_VIEWS 16
 #define NL_KNN_MAX_K 8
 
@@ -483,6 +483,23 @@ int nl_blend(const nl_config* cfg, const void* packed, const nl_frame* frame, co
              float* rgb_s, void* ws, size_t ws_bytes, void* stream);
 int nl_blend_backward(const nl_config* cfg, const void* packed, const nl_frame* frame, const float* query_center, const float* xyz, const float* feature_agg,
                       int64_t N, const float* g_rgb_s, float* g_xyz, float* g_feature_agg, float* g_query_center, void* ws, size_t ws_bytes, void* stream);
+
+/* ---- localisation head: the sparse-to-dense coarse matcher ----------------------------------------------------------------------------
+ * S2DMatching.forward in eval mode, models/matching/sparse_to_dense.py:80-151 (used by matcher.py:22,72): for N sparse 3-D descriptors desc0 (N,C) and M dense
+ * 2-D descriptors desc1 (M,C), score[n,m] = sigmoid(mlps(desc0[n] * desc1[m])) with mlps = C -> 128 -> ReLU -> 128 -> ReLU -> 1, then the mutual-nearest
+ * selection `mask = (s > thr) & (s == rowmax) & (s == colmax)` applied to the fp32 scores the kernel itself produced, ties included: match_j[n] is the FIRST
+ * column of row n's mask (-1: none), match_score[n] that score (0: none).  The N x M x C product and the hidden activations are never written.
+ * C: a multiple of 32, 32..256 (NL_ERR_UNSUPPORTED otherwise); N, M >= 1.  precision: NL_PREC_F32, NL_PREC_BF16X3 (parity modes), NL_PREC_BF16 (throughput);
+ * NL_PREC_F16MX is NL_ERR_UNSUPPORTED here.  desc0, desc1 and packed must be 16-byte aligned.
+ * The packed image holds mlps.0.weight (128,C), mlps.0.bias, mlps.2.weight (128,128), mlps.2.bias, mlps.4.weight (1,128), mlps.4.bias (DEVICE pointers, fp32,
+ * torch layout) in the kernels' fragment order for every precision.
+ * scores_out (N,M) may be NULL: the scores then live in the workspace (nl_s2d_min_workspace_bytes(.., want_scores = 0) grows by N*M*4). */
+size_t nl_s2d_packed_weights_bytes(int C);
+int nl_s2d_pack_weights(int C, const float* w1, const float* b1, const float* w2, const float* b2, const float* w3, const float* b3, void* packed,
+                        size_t packed_bytes, void* stream);
+size_t nl_s2d_min_workspace_bytes(int64_t N, int64_t M, int C, int want_scores);
+int nl_s2d_match(const void* packed, int C, int precision, const float* desc0, int64_t N, const float* desc1, int64_t M, float thr, float* scores_out,
+                 int32_t* match_j, float* match_score, void* workspace, size_t workspace_bytes, void* stream);
 
 #if defined(__GNUC__) || defined(__clang__)
 #pragma GCC visibility pop

@@ -1,0 +1,487 @@
+// Sparse-to-dense coarse matcher (reference: models/matching/sparse_to_dense.py:80-151): for N sparse 3-D descriptors and M dense 2-D descriptors, both C wide,
+//   score[n, m] = sigmoid( W3 . relu( W2 . relu( W1 . (desc0[n] * desc1[m]) + b1 ) + b2 ) + b3 )          (C -> 128 -> 128 -> 1)
+// then the mutual-nearest selection on those scores.  Nothing of size N x M x anything but the N x M scores is written.
+//
+// Score kernel (transposed form, as tgemm.hip: D[hidden unit][pair] = W . X): a wave owns 32 columns m and TWO rows n (two 32-pair column tiles that share every
+// weight fragment and every desc1 load); the product rows x = desc0[n] * desc1[m] are built in registers per 16-wide k-step and split to bf16 hi / lo; layer 1's
+// accumulators (4 x 32 hidden units x 32 pairs per tile) become layer 2's B operand without leaving the lane: layer 2's K order inside every 32-block is the
+// accumulator order (k-step s of block b takes accumulator registers 8 s .. 8 s + 7), the weights are packed to match.  The last 128 -> 1 layer is an in-lane dot
+// over the lane's 64 hidden units plus the other half-wave's 64.
+// Weights: one packed image (nl_s2d_pack_weights) of A fragments in lane order (16 B per lane, 1 KiB per fragment).  The hi planes of W1 and W2, the lo plane of W2
+// and the bias / W3 tables are copied to LDS once per workgroup (112 KiB at C = 192, 128 KiB at C = 256) by a persistent grid; the lo plane of W1 (48 .. 64 KiB) does
+// not fit next to them and is read from L2, where every workgroup reads the same bytes.  NL_PREC_F32 reads a second, fp32 fragment image (v_mfma_f32_32x32x2_f32) from L2.
+// The value of a pair depends on its two descriptor rows, the weights and the mode only: each output column of an MFMA is an independent dot product in a fixed
+// order, the cross-half sum of the last layer is commutative, and no float atomic touches a value.
+// Selection: the score kernel reduces rowmax[N] / colmax[M] with unsigned atomic max on the float bits (scores are >= 0); pass 2, one wave per row, finds the FIRST j
+// with s > thr, s == rowmax[i], s == colmax[j] — the reference's rule on the scores themselves, ties included.
+#include "common.h"
+
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef short bf16x8 __attribute__((ext_vector_type(8)));
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+
+namespace {
+
+constexpr int S2D_H = 128;                 // hidden width (fixed, as the reference)
+constexpr int S2D_SMALL_BYTES = 2048;      // b1p[2][64], b2p[2][64], w3p[2][64], b3
+constexpr int S2D_W2_BYTES = 32 * 1024;    // one bf16 plane of W2: 32 fragments
+constexpr int S2D_F32_LDS = 4 * 128 * 64 * 4;   // fp32 kernel: the hidden activations of 4 waves x 2 tiles, lane-private columns
+constexpr int S2D_NROWS = 32;              // rows n of one work item (4 waves x 2 rows x 4 iterations)
+
+struct S2dLayout {
+  size_t w1hi, w2hi, w2lo, small, w1lo, f32w1, f32w2, total;
+  size_t lds_bytes;   // the prefix [0, lds_bytes) is what the bf16 kernels keep in LDS
+};
+__host__ __device__ inline S2dLayout s2d_layout(int C) {
+  S2dLayout l;
+  const size_t w1 = (size_t)C * S2D_H * 2;   // one bf16 plane of W1
+  l.w1hi = 0;
+  l.w2hi = l.w1hi + w1;
+  l.w2lo = l.w2hi + S2D_W2_BYTES;
+  l.small = l.w2lo + S2D_W2_BYTES;
+  l.lds_bytes = l.small + S2D_SMALL_BYTES;
+  l.w1lo = l.lds_bytes;
+  l.f32w1 = l.w1lo + w1;
+  l.f32w2 = l.f32w1 + (size_t)C * S2D_H * 4;
+  l.total = l.f32w2 + (size_t)S2D_H * S2D_H * 4;
+  return l;
+}
+
+// hidden unit held by accumulator register r of 32-block b in half-wave hh (C/D layout of the 32x32 MFMAs: row = (r & 3) + 8 (r >> 2) + 4 hh)
+__host__ __device__ inline int s2d_unit(int b, int r, int hh) { return 32 * b + 8 * (r >> 2) + 4 * hh + (r & 3); }
+
+// ------------------------------------------------------------------------------------------ packing
+struct S2dPackArgs {
+  const float* w1; const float* b1; const float* w2; const float* b2; const float* w3; const float* b3;
+  unsigned char* img;
+  int C;
+};
+
+__device__ __forceinline__ unsigned short s2d_bf16(float x) {   // round to nearest even
+  unsigned u = __float_as_uint(x);
+  u += 0x7fffu + ((u >> 16) & 1u);
+  return (unsigned short)(u >> 16);
+}
+
+__global__ __launch_bounds__(256) void s2d_pack_kernel(const S2dPackArgs a) {
+  const S2dLayout L = s2d_layout(a.C);
+  const int C = a.C;
+  const int n1 = C * S2D_H, n2 = S2D_H * S2D_H;
+  const int total = 2 * n1 + 2 * n2 + 512;
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < total; i += gridDim.x * 256) {
+    if (i < n1) {   // W1, bf16 planes: fragment (s, rb), lane, slot j <-> W1[32 rb + (lane & 31)][16 s + 8 (lane >> 5) + j]
+      const int j = i & 7, lane = (i >> 3) & 63, f = i >> 9, rb = f & 3, s = f >> 2;
+      const float v = a.w1[(size_t)(32 * rb + (lane & 31)) * C + 16 * s + 8 * (lane >> 5) + j];
+      const unsigned short h = s2d_bf16(v);
+      ((unsigned short*)(a.img + L.w1hi))[i] = h;
+      ((unsigned short*)(a.img + L.w1lo))[i] = s2d_bf16(v - __uint_as_float((unsigned)h << 16));
+    } else if (i < n1 + n2) {   // W2, bf16 planes: fragment (b, s, rb): slot j <-> hidden unit of accumulator register 8 s + j of block b
+      const int e = i - n1;
+      const int j = e & 7, lane = (e >> 3) & 63, f = e >> 9, rb = f & 3, s = (f >> 2) & 1, b = f >> 3;
+      const float v = a.w2[(size_t)(32 * rb + (lane & 31)) * S2D_H + s2d_unit(b, 8 * s + j, lane >> 5)];
+      const unsigned short h = s2d_bf16(v);
+      ((unsigned short*)(a.img + L.w2hi))[e] = h;
+      ((unsigned short*)(a.img + L.w2lo))[e] = s2d_bf16(v - __uint_as_float((unsigned)h << 16));
+    } else if (i < 2 * n1 + n2) {   // W1, fp32: fragment (g, t, rb), lane <-> W1[32 rb + (lane & 31)][8 g + 4 (lane >> 5) + t]
+      const int e = i - n1 - n2;
+      const int lane = e & 63, f = e >> 6, rb = f & 3, t = (f >> 2) & 3, g = f >> 4;
+      ((float*)(a.img + L.f32w1))[e] = a.w1[(size_t)(32 * rb + (lane & 31)) * C + 8 * g + 4 * (lane >> 5) + t];
+    } else if (i < 2 * n1 + 2 * n2) {   // W2, fp32: fragment (b, t, rb), lane <-> W2[32 rb + (lane & 31)][unit of accumulator register t of block b]
+      const int e = i - 2 * n1 - n2;
+      const int lane = e & 63, f = e >> 6, rb = f & 3, t = (f >> 2) & 15, b = f >> 6;
+      ((float*)(a.img + L.f32w2))[e] = a.w2[(size_t)(32 * rb + (lane & 31)) * S2D_H + s2d_unit(b, t, lane >> 5)];
+    } else {   // b1p / b2p / w3p [hh][16 b + r] in accumulator order, then b3 and zero padding
+      const int e = i - 2 * n1 - 2 * n2;
+      float v = 0.f;
+      if (e < 384) {
+        const int which = e >> 7, q = e & 127, hh = q >> 6, b = (q >> 4) & 3, r = q & 15;
+        const float* src = which == 0 ? a.b1 : (which == 1 ? a.b2 : a.w3);
+        v = src[s2d_unit(b, r, hh)];
+      } else if (e == 384) {
+        v = a.b3[0];
+      }
+      ((float*)(a.img + L.small))[e] = v;
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------------ scores
+struct S2dArgs {
+  const unsigned char* img;
+  const float* desc0; const float* desc1;
+  float* scores;
+  unsigned* rowmax; unsigned* colmax;
+  int N, M, C;
+};
+
+__device__ __forceinline__ bf16x8 s2d_frag(const uint4 v) { return __builtin_bit_cast(bf16x8, v); }
+__device__ __forceinline__ bf16x8 s2d_frag(unsigned a, unsigned b, unsigned c, unsigned d) { return __builtin_bit_cast(bf16x8, u32x4{a, b, c, d}); }
+
+// bias + ReLU + last layer + sigmoid + stores + maxima, shared by the two score kernels.  acc[t][b]: tile t (row n0 + t), hidden 32-block b.
+__device__ __forceinline__ void s2d_finish(const S2dArgs& a, const float* small, const f32x16 (&acc)[2][4], int lane, int n0, bool has1, int m, unsigned& colmax) {
+  const int hh = lane >> 5;
+  const float* b2p = small + 128 + 64 * hh;
+  const float* w3p = small + 256 + 64 * hh;
+  float dot[2] = {0.f, 0.f};
+#pragma unroll
+  for (int b = 0; b < 4; ++b)
+#pragma unroll
+    for (int r4 = 0; r4 < 4; ++r4) {
+      const float4 bb = *(const float4*)(b2p + 16 * b + 4 * r4), ww = *(const float4*)(w3p + 16 * b + 4 * r4);
+      const float bv[4] = {bb.x, bb.y, bb.z, bb.w}, wv[4] = {ww.x, ww.y, ww.z, ww.w};
+#pragma unroll
+      for (int e = 0; e < 4; ++e)
+#pragma unroll
+        for (int t = 0; t < 2; ++t) dot[t] += fmaxf(acc[t][b][4 * r4 + e] + bv[e], 0.f) * wv[e];
+    }
+  const float b3 = small[384];
+  float sc[2];
+#pragma unroll
+  for (int t = 0; t < 2; ++t) {
+    const float tot = dot[t] + __shfl_xor(dot[t], 32);   // the two half-waves' 64 units each: a + b == b + a, both halves hold the same bits
+    sc[t] = nl_sigmoid(tot + b3);
+  }
+  const bool mok = m < a.M;
+  const bool ok0 = mok, ok1 = mok && has1;
+  const unsigned u0 = ok0 ? __float_as_uint(sc[0]) : 0u, u1 = ok1 ? __float_as_uint(sc[1]) : 0u;
+  colmax = max(colmax, max(u0, u1));
+  // half-wave hh stores tile hh: 32 consecutive floats of row n0 + hh
+  const bool okm = hh ? ok1 : ok0;
+  const float mine = hh ? sc[1] : sc[0];
+  const int nm = n0 + hh;
+  if (okm) a.scores[(size_t)nm * a.M + m] = mine;
+  unsigned rm = okm ? __float_as_uint(mine) : 0u;   // scores are >= 0: the order of the bits is the order of the values
+#pragma unroll
+  for (int o = 16; o >= 1; o >>= 1) rm = max(rm, (unsigned)__shfl_xor((int)rm, o));
+  if ((lane & 31) == 0 && (hh == 0 || has1)) atomicMax(a.rowmax + nm, rm);
+}
+
+template <bool X3>
+__global__ __launch_bounds__(256) void s2d_bf16_kernel(const S2dArgs a) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char s2d_lds[];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, hh = lane >> 5;
+  const int C = a.C, nk1 = C >> 4;
+  const S2dLayout L = s2d_layout(C);
+  {
+    const uint4* src = (const uint4*)a.img;
+    uint4* dst = (uint4*)s2d_lds;
+    const int n16 = (int)(L.lds_bytes >> 4);
+    for (int i = tid; i < n16; i += 256) dst[i] = src[i];
+  }
+  __syncthreads();
+  const uint4* w1hi = (const uint4*)(s2d_lds + L.w1hi);
+  const uint4* w2hi = (const uint4*)(s2d_lds + L.w2hi);
+  const uint4* w2lo = (const uint4*)(s2d_lds + L.w2lo);
+  const float* small = (const float*)(s2d_lds + L.small);
+  const uint4* w1lo = (const uint4*)(a.img + L.w1lo);
+  const float* b1p = small + 64 * hh;
+
+  const int MT = (a.M + 31) >> 5, NB = (a.N + S2D_NROWS - 1) / S2D_NROWS;
+  const long long items = (long long)MT * NB;
+  for (long long item = blockIdx.x; item < items; item += gridDim.x) {
+    const int mt = (int)(item / NB), nb = (int)(item - (long long)mt * NB);
+    const int m = mt * 32 + (lane & 31);
+    const float* d1p = a.desc1 + (size_t)min(m, a.M - 1) * C + 8 * hh;
+    unsigned colmax = 0u;
+    for (int it = 0; it < S2D_NROWS / 8; ++it) {
+      const int n0 = nb * S2D_NROWS + it * 8 + wave * 2;
+      if (n0 >= a.N) break;   // wave-uniform; no barrier inside the item loop
+      const bool has1 = n0 + 1 < a.N;
+      const float* d0a = a.desc0 + (size_t)n0 * C + 8 * hh;
+      const float* d0b = a.desc0 + (size_t)(has1 ? n0 + 1 : n0) * C + 8 * hh;
+
+      f32x16 acc[2][4];
+#pragma unroll
+      for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int b = 0; b < 4; ++b)
+#pragma unroll
+          for (int r = 0; r < 16; ++r) acc[t][b][r] = 0.f;
+
+      // ---- layer 1: K = C, the B operand built per k-step from desc1 (shared by both tiles) and the two desc0 rows
+      for (int s = 0; s < nk1; ++s) {
+        const float4 x0 = *(const float4*)(d1p + 16 * s), x1 = *(const float4*)(d1p + 16 * s + 4);
+        const float4 ya0 = *(const float4*)(d0a + 16 * s), ya1 = *(const float4*)(d0a + 16 * s + 4);
+        const float4 yb0 = *(const float4*)(d0b + 16 * s), yb1 = *(const float4*)(d0b + 16 * s + 4);
+        unsigned ph[2][4], pl[2][4];
+        nl_split_bf16_pair(x0.x * ya0.x, x0.y * ya0.y, ph[0][0], pl[0][0]);
+        nl_split_bf16_pair(x0.z * ya0.z, x0.w * ya0.w, ph[0][1], pl[0][1]);
+        nl_split_bf16_pair(x1.x * ya1.x, x1.y * ya1.y, ph[0][2], pl[0][2]);
+        nl_split_bf16_pair(x1.z * ya1.z, x1.w * ya1.w, ph[0][3], pl[0][3]);
+        nl_split_bf16_pair(x0.x * yb0.x, x0.y * yb0.y, ph[1][0], pl[1][0]);
+        nl_split_bf16_pair(x0.z * yb0.z, x0.w * yb0.w, ph[1][1], pl[1][1]);
+        nl_split_bf16_pair(x1.x * yb1.x, x1.y * yb1.y, ph[1][2], pl[1][2]);
+        nl_split_bf16_pair(x1.z * yb1.z, x1.w * yb1.w, ph[1][3], pl[1][3]);
+        bf16x8 bh[2], bl[2];
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+          bh[t] = s2d_frag(ph[t][0], ph[t][1], ph[t][2], ph[t][3]);
+          bl[t] = s2d_frag(pl[t][0], pl[t][1], pl[t][2], pl[t][3]);
+        }
+#pragma unroll
+        for (int rb = 0; rb < 4; ++rb) {
+          const int f = ((s << 2) + rb) * 64 + lane;
+          const bf16x8 ah = s2d_frag(w1hi[f]);
+          if (X3) {
+            const bf16x8 al = s2d_frag(w1lo[f]);
+#pragma unroll
+            for (int t = 0; t < 2; ++t) {
+              acc[t][rb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh[t], acc[t][rb], 0, 0, 0);
+              acc[t][rb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl[t], acc[t][rb], 0, 0, 0);
+            }
+          }
+#pragma unroll
+          for (int t = 0; t < 2; ++t) acc[t][rb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh[t], acc[t][rb], 0, 0, 0);
+        }
+      }
+
+      // ---- bias + ReLU + split: layer 2's B operand, k-step (b, s) = accumulator registers 8 s .. 8 s + 7 of block b
+      unsigned hhi[2][4][8], hlo[2][4][8];
+#pragma unroll
+      for (int b = 0; b < 4; ++b)
+#pragma unroll
+        for (int r4 = 0; r4 < 4; ++r4) {
+          const float4 bb = *(const float4*)(b1p + 16 * b + 4 * r4);
+#pragma unroll
+          for (int t = 0; t < 2; ++t) {
+            nl_split_bf16_pair(fmaxf(acc[t][b][4 * r4 + 0] + bb.x, 0.f), fmaxf(acc[t][b][4 * r4 + 1] + bb.y, 0.f), hhi[t][b][2 * r4], hlo[t][b][2 * r4]);
+            nl_split_bf16_pair(fmaxf(acc[t][b][4 * r4 + 2] + bb.z, 0.f), fmaxf(acc[t][b][4 * r4 + 3] + bb.w, 0.f), hhi[t][b][2 * r4 + 1], hlo[t][b][2 * r4 + 1]);
+          }
+        }
+
+      // ---- layer 2: K = 128
+#pragma unroll
+      for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int b = 0; b < 4; ++b)
+#pragma unroll
+          for (int r = 0; r < 16; ++r) acc[t][b][r] = 0.f;
+#pragma unroll
+      for (int b = 0; b < 4; ++b)
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+          bf16x8 bh[2], bl[2];
+#pragma unroll
+          for (int t = 0; t < 2; ++t) {
+            bh[t] = s2d_frag(hhi[t][b][4 * s], hhi[t][b][4 * s + 1], hhi[t][b][4 * s + 2], hhi[t][b][4 * s + 3]);
+            bl[t] = s2d_frag(hlo[t][b][4 * s], hlo[t][b][4 * s + 1], hlo[t][b][4 * s + 2], hlo[t][b][4 * s + 3]);
+          }
+#pragma unroll
+          for (int rb = 0; rb < 4; ++rb) {
+            const int f = (((b * 2 + s) << 2) + rb) * 64 + lane;
+            const bf16x8 ah = s2d_frag(w2hi[f]);
+            if (X3) {
+              const bf16x8 al = s2d_frag(w2lo[f]);
+#pragma unroll
+              for (int t = 0; t < 2; ++t) {
+                acc[t][rb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh[t], acc[t][rb], 0, 0, 0);
+                acc[t][rb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl[t], acc[t][rb], 0, 0, 0);
+              }
+            }
+#pragma unroll
+            for (int t = 0; t < 2; ++t) acc[t][rb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh[t], acc[t][rb], 0, 0, 0);
+          }
+        }
+
+      s2d_finish(a, small, acc, lane, n0, has1, m, colmax);
+    }
+    if (hh == 0 && m < a.M && colmax != 0u) atomicMax(a.colmax + m, colmax);
+  }
+}
+
+// NL_PREC_F32: the same walk with v_mfma_f32_32x32x2_f32; half-wave hh supplies k slot hh of every step.  Layer 1 takes 8 channels per group (a float4 of desc1 per
+// half-wave: step t of group g multiplies channel 8 g + 4 hh + t), layer 2's step t of block b takes accumulator register t.  Weight fragments come from L2 / L1.
+__global__ __launch_bounds__(256) void s2d_f32_kernel(const S2dArgs a) {
+  __shared__ __attribute__((aligned(16))) float small[S2D_SMALL_BYTES / 4];
+  extern __shared__ __attribute__((aligned(16))) float hidden[];   // S2D_F32_LDS bytes
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, hh = lane >> 5;
+  const int C = a.C, ng = C >> 3;
+  const S2dLayout L = s2d_layout(C);
+  for (int i = tid; i < S2D_SMALL_BYTES / 4; i += 256) small[i] = ((const float*)(a.img + L.small))[i];
+  __syncthreads();
+  const float* w1f = (const float*)(a.img + L.f32w1);
+  const float* w2f = (const float*)(a.img + L.f32w2);
+  const float* b1p = small + 64 * hh;
+  float* hbuf = hidden + wave * (128 * 64) + lane;   // [2 tiles x 64 values][64 lanes] per wave: only this lane reads what it wrote
+
+  const int MT = (a.M + 31) >> 5, NB = (a.N + S2D_NROWS - 1) / S2D_NROWS;
+  const long long items = (long long)MT * NB;
+  for (long long item = blockIdx.x; item < items; item += gridDim.x) {
+    const int mt = (int)(item / NB), nb = (int)(item - (long long)mt * NB);
+    const int m = mt * 32 + (lane & 31);
+    const float* d1p = a.desc1 + (size_t)min(m, a.M - 1) * C + 4 * hh;
+    unsigned colmax = 0u;
+    for (int it = 0; it < S2D_NROWS / 8; ++it) {
+      const int n0 = nb * S2D_NROWS + it * 8 + wave * 2;
+      if (n0 >= a.N) break;
+      const bool has1 = n0 + 1 < a.N;
+      const float* d0a = a.desc0 + (size_t)n0 * C + 4 * hh;
+      const float* d0b = a.desc0 + (size_t)(has1 ? n0 + 1 : n0) * C + 4 * hh;
+
+      f32x16 acc[2][4];
+#pragma unroll
+      for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int b = 0; b < 4; ++b)
+#pragma unroll
+          for (int r = 0; r < 16; ++r) acc[t][b][r] = 0.f;
+
+      for (int g = 0; g < ng; ++g) {
+        const float4 x = *(const float4*)(d1p + 8 * g), ya = *(const float4*)(d0a + 8 * g), yb = *(const float4*)(d0b + 8 * g);
+        const float pa[4] = {x.x * ya.x, x.y * ya.y, x.z * ya.z, x.w * ya.w};
+        const float pb[4] = {x.x * yb.x, x.y * yb.y, x.z * yb.z, x.w * yb.w};
+#pragma unroll
+        for (int t = 0; t < 4; ++t)
+#pragma unroll
+          for (int rb = 0; rb < 4; ++rb) {
+            const float w = w1f[(((g * 4 + t) << 2) + rb) * 64 + lane];
+            acc[0][rb] = __builtin_amdgcn_mfma_f32_32x32x2f32(w, pa[t], acc[0][rb], 0, 0, 0);
+            acc[1][rb] = __builtin_amdgcn_mfma_f32_32x32x2f32(w, pb[t], acc[1][rb], 0, 0, 0);
+          }
+      }
+
+      // bias + ReLU; the 128 values per lane are parked in a lane-private LDS column so that layer 2 can be a rolled loop (fully unrolled, its 256 fragment
+      // loads are hoisted and the kernel spills)
+#pragma unroll
+      for (int b = 0; b < 4; ++b)
+#pragma unroll
+        for (int r4 = 0; r4 < 4; ++r4) {
+          const float4 bb = *(const float4*)(b1p + 16 * b + 4 * r4);
+          const float bv[4] = {bb.x, bb.y, bb.z, bb.w};
+#pragma unroll
+          for (int e = 0; e < 4; ++e)
+#pragma unroll
+            for (int t = 0; t < 2; ++t) hbuf[(t * 64 + 16 * b + 4 * r4 + e) * 64] = fmaxf(acc[t][b][4 * r4 + e] + bv[e], 0.f);
+        }
+#pragma unroll
+      for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int b = 0; b < 4; ++b)
+#pragma unroll
+          for (int r = 0; r < 16; ++r) acc[t][b][r] = 0.f;
+#pragma unroll 2
+      for (int k = 0; k < 64; ++k) {   // k = 16 b + t: step t of block b takes accumulator register t
+        const float h0 = hbuf[k * 64], h1 = hbuf[(64 + k) * 64];
+#pragma unroll
+        for (int rb = 0; rb < 4; ++rb) {
+          const float w = w2f[((k << 2) + rb) * 64 + lane];
+          acc[0][rb] = __builtin_amdgcn_mfma_f32_32x32x2f32(w, h0, acc[0][rb], 0, 0, 0);
+          acc[1][rb] = __builtin_amdgcn_mfma_f32_32x32x2f32(w, h1, acc[1][rb], 0, 0, 0);
+        }
+      }
+
+      s2d_finish(a, small, acc, lane, n0, has1, m, colmax);
+    }
+    if (hh == 0 && m < a.M && colmax != 0u) atomicMax(a.colmax + m, colmax);
+  }
+}
+
+// ------------------------------------------------------------------------------------------ selection
+// one wave per row: the first column j with s > thr, s == rowmax[i], s == colmax[j] (sparse_to_dense.py:136-142 on the kernel's own scores)
+__global__ __launch_bounds__(256) void s2d_select_kernel(const float* scores, const unsigned* rowmax, const unsigned* colmax, int N, int M, float thr,
+                                                         int32_t* match_j, float* match_score) {
+  const int lane = threadIdx.x & 63;
+  const int n = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (n >= N) return;
+  const unsigned rm = rowmax[n];
+  int found = -1;
+  if (__uint_as_float(rm) > thr) {
+    const float* row = scores + (size_t)n * M;
+    for (int j0 = 0; j0 < M; j0 += 64) {
+      const int j = j0 + lane;
+      bool hit = false;
+      if (j < M) {
+        const unsigned s = __float_as_uint(row[j]);
+        hit = s == rm && s == colmax[j];
+      }
+      const unsigned long long bal = __ballot(hit);
+      if (bal) { found = j0 + __builtin_ctzll(bal); break; }
+    }
+  }
+  if (lane == 0) {
+    match_j[n] = found;
+    match_score[n] = found >= 0 ? __uint_as_float(rm) : 0.f;
+  }
+}
+
+bool s2d_c_ok(int C) { return C >= 32 && C <= 256 && (C & 31) == 0; }
+
+struct S2dWs { size_t rowmax, colmax, scores, total; };
+S2dWs s2d_ws(int64_t N, int64_t M, bool want_scores) {
+  S2dWs w;
+  w.rowmax = 0;
+  w.colmax = nl_align_up((size_t)N * 4, 256);
+  w.scores = w.colmax + nl_align_up((size_t)M * 4, 256);
+  w.total = w.scores + (want_scores ? 0 : nl_align_up((size_t)N * (size_t)M * 4, 256));
+  return w;
+}
+bool s2d_shape_ok(int64_t N, int64_t M) { return N >= 1 && M >= 1 && N <= (1 << 30) && M <= (1 << 30); }
+
+}  // namespace
+
+extern "C" {
+
+size_t nl_s2d_packed_weights_bytes(int C) { return s2d_c_ok(C) ? s2d_layout(C).total : 0; }
+
+int nl_s2d_pack_weights(int C, const float* w1, const float* b1, const float* w2, const float* b2, const float* w3, const float* b3, void* packed,
+                        size_t packed_bytes, void* stream) {
+  if (!s2d_c_ok(C)) return C > 0 ? NL_ERR_UNSUPPORTED : NL_ERR_BAD_ARG;
+  if (!w1 || !b1 || !w2 || !b2 || !w3 || !b3 || !packed) return NL_ERR_BAD_ARG;
+  if (((uintptr_t)packed & 15) != 0) return NL_ERR_BAD_ARG;
+  if (packed_bytes < s2d_layout(C).total) return NL_ERR_WORKSPACE;
+  S2dPackArgs a{w1, b1, w2, b2, w3, b3, (unsigned char*)packed, C};
+  hipLaunchKernelGGL(s2d_pack_kernel, dim3(128), dim3(256), 0, (hipStream_t)stream, a);
+  NL_LAUNCH_CHECK();
+  return NL_OK;
+}
+
+size_t nl_s2d_min_workspace_bytes(int64_t N, int64_t M, int C, int want_scores) {
+  if (!s2d_c_ok(C) || !s2d_shape_ok(N, M)) return 0;
+  return s2d_ws(N, M, want_scores != 0).total;
+}
+
+int nl_s2d_match(const void* packed, int C, int precision, const float* desc0, int64_t N, const float* desc1, int64_t M, float thr, float* scores_out,
+                 int32_t* match_j, float* match_score, void* workspace, size_t workspace_bytes, void* stream) {
+  if (N < 1 || M < 1 || C < 1) return NL_ERR_BAD_ARG;
+  if (!s2d_c_ok(C) || !s2d_shape_ok(N, M)) return NL_ERR_UNSUPPORTED;
+  if (precision == NL_PREC_F16MX) return NL_ERR_UNSUPPORTED;
+  if (precision != NL_PREC_F32 && precision != NL_PREC_BF16X3 && precision != NL_PREC_BF16) return NL_ERR_BAD_ARG;
+  if (!packed || !desc0 || !desc1 || !match_j || !match_score) return NL_ERR_BAD_ARG;
+  if ((((uintptr_t)packed | (uintptr_t)desc0 | (uintptr_t)desc1) & 15) != 0) return NL_ERR_BAD_ARG;   // read as 16-byte pieces
+  if ((((uintptr_t)scores_out | (uintptr_t)match_j | (uintptr_t)match_score) & 3) != 0) return NL_ERR_BAD_ARG;
+  const S2dWs w = s2d_ws(N, M, scores_out != nullptr);
+  if (!workspace || workspace_bytes < w.total || ((uintptr_t)workspace & 15) != 0) return NL_ERR_WORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  unsigned char* ws = (unsigned char*)workspace;
+  S2dArgs a;
+  a.img = (const unsigned char*)packed;
+  a.desc0 = desc0; a.desc1 = desc1;
+  a.scores = scores_out ? scores_out : (float*)(ws + w.scores);
+  a.rowmax = (unsigned*)(ws + w.rowmax);
+  a.colmax = (unsigned*)(ws + w.colmax);
+  a.N = (int)N; a.M = (int)M; a.C = C;
+  const int cus = nl_persistent_cus();
+  if (cus < 0) return cus;
+  NL_CHECK_HIP(hipMemsetAsync(ws, 0, w.scores, st));
+  const int64_t items = nl_cdiv(M, 32) * nl_cdiv(N, S2D_NROWS);
+  const unsigned grid = (unsigned)(items < cus ? items : cus);
+  if (precision == NL_PREC_F32) {
+    NL_CHECK_HIP(hipFuncSetAttribute((const void*)s2d_f32_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, S2D_F32_LDS));
+    hipLaunchKernelGGL(s2d_f32_kernel, dim3(grid), dim3(256), S2D_F32_LDS, st, a);
+  } else {
+    const size_t lds = s2d_layout(C).lds_bytes;
+    if (precision == NL_PREC_BF16X3) {
+      NL_CHECK_HIP(hipFuncSetAttribute((const void*)s2d_bf16_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+      hipLaunchKernelGGL(s2d_bf16_kernel<true>, dim3(grid), dim3(256), lds, st, a);
+    } else {
+      NL_CHECK_HIP(hipFuncSetAttribute((const void*)s2d_bf16_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+      hipLaunchKernelGGL(s2d_bf16_kernel<false>, dim3(grid), dim3(256), lds, st, a);
+    }
+  }
+  NL_LAUNCH_CHECK();
+  hipLaunchKernelGGL(s2d_select_kernel, dim3((unsigned)nl_cdiv(N, 4)), dim3(256), 0, st, a.scores, a.rowmax, a.colmax, (int)N, (int)M, thr, match_j, match_score);
+  NL_LAUNCH_CHECK();
+  return NL_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,129 @@
+"""Drop-in for the reference's coarse matcher, `S2DMatching` (models/matching/sparse_to_dense.py:80-151, used by matcher.py:22,72).
+
+Eval mode on a HIP device is one library call (nl_s2d_match, csrc/s2d.hip): the N x M x C outer product and the two hidden tensors of the reference's
+formulation are never materialised.  Training mode, or an input that requires grad, runs the reference's formulation in eager PyTorch in row chunks (plumbing
+so that swapping the class does not break a training script; there is no gradient kernel).  Eval mode on CPU tensors is refused: no CPU fallback.
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+import torch
+import torch.nn as nn
+
+from . import _lib
+
+_HIDDEN = 128
+_PARAMS = ("mlps.0.weight", "mlps.0.bias", "mlps.2.weight", "mlps.2.bias", "mlps.4.weight", "mlps.4.bias")
+
+
+def sigmoid_focal_loss(logits: torch.Tensor, target: torch.Tensor, alpha: float = 0.25, gamma: float = 2.0) -> torch.Tensor:
+    """Element-wise sigmoid focal loss with unit anchor weights (sparse_to_dense.py:14-78); the caller takes the mean."""
+    p = torch.sigmoid(logits)
+    alpha_w = target * alpha + (1 - target) * (1 - alpha)
+    pt = target * (1.0 - p) + (1.0 - target) * p
+    bce = torch.clamp(logits, min=0) - logits * target + torch.log1p(torch.exp(-torch.abs(logits)))
+    return alpha_w * torch.pow(pt, gamma) * bce
+
+
+def select_mutual_nearest(score: torch.Tensor, thr: float):
+    """The reference's selection (sparse_to_dense.py:136-142): (i_ids, j_ids)."""
+    mask = (score > thr) & (score == score.max(dim=1, keepdim=True)[0]) & (score == score.max(dim=0, keepdim=True)[0])
+    mask_v, all_j = mask.max(dim=1)
+    i_ids = torch.where(mask_v)[0]
+    return i_ids, all_j[i_ids]
+
+
+class S2DMatching(nn.Module):
+    """`S2DMatching(feat_dim, thr)` with the reference's parameter names, so `matcher.coarse_matcher.*` of a NeRF-Loc checkpoint loads with strict=True.
+
+    precision: "bf16x3" (default: three-term split-bf16 MFMA, within 1e-4 of the fp32 reference), "fp32" (exact fp32 products) or "bf16" (throughput, not
+    held to the parity bar).  want_score_matrix=False leaves data['score_matrix'] = None and skips the N x M output tensor.
+    eager_chunk_rows: rows of desc0 per chunk of the eager (training) path.
+    """
+
+    def __init__(self, feat_dim, thr=0.1, precision: str = "bf16x3", want_score_matrix: bool = True, eager_chunk_rows: int = 32):
+        super().__init__()
+        self.mlps = nn.Sequential(nn.Linear(feat_dim, _HIDDEN), nn.ReLU(inplace=True), nn.Linear(_HIDDEN, _HIDDEN), nn.ReLU(inplace=True),
+                                  nn.Linear(_HIDDEN, 1))
+        self.feat_dim = int(feat_dim)
+        self.thr = thr
+        if precision not in _lib.PRECISIONS:
+            raise ValueError(f"unknown precision {precision!r}")
+        self.precision = precision
+        self.want_score_matrix = bool(want_score_matrix)
+        self.eager_chunk_rows = int(eager_chunk_rows)
+        self._packed = None
+        self._packed_key = None
+        self.pack_count = 0   # how often the weights were packed (tests watch the cache)
+
+    # ------------------------------------------------------------------ eager path (training / autograd)
+    def get_loss(self, conf, conf_gt):
+        return sigmoid_focal_loss(conf.unsqueeze(2), conf_gt.unsqueeze(2)).mean()
+
+    def _eager_logits(self, desc0, desc1):
+        rows = []
+        for a in range(0, desc0.shape[0], self.eager_chunk_rows):
+            x = torch.einsum("nc,mc->nmc", desc0[a:a + self.eager_chunk_rows], desc1)
+            rows.append(self.mlps(x).squeeze(-1))
+        return torch.cat(rows, dim=0)
+
+    # ------------------------------------------------------------------ library path
+    def _packed_weights(self, device):
+        ps = [self.get_parameter(n) for n in _PARAMS]
+        key = (str(device),) + tuple((p.data_ptr(), p._version, p.dtype) for p in ps)
+        if self._packed is None or key != self._packed_key:
+            lib = _lib.load()
+            need = lib.nl_s2d_packed_weights_bytes(self.feat_dim)
+            if need == 0:
+                raise RuntimeError(f"S2DMatching: feat_dim {self.feat_dim} is not supported by the HIP kernel (a multiple of 32, 32..256)")
+            ts = [p.detach().to(device=device, dtype=torch.float32).contiguous() for p in ps]
+            packed = torch.empty(need, dtype=torch.uint8, device=device)
+            st = torch.cuda.current_stream(device).cuda_stream
+            _lib.check(lib.nl_s2d_pack_weights(self.feat_dim, *[t.data_ptr() for t in ts], packed.data_ptr(), need, st), "nl_s2d_pack_weights")
+            self._packed, self._packed_key = packed, key
+            self._pack_sources = ts   # alive until the stream has consumed them
+            self.pack_count += 1
+        return self._packed
+
+    def match(self, desc0, desc1, want_scores=None):
+        """The library call: (score_matrix or None, match_j (N) int32 with -1 = unmatched, match_score (N))."""
+        if not (desc0.is_cuda and desc1.is_cuda):
+            raise RuntimeError("S2DMatching's eval path runs only on a HIP device (no CPU fallback); move the module and its inputs to cuda")
+        if desc0.dim() != 2 or desc1.dim() != 2 or desc0.shape[1] != self.feat_dim or desc1.shape[1] != self.feat_dim:
+            raise ValueError(f"S2DMatching: descriptors must be (N, {self.feat_dim}) and (M, {self.feat_dim})")
+        want = self.want_score_matrix if want_scores is None else bool(want_scores)
+        dev = desc0.device
+        lib = _lib.load()
+        d0 = desc0.detach().to(torch.float32).contiguous()
+        d1 = desc1.detach().to(torch.float32).contiguous()
+        N, M = d0.shape[0], d1.shape[0]
+        with torch.cuda.device(dev):
+            packed = self._packed_weights(dev)
+            ws_bytes = lib.nl_s2d_min_workspace_bytes(N, M, self.feat_dim, int(want))
+            if ws_bytes == 0:
+                raise RuntimeError("S2DMatching: unsupported shape")
+            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+            scores = torch.empty((N, M), dtype=torch.float32, device=dev) if want else None
+            match_j = torch.empty(N, dtype=torch.int32, device=dev)
+            match_s = torch.empty(N, dtype=torch.float32, device=dev)
+            st = torch.cuda.current_stream(dev).cuda_stream
+            _lib.check(lib.nl_s2d_match(packed.data_ptr(), self.feat_dim, _lib.PRECISIONS[self.precision], d0.data_ptr(), N, d1.data_ptr(), M,
+                                        C.c_float(float(self.thr)), scores.data_ptr() if want else None, match_j.data_ptr(), match_s.data_ptr(),
+                                        ws.data_ptr(), ws_bytes, st), "nl_s2d_match")
+        return scores, match_j, match_s
+
+    def forward(self, desc0, desc1, data):
+        assert (desc0.shape[0] > 0) and (desc1.shape[0] > 0)
+        if self.training or (torch.is_grad_enabled() and (desc0.requires_grad or desc1.requires_grad)):
+            conf = self._eager_logits(desc0, desc1)
+            score = torch.sigmoid(conf)
+            i_ids, j_ids = select_mutual_nearest(score, self.thr)
+            data.update({"i_ids": i_ids, "j_ids": j_ids, "score_matrix": score})
+            if self.training:
+                data["coarse_loss"] = self.get_loss(conf, data["conf_matrix_gt"].float())
+            return data
+        scores, match_j, _ = self.match(desc0, desc1)
+        i_ids = torch.nonzero(match_j >= 0).squeeze(1)
+        data.update({"i_ids": i_ids, "j_ids": match_j[i_ids].to(torch.int64), "score_matrix": scores})
+        return data
