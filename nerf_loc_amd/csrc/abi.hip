@@ -9,124 +9,7 @@
 #include <unordered_map>
 #include "common.h"
 
-// ---- launchers implemented in the other translation units -------------------------------------------
-struct NlKnnGrid {
-  NlGridParams* params; int* starts; int* counts; int* cursor; int* cell_of; float4* sorted; int M;
-};
-size_t nl_knn_grid_bytes(int64_t M);
-int nl_knn_grid_build(NlKnnGrid* g, void* mem, const float* xyz, int64_t M, hipStream_t st);
-int nl_knn_search(const NlKnnGrid* g, const float* xyz, int64_t N, int K, int* idx, float* d2, hipStream_t st);
-int nl_launch_chw_to_hwc(const float* src, float* dst, int V, int Cc, int HW, hipStream_t st);
-int nl_launch_mv_vis(const NlViews& vw, const float* visf_hwc, const float* dec_w, const float* xyz, int64_t N, float* vis_out, float* dd_out, hipStream_t st);
-size_t nl_mv_decoder_pack_bytes();
-int nl_pack_mv_decoder(const float* dec_valu_layout, void* out, hipStream_t st);
-int nl_launch_mv_vis_mfma(const NlViews& vw, const float* visf_hwc, const void* dpack, const float* xyz, int64_t N, float* vis_out,
-                          float* dd_out, bool x3, hipStream_t st);
-int nl_launch_mv_stats(const NlViews& vw, const float* viewsdev, const float* images, const float* feat, int C, const float* xyz, int64_t N, const float* vis_in,
-                       const float* dd_in, float* g393, int ldg, float* rgb_feat, float* vis_ang, int* valid_s, const float* pfeat, const float* blw,
-                       float* bl1, float* rgbv, hipStream_t st);
-int nl_launch_point_encode(const float* xyz, const float* dir, int dir_stride, int dir_div, int64_t N, int K, int64_t M, const int* idx, const float* d2,
-                           const float* sp_xyz, const float* sp_feat, int F, const float* sp_conf, const float* sp_dir, const float* rd_w,
-                           float inv_span, float* X, int ldx, float* wscale, hipStream_t st);
-int nl_launch_attn(const float* Q, const float* KV, int64_t N, int K, float* O, hipStream_t st, unsigned* logit_amax = nullptr);
-int nl_launch_ln_agg(const float* FC, const float* G, int64_t N, int W, const float* gamma, const float* beta, float eps, const float* wscale, float* out, hipStream_t st);
-int nl_launch_ln_slab_elu(const float* in, int64_t R, int L, int Cc, const float* gamma, const float* beta, float eps, float* out, float* pooled, hipStream_t st);
-bool nl_unet_inner_supported(int S, int precision);
-int nl_launch_unet_inner(const NlUnetInnerArgs& a, int precision, hipStream_t st);
-size_t nl_tgemm_mx_image_bytes(int Kpad);
-int nl_launch_sample_points(const float* rays_o, const float* rays_d, int64_t R, int S, float near_, float far_, const float* z_in, float* z_out, float* xyz, hipStream_t st);
-int nl_launch_sigma(const float* geo, int64_t N, int W, const float* w, const float* b, float* sigma, hipStream_t st);
-int nl_launch_sigma_max(const float* sigma, int64_t N, unsigned* slot, hipStream_t st);
-int nl_launch_blend(const float* hA, const float* h1, const float* rgbv, int64_t N, int V, const float* w2, const float* b2, const float* w4, const float* b4, float* rgb_s, hipStream_t st,
-                    const int* n_alive = nullptr, int S = 1);
-int nl_launch_blend_taps(const NlViews& vw, const float* viewsdev, const float* pfeat, const float* blw, const float* xyz, const float* hA, const float* rgbv, int64_t N,
-                         const float* w2, const float* b2, const float* w4, const float* b4, float* rgb_s, hipStream_t st, const int* n_alive, int S);
-size_t nl_mv_front_pack_bytes();
-int nl_pack_mv_front(const float* w_outfc0, const float* b_outfc0, void* out, hipStream_t st);
-bool nl_mv_front_supported(int C, int V, int64_t N);
-int nl_launch_mv_front(const NlViews& vw, const float* viewsdev, const float* images, const float* feat, const float* xyz, int64_t N, const float* vis_in,
-                       const float* dd_in, const void* pack, float* t64, int* valid_s, float* rgbv, hipStream_t st);
-int nl_launch_termination(const float* z_vals, const float* sigma, int64_t R, int S, float eps, int* n_alive, int* tile_list, int* tile_count, hipStream_t st);
-int nl_launch_coarse_weights(const NlViews& vw, const float* w2c_kinv_host, const float* visf_hwc, const float* dec_w, const void* dpack,
-                             int precision, const float* pix, const float* zc, int64_t R, int Sc, float* ws_alpha, float* ws_vis, float* ws_mask,
-                             float* weights, float* depth_coarse, hipStream_t st);
-int nl_launch_sample_pdf(const float* zc, const float* wc, int Sc, const float* u, int Ni, const float* zb, int Sb, int64_t R,
-                         float* z_out, hipStream_t st);
-int nl_launch_composite(const float* z_vals, const float* sigma, const float* rgb_s, const float* ft, const int* valid_s, int64_t R, int S, int C,
-                        int white_bkgd, const nl_render_out* out, int64_t ray0, float* feat_dst, float* wsum_dst, hipStream_t st, const int* n_alive = nullptr,
-                        float* w_scratch = nullptr);
-
-size_t nl_point_stream_bytes(int W);
-int nl_pack_point_stream(const float* w1, const float* w2, const float* w3, const float* wk, const float* wv, void* out, int W, int F, hipStream_t st);
-int nl_pack_ptt(const float* w1, const float* b1, int W, int F, int Kpad, int Npad, float* B32, float* bias, hipStream_t st);
-int nl_launch_wscale(const int* idx, const float* d2, const float* conf, int64_t N, int K, int64_t M, float* wscale, hipStream_t st);
-bool nl_point_fused_supported(int W, int precision);
-int nl_launch_point_fused(const NlPointFusedArgs& a, int W, int precision, hipStream_t st);
-size_t nl_point_stream2_bytes(int W);
-int nl_pack_point_stream2(const float* w1, const float* w2, const float* w3, const float* wk, const float* wv, const float* b2, const float* b3,
-                          const float* rd_w, void* out, int W, int F, hipStream_t st, int mx = 0);
-bool nl_point_fused2_supported(int W, int precision);
-int nl_launch_sample_chain(const float* O, const float* T64, const float* wscale, const float* gamma, const float* beta, float eps, const void* wbase,
-                           size_t off_g2, const float* bias_g2, size_t off_fc, size_t off_f0, size_t off_ba, const float* bias_f0, float* FA, float* fth,
-                           float* blA, int64_t M, int precision, hipStream_t st, bool frag_out = false, bool frag_f16 = false);
-int nl_launch_query_chain(const float* T64, const void* wbase, size_t off_g2, const float* bias_g2, size_t off_q, float* Q, int64_t M, int precision,
-                          hipStream_t st);
-int nl_launch_point_fused2(const NlPointFusedArgs& a, int W, int precision, hipStream_t st, bool mx = false, float* keep_kv = nullptr, unsigned* const* keep_mk = nullptr,
-                           unsigned* logit_amax = nullptr, unsigned long long* clk = nullptr);
-int nl_table_absmax(const float* x, size_t n, float* out, hipStream_t st);
-bool nl_point_bwd_chain_supported(int W);
-size_t nl_point_bwd_stream_bytes(int W);
-int nl_pack_point_bwd_stream(const float* w1, const float* w2, const float* w3, const float* wk, const float* wv, void* out, int W, int F, hipStream_t st);
-int nl_launch_point_bwd_chain(const float* gkv, const unsigned* const* mk, const void* wstream, float* gx, int64_t NK, int W, hipStream_t st, const float* q = nullptr,
-                              const float* kv = nullptr, const float* go = nullptr, float* gq = nullptr);
-// backward.hip: glue kernels of the neural-point branch's input gradient
-int nl_launch_wgrad(const float* dY, int ldy, int M, const float* X, int ldx, int N, int64_t rows, int shift, int period, float* gW, int ldc, int cs, int co,
-                    float* gb, float* scratch, size_t scratch_floats, hipStream_t st);
-size_t nl_wgrad_scratch_floats(int64_t rows, int M, int N);
-int nl_launch_wgrad_multi(int nsub, const float* const* dY, int ldy, int M, const float* const* X, int ldx, int N, int64_t rows, const int* shift, int period,
-                          float* gW, int ldc, int cs, const int* co, float* gb, int bias_sub, float* scratch, size_t scratch_floats, hipStream_t st);
-int nl_launch_colsum(const float* Y, int ldy, int64_t rows, int M, float* out, float* scratch, hipStream_t st);
-int nl_launch_sp_feat_scatter(const float* gXF, int ld, int F, const int* idx, int64_t N, int K, int64_t M, float* g_sp_feat, hipStream_t st);
-int nl_launch_ln_agg_backward(const float* FC, const float* G, const float* gy, int64_t N, int W, const float* gamma, float eps, const float* wscale, float* gx,
-                              float* aff, hipStream_t st);
-int nl_launch_attn_backward(const float* Q, const float* KV, const float* gO, int64_t N, int K, float* gQ, float* gKV, hipStream_t st);
-int nl_launch_lrelu_mask(float* g, const float* h, size_t n, hipStream_t st);
-int nl_launch_add(const float* a, const float* b, float* o, size_t n, hipStream_t st);
-int nl_launch_mv_geom_backward(const NlViews& vw, const float* viewsdev, const float* images, const float* feat, int C, const float* pfeat, const float* xyz,
-                               int64_t N, const float* vis_in, const float* dd_in, const float* g393, int ldg, const float* g_pf, const float* g_rgbv,
-                               const float* g_ang, float* g_xyz, float* g_qc, float* g_vis, float* g_dd, float* sc_feat, float* sc_pfeat, const float* stats,
-                               hipStream_t st);
-int nl_dec_train_row(void);
-size_t nl_dec_wpart_floats(void);
-int nl_launch_copy_rows(const float* src, int lds, float* dst, int ldd, int64_t rows, int cols, bool add, hipStream_t st);
-int nl_launch_dec_backward(const NlViews& vw, const float* visf_hwc, const float* dec_w, const void* dpack, const float* xyz, int64_t N, const float* g_vis,
-                           const float* g_dd, float* part, float* g_xyz, float* tr, float* const* decw, float* scratch, size_t scratch_floats, float* sc_vis,
-                           hipStream_t st);
-int nl_launch_blend_backward(const float* hA, const float* h1, const float* rgbv, int64_t N, int V, const float* w2, const float* b2, const float* w4,
-                             const float* b4, const float* blw, const float* g_rgb_s, float* g_hA, float* g_pf, float* g_rgbv, float* g_ang, float* tr,
-                             hipStream_t st);
-int nl_launch_blend_inputs8(const NlViews& vw, const float* viewsdev, const float* xyz, int64_t N, const float* rgbv, float* x8, hipStream_t st);
-int nl_launch_blw_unpack(const float* t, float* g, int W, int F, hipStream_t st);
-int nl_launch_elu_mask(float* g, const float* e, size_t n, hipStream_t st);
-int nl_launch_ln_slab_elu_backward(const float* x, int64_t R, int L, int Cc, const float* gamma, const float* beta, float eps, const float* g_out, int ldgo, int pool,
-                                   float* g_x, float* aff, hipStream_t st);
-int nl_launch_table_add_t(const float* t, float* g, int L, int Cc, hipStream_t st);
-int nl_launch_colsum_tables(const float* Y, int64_t rows, int L, int Cc, float* gw, float* gb, float* scratch, hipStream_t st);
-int nl_launch_ray_feat_sum(const float* z, const float* sigma, const float* ft, int64_t R, int S, int C, float* hc, float* wsum4, hipStream_t st);
-int nl_launch_sigma_backward(const float* geo, int64_t N, int W, const float* w, const float* b, const float* g_sigma, float* g_geo, float* gpre4, hipStream_t st);
-int nl_launch_gw_total(const float* g_wts, const float* g_feat, const float* b2, int64_t R, int S, int C, float* gw, const float* g_beta, const float* bv,
-                       hipStream_t st);
-int nl_launch_beta_forward(const float* wts, const float* bv, int64_t R, int S, float beta_min, float* beta, hipStream_t st);
-int nl_launch_beta_backward(const float* geo, int64_t N, int S, int W, const float* wb, const float* bb, const float* wts, const float* g_beta, float* g_geo, float* gpre4,
-                            hipStream_t st);
-int nl_launch_ray_reduce(const float* ga, const float* gb, const float* gc, const float* g_dir, const float* g_qcN, const float* z, int64_t R, int S, float* g_o,
-                         float* g_d, float* g_qc, hipStream_t st);
-int nl_launch_add2d(const float* a, int lda, const float* b, int ldb, float* o, int ldo, int64_t rows, int cols, hipStream_t st);
-int nl_launch_point_encode_backward(const float* xyz, const float* dir, int dir_stride, int dir_div, int64_t N, int K, int64_t M, const int* idx,
-                                    const float* sp_xyz, const float* sp_dir, const float* rd_w, float inv_span, const float* gX, int ldg, float* g_xyz,
-                                    float* g_dir, float* tr, hipStream_t st);
-
-// CU count for persistent kernels, per device id (common.h)
+// CU count for persistent kernels, per device id (launch.h)
 int nl_persistent_cus() {
   static std::mutex mu;
   static int cus[64] = {0};
@@ -580,6 +463,13 @@ struct Bump {
     return base ? (T*)(base + o) : nullptr;
   }
 };
+// "largest chunk whose buffers fit the workspace": the largest n in [1, n_max] with bytes_of(n) <= ws_bytes (bytes_of grows with n); 0 when not even one row fits
+template <class F> int64_t largest_chunk(int64_t n_max, size_t ws_bytes, F bytes_of) {
+  if (bytes_of(1) > ws_bytes) return 0;
+  int64_t lo = 1, hi = n_max;
+  while (lo < hi) { const int64_t mid = (lo + hi + 1) / 2; if (bytes_of(mid) <= ws_bytes) lo = mid; else hi = mid - 1; }
+  return lo;
+}
 
 // ---- per-stage buffers ---------------------------------------------------------------------------
 struct MvBufs { float *vis, *dd, *g393, *t64; };
@@ -2165,19 +2055,15 @@ int nl_point_mlp_backward_train(const nl_config* cfg, const void* packed, const 
   TrainOut T;
   NL_TRY(resolve_train(cfg, grads, T));   // (validated before anything is dereferenced)
   if (f->M < 1) return NL_ERR_UNSUPPORTED;
-  if (ws_bytes < point_bwd_bytes(cfg, 1, train)) return NL_ERR_WORKSPACE;
+  const int64_t fit = largest_chunk(N, ws_bytes, [&](int64_t n) { return point_bwd_bytes(cfg, n, train); });   // largest sample chunk whose buffers fit the workspace
+  if (fit == 0) return NL_ERR_WORKSPACE;
   // Precision of the two halves (measured):
   //  * the RECOMPUTED FORWARD must be much better than split-bf16: the derivative of a LeakyReLU network is piecewise constant, and a forward that
   //    is 1e-5 off flips the sign of a few pre-activations near zero — every flip changes that neighbour row's gradient by a few percent (2e-2 in
   //    the max-norm of g_xyz with a split-bf16 recompute against 4e-6 with exact fp32; plain fp32 autograd is 4e-3 from the fp64 gradient for the
   //    same reason).  Exact fp32 in the fp32 mode; three-term split-FP16 (~2^-22) otherwise: 40x fewer flips than split-bf16 at the same speed;
   //  * the transposed-weight products of the way back are linear in the incoming gradient and run in split-bf16 (1e-5, no discontinuity).
-  int64_t lo = 1, hi = N;
-  while (lo < hi) {   // largest sample chunk whose buffers fit the workspace
-    const int64_t mid = (lo + hi + 1) / 2;
-    if (point_bwd_bytes(cfg, mid, train) <= ws_bytes) lo = mid; else hi = mid - 1;
-  }
-  const int64_t NC = lo < (1 << 17) ? lo : (1 << 17);
+  const int64_t NC = fit < (1 << 17) ? fit : (1 << 17);
   BwdCtx B; make_bwd_ctx(B, cfg, packed, stream);
   const Ctx &xf = B.x32, &xb = B.xb;   // recomputed forward / way back
   const int W = cfg->W;
@@ -2195,10 +2081,8 @@ static size_t mv_bwd_bytes(const nl_config* cfg, int V, int64_t n, bool blend, b
   Bump b{nullptr, 0}; MvBwdBufs m; carve_mvb(b, cfg, V, n, blend, m, train); return b.off;
 }
 static int64_t mv_bwd_chunk(const nl_config* cfg, int V, int64_t N, bool blend, size_t ws_bytes, bool train = false) {
-  if (ws_bytes < mv_bwd_bytes(cfg, V, 1, blend, train)) return 0;
-  int64_t lo = 1, hi = N;
-  while (lo < hi) { const int64_t mid = (lo + hi + 1) / 2; if (mv_bwd_bytes(cfg, V, mid, blend, train) <= ws_bytes) lo = mid; else hi = mid - 1; }
-  return lo < (1 << 18) ? lo : (1 << 18);
+  const int64_t fit = largest_chunk(N, ws_bytes, [&](int64_t n) { return mv_bwd_bytes(cfg, V, n, blend, train); });
+  return fit < (1 << 18) ? fit : (1 << 18);
 }
 size_t nl_mv_aggregate_backward_train_workspace_bytes(const nl_config* cfg, int V, int64_t N) {
   NL_EFF_CFG(cfg);
@@ -2304,10 +2188,8 @@ int nl_render_rays_backward(const nl_config* cfg, const void* packed, const nl_f
   NL_TRY(resolve_train(cfg, grads, T));
   if (f->M < 1) return NL_ERR_UNSUPPORTED;
   const int V = f->views.V, S = cfg->S, C = cfg->C;
-  if (ws_bytes < render_bwd_bytes(cfg, V, 1, train)) return NL_ERR_WORKSPACE;
-  int64_t lo = 1, hi = R;
-  while (lo < hi) { const int64_t mid = (lo + hi + 1) / 2; if (render_bwd_bytes(cfg, V, mid, train) <= ws_bytes) lo = mid; else hi = mid - 1; }
-  const int64_t RC = lo;
+  const int64_t RC = largest_chunk(R, ws_bytes, [&](int64_t r) { return render_bwd_bytes(cfg, V, r, train); });
+  if (RC == 0) return NL_ERR_WORKSPACE;
   BwdCtx B; make_bwd_ctx(B, cfg, packed, stream);
   for (int64_t r0 = 0; r0 < R; r0 += RC) {
     const int64_t rc = R - r0 < RC ? R - r0 : RC;
@@ -2388,10 +2270,8 @@ int nl_ray_unet_backward_train(const nl_config* cfg, const void* packed, const f
   const bool train = grads != nullptr;
   TrainOut T;
   NL_TRY(resolve_train(cfg, grads, T));
-  if (ws_bytes < unet_bwd_bytes(cfg, 1, train)) return NL_ERR_WORKSPACE;
-  int64_t lo = 1, hi = R;
-  while (lo < hi) { const int64_t mid = (lo + hi + 1) / 2; if (unet_bwd_bytes(cfg, mid, train) <= ws_bytes) lo = mid; else hi = mid - 1; }
-  const int64_t RC = lo;
+  const int64_t RC = largest_chunk(R, ws_bytes, [&](int64_t r) { return unet_bwd_bytes(cfg, r, train); });
+  if (RC == 0) return NL_ERR_WORKSPACE;
   BwdCtx B; make_bwd_ctx(B, cfg, packed, stream);
   const size_t row = (size_t)cfg->S * cfg->W;
   for (int64_t r0 = 0; r0 < R; r0 += RC) {
@@ -2524,14 +2404,8 @@ int render_rays_impl(const nl_config* cfg, const void* packed, const nl_frame* f
   if (!cfg_ok(cfg) || !packed || !f || (!qc && !ray_centers) || !rays_o || !rays_d || !out || !ws || R < 0) return NL_ERR_BAD_ARG;
   const int V = f->views.V, S = cfg->S, W = cfg->W;
   // largest ray chunk whose buffers fit the workspace
-  const size_t b1 = render_bytes(cfg, V, 1);
-  if (ws_bytes < b1) return NL_ERR_WORKSPACE;
-  int64_t lo = 1, hi = R > 1 ? R : 1;
-  while (lo < hi) {
-    int64_t mid = (lo + hi + 1) / 2;
-    if (render_bytes(cfg, V, mid) <= ws_bytes) lo = mid; else hi = mid - 1;
-  }
-  int64_t RC = lo;
+  int64_t RC = largest_chunk(R > 1 ? R : 1, ws_bytes, [&](int64_t r) { return render_bytes(cfg, V, r); });
+  if (RC == 0) return NL_ERR_WORKSPACE;
   {   // the buffer-addressed kernels use 32-bit byte offsets: at most 2^21 samples per chunk (twice the recommended workspace's chunk)
     const int64_t cap = ((int64_t)1 << 21) / S > 0 ? ((int64_t)1 << 21) / S : 1;
     if (RC > cap) RC = cap;

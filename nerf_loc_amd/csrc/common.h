@@ -20,9 +20,6 @@
   } while (0)
 
 static inline size_t nl_align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
-// Workgroups of a persistent kernel on the CURRENT device: its CU count rounded down to a multiple of the 8 XCDs (>= 8); cached per device id
-// (abi.hip) — a process may drive several GPUs through several HipRenderers.  < 0: NL_ERR_HIP
-int nl_persistent_cus();
 static inline int64_t nl_cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
 // ------------------------------------------------------------------ activations (match torch fp32 CPU ops)
@@ -257,15 +254,5 @@ enum { NL_EPI_NONE = 0, NL_EPI_LNROW = 1, NL_EPI_LNSLAB = 2 };
 // their recomputed forward; falls back to exact fp32 where the streaming kernel does not apply
 #define NL_PREC_F16X3_INTERNAL 16
 
-int nl_gemm_launch(const NlGemmArgs& a, int precision, hipStream_t stream);
-// streaming transposed GEMM (tgemm.hip): bf16 modes, N <= 256, 16-B aligned segments
-int nl_tgemm_nrt(int N);
-size_t nl_tgemm_stream_bytes(int Kpad, int N);
-bool nl_tgemm_supported(const NlGemmArgs& a, int precision);
-int nl_tgemm_launch(const NlGemmArgs& a, int precision, hipStream_t stream);
-// feat_mlp.0 + LeakyReLU + the compositing of its rows along the ray in the f16mx arithmetic (tgemm.hip: feat_comp_mx_kernel): hc (N / S, 256) from feature_agg's
-// fragment image, the samples' compositing weights, G_FEAT0P's fp16 stream and its fp6 images
-bool nl_feat_comp_mx_supported(int W, int S, int64_t N);
-// w2 != null: feat_mlp.2 too (G_FEAT2's packed fp32 matrix [k][npad], row 256 = the bias that meets the weight sum): feat (N / S, C) is written, hc is not
-int nl_launch_feat_comp_mx(const float* fa_frag, const float* wts, int64_t N, int S, const void* bsh, const void* bmx, const float* bias, float* hc, hipStream_t st,
-                           const float* w2 = nullptr, int npad = 0, int C = 0, const float* wsum = nullptr, float* feat = nullptr, bool frag_f16 = false);
+// every host function that one unit defines and another calls (included last: it needs the types above)
+#include "launch.h"

@@ -510,17 +510,7 @@ __global__ __launch_bounds__(256) void knn_wave_kernel(const float* __restrict__
 
 }  // namespace
 
-// ---- host side (called from abi.hip) ------------------------------------------------------------
-struct NlKnnGrid {
-  NlGridParams* params;  // device
-  int* starts;           // device [GRID_CELLS + 1]
-  int* counts;           // device [GRID_CELLS]
-  int* cursor;           // device [GRID_CELLS]
-  int* cell_of;          // device [M]
-  float4* sorted;        // device [M]
-  int M;
-};
-
+// ---- host side (called from abi.hip; NlKnnGrid: launch.h) -----------------------------------------
 size_t nl_knn_grid_bytes(int64_t M) {
   size_t b = 0;
   b += nl_align_up(sizeof(NlGridParams), 256);

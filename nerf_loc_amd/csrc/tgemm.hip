@@ -1781,7 +1781,7 @@ bool nl_tgemm_supported(const NlGemmArgs& a, int precision) {
 }
 
 // f16mx form of an LNSLAB launch (conv_out): 256-wide, one ray = 128 rows, whole 32-k chunks from 16-byte-aligned sources, both weight images present
-bool nl_tgemm_mx_supported(const NlGemmArgs& a, int precision) {
+static bool nl_tgemm_mx_supported(const NlGemmArgs& a, int precision) {
   if (precision != NL_PREC_BF16X3 || !a.Bsh_mx || !a.Bmx || a.epi != NL_EPI_LNSLAB || a.So != 128 || a.Li != 128 || a.N != 256 || a.ep_pool || a.tile_map) return false;
   // conv_out's K structure at W = 256 (the kernel's chunk table is a compile-time constant): [feature_agg: 8 blocks x 3 taps | x2: 1 block x 3 taps]
   if (a.nseg != 2 || a.Kpad != 864 || a.seg[0].k != 256 || a.seg[0].ntap != 3 || a.seg[0].ioff != 0 || a.seg[1].k != 32 || a.seg[1].ntap != 3 || a.seg[1].ioff != 0 ||
@@ -1791,7 +1791,7 @@ bool nl_tgemm_mx_supported(const NlGemmArgs& a, int precision) {
 }
 
 // conv1 of the ray U-Net at W = 256, S = 128 (tgemm_conv1_kernel): one segment of 256 channels x 3 taps, 64 columns, one ray = 128 rows per workgroup
-bool nl_tgemm_conv1_supported(const NlGemmArgs& a, int precision) {
+static bool nl_tgemm_conv1_supported(const NlGemmArgs& a, int precision) {
   if ((precision != NL_PREC_BF16X3 && precision != NL_PREC_BF16) || a.epi != NL_EPI_LNSLAB || a.So != 128 || a.Li != 128 || a.N != 64 || a.tile_map || a.ep_sig_w || !a.C) return false;
   if (a.nseg != 1 || a.Kpad != 768 || a.seg[0].k != 256 || a.seg[0].ntap != 3 || a.seg[0].ioff != 0) return false;
   return nl_tgemm_supported(a, precision);

@@ -5,8 +5,8 @@ set -e
 cd "$(dirname "$0")/../nerf_loc_amd/csrc"
 name=$1; src=$2; flags=$3
 mkdir -p variants/obj_$name
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -fvisibility=hidden -ffp-contract=off -fno-slp-vectorize -Wall -Wno-unused-function $flags -c $src -o variants/obj_$name/${src%.hip}.o
+/opt/rocm/bin/hipcc $(make -s print-flags) $flags -c $src -o variants/obj_$name/${src%.hip}.o
 objs=""
-for o in build/*.o; do b=$(basename $o); if [ "$b" == "${src%.hip}.o" ]; then objs="$objs variants/obj_$name/$b"; else objs="$objs $o"; fi; done
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o variants/libnerfloc_$name.so $objs
+for b in $(make -s print-objs); do o=build/$b; if [ "$b" == "${src%.hip}.o" ]; then objs="$objs variants/obj_$name/$b"; else objs="$objs $o"; fi; done
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -Wl,--version-script=exports.map -Wl,--no-undefined -o variants/libnerfloc_$name.so $objs
 echo built variants/libnerfloc_$name.so
