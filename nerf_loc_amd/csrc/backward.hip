@@ -143,7 +143,7 @@ __global__ void knn_backward_kernel(const float* __restrict__ xyz, const float* 
   if (g_xyz) { g_xyz[3 * (size_t)n] = ax; g_xyz[3 * (size_t)n + 1] = ay; g_xyz[3 * (size_t)n + 2] = az; }
 }
 
-// ---- glue of the whole-path backward (abi.hip: do_render_backward) -----------------------------------------------------------------------
+// ---- glue of the whole-path backward (render_bwd.hip: do_render_backward) -----------------------------------------------------------------------
 // hc[r][c] = sum_s w_s ft[r][s][c], wsum4[r] = (sum_s w_s, 0, 0, 0): the composited hidden rows feat_mlp.2's weight gradient multiplies
 template <int CH>
 __global__ __launch_bounds__(256) void ray_feat_sum_kernel(const float* __restrict__ z_vals, const float* __restrict__ sigma, const float* __restrict__ ft, int R,
@@ -339,7 +339,7 @@ int nl_knn_backward(const float* xyz, const float* sp_xyz, const int32_t* idx, c
 
 // =====================================================================================================================
 // Neural-point branch (rows a9-a12), gradient w.r.t. its INPUTS with frozen weights (what PoseOptimizer needs, pose_optimizer.py:131-168,
-// and the input-gradient half of a training step): the glue kernels between the transposed-weight GEMMs (abi.hip: do_point_backward).
+// and the input-gradient half of a training step): the glue kernels between the transposed-weight GEMMs (render_bwd.hip: do_point_backward).
 // A Linear layer's input gradient needs no activations, LeakyReLU's needs the sign of its output, the attention needs q / k / v — so the
 // backward pass re-runs the staged forward (point_encode -> GEMMs -> attention, the kernels of point.hip) into its workspace and walks back.
 namespace {
@@ -2139,7 +2139,7 @@ int nl_launch_mv_geom_backward(const NlViews& vw, const float* viewsdev, const f
 }
 
 int nl_dec_train_row(void) { return DEC_TR_ROW; }
-// decw: the 24 decoder tensors' gradient pointers (T_DEC order; entries may be null) or null.  fp32 mode emits the rows `tr` for abi.hip's dec_wgrads; the MFMA
+// decw: the 24 decoder tensors' gradient pointers (T_DEC order; entries may be null) or null.  fp32 mode emits the rows `tr` for render_bwd.hip's dec_wgrads; the MFMA
 // kernel accumulates the weight gradients itself (one partial set per wave in `scratch`, >= nl_dec_wpart_floats() floats) and adds them here.
 size_t nl_dec_wpart_floats(void) { return (size_t)1024 * DEC_WP; }
 int nl_launch_dec_backward(const NlViews& vw, const float* visf_hwc, const float* dec_w, const void* dpack, const float* xyz, int64_t N, const float* g_vis,
@@ -2203,7 +2203,7 @@ int nl_launch_elu_mask(float* g, const float* e, size_t n, hipStream_t st) {
 
 // =====================================================================================================================
 // Ray U-Net (row a13; ray_unet.py:5-69), gradient w.r.t. its input with frozen weights: between the transposed-weight convolutions (segment
-// GEMMs, abi.hip: do_unet_backward) sits the backward of [LayerNorm over the ray's whole (L x C) slab, per-(position, channel) affine] -> ELU ->
+// GEMMs, render_bwd.hip: do_unet_backward) sits the backward of [LayerNorm over the ray's whole (L x C) slab, per-(position, channel) affine] -> ELU ->
 // optional MaxPool1d(2).
 namespace {
 

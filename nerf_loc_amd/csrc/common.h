@@ -182,7 +182,7 @@ struct NlUnetInnerArgs {
   float* x2;                  // (R, 128, 32) fp32: trans_conv1's block output (conv_out's second source)
   const char* w[5];           // weight streams in tgemm_kernel's chunk layout: conv2, conv3, trans_conv3 / 2 / 1 (merged phases)
   const float* bias[5];
-  const float* gl[5];         // LayerNorm tables in accumulator-lane order (abi.hip: ln_lane_major_kernel)
+  const float* gl[5];         // LayerNorm tables in accumulator-lane order (pack.hip: ln_lane_major_kernel)
   const float* bl[5];
   int R;
   float eps;

@@ -504,7 +504,7 @@ int nl_launch_blend_taps(const NlViews& vw, const float* viewsdev, const float* 
   return NL_OK;
 }
 
-// `ft` (R*S, C) is composited into feat_dst (R, C) (any channel count; the caller passes feat_mlp's hidden layer, see abi.hip)
+// `ft` (R*S, C) is composited into feat_dst (R, C) (any channel count; the caller passes feat_mlp's hidden layer, see render.hip: do_heads)
 int nl_launch_composite(const float* z_vals, const float* sigma, const float* rgb_s, const float* ft, const int* valid_s,
                         int64_t R, int S, int C, int white_bkgd, const nl_render_out* out, int64_t ray0, float* feat_dst, float* wsum_dst,
                         hipStream_t st, const int* n_alive, float* w_scratch) {

@@ -510,7 +510,7 @@ __global__ __launch_bounds__(256) void knn_wave_kernel(const float* __restrict__
 
 }  // namespace
 
-// ---- host side (called from abi.hip; NlKnnGrid: launch.h) -----------------------------------------
+// ---- host side (called from abi.hip, render.hip and render_bwd.hip; NlKnnGrid: launch.h) -----------------------------------------
 size_t nl_knn_grid_bytes(int64_t M) {
   size_t b = 0;
   b += nl_align_up(sizeof(NlGridParams), 256);

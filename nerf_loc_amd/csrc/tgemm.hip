@@ -324,7 +324,7 @@ __global__ __launch_bounds__(64 * NW, NW > 4 ? 1 : 2) void tgemm_kernel(const Nl
     }
     const float rstd = 1.f / sqrtf(tot2 / cnt + a.ep_eps);
     TG_T(49);
-    // the affine tables come in accumulator-lane order (abi.hip ln_lane_major_kernel): [wave of the ray][rt][gq][lane][4] — one contiguous
+    // the affine tables come in accumulator-lane order (pack.hip ln_lane_major_kernel): [wave of the ray][rt][gq][lane][4] — one contiguous
     // KB per load instruction; a row tile's eight loads are issued one row tile ahead of their use
     const float* grow = a.ep_gamma + ((size_t)(wave % wpr) * NRT * 4 * 64 + lane) * 4;
     const float* brow = a.ep_beta + ((size_t)(wave % wpr) * NRT * 4 * 64 + lane) * 4;
@@ -469,7 +469,7 @@ __global__ __launch_bounds__(64 * NW, NW > 4 ? 1 : 2) void tgemm_kernel(const Nl
 //     v_cvt_scalef32_pk32_fp6_f16 for the hi image and ONE v_cvt_scalef32_2xpk16_fp6_f32 for the residual image (on the hi image's scale x 2^-11).  No producer changes
 //     its output format; the conversion (~170 vector instructions per slab) is paid once per 32 rows x 256 columns = 48 matrix instructions.
 //   * A operand (weights): the layer's fp16 stream (hi fragments: the `bsh` image nl_pack_weights writes anyway) + fp6 images of f16(w) and w - f16(w) with one E8M0
-//     scale per (output row, half-wave, slab) (abi.hip: pack_tgemm_mx6_kernel), both in the natural position order P = 8 s + t (k-step s, element t) that the
+//     scale per (output row, half-wave, slab) (pack.hip: pack_tgemm_mx6_kernel), both in the natural position order P = 8 s + t (k-step s, element t) that the
 //     activation images have.  64 KB per slab through a two-slot LDS ring by LDS-DMA (no staging registers: 128 accumulators + the next slab's 32 raw activation
 //     words + the converted operand leave no room for them at two waves per SIMD).
 //   * 130 KB of LDS = ONE workgroup per CU, so the workgroup is eight waves = 256 rows = two rays: the same two waves per SIMD as the two four-wave workgroups of
@@ -859,7 +859,7 @@ __global__ __launch_bounds__(64 * TGMX_NW, 1) void tgemm_mx_kernel(const NlGemmA
 // ====================================================================================================================
 // feat_mlp.0 + LeakyReLU + the compositing of its rows along the ray as ONE kernel in the f16mx arithmetic (round 6; NL_PREC_F16MX, W = 256):
 //   hc[ray][c] = sum_s w_s LeakyReLU(feat_mlp.0 . feature_agg_s + b)[c]          (model.py:594-597 composites feat_mlp's output; its last Linear is applied afterwards:
-// abi.hip do_heads).  Before, the chain kernel ran feat_mlp.0 as 8 of its 22 chunks (three-term split-bf16: 384 of a tile's 720 matrix instructions), wrote the hidden rows
+// render.hip do_heads).  Before, the chain kernel ran feat_mlp.0 as 8 of its 22 chunks (three-term split-bf16: 384 of a tile's 720 matrix instructions), wrote the hidden rows
 // (N x 256 fp32 = 0.54 GB at config 2) and composite_kernel read them back to weight and sum them.  Here the product runs AFTER the density is known, with the weights of
 // the samples at hand: the hidden rows are never written, feature_agg's fragment image (which conv1 and conv_out read anyway) is read once more.
 // The main loop is tgemm_mx_kernel's with K = 256 (four 64-k slabs, chunks = the eight 32-channel blocks of the fragment image) and the two MFMA operands SWAPPED:
@@ -1068,7 +1068,7 @@ __global__ __launch_bounds__(64 * NW, 1) void feat_comp_mx_kernel(const float* _
   __syncthreads();   // `red` is read: the next group's first slab may stage slab 1 over it
   P = Pn;
   if (w2) {
-    // ---- feat_mlp.2 on the composited rows (it is linear: applied after the sum, abi.hip do_heads), for the rays this workgroup has collected: once per HB rays and
+    // ---- feat_mlp.2 on the composited rows (it is linear: applied after the sum, render.hip do_heads), for the rays this workgroup has collected: once per HB rays and
     // after the last group — the per-ray GEMM launch this replaces cost 33 us whatever the batch.  feat[ray][n] = sum_k hc[ray][k] W2[n][k] + wsum[ray] b2[n]; the weights
     // are G_FEAT2's packed fp32 matrix ([k][npad], row 256 = the bias), read once per flush, coalesced over n; two thread sets of npad, eight rays each.
     if (nbuf == 0) grp0 = grp;
@@ -1756,7 +1756,7 @@ __global__ __launch_bounds__(256, 1) void sample_chain_kernel(const NlChainArgs 
 
 }  // namespace
 
-// stream layout helpers (also used by the packer in abi.hip)
+// stream layout helpers (also used by the packer in pack.hip)
 int nl_tgemm_nrt(int N) { return N <= 64 ? 2 : (N <= 128 ? 4 : 8); }
 size_t nl_tgemm_mx_image_bytes(int Kpad) { return (size_t)((Kpad / 32 + 1) / 2) * TGMX_IMG; }   // fp6 images + scales of a 256-column layer (pack_tgemm_mx6_kernel)
 size_t nl_tgemm_stream_bytes(int Kpad, int N) { return (size_t)(Kpad / 32) * 4 * nl_tgemm_nrt(N) * 1024; }
