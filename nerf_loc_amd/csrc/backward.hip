@@ -11,9 +11,6 @@
 
 namespace {
 
-__device__ __forceinline__ float bk_rl(float v, int lane) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), lane)); }
-__device__ __forceinline__ int bk_rli(int v, int lane) { return __builtin_amdgcn_readlane(v, lane); }
-
 // w_s = a_s T_s, a_s = 1 - exp(-delta_s sigma_s), T_s = prod_{j<s} (1 - a_j).  With q_s = dL/dw_s:
 //   dL/dsigma_s = delta_s ( q_s T_{s+1} - B_s ),  B_s = sum_{j>s} q_j w_j          (no division: exp(-delta sigma) may underflow to 0)
 // q_s = g_rgb . rgb_s - [white] sum_c g_rgb_c + g_depth z_s + g_unc ((z_s - D)^2 - 2 D (1 - W) z_s) + g_feat . ft_s + g_w_s
@@ -505,11 +502,11 @@ __global__ __launch_bounds__(256) void point_encode_backward_kernel(const float*
       const float hj = nl_lrelu(a1);
       float a2 = w2[27 * 16 + lu];
 #pragma unroll
-      for (int j = 0; j < 16; ++j) a2 = fmaf(w2[lu * 16 + j], bk_rl(hj, j), a2);
+      for (int j = 0; j < 16; ++j) a2 = fmaf(w2[lu * 16 + j], nl_rl(hj, j), a2);
       const float ga2 = lane < 27 ? grow[63 + lane] * (a2 > 0.f ? 1.f : 0.01f) : 0.f;
       float gh = 0.f;
 #pragma unroll
-      for (int l = 0; l < 27; ++l) gh = fmaf(w2[l * 16 + ju], bk_rl(ga2, l), gh);
+      for (int l = 0; l < 27; ++l) gh = fmaf(w2[l * 16 + ju], nl_rl(ga2, l), gh);
       const float ga1 = lane < 16 ? gh * (a1 > 0.f ? 1.f : 0.01f) : 0.f;
       const float gr0 = wave_sum(rd_w[ju * 4 + 0] * ga1), gr1 = wave_sum(rd_w[ju * 4 + 1] * ga1), gr2 = wave_sum(rd_w[ju * 4 + 2] * ga1),
                   gr3 = wave_sum(rd_w[ju * 4 + 3] * ga1);
@@ -538,19 +535,6 @@ __global__ __launch_bounds__(256) void point_encode_backward_kernel(const float*
 // axis + the double-angle recurrence, like the forward kernel) and the whole ray_diff_fc 4 -> 16 -> 27 forward + backward (~1000 FMAs against wave-uniform weights, which
 // the compiler keeps in SGPRs) stay in the lane; the 8 rows of a sample are summed with three DPP steps.  The wave-per-sample kernel above walks the neighbours one after
 // the other with five wave reductions each: 0.44 ms per 512-ray pose step against 0.06 ms here.
-__device__ __forceinline__ void bk_sincos_d(double x, double& s, double& c) {   // Cody-Waite to [-pi/4, pi/4] + Taylor (error < 1e-11), branch-free
-  const double kd = rint(x * 0.63661977236758134308);
-  const int k = (int)kd;
-  double r = fma(-kd, 1.5707963267948966, x);
-  r = fma(-kd, 6.123233995736766e-17, r);
-  const double r2 = r * r;
-  const double ps = r + r * r2 * (-1.0 / 6 + r2 * (1.0 / 120 + r2 * (-1.0 / 5040 + r2 * (1.0 / 362880 + r2 * (-1.0 / 39916800)))));
-  const double pc = 1.0 + r2 * (-0.5 + r2 * (1.0 / 24 + r2 * (-1.0 / 720 + r2 * (1.0 / 40320 + r2 * (-1.0 / 3628800 + r2 * (1.0 / 479001600))))));
-  const bool sw = k & 1;
-  const double ss = sw ? pc : ps, cc = sw ? ps : pc;
-  s = (k & 2) ? -ss : ss;
-  c = ((k + 1) & 2) ? -cc : cc;
-}
 __global__ __launch_bounds__(256) void point_encode_backward_rows_kernel(const float* __restrict__ xyz, const float* __restrict__ dir, int dir_stride, int dir_div,
                                                                          int N, int M, const int* __restrict__ idx, const float* __restrict__ sp_xyz,
                                                                          const float* __restrict__ sp_dir, const float* __restrict__ rd_w, float inv_span,
@@ -573,7 +557,7 @@ __global__ __launch_bounds__(256) void point_encode_backward_rows_kernel(const f
   for (int ax = 0; ax < 3; ++ax) {
     const float off = (q[ax] - (have ? sp_xyz[3 * (size_t)i + ax] : 0.f)) * inv_span;
     double sn, cs;
-    bk_sincos_d((double)off, sn, cs);
+    nl_sincos_d((double)off, sn, cs);
     double a = (double)g[ax];
     double sc2 = 1.0;
 #pragma unroll
@@ -921,7 +905,7 @@ __global__ __launch_bounds__(SC ? 512 : 256) void mv_geom_backward_kernel(const 
         const int b0 = __ffs((int)mask) - 1;
         mask &= mask - 1;
         const int b1 = mask ? __ffs((int)mask) - 1 : b0;
-        const float w0 = bk_rl(ww, b0), w1 = mask ? bk_rl(ww, b1) : 0.f;
+        const float w0 = nl_rl(ww, b0), w1 = mask ? nl_rl(ww, b1) : 0.f;
         mask &= mask - (mask != 0u);
         if (pf) {
           if (lane < 32) { const float p0_ = sc_pvec[b][b0 >> 2][lane], p1_ = sc_pvec[b][b1 >> 2][lane]; a0 = fmaf(w0, p0_, a0); a0 = fmaf(w1, p1_, a0); }
@@ -959,11 +943,11 @@ __global__ __launch_bounds__(SC ? 512 : 256) void mv_geom_backward_kernel(const 
   const float a_vis = vact ? vis_in[(size_t)vl * N + n] : 0.f, a_dd = vact ? dd_in[(size_t)vl * N + n] : 0.f;
   float vsum = 0.f;
 #pragma unroll
-  for (int v = 0; v < VT; ++v) vsum += v < V ? bk_rl(a_vis, v) : 0.f;
+  for (int v = 0; v < VT; ++v) vsum += v < V ? nl_rl(a_vis, v) : 0.f;
   const float a_wgt = a_vis / (vsum + 1e-8f);
   float Wt = 0.f;   // sum of the weights (< 1 by the 1e-8)
 #pragma unroll
-  for (int v = 0; v < VT; ++v) Wt += v < V ? bk_rl(a_wgt, v) : 0.f;
+  for (int v = 0; v < VT; ++v) Wt += v < V ? nl_rl(a_wgt, v) : 0.f;
   const float omW = 1.f - Wt;
 
   // ---------------------------------------------------------------- statistics part: pass 1 = weighted means, pass 2 = gradients
@@ -991,8 +975,8 @@ __global__ __launch_bounds__(SC ? 512 : 256) void mv_geom_backward_kernel(const 
       if (v < V && !stats) {
         int o[4]; float m[4]; float t[4];
 #pragma unroll
-        for (int k = 0; k < 4; ++k) { o[k] = bk_rli(tf.o[k], v); m[k] = bk_rl(tf.m[k], v); }
-        const float e = bk_rl(tf.e, v), w = bk_rl(tf.w, v), s = bk_rl(tf.s, v), nn = bk_rl(tf.n, v), wg = bk_rl(a_wgt, v);
+        for (int k = 0; k < 4; ++k) { o[k] = nl_rli(tf.o[k], v); m[k] = nl_rl(tf.m[k], v); }
+        const float e = nl_rl(tf.e, v), w = nl_rl(tf.w, v), s = nl_rl(tf.s, v), nn = nl_rl(tf.n, v), wg = nl_rl(a_wgt, v);
         const float* fb = feat + (size_t)v * fmap * C;
 #pragma unroll
         for (int j = 0; j < 3; ++j) {
@@ -1001,8 +985,8 @@ __global__ __launch_bounds__(SC ? 512 : 256) void mv_geom_backward_kernel(const 
         }
         if (lane < 3) {
 #pragma unroll
-          for (int k = 0; k < 4; ++k) { o[k] = bk_rli(ti.o[k], v); m[k] = bk_rl(ti.m[k], v); }
-          const float ei = bk_rl(ti.e, v), wi = bk_rl(ti.w, v), si = bk_rl(ti.s, v), ni = bk_rl(ti.n, v);
+          for (int k = 0; k < 4; ++k) { o[k] = nl_rli(ti.o[k], v); m[k] = nl_rl(ti.m[k], v); }
+          const float ei = nl_rl(ti.e, v), wi = nl_rl(ti.w, v), si = nl_rl(ti.s, v), ni = nl_rl(ti.n, v);
           tapval(images + (size_t)v * 3 * imap + (size_t)lane * imap, 1, o, m, t);
           mean[3] = fmaf((si * ei * t[0] + si * wi * t[1]) + (ni * ei * t[2] + ni * wi * t[3]), wg, mean[3]);
         }
@@ -1017,8 +1001,8 @@ __global__ __launch_bounds__(SC ? 512 : 256) void mv_geom_backward_kernel(const 
       if (v < V) {
         int o[4]; float m[4]; float t[4];
 #pragma unroll
-        for (int k = 0; k < 4; ++k) { o[k] = bk_rli(tf.o[k], v); m[k] = bk_rl(tf.m[k], v); }
-        const float e = bk_rl(tf.e, v), w = bk_rl(tf.w, v), s = bk_rl(tf.s, v), nn = bk_rl(tf.n, v), wg = bk_rl(a_wgt, v);
+        for (int k = 0; k < 4; ++k) { o[k] = nl_rli(tf.o[k], v); m[k] = nl_rl(tf.m[k], v); }
+        const float e = nl_rl(tf.e, v), w = nl_rl(tf.w, v), s = nl_rl(tf.s, v), nn = nl_rl(tf.n, v), wg = nl_rl(a_wgt, v);
         const float* fb = feat + (size_t)v * fmap * C;
         float six = 0.f, siy = 0.f, sw = 0.f;
 #pragma unroll
@@ -1039,8 +1023,8 @@ __global__ __launch_bounds__(SC ? 512 : 256) void mv_geom_backward_kernel(const 
         float sixI = 0.f, siyI = 0.f;
         if (lane < 3) {
 #pragma unroll
-          for (int k = 0; k < 4; ++k) { o[k] = bk_rli(ti.o[k], v); m[k] = bk_rl(ti.m[k], v); }
-          const float ei = bk_rl(ti.e, v), wi = bk_rl(ti.w, v), si = bk_rl(ti.s, v), ni = bk_rl(ti.n, v);
+          for (int k = 0; k < 4; ++k) { o[k] = nl_rli(ti.o[k], v); m[k] = nl_rl(ti.m[k], v); }
+          const float ei = nl_rl(ti.e, v), wi = nl_rl(ti.w, v), si = nl_rl(ti.s, v), ni = nl_rl(ti.n, v);
           tapval(images + (size_t)v * 3 * imap + (size_t)lane * imap, 1, o, m, t);
           const float x = (si * ei * t[0] + si * wi * t[1]) + (ni * ei * t[2] + ni * wi * t[3]);
           const float d = x - mean[3];
@@ -1062,8 +1046,8 @@ __global__ __launch_bounds__(SC ? 512 : 256) void mv_geom_backward_kernel(const 
         float six = 0.f, siy = 0.f, sixI = 0.f, siyI = 0.f;
         if (lane < 32) {
 #pragma unroll
-          for (int k = 0; k < 4; ++k) { o[k] = bk_rli(tf.o[k], v); m[k] = bk_rl(tf.m[k], v); }
-          const float e = bk_rl(tf.e, v), w = bk_rl(tf.w, v), s = bk_rl(tf.s, v), nn = bk_rl(tf.n, v);
+          for (int k = 0; k < 4; ++k) { o[k] = nl_rli(tf.o[k], v); m[k] = nl_rl(tf.m[k], v); }
+          const float e = nl_rl(tf.e, v), w = nl_rl(tf.w, v), s = nl_rl(tf.s, v), nn = nl_rl(tf.n, v);
           tapval(pfeat + (size_t)v * fmap * 32 + lane, 32, o, m, t);
           const float gx = g_pf[((size_t)n * V + v) * 32 + lane];
           six = gx * (s * (t[1] - t[0]) + nn * (t[3] - t[2]));
@@ -1073,14 +1057,14 @@ __global__ __launch_bounds__(SC ? 512 : 256) void mv_geom_backward_kernel(const 
         if constexpr (SC) {   // (the statistics part published this view's keys unless it did not run)
           if (sc_pfeat && !(g393 && sc_feat)) {
 #pragma unroll
-            for (int k = 0; k < 4; ++k) { o[k] = bk_rli(tf.o[k], v); m[k] = bk_rl(tf.m[k], v); }
-            publish(v, o, m, bk_rl(tf.s, v), bk_rl(tf.e, v), bk_rl(tf.w, v), bk_rl(tf.n, v));
+            for (int k = 0; k < 4; ++k) { o[k] = nl_rli(tf.o[k], v); m[k] = nl_rl(tf.m[k], v); }
+            publish(v, o, m, nl_rl(tf.s, v), nl_rl(tf.e, v), nl_rl(tf.w, v), nl_rl(tf.n, v));
           }
         }
         if (lane < 3 && g_rgbv) {
 #pragma unroll
-          for (int k = 0; k < 4; ++k) { o[k] = bk_rli(ti.o[k], v); m[k] = bk_rl(ti.m[k], v); }
-          const float ei = bk_rl(ti.e, v), wi = bk_rl(ti.w, v), si = bk_rl(ti.s, v), ni = bk_rl(ti.n, v);
+          for (int k = 0; k < 4; ++k) { o[k] = nl_rli(ti.o[k], v); m[k] = nl_rl(ti.m[k], v); }
+          const float ei = nl_rl(ti.e, v), wi = nl_rl(ti.w, v), si = nl_rl(ti.s, v), ni = nl_rl(ti.n, v);
           tapval(images + (size_t)v * 3 * imap + (size_t)lane * imap, 1, o, m, t);
           const float gx = g_rgbv[((size_t)n * V + v) * 4 + lane];
           sixI = gx * (si * (t[1] - t[0]) + ni * (t[3] - t[2]));
@@ -1097,7 +1081,7 @@ __global__ __launch_bounds__(SC ? 512 : 256) void mv_geom_backward_kernel(const 
       if (v < V) {
         int o[4]; float m[4];
 #pragma unroll
-        for (int k = 0; k < 4; ++k) { o[k] = bk_rli(tf.o[k], v); m[k] = bk_rl(tf.m[k], v); }
+        for (int k = 0; k < 4; ++k) { o[k] = nl_rli(tf.o[k], v); m[k] = nl_rl(tf.m[k], v); }
         if (g393 && sc_feat) merge_scatter(v, o, m, sc_feat, C, v, fmap, false);
         if (g_pf && sc_pfeat) merge_scatter(v, o, m, sc_pfeat, 32, v, fmap, true);
       }
@@ -1110,7 +1094,7 @@ __global__ __launch_bounds__(SC ? 512 : 256) void mv_geom_backward_kernel(const 
 
   float mdd = 0.f;   // weighted mean of the depth differences (all lanes: cross-lane reads stay outside divergent code)
 #pragma unroll
-  for (int v = 0; v < VT; ++v) mdd += v < V ? bk_rl(a_dd, v) * bk_rl(a_wgt, v) : 0.f;
+  for (int v = 0; v < VT; ++v) mdd += v < V ? nl_rl(a_dd, v) * nl_rl(a_wgt, v) : 0.f;
   // ---------------------------------------------------------------- per-view scalar backward (lane = view)
   float gX = 0.f, gY = 0.f, gZ = 0.f, gq0 = 0.f, gq1 = 0.f, gq2 = 0.f, gvis_out = 0.f, gdd_out = 0.f;
   if (vact) {
@@ -1621,12 +1605,12 @@ __global__ __launch_bounds__(256) void dec_backward_kernel(const NlViews vw, con
 // partial set (DEC_WP floats) behind; dec_wpart_reduce_kernel adds them in a fixed order.  Before: a 560-float row per (view, sample) through HBM (1.5 GB
 // per 65 k samples, written a dword per lane and row), a memset of it and 24 small launches.
 constexpr int DEC_WP = 9 * 1024 + 9 * 64;   // per wave: [k 9][lane 64][r 16] accumulators + [k 9][lane 64] bias partials (k: W1 d 0..3, W2 d 4..7, output layers 8)
-struct DecTrFrag { mvd_bf16x8 h[2], l[2]; };
+struct DecTrFrag { nl_bf16x8 h[2], l[2]; };
 // lane <-> register turn of one 32 (rows) x 32 (features) operand; sh / sl = the lane's 16 values as bf16 hi / lo in register order; rowsum += the feature's
 // sum over this half's 16 rows
 template <int STEPS>
-__device__ __forceinline__ void dec_turn(const mvd_bf16x8 (&sh)[2], const mvd_bf16x8 (&sl)[2], const mvd_bf16x8 (&pm)[2], DecTrFrag& o, float* rowsum) {
-  mvd_f32x16 dh, dl;
+__device__ __forceinline__ void dec_turn(const nl_bf16x8 (&sh)[2], const nl_bf16x8 (&sl)[2], const nl_bf16x8 (&pm)[2], DecTrFrag& o, float* rowsum) {
+  nl_f32x16 dh, dl;
 #pragma unroll
   for (int r = 0; r < 16; ++r) { dh[r] = 0.f; dl[r] = 0.f; }
 #pragma unroll
@@ -1646,7 +1630,7 @@ __device__ __forceinline__ void dec_turn(const mvd_bf16x8 (&sh)[2], const mvd_bf
     for (int t = 0; t < 8; ++t) { o.h[s][t] = (__bf16)dh[8 * s + t]; o.l[s][t] = (__bf16)dl[8 * s + t]; }
 }
 // acc[lane = b's feature][register ~ a's feature] += sum over the 32 rows a . b
-__device__ __forceinline__ void dec_wacc(mvd_f32x16& acc, const DecTrFrag& a, const DecTrFrag& b) {
+__device__ __forceinline__ void dec_wacc(nl_f32x16& acc, const DecTrFrag& a, const DecTrFrag& b) {
 #pragma unroll
   for (int s = 0; s < 2; ++s) {
     acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.l[s], b.h[s], acc, 0, 0, 0);
@@ -1673,8 +1657,8 @@ __global__ __launch_bounds__(256) void dec_backward_mfma_kernel(const NlViews vw
   typedef MvdOps<true> OP;
   const float ni = -1.f / vw.near_, fi = -1.f / vw.far_, span = vw.far_ - vw.near_;
   // TRAIN: k-slot (s, hh, t) -> feature maps (identity for the tap's channels, accumulator order for hidden units / their gradients), weight-gradient accumulators
-  mvd_bf16x8 pmI[2], pmU[2];
-  mvd_f32x16 wacc[TRAIN ? 9 : 1];
+  nl_bf16x8 pmI[2], pmU[2];
+  nl_f32x16 wacc[TRAIN ? 9 : 1];
   float bsum[TRAIN ? 9 : 1];
   if constexpr (TRAIN) {
 #pragma unroll
@@ -1775,17 +1759,17 @@ __global__ __launch_bounds__(256) void dec_backward_mfma_kernel(const NlViews vw
     OP::split(x1, xh[1], xl[1]);
     DecTrFrag tx;   // TRAIN: the tap, lane = channel, k = rows
     if constexpr (TRAIN) {
-      mvd_bf16x8 sh[2], sl[2];
-      mvd_split_bf16(x0, sh[0], sl[0]);
-      mvd_split_bf16(x1, sh[1], sl[1]);
+      nl_bf16x8 sh[2], sl[2];
+      nl_split8_elem(x0, sh[0], sl[0]);
+      nl_split8_elem(x1, sh[1], sl[1]);
       dec_turn<2>(sh, sl, pmI, tx, nullptr);
     }
-    mvd_f32x16 gxa;
+    nl_f32x16 gxa;
 #pragma unroll
     for (int r = 0; r < 16; ++r) gxa[r] = 0.f;
 #pragma unroll
     for (int d = 0; d < 4; ++d) {
-      mvd_f32x16 acc;
+      nl_f32x16 acc;
 #pragma unroll
       for (int g = 0; g < 4; ++g) { const float4 b = *(const float4*)(b1 + 32 * d + 8 * g + 4 * hh); acc[4 * g] = b.x; acc[4 * g + 1] = b.y; acc[4 * g + 2] = b.z; acc[4 * g + 3] = b.w; }
 #pragma unroll
@@ -1804,15 +1788,15 @@ __global__ __launch_bounds__(256) void dec_backward_mfma_kernel(const NlViews vw
         for (int t = 0; t < 8; ++t) vv[t] = h1[8 * s2 + t];
         OP::split(vv, gh[s2], gl[s2]); }
       if constexpr (TRAIN) {
-        mvd_bf16x8 sh[2], sl[2];
+        nl_bf16x8 sh[2], sl[2];
 #pragma unroll
         for (int s2 = 0; s2 < 2; ++s2) { float vv[8];
 #pragma unroll
           for (int t = 0; t < 8; ++t) vv[t] = h1[8 * s2 + t];
-          mvd_split_bf16(vv, sh[s2], sl[s2]); }
+          nl_split8_elem(vv, sh[s2], sl[s2]); }
         dec_turn<2>(sh, sl, pmU, th1, nullptr);
       }
-      mvd_f32x16 acc2;
+      nl_f32x16 acc2;
 #pragma unroll
       for (int g = 0; g < 4; ++g) { const float4 b = *(const float4*)(b2 + 32 * d + 8 * g + 4 * hh); acc2[4 * g] = b.x; acc2[4 * g + 1] = b.y; acc2[4 * g + 2] = b.z; acc2[4 * g + 3] = b.w; }
 #pragma unroll
@@ -1830,17 +1814,17 @@ __global__ __launch_bounds__(256) void dec_backward_mfma_kernel(const NlViews vw
         if constexpr (TRAIN) h2v[r] = h2;
       }
       if constexpr (TRAIN) {   // output layer: rows 2 d, 2 d + 1 of the ninth tile = d(out 0), d(out 1) x hidden 2
-        mvd_bf16x8 sh[2], sl[2], pg[2];
+        nl_bf16x8 sh[2], sl[2], pg[2];
 #pragma unroll
         for (int s2 = 0; s2 < 2; ++s2) { float vv[8];
 #pragma unroll
           for (int t = 0; t < 8; ++t) vv[t] = h2v[8 * s2 + t];
-          mvd_split_bf16(vv, sh[s2], sl[s2]); }
+          nl_split8_elem(vv, sh[s2], sl[s2]); }
         dec_turn<2>(sh, sl, pmU, th2, nullptr);
         float gv8[8];
 #pragma unroll
         for (int t = 0; t < 8; ++t) gv8[t] = (hh == 0 && t < 2) ? go[d][t] : 0.f;
-        mvd_split_bf16(gv8, sh[0], sl[0]);
+        nl_split8_elem(gv8, sh[0], sl[0]);
 #pragma unroll
         for (int t = 0; t < 8; ++t) pg[0][t] = (__bf16)((hh == 0 && t < 2 && j == 2 * d + t) ? 1.f : 0.f);
         pg[1] = pg[0];   // (unused: one k-step)
@@ -1848,23 +1832,23 @@ __global__ __launch_bounds__(256) void dec_backward_mfma_kernel(const NlViews vw
         dec_turn<1>(sh, sl, pg, tgo, &bsum[8]);
         dec_wacc(wacc[8], tgo, th2);
       }
-      mvd_bf16x8 bh[2], bl[2];
+      nl_bf16x8 bh[2], bl[2];
 #pragma unroll
       for (int s2 = 0; s2 < 2; ++s2) { float vv[8];
 #pragma unroll
         for (int t = 0; t < 8; ++t) vv[t] = ga[8 * s2 + t];
-        mvd_split_bf16(vv, bh[s2], bl[s2]); }
+        nl_split8_elem(vv, bh[s2], bl[s2]); }
       if constexpr (TRAIN) {
         DecTrFrag tda;
         dec_turn<2>(bh, bl, pmU, tda, &bsum[4 + d]);
         dec_wacc(wacc[4 + d], tda, th1);
       }
-      mvd_f32x16 accb;
+      nl_f32x16 accb;
 #pragma unroll
       for (int r = 0; r < 16; ++r) accb[r] = 0.f;
 #pragma unroll
       for (int s2 = 0; s2 < 2; ++s2) {
-        const mvd_bf16x8 ah = __builtin_bit_cast(mvd_bf16x8, swt[(d * 2 + s2) * 64 + lane]), al = __builtin_bit_cast(mvd_bf16x8, swt[512 + (d * 2 + s2) * 64 + lane]);
+        const nl_bf16x8 ah = __builtin_bit_cast(nl_bf16x8, swt[(d * 2 + s2) * 64 + lane]), al = __builtin_bit_cast(nl_bf16x8, swt[512 + (d * 2 + s2) * 64 + lane]);
         accb = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh[s2], accb, 0, 0, 0);
         accb = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl[s2], accb, 0, 0, 0);
         accb = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh[s2], accb, 0, 0, 0);
@@ -1875,7 +1859,7 @@ __global__ __launch_bounds__(256) void dec_backward_mfma_kernel(const NlViews vw
         for (int t = 0; t < 8; ++t) {
           const int r = 8 * s2 + t; vv[t] = accb[r] * (h1[r] > 0.f ? 1.f : h1[r] + 1.f);
         }
-        mvd_split_bf16(vv, bh[s2], bl[s2]); }
+        nl_split8_elem(vv, bh[s2], bl[s2]); }
       if constexpr (TRAIN) {
         DecTrFrag tda;
         dec_turn<2>(bh, bl, pmU, tda, &bsum[d]);
@@ -1884,7 +1868,7 @@ __global__ __launch_bounds__(256) void dec_backward_mfma_kernel(const NlViews vw
       if constexpr (!TRAIN)
 #pragma unroll
       for (int s2 = 0; s2 < 2; ++s2) {
-        const mvd_bf16x8 ah = __builtin_bit_cast(mvd_bf16x8, swt[1024 + (d * 2 + s2) * 64 + lane]), al = __builtin_bit_cast(mvd_bf16x8, swt[1024 + 512 + (d * 2 + s2) * 64 + lane]);
+        const nl_bf16x8 ah = __builtin_bit_cast(nl_bf16x8, swt[1024 + (d * 2 + s2) * 64 + lane]), al = __builtin_bit_cast(nl_bf16x8, swt[1024 + 512 + (d * 2 + s2) * 64 + lane]);
         gxa = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh[s2], gxa, 0, 0, 0);
         gxa = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl[s2], gxa, 0, 0, 0);
         gxa = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh[s2], gxa, 0, 0, 0);

@@ -46,6 +46,12 @@ __device__ __forceinline__ float nl_max_lane_xor1(float v) {
   asm("s_nop 1\n\tv_max_f32_dpp %0, %1, %1 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf" : "=v"(r) : "v"(v));
   return r;
 }
+// float -> bf16 bits, round to nearest even (the packing kernels' scalar form; the hot paths use the packed conversions below)
+__device__ __forceinline__ unsigned short nl_f2bf(float x) {
+  unsigned int u = __float_as_uint(x);
+  u += 0x7fffu + ((u >> 16) & 1u);
+  return (unsigned short)(u >> 16);
+}
 // Split-bf16 of a PAIR: hi = the pair rounded to bf16 (one v_cvt_pk_bf16_f32), lo = bf16(v - float(hi)) with the subtraction as one packed instruction — per element the
 // same two roundings as `h = (__bf16)v; l = (__bf16)(v - (float)h)`, which hipcc lowers to a conversion per ELEMENT for the subtraction and a second, packed one for the
 // store (32 vector instructions per 8 values; this form: 20).  Results as raw 32-bit words: element 0 in the low half.
@@ -125,6 +131,28 @@ __device__ __forceinline__ float wave_max(float v) {
   v = fmaxf(v, nl_dpp<0x111>(v, ninf)); v = fmaxf(v, nl_dpp<0x112>(v, ninf)); v = fmaxf(v, nl_dpp<0x114>(v, ninf)); v = fmaxf(v, nl_dpp<0x118>(v, ninf));
   v = fmaxf(v, nl_dpp<0x142, 0xa>(v, ninf)); v = fmaxf(v, nl_dpp<0x143, 0xc>(v, ninf));
   return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
+}
+
+// v_readlane of a float / an int (constant or wave-uniform lane -> an SGPR)
+__device__ __forceinline__ float nl_rl(float v, int lane) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), lane)); }
+__device__ __forceinline__ int nl_rli(int v, int lane) { return __builtin_amdgcn_readlane(v, lane); }
+
+// ------------------------------------------------------------------ positional encoding
+constexpr double NL_TWO_OVER_PI = 0.63661977236758134308, NL_PIO2_HI = 1.5707963267948966, NL_PIO2_LO = 6.123233995736766e-17;   // the Cody-Waite constants live here only (point_fused2.hip runs the same reduction step by step in its MFMA shadow)
+// branch-free sin/cos in fp64 (|x| up to ~1e5): Cody-Waite reduction to [-pi/4, pi/4] + Taylor (error < 1e-11).  ONE function for the fused forward kernels
+// (point_fused.hip, point_fused2.hip) and the encoding's derivative (backward.hip): the gradient tests take them to be the same.
+__device__ __forceinline__ void nl_sincos_d(double x, double& s, double& c) {
+  const double kd = rint(x * NL_TWO_OVER_PI);
+  const int k = (int)kd;
+  double r = fma(-kd, NL_PIO2_HI, x);
+  r = fma(-kd, NL_PIO2_LO, r);
+  const double r2 = r * r;
+  const double ps = r + r * r2 * (-1.0 / 6 + r2 * (1.0 / 120 + r2 * (-1.0 / 5040 + r2 * (1.0 / 362880 + r2 * (-1.0 / 39916800)))));
+  const double pc = 1.0 + r2 * (-0.5 + r2 * (1.0 / 24 + r2 * (-1.0 / 720 + r2 * (1.0 / 40320 + r2 * (-1.0 / 3628800 + r2 * (1.0 / 479001600))))));
+  const bool sw = k & 1;
+  const double ss = sw ? pc : ps, cc = sw ? ps : pc;
+  s = (k & 2) ? -ss : ss;
+  c = ((k + 1) & 2) ? -cc : cc;
 }
 
 // ------------------------------------------------------------------ XCD-aware block order

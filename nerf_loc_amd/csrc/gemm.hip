@@ -12,20 +12,13 @@
 //   NL_PREC_BF16   : staged ([m][k] rows padded to 80 B -> conflict-free ds_read_b128), weights pre-split
 // Global loads of tile t+1 are issued before the MFMAs of tile t (register prefetch).
 #include "common.h"
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
+#include "mfma.h"
 
 namespace {
 
 constexpr int BM = 128;
 constexpr int BK = 32;
 
-__device__ __forceinline__ unsigned short f2bf(float x) {  // round-to-nearest-even
-  unsigned int u = __float_as_uint(x);
-  u += 0x7fffu + ((u >> 16) & 1u);
-  return (unsigned short)(u >> 16);
-}
 __device__ __forceinline__ float bf2f(unsigned short h) { return __uint_as_float(((unsigned int)h) << 16); }
 
 struct RowMap {
@@ -135,7 +128,7 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(const NlGemmArgs a) {
     }
   };
 
-  f32x16 acc[BN / 32];
+  nl_f32x16 acc[BN / 32];
 #pragma unroll
   for (int c = 0; c < BN / 32; ++c)
 #pragma unroll
@@ -230,7 +223,7 @@ __global__ __launch_bounds__(256) void gemm_bf16_kernel(const NlGemmArgs a) {
     }
   };
 
-  f32x16 acc[BN / 32];
+  nl_f32x16 acc[BN / 32];
 #pragma unroll
   for (int c = 0; c < BN / 32; ++c)
 #pragma unroll
@@ -241,8 +234,7 @@ __global__ __launch_bounds__(256) void gemm_bf16_kernel(const NlGemmArgs a) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const float v[4] = {areg[i].x, areg[i].y, areg[i].z, areg[i].w};
-      typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-      bf16x4 h, l;
+      nl_bf16x4 h, l;
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         h[j] = (__bf16)v[j];
@@ -263,14 +255,14 @@ __global__ __launch_bounds__(256) void gemm_bf16_kernel(const NlGemmArgs a) {
 #pragma unroll
     for (int ks = 0; ks < BK / 16; ++ks) {  // two 16-deep MFMA k-steps per 32-wide tile
       const int ko = ks * 16 + 8 * (lane >> 5);
-      const bf16x8 ah = *(const bf16x8*)&Ah[(32 * wave + (lane & 31)) * LDS_ROW + ko];
-      bf16x8 al;
-      if (X3) al = *(const bf16x8*)&Al[(32 * wave + (lane & 31)) * LDS_ROW + ko];
+      const nl_i16x8 ah = *(const nl_i16x8*)&Ah[(32 * wave + (lane & 31)) * LDS_ROW + ko];
+      nl_i16x8 al;
+      if (X3) al = *(const nl_i16x8*)&Al[(32 * wave + (lane & 31)) * LDS_ROW + ko];
 #pragma unroll
       for (int c = 0; c < BN / 32; ++c) {
-        const bf16x8 bhv = *(const bf16x8*)&Bh[(32 * c + (lane & 31)) * LDS_ROW + ko];
+        const nl_i16x8 bhv = *(const nl_i16x8*)&Bh[(32 * c + (lane & 31)) * LDS_ROW + ko];
         if (X3) {
-          const bf16x8 blv = *(const bf16x8*)&Bl[(32 * c + (lane & 31)) * LDS_ROW + ko];
+          const nl_i16x8 blv = *(const nl_i16x8*)&Bl[(32 * c + (lane & 31)) * LDS_ROW + ko];
           acc[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bhv, acc[c], 0, 0, 0);
           acc[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, blv, acc[c], 0, 0, 0);
         }

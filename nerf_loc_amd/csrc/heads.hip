@@ -335,9 +335,6 @@ int nl_launch_blend(const float* hA, const float* h1, const float* rgbv, int64_t
 // v_mfma_f32_16x16x32_bf16 (split-bf16 like every parity-mode product; its A fragments are built from the fp32 weights at kernel start) — the lane's octet IS its slice of
 // the B operand — LeakyReLU, the 16 -> 1 layer as 4 FMAs + two cross-lane adds, and a streaming softmax over the views (no per-view array).
 namespace {
-typedef __bf16 bt_bf16x8 __attribute__((ext_vector_type(8)));
-typedef float bt_f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned bt_u32x4 __attribute__((ext_vector_type(4)));
 constexpr int BT_SLOT = 9;    // dwords per (row, view): cell, w0 .. w3, the four view-angle features (an odd stride: dword accesses, no bank conflicts; 24 KB at 10 views)
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 8))) void blend_taps_mfma_kernel(const NlViews vw, const float* __restrict__ viewsdev, const float* __restrict__ pfeat /*(V,h,w,32)*/,
                                                               const float* __restrict__ blw /*[32][8], bias[32]*/, const float* __restrict__ xyz,
@@ -358,21 +355,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 8))) voi
   const float* wls = bt_lds + 64 * g;        // rows 8 g .. 8 g + 7 of the [32][8] block
   const float* bls = bt_lds + 256 + 8 * g;
   // ---- resident: layer 2 as A fragments (row n = r, k = 8 g + t), the output layer's slice
-  bt_u32x4 ah, al;
+  nl_u32x4 ah, al;
   {
     unsigned hw[8], lw[8];
 #pragma unroll
     for (int t = 0; t < 8; ++t) {
       const float w = w2[r * 32 + 8 * g + t];
-      unsigned u = __float_as_uint(w);
-      u += 0x7fffu + ((u >> 16) & 1u);
-      hw[t] = u >> 16;
-      unsigned v = __float_as_uint(w - __uint_as_float(hw[t] << 16));
-      v += 0x7fffu + ((v >> 16) & 1u);
-      lw[t] = v >> 16;
+      hw[t] = nl_f2bf(w);
+      lw[t] = nl_f2bf(w - __uint_as_float(hw[t] << 16));
     }
-    ah = bt_u32x4{hw[0] | (hw[1] << 16), hw[2] | (hw[3] << 16), hw[4] | (hw[5] << 16), hw[6] | (hw[7] << 16)};
-    al = bt_u32x4{lw[0] | (lw[1] << 16), lw[2] | (lw[3] << 16), lw[4] | (lw[5] << 16), lw[6] | (lw[7] << 16)};
+    ah = nl_u32x4{hw[0] | (hw[1] << 16), hw[2] | (hw[3] << 16), hw[4] | (hw[5] << 16), hw[6] | (hw[7] << 16)};
+    al = nl_u32x4{lw[0] | (lw[1] << 16), lw[2] | (lw[3] << 16), lw[4] | (lw[5] << 16), lw[6] | (lw[7] << 16)};
   }
   float b2q[4], w4q[4];
 #pragma unroll
@@ -463,19 +456,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 8))) voi
         a = fmaf(wa.x, in8[0], a); a = fmaf(wa.y, in8[1], a); a = fmaf(wa.z, in8[2], a); a = fmaf(wa.w, in8[3], a);
         a = fmaf(wb.x, in8[4], a); a = fmaf(wb.y, in8[5], a); a = fmaf(wb.z, in8[6], a); a = fmaf(wb.w, in8[7], a);
         const float hv = nl_lrelu(xa[j] + a);
-        unsigned u = __float_as_uint(hv);
-        u += 0x7fffu + ((u >> 16) & 1u);
-        hh[j] = u >> 16;
-        unsigned w = __float_as_uint(hv - __uint_as_float(hh[j] << 16));
-        w += 0x7fffu + ((w >> 16) & 1u);
-        hl[j] = w >> 16;
+        hh[j] = nl_f2bf(hv);
+        hl[j] = nl_f2bf(hv - __uint_as_float(hh[j] << 16));
       }
-      const bt_u32x4 bh = {hh[0] | (hh[1] << 16), hh[2] | (hh[3] << 16), hh[4] | (hh[5] << 16), hh[6] | (hh[7] << 16)};
-      const bt_u32x4 blo = {hl[0] | (hl[1] << 16), hl[2] | (hl[3] << 16), hl[4] | (hl[5] << 16), hl[6] | (hl[7] << 16)};
-      bt_f32x4 acc = {b2q[0], b2q[1], b2q[2], b2q[3]};
-      acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bt_bf16x8, al), __builtin_bit_cast(bt_bf16x8, bh), acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bt_bf16x8, ah), __builtin_bit_cast(bt_bf16x8, blo), acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bt_bf16x8, ah), __builtin_bit_cast(bt_bf16x8, bh), acc, 0, 0, 0);
+      const nl_u32x4 bh = {hh[0] | (hh[1] << 16), hh[2] | (hh[3] << 16), hh[4] | (hh[5] << 16), hh[6] | (hh[7] << 16)};
+      const nl_u32x4 blo = {hl[0] | (hl[1] << 16), hl[2] | (hl[3] << 16), hl[4] | (hl[5] << 16), hl[6] | (hl[7] << 16)};
+      nl_f32x4 acc = {b2q[0], b2q[1], b2q[2], b2q[3]};
+      acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(nl_bf16x8, al), __builtin_bit_cast(nl_bf16x8, bh), acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(nl_bf16x8, ah), __builtin_bit_cast(nl_bf16x8, blo), acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(nl_bf16x8, ah), __builtin_bit_cast(nl_bf16x8, bh), acc, 0, 0, 0);
       float op = w4q[0] * nl_lrelu(acc[0]);
       op = fmaf(w4q[1], nl_lrelu(acc[1]), op); op = fmaf(w4q[2], nl_lrelu(acc[2]), op); op = fmaf(w4q[3], nl_lrelu(acc[3]), op);
       op += __shfl_xor(op, 16, 64);

@@ -111,15 +111,14 @@ __global__ void pack_mv_decoder_kernel(const float* __restrict__ dec /* packed V
   unsigned short* h16 = reinterpret_cast<unsigned short*>(out + MVD_F16);
   float* of = reinterpret_cast<float*>(out + MVD_F32);
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  auto f2bf = [](float x) { unsigned int u = __float_as_uint(x); u += 0x7fffu + ((u >> 16) & 1u); return (unsigned short)(u >> 16); };
   auto f2h = [](float x) { const _Float16 h = (_Float16)x; return __builtin_bit_cast(unsigned short, h); };
   auto h2f = [](unsigned short b) { return (float)__builtin_bit_cast(_Float16, b); };
   if (i < 4096) {          // layer 1: element (q, d, lane, t)
     const int t = i & 7, lane = (i >> 3) & 63, d = (i >> 9) & 3, q = i >> 11;
     const float v = dec[d * DEC_STRIDE + (lane & 31) * 32 + 16 * q + 8 * (lane >> 5) + t];
-    const unsigned short h = f2bf(v);
+    const unsigned short h = nl_f2bf(v);
     o16[(size_t)MVD_W1 * 8 + i] = h;
-    o16[(size_t)(MVD_W1 + 512) * 8 + i] = f2bf(v - __uint_as_float(((unsigned)h) << 16));
+    o16[(size_t)(MVD_W1 + 512) * 8 + i] = nl_f2bf(v - __uint_as_float(((unsigned)h) << 16));
     const unsigned short g = f2h(v);
     h16[(size_t)MVD_W1 * 8 + i] = g;
     h16[(size_t)(MVD_W1 + 512) * 8 + i] = f2h(v - h2f(g));
@@ -128,9 +127,9 @@ __global__ void pack_mv_decoder_kernel(const float* __restrict__ dec /* packed V
     const int t = e & 7, lane = (e >> 3) & 63, s = (e >> 9) & 1, d = e >> 10;
     const int fin = 16 * s + (t & 3) + 8 * (t >> 2) + 4 * (lane >> 5);
     const float v = dec[d * DEC_STRIDE + 1056 + (lane & 31) * 32 + fin];
-    const unsigned short h = f2bf(v);
+    const unsigned short h = nl_f2bf(v);
     o16[(size_t)MVD_W2 * 8 + e] = h;
-    o16[(size_t)(MVD_W2 + 512) * 8 + e] = f2bf(v - __uint_as_float(((unsigned)h) << 16));
+    o16[(size_t)(MVD_W2 + 512) * 8 + e] = nl_f2bf(v - __uint_as_float(((unsigned)h) << 16));
     const unsigned short g = f2h(v);
     h16[(size_t)MVD_W2 * 8 + e] = g;
     h16[(size_t)(MVD_W2 + 512) * 8 + e] = f2h(v - h2f(g));
@@ -139,7 +138,7 @@ __global__ void pack_mv_decoder_kernel(const float* __restrict__ dec /* packed V
   else if (i < 8192 + 512) {                                                                                               // w4p[d][u][hh][r]
     const int e = i - 8192 - 256;
     const int r = e & 15, hh = (e >> 4) & 1, u = (e >> 5) & 1, d = e >> 6;
-    const int idx = (r & 3) + 8 * (r >> 2) + 4 * hh;
+    const int idx = nl_acc_row(r, hh);
     of[256 + e] = dec[d * DEC_STRIDE + 2112 + u * 32 + idx];
   } else if (i < 8192 + 520) { const int e = i - 8192 - 512; of[512 + e] = dec[(e >> 1) * DEC_STRIDE + 2176 + (e & 1)]; }   // b4
   // transposed fragments for the input gradient (bf16 hi / lo): element (which, d, s, lane, t), which 0 = W2T, 1 = W1T
@@ -156,14 +155,11 @@ __global__ void pack_mv_decoder_kernel(const float* __restrict__ dec /* packed V
       const int chan = r < 8 ? 8 * hh + r : 16 + 8 * hh + (r - 8);
       v = dec[d * DEC_STRIDE + u * 32 + chan];                          // W1[u][chan]
     }
-    const unsigned short h = f2bf(v);
+    const unsigned short h = nl_f2bf(v);
     t16[(size_t)which * 1024 * 8 + e] = h;
-    t16[(size_t)which * 1024 * 8 + 512 * 8 + e] = f2bf(v - __uint_as_float(((unsigned)h) << 16));
+    t16[(size_t)which * 1024 * 8 + 512 * 8 + e] = nl_f2bf(v - __uint_as_float(((unsigned)h) << 16));
   }
 }
-
-__device__ __forceinline__ float rl(float v, int lane) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), lane)); }
-__device__ __forceinline__ int rli(int v, int lane) { return __builtin_amdgcn_readlane(v, lane); }
 
 // One wave per sample.  Phase A: lane v (< V) does view v's scalar work once — IBRNet projection, tap offsets / weights for
 // the feature map and the image (validity folded into zero weights + clamped offsets, so phase-B loads are unconditional),
@@ -237,7 +233,7 @@ __global__ __launch_bounds__(256, VT <= 4 ? 4 : (VT <= 10 ? 3 : 2)) void mv_stat
     // weight = vis / (sum_v vis + 1e-8): sequential sum over views like the reference's reduction
     float vsum = 0.f;
 #pragma unroll
-    for (int v = 0; v < VT; ++v) vsum += v < V ? rl(a_vis, v) : 0.f;
+    for (int v = 0; v < VT; ++v) vsum += v < V ? nl_rl(a_vis, v) : 0.f;
     a_wgt = a_vis / (vsum + 1e-8f);
   }
 
@@ -257,8 +253,8 @@ __global__ __launch_bounds__(256, VT <= 4 ? 4 : (VT <= 10 ? 3 : 2)) void mv_stat
   auto issue = [&](int v) __attribute__((always_inline)) {
     ViewTaps t;
     int o[4], oi[4];
-    unpack_taps((unsigned)rli((int)a_fo, v), vw.w, o);
-    unpack_taps((unsigned)rli((int)a_io, v), vw.Wimg, oi);
+    unpack_taps((unsigned)nl_rli((int)a_fo, v), vw.w, o);
+    unpack_taps((unsigned)nl_rli((int)a_io, v), vw.Wimg, oi);
     const float* fb = feat + (size_t)v * vw.h * vw.w * C;
     if constexpr (V4) {
 #pragma unroll
@@ -282,7 +278,7 @@ __global__ __launch_bounds__(256, VT <= 4 ? 4 : (VT <= 10 ? 3 : 2)) void mv_stat
     return t;
   };
   auto finish = [&](int v, const ViewTaps& t) __attribute__((always_inline)) {
-    const float w0 = rl(a_fw[0], v), w1 = rl(a_fw[1], v), w2 = rl(a_fw[2], v), w3 = rl(a_fw[3], v);
+    const float w0 = nl_rl(a_fw[0], v), w1 = nl_rl(a_fw[1], v), w2 = nl_rl(a_fw[2], v), w3 = nl_rl(a_fw[3], v);
     if constexpr (V4) {
       // explicit fma chains: the file is built with -ffp-contract=off (the bit-exact kernels need it), which would cost 7
       // instructions per bilinear tap sum instead of 4
@@ -295,21 +291,21 @@ __global__ __launch_bounds__(256, VT <= 4 ? 4 : (VT <= 10 ? 3 : 2)) void mv_stat
       for (int j = 0; j < 3; ++j) xv[v][j] = fmaf(t.fs[j][3], w3, fmaf(t.fs[j][2], w2, fmaf(t.fs[j][1], w1, t.fs[j][0] * w0)));
     }
     {
-      const float i0 = rl(a_iw[0], v), i1 = rl(a_iw[1], v), i2 = rl(a_iw[2], v), i3 = rl(a_iw[3], v);
+      const float i0 = nl_rl(a_iw[0], v), i1 = nl_rl(a_iw[1], v), i2 = nl_rl(a_iw[2], v), i3 = nl_rl(a_iw[3], v);
       const float val = fmaf(t.im[3], i3, fmaf(t.im[2], i2, fmaf(t.im[1], i1, t.im[0] * i0)));
       xv[v][4] = lane < 3 ? val : 0.f;
     }
-    const float s_vis = rl(a_vis, v);
+    const float s_vis = nl_rl(a_vis, v);
     if (bl1) {
       // colour-blend layer 1, per-(sample, view) part, by linearity of the bilinear tap (model.py:532-535):
       //   W[:, feat] . bilinear(featmap) == bilinear(W[:, feat] . featmap); plus rgb / visibility / angle columns + bias
       const float pv = fmaf(t.pf[3], w3, fmaf(t.pf[2], w2, fmaf(t.pf[1], w1, t.pf[0] * w0)));
-      const float r = rl(xv[v][4], 0), g = rl(xv[v][4], 1), bb = rl(xv[v][4], 2);
+      const float r = nl_rl(xv[v][4], 0), g = nl_rl(xv[v][4], 1), bb = nl_rl(xv[v][4], 2);
       float o = pv + bbias;
       o = fmaf(bwr[0], r, o); o = fmaf(bwr[1], g, o); o = fmaf(bwr[2], bb, o);
       o = fmaf(bwr[3], s_vis, o);
-      o = fmaf(bwr[4], rl(a_ang[0], v), o); o = fmaf(bwr[5], rl(a_ang[1], v), o);
-      o = fmaf(bwr[6], rl(a_ang[2], v), o); o = fmaf(bwr[7], rl(a_ang[3], v), o);
+      o = fmaf(bwr[4], nl_rl(a_ang[0], v), o); o = fmaf(bwr[5], nl_rl(a_ang[1], v), o);
+      o = fmaf(bwr[6], nl_rl(a_ang[2], v), o); o = fmaf(bwr[7], nl_rl(a_ang[3], v), o);
       if (lane < 32) bl1[((size_t)n * V + v) * 32 + lane] = o;
       if (lane < 4) rgbv[((size_t)n * V + v) * 4 + lane] = lane < 3 ? xv[v][4] : s_vis;
     }
@@ -324,8 +320,8 @@ __global__ __launch_bounds__(256, VT <= 4 ? 4 : (VT <= 10 ? 3 : 2)) void mv_stat
       if (lane == 3) row[F] = 0.f;
       if (lane == 0 && vis_ang) {
         float* va = vis_ang + ((size_t)n * V + v) * 8;
-        *(float4*)va = make_float4(s_vis, rl(a_ang[0], v), rl(a_ang[1], v), rl(a_ang[2], v));
-        *(float4*)(va + 4) = make_float4(rl(a_ang[3], v), 0.f, 0.f, 0.f);
+        *(float4*)va = make_float4(s_vis, nl_rl(a_ang[0], v), nl_rl(a_ang[1], v), nl_rl(a_ang[2], v));
+        *(float4*)(va + 4) = make_float4(nl_rl(a_ang[3], v), 0.f, 0.f, 0.f);
       }
     }
   };
@@ -350,7 +346,7 @@ __global__ __launch_bounds__(256, VT <= 4 ? 4 : (VT <= 10 ? 3 : 2)) void mv_stat
   // visibility-weighted mean / variance over views (ibrnet.py:8-12)
   float wg[VT];
 #pragma unroll
-  for (int v = 0; v < VT; ++v) wg[v] = v < V ? rl(a_wgt, v) : 0.f;
+  for (int v = 0; v < VT; ++v) wg[v] = v < V ? nl_rl(a_wgt, v) : 0.f;
   float* g = g393 + (size_t)n * ldg;
 #pragma unroll
   for (int j = 0; j < 5; ++j) {
@@ -369,10 +365,10 @@ __global__ __launch_bounds__(256, VT <= 4 ? 4 : (VT <= 10 ? 3 : 2)) void mv_stat
   if (lane == 0) {
     float mean = 0.f, wsum = 0.f;
 #pragma unroll
-    for (int v = 0; v < VT; ++v) { if (v < V) { mean += rl(a_dd, v) * wg[v]; wsum += wg[v]; } }
+    for (int v = 0; v < VT; ++v) { if (v < V) { mean += nl_rl(a_dd, v) * wg[v]; wsum += wg[v]; } }
     float var = 0.f;
 #pragma unroll
-    for (int v = 0; v < VT; ++v) { if (v < V) { float d = rl(a_dd, v) - mean; var += wg[v] * (d * d); } }
+    for (int v = 0; v < VT; ++v) { if (v < V) { float d = nl_rl(a_dd, v) - mean; var += wg[v] * (d * d); } }
     g[2 * F] = mean;
     g[2 * F + 1] = var;
     g[2 * F + 2] = wsum / (float)V;

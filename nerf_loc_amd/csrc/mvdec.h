@@ -2,6 +2,7 @@
 // decoders (visibility_decoder.py:64-107) evaluated per lane with wave-uniform (scalar-loaded) weights.
 #pragma once
 #include "common.h"
+#include "mfma.h"
 
 namespace nlmv {
 
@@ -148,9 +149,6 @@ __device__ __forceinline__ void decode_all(const float* __restrict__ dw, const f
 // path where split-bf16's 2^-17 showed (a sample whose views are all almost invisible turned 7e-6 of visibility error into 2e-4 of
 // compositing weight, tools/precision_budget.py); the visibility features are O(1) outputs of the per-frame CNN, far inside fp16's
 // range.  !X3 = one bf16 MFMA per product (throughput mode).
-typedef __bf16 mvd_bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 mvd_f16x8 __attribute__((ext_vector_type(8)));
-typedef float mvd_f32x16 __attribute__((ext_vector_type(16)));
 
 // dpack (uint4 units): [0, 2048) bf16 fragments: W1 hi [q 2][d 4][lane 64] at 0, lo at +512; W2 hi [d 4][s 2][lane 64] at 1024, lo at
 // +512.  [2048, 2048 + 130) floats: b1[128] b2[128] w4p[4][2][2][16] b4[8].  [2178, 2178 + 2048) the same fragments in fp16 hi / lo.
@@ -175,13 +173,12 @@ __device__ __forceinline__ void mvd_load_lds(uint4* sw, const uint4* __restrict_
 }
 
 template <bool X3> struct MvdOps;
-typedef unsigned mvd_u32x4 __attribute__((ext_vector_type(4)));
 template <> struct MvdOps<true> {
-  typedef mvd_f16x8 v8;
+  typedef nl_f16x8 v8;
   // hi = f16(v), lo = f16(v - hi): per pair v_cvt_pk_f16_f32 | 2 x v_fma_mix_f32 (reads the f16 half directly: no v_cvt_f32_f16, no separate subtraction) |
   // v_cvt_pk_f16_f32 = 2 vector instructions per value instead of 3.5 (round 4: the kernel is bound by its vector instruction count, profiles/r4_pmc_sq.csv)
   static __device__ __forceinline__ void split(const float (&v)[8], v8& hi, v8& lo) {
-    mvd_u32x4 h, l;
+    nl_u32x4 h, l;
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
       unsigned hp, lp; float l0, l1;
@@ -192,34 +189,20 @@ template <> struct MvdOps<true> {
     }
     hi = __builtin_bit_cast(v8, h); lo = __builtin_bit_cast(v8, l);
   }
-  static __device__ __forceinline__ mvd_f32x16 mfma(v8 a, v8 b, mvd_f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
+  static __device__ __forceinline__ nl_f32x16 mfma(v8 a, v8 b, nl_f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
 };
 template <> struct MvdOps<false> {
-  typedef mvd_bf16x8 v8;
+  typedef nl_bf16x8 v8;
   static __device__ __forceinline__ void split(const float (&v)[8], v8& hi, v8& lo) {
 #pragma unroll
     for (int t = 0; t < 8; ++t) hi[t] = (__bf16)v[t];
     lo = hi;
   }
-  static __device__ __forceinline__ mvd_f32x16 mfma(v8 a, v8 b, mvd_f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0); }
+  static __device__ __forceinline__ nl_f32x16 mfma(v8 a, v8 b, nl_f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0); }
 };
 
-__device__ __forceinline__ void mvd_split_bf16(const float (&v)[8], mvd_bf16x8& hi, mvd_bf16x8& lo) {
-#pragma unroll
-  for (int t = 0; t < 8; ++t) { const __bf16 h = (__bf16)v[t]; hi[t] = h; lo[t] = (__bf16)(v[t] - (float)h); }
-}
-
-// ELU of two values at once (x > 0 ? x : exp(x) - 1 with the exponential on the hardware exp2 unit, as nl_elu_fast): the scale by log2(e) and the -1 are ONE packed
-// instruction each for the pair (v_pk_mul_f32, v_pk_add_f32), the select is a median — 6 vector instructions per pair (round 4: 8; scalar form: 10)
-typedef float mvd_f32x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ void mvd_elu2(float& a, float& b) {
-  const mvd_f32x2 x = {a, b};
-  const mvd_f32x2 y = x * mvd_f32x2{1.4426950408889634f, 1.4426950408889634f};
-  mvd_f32x2 e = {__builtin_amdgcn_exp2f(y[0]), __builtin_amdgcn_exp2f(y[1])};
-  e = e - mvd_f32x2{1.f, 1.f};
-  a = __builtin_amdgcn_fmed3f(x[0], e[0], 0.f);   // = x > 0 ? x : e up to the rounding of e near 0 (e^x - 1 >= x: the median of {x, e, 0} is ELU(x); common.h: nl_elu_fast)
-  b = __builtin_amdgcn_fmed3f(x[1], e[1], 0.f);
-}
+// ELU of two values at once, in place (common.h: nl_elu_fast2 — 6 vector instructions per pair; round 4: 8; scalar form: 10)
+__device__ __forceinline__ void mvd_elu2(float& a, float& b) { const nl_f32x2 e = nl_elu_fast2(nl_f32x2{a, b}); a = e[0]; b = e[1]; }
 
 // this lane's 16 channels of the bilinear (border, align_corners = False) tap of the channels-last 32-channel visibility map at
 // pixel (px, py) of view `base`; zero when !valid (depth_fusion.py:60-76, neuray_ops.py:14-36)
@@ -267,7 +250,7 @@ __device__ __forceinline__ void mvd_decode_tile(const uint4* sw, int lane, const
   float o[4][2];
 #pragma unroll
   for (int d = 0; d < 4; ++d) {
-    mvd_f32x16 acc;
+    nl_f32x16 acc;
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
       const float4 b = *(const float4*)(b1 + 32 * d + 8 * g + 4 * hh);
@@ -293,7 +276,7 @@ __device__ __forceinline__ void mvd_decode_tile(const uint4* sw, int lane, const
       for (int t = 0; t < 8; t += 2) mvd_elu2(vv[t], vv[t + 1]);
       OP::split(vv, gh[s], gl[s]);
     }
-    mvd_f32x16 acc2;
+    nl_f32x16 acc2;
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
       const float4 b = *(const float4*)(b2 + 32 * d + 8 * g + 4 * hh);

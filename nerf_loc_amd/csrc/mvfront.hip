@@ -23,11 +23,6 @@
 namespace {
 using namespace nlmv;
 
-typedef __bf16 mf_bf16x8 __attribute__((ext_vector_type(8)));
-typedef float mf_f32x4 __attribute__((ext_vector_type(4)));
-typedef float mf_f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned mf_u32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int MF_C = 192;          // feature channels (3 per lane in phase B: all 64 lanes, 12-byte loads)
 constexpr int MF_KS = 12;          // k-steps of 32: [mean 192 | variance 192]
 constexpr int MF_LD = 400;         // staging row stride in halves (384 + pad): 200 dwords = 8 (mod 64) — the MFMA phase's ds_read_b128 (lane = (row, k-quarter), 16-lane
@@ -43,23 +38,21 @@ __device__ __forceinline__ float mf_sum16(float v) {   // sum over an aligned gr
   v += nl_dpp<0x140>(v);   // row_mirror
   return v;
 }
-__device__ __forceinline__ float mf_rl(float v, int lane) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), lane)); }
 
 // A fragments of out_fc.0 for v_mfma_f32_16x16x32_bf16: [n-tile 4][k-step 12][part hi / lo][lane 64] x 8 bf16; lane: row n = 16 nt + (lane & 15), k = 32 ks + 8 (lane >> 4) + t,
 // k < 192: mean of feature channel k (column 3 + k of the layer), k >= 192: its variance (column F + 3 + k - 192).  w9 [64][12]: the nine other columns + the bias.
 __global__ void pack_mv_front_kernel(const float* __restrict__ w /*(64, 393)*/, const float* __restrict__ b, unsigned short* __restrict__ out, float* __restrict__ w9) {
   const int e = blockIdx.x * blockDim.x + threadIdx.x;
   constexpr int F = MF_C + 3, LDW = 2 * F + 3;
-  auto f2bf = [](float x) { unsigned u = __float_as_uint(x); u += 0x7fffu + ((u >> 16) & 1u); return (unsigned short)(u >> 16); };
   if (e < 4 * MF_KS * 64 * 8) {
     const int t = e & 7, lane = (e >> 3) & 63, ks = (e >> 9) % MF_KS, nt = (e >> 9) / MF_KS;
     const int n = 16 * nt + (lane & 15), k = 32 * ks + 8 * (lane >> 4) + t;
     const int col = k < MF_C ? 3 + k : F + 3 + (k - MF_C);
     const float v = w[n * LDW + col];
-    const unsigned short h = f2bf(v);
+    const unsigned short h = nl_f2bf(v);
     const size_t base = ((size_t)(nt * MF_KS + ks) * 2) * 512 + lane * 8 + t;
     out[base] = h;
-    out[base + 512] = f2bf(v - __uint_as_float(((unsigned)h) << 16));
+    out[base + 512] = nl_f2bf(v - __uint_as_float(((unsigned)h) << 16));
   }
   if (e < 64 * 12) {
     const int n = e / 12, i = e % 12;
@@ -75,7 +68,7 @@ __global__ void pack_mv_front_kernel(const float* __restrict__ w /*(64, 393)*/, 
 __global__ __launch_bounds__(64 * MF_NWAVES, 1) void mv_front_kernel(const NlViews vw, const float* __restrict__ viewsdev, const float* __restrict__ images,
                                                           const float* __restrict__ feat /*(V,h,w,192)*/, const float* __restrict__ xyz, int N,
                                                           const float* __restrict__ vis_in, const float* __restrict__ dd_in,
-                                                          const mf_u32x4* __restrict__ wpack, const float* __restrict__ w9g, float* __restrict__ t64,
+                                                          const nl_u32x4* __restrict__ wpack, const float* __restrict__ w9g, float* __restrict__ t64,
                                                           int* __restrict__ valid_s, float* __restrict__ rgbv, int nrounds, int rounds_per_block) {
   extern __shared__ __attribute__((aligned(16))) unsigned char mf_lds[];
   unsigned short* st_hi = reinterpret_cast<unsigned short*>(mf_lds);
@@ -90,7 +83,7 @@ __global__ __launch_bounds__(64 * MF_NWAVES, 1) void mv_front_kernel(const NlVie
 
   // ---- resident: this wave's slice of out_fc.0 (n-tile nt) as A fragments, the small columns' row of output unit `lane`
   const int nt = wave & 3, half = wave >> 2;
-  mf_u32x4 wa[MF_KS][2];
+  nl_u32x4 wa[MF_KS][2];
 #pragma unroll
   for (int ks = 0; ks < MF_KS; ++ks) {
     wa[ks][0] = wpack[((nt * MF_KS + ks) * 2 + 0) * 64 + lane];
@@ -191,9 +184,9 @@ __global__ __launch_bounds__(64 * MF_NWAVES, 1) void mv_front_kernel(const NlVie
       for (int sI = 0; sI < 4; ++sI) {
         const int src = 16 * sI;
         float a = w9[9];
-        a = fmaf(w9[0], mf_rl(mean[0], src), a); a = fmaf(w9[1], mf_rl(mean[1], src), a); a = fmaf(w9[2], mf_rl(mean[2], src), a);
-        a = fmaf(w9[3], mf_rl(var[0], src), a); a = fmaf(w9[4], mf_rl(var[1], src), a); a = fmaf(w9[5], mf_rl(var[2], src), a);
-        a = fmaf(w9[6], mf_rl(mean[3], src), a); a = fmaf(w9[7], mf_rl(var[3], src), a); a = fmaf(w9[8], mf_rl(wm, src), a);
+        a = fmaf(w9[0], nl_rl(mean[0], src), a); a = fmaf(w9[1], nl_rl(mean[1], src), a); a = fmaf(w9[2], nl_rl(mean[2], src), a);
+        a = fmaf(w9[3], nl_rl(var[0], src), a); a = fmaf(w9[4], nl_rl(var[1], src), a); a = fmaf(w9[5], nl_rl(var[2], src), a);
+        a = fmaf(w9[6], nl_rl(mean[3], src), a); a = fmaf(w9[7], nl_rl(var[3], src), a); a = fmaf(w9[8], nl_rl(wm, src), a);
         partial[(wave * 4 + sI) * 64 + lane] = a;
       }
     }
@@ -241,11 +234,11 @@ __global__ __launch_bounds__(64 * MF_NWAVES, 1) void mv_front_kernel(const NlVie
         }
         const float w0 = c4.y, w1 = c4.z, w2 = c4.w, w3 = c2.x, wg = c2.y;
         // channels 0, 1 as one packed operation each (v_pk_mul_f32 / v_pk_fma_f32 / v_pk_add_f32: the same roundings in the same order, two thirds of the instructions)
-        const mf_f32x2 t0 = {T[0][0], T[0][1]}, t1 = {T[1][0], T[1][1]}, t2 = {T[2][0], T[2][1]}, t3 = {T[3][0], T[3][1]};
-        const mf_f32x2 W0 = {w0, w0}, W1 = {w1, w1}, W2 = {w2, w2}, W3 = {w3, w3}, WG = {wg, wg};
-        const mf_f32x2 x = __builtin_elementwise_fma(t3, W3, __builtin_elementwise_fma(t2, W2, __builtin_elementwise_fma(t1, W1, t0 * W0)));
-        const mf_f32x2 t = WG * x;
-        mf_f32x2 A1 = {a1[s][0], a1[s][1]}, A2 = {a2[s][0], a2[s][1]};
+        const nl_f32x2 t0 = {T[0][0], T[0][1]}, t1 = {T[1][0], T[1][1]}, t2 = {T[2][0], T[2][1]}, t3 = {T[3][0], T[3][1]};
+        const nl_f32x2 W0 = {w0, w0}, W1 = {w1, w1}, W2 = {w2, w2}, W3 = {w3, w3}, WG = {wg, wg};
+        const nl_f32x2 x = __builtin_elementwise_fma(t3, W3, __builtin_elementwise_fma(t2, W2, __builtin_elementwise_fma(t1, W1, t0 * W0)));
+        const nl_f32x2 t = WG * x;
+        nl_f32x2 A1 = {a1[s][0], a1[s][1]}, A2 = {a2[s][0], a2[s][1]};
         A1 += t;
         A2 = __builtin_elementwise_fma(t, x, A2);
         a1[s][0] = A1[0]; a1[s][1] = A1[1]; a2[s][0] = A2[0]; a2[s][1] = A2[1];
@@ -283,14 +276,14 @@ __global__ __launch_bounds__(64 * MF_NWAVES, 1) void mv_front_kernel(const NlVie
     {
       const int col = lane & 15, kq = lane >> 4;
       const int srow = 16 * half + col;
-      mf_f32x4 acc = *(const mf_f32x4*)(partial + srow * 64 + 16 * nt + 4 * kq);
+      nl_f32x4 acc = *(const nl_f32x4*)(partial + srow * 64 + 16 * nt + 4 * kq);
 #pragma unroll
       for (int ks = 0; ks < MF_KS; ++ks) {
-        const mf_u32x4 bh = *(const mf_u32x4*)(st_hi + srow * MF_LD + 32 * ks + 8 * kq);
-        const mf_u32x4 bl = *(const mf_u32x4*)(st_lo + srow * MF_LD + 32 * ks + 8 * kq);
-        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(mf_bf16x8, wa[ks][1]), __builtin_bit_cast(mf_bf16x8, bh), acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(mf_bf16x8, wa[ks][0]), __builtin_bit_cast(mf_bf16x8, bl), acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(mf_bf16x8, wa[ks][0]), __builtin_bit_cast(mf_bf16x8, bh), acc, 0, 0, 0);
+        const nl_u32x4 bh = *(const nl_u32x4*)(st_hi + srow * MF_LD + 32 * ks + 8 * kq);
+        const nl_u32x4 bl = *(const nl_u32x4*)(st_lo + srow * MF_LD + 32 * ks + 8 * kq);
+        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(nl_bf16x8, wa[ks][1]), __builtin_bit_cast(nl_bf16x8, bh), acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(nl_bf16x8, wa[ks][0]), __builtin_bit_cast(nl_bf16x8, bl), acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(nl_bf16x8, wa[ks][0]), __builtin_bit_cast(nl_bf16x8, bh), acc, 0, 0, 0);
       }
       const int ng = round * MF_NS + srow;
       // (the round's rows from a SCALAR base + a small lane offset: a hoisted 64-bit lane pointer was the last value this kernel spilled to scratch)
@@ -326,7 +319,7 @@ int nl_launch_mv_front(const NlViews& vw, const float* viewsdev, const float* im
   const int blocks = nrounds < g_mf_cus ? (int)nl_xcd_grid(nrounds) : g_mf_cus;
   const int rpb = (int)nl_cdiv(nrounds, blocks);
   const float* w9 = reinterpret_cast<const float*>((const char*)pack + (size_t)4 * MF_KS * 2 * 64 * 16);
-  hipLaunchKernelGGL(mv_front_kernel, dim3(blocks), dim3(64 * MF_NWAVES), MF_LDS_BYTES, st, vw, viewsdev, images, feat, xyz, (int)N, vis_in, dd_in, (const mf_u32x4*)pack, w9, t64,
+  hipLaunchKernelGGL(mv_front_kernel, dim3(blocks), dim3(64 * MF_NWAVES), MF_LDS_BYTES, st, vw, viewsdev, images, feat, xyz, (int)N, vis_in, dd_in, (const nl_u32x4*)pack, w9, t64,
                      valid_s, rgbv, nrounds, rpb);
   NL_LAUNCH_CHECK();
   return NL_OK;

@@ -5,6 +5,7 @@
 #include <mutex>
 #include <unordered_map>
 #include "common.h"
+#include "mfma.h"
 #include "host.h"
 using namespace nlhost;
 
@@ -159,11 +160,6 @@ Layout make_layout(const nl_config* c) {
 namespace {
 
 // ------------------------------------------------------------------------------------------ pack kernels
-__device__ __forceinline__ unsigned short pk_f2bf(float x) {
-  unsigned int u = __float_as_uint(x);
-  u += 0x7fffu + ((u >> 16) & 1u);
-  return (unsigned short)(u >> 16);
-}
 
 // dst[k0+k][n] (f32 [Kpad][Npad]) and bf16 hi/lo [n][Kpad] <- src[off + n*ld_n + k*ld_k], k < kc, n < N
 __global__ void pack_block_kernel(const float* __restrict__ src, int off, int ld_n, int ld_k, int kc, int N, int k0,
@@ -176,13 +172,13 @@ __global__ void pack_block_kernel(const float* __restrict__ src, int off, int ld
   // perm (k0 == 0 only): K position k of the packed matrix holds source column 32 c + m(8 ks + t, hh) for k = 32 c + 16 ks + 8 hh + t,
   // m(r, hh) = (r & 3) + 8 (r >> 2) + 4 hh — the order in which a 32x32 accumulator tile hands its rows to the next MFMA as B operand
   int ksrc = k;
-  if (perm) { const int r = 8 * ((k >> 4) & 1) + (k & 7), hh = (k >> 3) & 1; ksrc = (k & ~31) + (r & 3) + 8 * (r >> 2) + 4 * hh; }
+  if (perm) { const int r = 8 * ((k >> 4) & 1) + (k & 7), hh = (k >> 3) & 1; ksrc = (k & ~31) + (r & 3) + 8 * (r >> 2) + 4 * hh; }   // (nl_acc_row written out: as one parenthesised term the sum associates differently and the kernel compiles to other code)
   float v = src[off + (size_t)n * ld_n + (size_t)ksrc * ld_k];
   b32[(size_t)(k0 + k) * Npad + n] = v;
-  unsigned short h = pk_f2bf(v);
+  unsigned short h = nl_f2bf(v);
   float hf = __uint_as_float(((unsigned int)h) << 16);
   bhi[(size_t)n * Kpad + k0 + k] = h;
-  const unsigned short l = pk_f2bf(v - hf);
+  const unsigned short l = nl_f2bf(v - hf);
   blo[(size_t)n * Kpad + k0 + k] = l;
   // weight stream of tgemm.hip: chunk (32 k) = [part hi/lo][k-step][row tile][lane = (n&31) + 32*((k>>3)&1)][k&7]
   if (!bst) return;   // (matrices wider than 256 columns have no streaming layout: generic kernels only)
@@ -202,14 +198,6 @@ __global__ void pack_block_kernel(const float* __restrict__ src, int off, int ld
 // kernel's activation images have): image 0 = e2m3(f16(w)) (meets the activations' residual image), image 1 = e2m3(w - f16(w)) (meets their hi image).  Block scale
 // 2^(floor(log2 max) - 2): the largest magnitude lands in [4, 8) (e2m3 saturates at 7.5).  Per slab: [rt][image][lane] dwords 0-3 (16 KB) | [rt][image][lane]
 // {dword 4, dword 5, E8M0 scale, 0} (16 KB).  K rows past Kpad are zero.
-__device__ __forceinline__ unsigned pk_e2m3(float a) {   // a >= 0, already divided by the block scale; round to nearest even, saturating
-  if (!(a < 7.5f)) return 31u;
-  if (a < 1.f) return (unsigned)rintf(a * 8.f);
-  const int e = a < 2.f ? 0 : a < 4.f ? 1 : 2;
-  unsigned m = (unsigned)rintf(ldexpf(a, 3 - e));
-  unsigned c = ((unsigned)(e + 1) << 3) + (m - 8u);
-  return c > 31u ? 31u : c;
-}
 __global__ void pack_tgemm_mx6_kernel(const float* __restrict__ b32, int Kpad, int Npad, int N, int nslab, unsigned char* __restrict__ out) {
   const int e = blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= nslab * 8 * 64 * 2) return;
@@ -230,7 +218,7 @@ __global__ void pack_tgemm_mx6_kernel(const float* __restrict__ b32, int Kpad, i
   const float inv = ldexpf(1.f, 127 - sb);
   unsigned d[6] = {0u, 0u, 0u, 0u, 0u, 0u};
   for (int P = 0; P < 32; ++P) {
-    const unsigned c = pk_e2m3(fabsf(v[P]) * inv) | (v[P] < 0.f ? 32u : 0u);
+    const unsigned c = nl_e2m3(fabsf(v[P]) * inv) | (v[P] < 0.f ? 32u : 0u);
     const int b = 6 * P;
     d[b >> 5] |= c << (b & 31);
     if ((b & 31) > 26) d[(b >> 5) + 1] |= c >> (32 - (b & 31));

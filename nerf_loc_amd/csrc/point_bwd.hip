@@ -13,13 +13,8 @@
 // DMA pieces of the chunk three ahead and the next tile's input rows are issued in the MFMA shadow (`fill`).  Per row: 1 KB read, 384 B written.
 // Arithmetic: three-term split-bf16 like every product of the way back (fp32's exponent range: gradients are small numbers).
 #include <string.h>
-#include <utility>
 #include "common.h"
-
-typedef __bf16 pb_bf16x8 __attribute__((ext_vector_type(8)));
-typedef float pb_f32x16 __attribute__((ext_vector_type(16)));
-typedef float pb_f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int pb_u32x4 __attribute__((ext_vector_type(4)));
+#include "mfma.h"
 
 namespace {
 
@@ -58,31 +53,6 @@ struct BGeo {
   static constexpr int rpos(int runks) { return runks % RL; }
   static_assert(NC % PB_NBUF == 0 && cumks(NC) % RL == 0, "ring positions must be tile-periodic");
 };
-
-template <int N>
-__device__ __forceinline__ void pb_wait_vmcnt() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"i"(N) : "memory");
-}
-template <int... Is, class F>
-__device__ __forceinline__ void pb_static_for_impl(std::integer_sequence<int, Is...>, F&& f) {
-  (f(std::integral_constant<int, Is>{}), ...);
-}
-template <int N, class F>
-__device__ __forceinline__ void pb_static_for(F&& f) {
-  pb_static_for_impl(std::make_integer_sequence<int, (N > 0 ? N : 0)>{}, static_cast<F&&>(f));
-}
-__device__ __forceinline__ unsigned pb_cvt_pk_bf16(float a, float b) {   // low half = bf16(a), high half = bf16(b), round to nearest even
-  unsigned r;
-  asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-  return r;
-}
-// lo word of a pair: bf16(v - float(hi))
-__device__ __forceinline__ unsigned pb_lo2(float v0, float v1, unsigned hi) {
-  unsigned lo; float t0, t1;
-  asm("v_lshlrev_b32 %1, 16, %5\n\tv_and_b32 %2, 0xffff0000, %5\n\tv_sub_f32 %1, %3, %1\n\tv_sub_f32 %2, %4, %2\n\tv_cvt_pk_bf16_f32 %0, %1, %2"
-      : "=&v"(lo), "=&v"(t0), "=&v"(t1) : "v"(v0), "v"(v1), "v"(hi));
-  return lo;
-}
 
 struct PbArgs {
   const float* q; const float* kv; const float* go; float* gq;   // ATT: query (N, 128), kept k | v rows (NK, 256), d attention output (N, 128) -> d query (N, 128)
@@ -139,26 +109,26 @@ __global__ __launch_bounds__(256, 1) void point_bwd_chain_kernel(const PbArgs a)
   // gradients as B fragments (hi / lo), ping-pong between layers; X[1] also takes the tile's input rows (free while the encode columns are multiplied out of X[0]).
   // Scalar dwords, assembled into a 4-dword operand at the MFMA (point_fused2.hip: vector-typed storage keeps both halves alive across the tile loop)
   unsigned Xh[2][GG::KSM][4], Xl[2][GG::KSM][4];
-  pb_u32x4 frh[GG::RL], frl[GG::RL];   // A-fragment ring, position = (running k-step) % RL
-  pb_f32x16 acc[2];                    // accumulator of chunk c = acc[c & 1]: region G accumulates one while the epilogue of G-1 drains the other
-  pb_f32x4 raw[4][2];                  // !ATT: input rows in flight: k-step e of the next tile sits in raw[e & 3] until it is split three events later
+  nl_u32x4 frh[GG::RL], frl[GG::RL];   // A-fragment ring, position = (running k-step) % RL
+  nl_f32x16 acc[2];                    // accumulator of chunk c = acc[c & 1]: region G accumulates one while the epilogue of G-1 drains the other
+  nl_f32x4 raw[4][2];                  // !ATT: input rows in flight: k-step e of the next tile sits in raw[e & 3] until it is split three events later
   // ATT: this lane's 16 dims of a head: query, d output (per sample), k, v (per row) — two sets: head h + 1 is in flight (a whole region ahead: the loads are lane = row
   // gathers with HBM latency; issued half a region ahead they cost 6 000 idle cycles per head) while head h is worked on.  (The allocator finds the second set in the
   // k-steps of X[1] that the later heads have not written yet.)
-  pb_f32x4 qv[2][4], gov[2][4], kk[2][4], vv[2][4];
+  nl_f32x4 qv[2][4], gov[2][4], kk[2][4], vv[2][4];
   float asc = 0.f, agp = 0.f, amx = 0.f, aee = 0.f, aat = 0.f, ags = 0.f, agsq = 0.f;
   unsigned qoff = 0, gqoff = 0, pn_qoff = 0, pn_gqoff = 0;
-  pb_u32x4 mkw[3];                     // the tile's sign bits of forward layers 3, 2, 1 (= way-back layers 0, 1, 2)
+  nl_u32x4 mkw[3];                     // the tile's sign bits of forward layers 3, 2, 1 (= way-back layers 0, 1, 2)
   float ev0 = 0.f, ev1 = 0.f;
   unsigned ehi = 0;
   unsigned inoff = 0, pn_inoff = 0, outoff = 0;
   int pn_tile = tile;
-  const pb_f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  const nl_f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
 
-  auto mfma = [](const pb_u32x4& x, const pb_u32x4& y, const pb_f32x16& c) __attribute__((always_inline)) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(pb_bf16x8, x), __builtin_bit_cast(pb_bf16x8, y), c, 0, 0, 0);
+  auto mfma = [](const nl_u32x4& x, const nl_u32x4& y, const nl_f32x16& c) __attribute__((always_inline)) {
+    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(nl_bf16x8, x), __builtin_bit_cast(nl_bf16x8, y), c, 0, 0, 0);
   };
-  auto frag4 = [](const unsigned (&d)[4]) __attribute__((always_inline)) { return pb_u32x4{d[0], d[1], d[2], d[3]}; };
+  auto frag4 = [](const unsigned (&d)[4]) __attribute__((always_inline)) { return nl_u32x4{d[0], d[1], d[2], d[3]}; };
 
   // ---------------------------------------------------------------- tile prologue: the tile's 128 d kv rows -> X[1]
   // Lane (row j, half hh) holds k-slots 8 hh .. 8 hh + 7 of every k-step: columns 16 ks + 8 hh .. + 7 of its row, two 16-byte loads.  19 events: event e loads
@@ -168,17 +138,17 @@ __global__ __launch_bounds__(256, 1) void point_bwd_chain_kernel(const PbArgs a)
     constexpr int e = decltype(Ec)::value;
     if constexpr (e >= 3) {
       constexpr int k = e - 3;
-      pb_static_for<4>([&](auto Dc) __attribute__((always_inline)) {
+      nl_static_for<4>([&](auto Dc) __attribute__((always_inline)) {
         constexpr int d = decltype(Dc)::value;
         const float v0 = raw[k & 3][d >> 1][2 * (d & 1)], v1 = raw[k & 3][d >> 1][2 * (d & 1) + 1];
-        const unsigned h = pb_cvt_pk_bf16(v0, v1);
+        const unsigned h = nl_cvt_pk_bf16(v0, v1);
         Xh[1][k][d] = h;
-        Xl[1][k][d] = pb_lo2(v0, v1, h);
+        Xl[1][k][d] = nl_lo2(v0, v1, h);
       });
     }
     if constexpr (e < 16) {
-      raw[e & 3][0] = __builtin_bit_cast(pb_f32x4, __builtin_amdgcn_raw_buffer_load_b128(rIn, off + 64u * e, 0, 0));
-      raw[e & 3][1] = __builtin_bit_cast(pb_f32x4, __builtin_amdgcn_raw_buffer_load_b128(rIn, off + 64u * e + 16u, 0, 0));
+      raw[e & 3][0] = __builtin_bit_cast(nl_f32x4, __builtin_amdgcn_raw_buffer_load_b128(rIn, off + 64u * e, 0, 0));
+      raw[e & 3][1] = __builtin_bit_cast(nl_f32x4, __builtin_amdgcn_raw_buffer_load_b128(rIn, off + 64u * e + 16u, 0, 0));
     }
   };
   // ATT: 13 events per head h (= encode-column region h): 0 the 16 loads | 1-4 scores, softmax, its way back | 5-8 d k / d v -> k-steps 2 h + u / 8 + 2 h + u of X[1] |
@@ -190,19 +160,19 @@ __global__ __launch_bounds__(256, 1) void point_bwd_chain_kernel(const PbArgs a)
     // next to each other the line is fetched once (32 KB of vector L1 hold one head's k + v lines of the CU's four waves, nothing more)
     constexpr int h = decltype(Hc)::value, l = decltype(Lc)::value, i = l & 3, w = l < 4 ? 2 : l < 8 ? 3 : l < 12 ? 0 : 1;
     constexpr unsigned o = 128u * h + 64u * (i >> 1) + 16u * (i & 1);
-    if constexpr (w == 0) qv[h & 1][i] = __builtin_bit_cast(pb_f32x4, __builtin_amdgcn_raw_buffer_load_b128(rQ, qo + o, 0, 0));
-    else if constexpr (w == 1) gov[h & 1][i] = __builtin_bit_cast(pb_f32x4, __builtin_amdgcn_raw_buffer_load_b128(rGO, qo + o, 0, 0));
-    else if constexpr (w == 2) kk[h & 1][i] = __builtin_bit_cast(pb_f32x4, __builtin_amdgcn_raw_buffer_load_b128(rIn, ko + o, 0, 0));
-    else vv[h & 1][i] = __builtin_bit_cast(pb_f32x4, __builtin_amdgcn_raw_buffer_load_b128(rIn, ko + 512u + o, 0, 0));
+    if constexpr (w == 0) qv[h & 1][i] = __builtin_bit_cast(nl_f32x4, __builtin_amdgcn_raw_buffer_load_b128(rQ, qo + o, 0, 0));
+    else if constexpr (w == 1) gov[h & 1][i] = __builtin_bit_cast(nl_f32x4, __builtin_amdgcn_raw_buffer_load_b128(rGO, qo + o, 0, 0));
+    else if constexpr (w == 2) kk[h & 1][i] = __builtin_bit_cast(nl_f32x4, __builtin_amdgcn_raw_buffer_load_b128(rIn, ko + o, 0, 0));
+    else vv[h & 1][i] = __builtin_bit_cast(nl_f32x4, __builtin_amdgcn_raw_buffer_load_b128(rIn, ko + 512u + o, 0, 0));
   };
   auto att_event = [&](auto Hc, auto Ec, unsigned qo, unsigned ko, unsigned gqo) __attribute__((always_inline)) {
     constexpr int h = decltype(Hc)::value, e = decltype(Ec)::value;
     constexpr float itemp = 1.0f / 5.656854249492381f;   // temperature sqrt(d_k) (ibrnet.py:84)
     if constexpr (e == 0) {   // (the first tile: all 16 at once)
-      pb_static_for<16>([&](auto Lc) __attribute__((always_inline)) { att_load(Hc, Lc, qo, ko); });
+      nl_static_for<16>([&](auto Lc) __attribute__((always_inline)) { att_load(Hc, Lc, qo, ko); });
     } else if constexpr (e == 1) {
       float x = 0.f, y = 0.f;
-      pb_static_for<16>([&](auto Ic) __attribute__((always_inline)) {
+      nl_static_for<16>([&](auto Ic) __attribute__((always_inline)) {
         constexpr int i = decltype(Ic)::value >> 2, c = decltype(Ic)::value & 3;
         x = fmaf(qv[h & 1][i][c], kk[h & 1][i][c], x); y = fmaf(gov[h & 1][i][c], vv[h & 1][i][c], y);
       });
@@ -219,17 +189,17 @@ __global__ __launch_bounds__(256, 1) void point_bwd_chain_kernel(const PbArgs a)
       agsq = ags * itemp;
     } else if constexpr (e < 9) {
       constexpr int kind = (e - 5) >> 1, u = (e - 5) & 1, ks = (kind ? 8 : 0) + 2 * h + u;
-      pb_static_for<4>([&](auto Dc) __attribute__((always_inline)) {
+      nl_static_for<4>([&](auto Dc) __attribute__((always_inline)) {
         constexpr int d = decltype(Dc)::value, i = 2 * u + (d >> 1), c0 = 2 * (d & 1);
         const float v0 = kind ? aat * gov[h & 1][i][c0] : agsq * qv[h & 1][i][c0], v1 = kind ? aat * gov[h & 1][i][c0 + 1] : agsq * qv[h & 1][i][c0 + 1];
-        const unsigned hw = pb_cvt_pk_bf16(v0, v1);
+        const unsigned hw = nl_cvt_pk_bf16(v0, v1);
         Xh[1][ks][d] = hw;
-        Xl[1][ks][d] = pb_lo2(v0, v1, hw);
+        Xl[1][ks][d] = nl_lo2(v0, v1, hw);
       });
     } else {
       constexpr int i = e - 9;
       const float x0 = nl_sum8(ags * kk[h & 1][i][0]) * itemp, x1 = nl_sum8(ags * kk[h & 1][i][1]) * itemp, x2 = nl_sum8(ags * kk[h & 1][i][2]) * itemp, x3 = nl_sum8(ags * kk[h & 1][i][3]) * itemp;
-      __builtin_amdgcn_raw_buffer_store_b128(pb_u32x4{__float_as_uint(x0), __float_as_uint(x1), __float_as_uint(x2), __float_as_uint(x3)}, rGQ,
+      __builtin_amdgcn_raw_buffer_store_b128(nl_u32x4{__float_as_uint(x0), __float_as_uint(x1), __float_as_uint(x2), __float_as_uint(x3)}, rGQ,
                                              gqo + 128u * h + 64u * (i >> 1) + 16u * (i & 1), 0, 0);
     }
   };
@@ -242,7 +212,7 @@ __global__ __launch_bounds__(256, 1) void point_bwd_chain_kernel(const PbArgs a)
   };
   auto load_mask = [&](auto Lc, int t) __attribute__((always_inline)) {   // way-back layer L reads the sign bits of forward layer 3 - L
     constexpr int L = decltype(Lc)::value;
-    mkw[L] = __builtin_bit_cast(pb_u32x4, __builtin_amdgcn_raw_buffer_load_b128(L == 0 ? rM2 : L == 1 ? rM1 : rM0, (unsigned)(t * 4 + wave) * 1024u + lane * 16u, 0, 0));
+    mkw[L] = __builtin_bit_cast(nl_u32x4, __builtin_amdgcn_raw_buffer_load_b128(L == 0 ? rM2 : L == 1 ? rM1 : rM0, (unsigned)(t * 4 + wave) * 1024u + lane * 16u, 0, 0));
   };
 
   // A fragments of k-step t of chunk G (t >= nks(G): k-step t - nks(G) of chunk G+1) -> ring position of that running k-step
@@ -251,9 +221,9 @@ __global__ __launch_bounds__(256, 1) void point_bwd_chain_kernel(const PbArgs a)
     constexpr int c = t >= GG::nks(G) ? GG::cm(G + 1) : GG::cm(G), ks = t >= GG::nks(G) ? t - GG::nks(G) : t;
     constexpr int pos = GG::rpos(GG::cumks(GG::cm(G)) + t);
     constexpr int li = (c % PB_NBUF) * SLOT + (part * GG::nks(c) + ks) * 64;
-    pb_u32x4 v;
-    if constexpr (li >= 4096) v = __builtin_bit_cast(pb_u32x4, lds_hi[li - 4096]);
-    else v = __builtin_bit_cast(pb_u32x4, lds_all[li + lane]);
+    nl_u32x4 v;
+    if constexpr (li >= 4096) v = __builtin_bit_cast(nl_u32x4, lds_hi[li - 4096]);
+    else v = __builtin_bit_cast(nl_u32x4, lds_all[li + lane]);
     if (part == 0) frh[pos] = v; else frl[pos] = v;
   };
 
@@ -269,13 +239,13 @@ __global__ __launch_bounds__(256, 1) void point_bwd_chain_kernel(const PbArgs a)
         const unsigned w = mkw[L][RT >> 1] >> (16 * (RT & 1) + 2 * p);
         ev0 = acc[AB][2 * p] * ((w & 1u) ? 1.f : 0.01f);
         ev1 = acc[AB][2 * p + 1] * ((w & 2u) ? 1.f : 0.01f);
-        ehi = pb_cvt_pk_bf16(ev0, ev1);
+        ehi = nl_cvt_pk_bf16(ev0, ev1);
         Xh[out][fo][d] = ehi;
-      } else Xl[out][fo][d] = pb_lo2(ev0, ev1, ehi);
+      } else Xl[out][fo][d] = nl_lo2(ev0, ev1, ehi);
     } else if constexpr (RT < 3) {   // encode columns 32 RT + 8 g + 4 hh .. + 3 of this lane's row
       constexpr int g = E;
       const float x0 = acc[AB][4 * g], x1 = acc[AB][4 * g + 1], x2 = acc[AB][4 * g + 2], x3 = acc[AB][4 * g + 3];
-      __builtin_amdgcn_raw_buffer_store_b128(pb_u32x4{__float_as_uint(x0), __float_as_uint(x1), __float_as_uint(x2), __float_as_uint(x3)}, rOut,
+      __builtin_amdgcn_raw_buffer_store_b128(nl_u32x4{__float_as_uint(x0), __float_as_uint(x1), __float_as_uint(x2), __float_as_uint(x3)}, rOut,
                                              outoff + (unsigned)(32 * RT + 8 * g + 4 * hh) * 4u, 0, 0);
     }
   };
@@ -287,7 +257,7 @@ __global__ __launch_bounds__(256, 1) void point_bwd_chain_kernel(const PbArgs a)
     // LDS-DMA pieces of chunk G+3 (its slot held chunk G-1, which every wave left behind at the previous barrier)
     if constexpr (K < NSD) {
       constexpr int ND = GG::ppw(G + 3), d0 = K * ND / NSD, d1 = (K + 1) * ND / NSD;
-      pb_static_for<d1 - d0>([&](auto Ic) __attribute__((always_inline)) { dma_piece(std::integral_constant<int, G + 3>{}, std::integral_constant<int, d0 + decltype(Ic)::value>{}); });
+      nl_static_for<d1 - d0>([&](auto Ic) __attribute__((always_inline)) { dma_piece(std::integral_constant<int, G + 3>{}, std::integral_constant<int, d0 + decltype(Ic)::value>{}); });
     }
     // sign bits: two regions before their layer's first epilogue
     if constexpr (K == 0 && G == NC - 2) load_mask(std::integral_constant<int, 0>{}, pn_tile);
@@ -297,7 +267,7 @@ __global__ __launch_bounds__(256, 1) void point_bwd_chain_kernel(const PbArgs a)
     if constexpr (G >= 3 * NRT && !ATT) {
       if constexpr (K == 0 && G == 3 * NRT) pn_inoff = row_off(pn_tile) * 1024u + 32u * hh;
       constexpr int s = (G - 3 * NRT) * NS + K, T = 4 * NS, e0 = s * EV / T, e1 = (s + 1) * EV / T;
-      pb_static_for<e1 - e0>([&](auto Ic) __attribute__((always_inline)) { pro_event(std::integral_constant<int, e0 + decltype(Ic)::value>{}, pn_inoff); });
+      nl_static_for<e1 - e0>([&](auto Ic) __attribute__((always_inline)) { pro_event(std::integral_constant<int, e0 + decltype(Ic)::value>{}, pn_inoff); });
     }
     if constexpr (ATT) {   // head h is worked on under encode-column region h; its 16 loads went out one by one under the region before
       if constexpr (G >= 3 * NRT - 1 && G < 3 * NRT + 3) {
@@ -306,7 +276,7 @@ __global__ __launch_bounds__(256, 1) void point_bwd_chain_kernel(const PbArgs a)
         // (in the region's FIRST half: the arithmetic of this head starts half a region into the next one — a whole region of latency cover for the last load)
         if constexpr (K < NS / 2) {
           constexpr int l0 = K * 16 / (NS / 2), l1 = (K + 1) * 16 / (NS / 2);
-          pb_static_for<l1 - l0>([&](auto Ic) __attribute__((always_inline)) {
+          nl_static_for<l1 - l0>([&](auto Ic) __attribute__((always_inline)) {
             att_load(std::integral_constant<int, hl>{}, std::integral_constant<int, l0 + decltype(Ic)::value>{}, pn_qoff, pn_inoff);
           });
         }
@@ -315,7 +285,7 @@ __global__ __launch_bounds__(256, 1) void point_bwd_chain_kernel(const PbArgs a)
         constexpr int h = G - 3 * NRT, S0 = NS / 2, H2 = NS - S0;
         if constexpr (K >= S0) {
           constexpr int e0 = 1 + (K - S0) * 12 / H2, e1 = 1 + (K - S0 + 1) * 12 / H2;
-          pb_static_for<e1 - e0>([&](auto Ic) __attribute__((always_inline)) {
+          nl_static_for<e1 - e0>([&](auto Ic) __attribute__((always_inline)) {
             att_event(std::integral_constant<int, h>{}, std::integral_constant<int, e0 + decltype(Ic)::value>{}, pn_qoff, pn_inoff, pn_gqoff);
           });
         }
@@ -327,7 +297,7 @@ __global__ __launch_bounds__(256, 1) void point_bwd_chain_kernel(const PbArgs a)
       constexpr int NE = GG::epi_steps(G - 1), NSE = GG::layer(G - 1) < 3 ? NSD : NS;
       if constexpr (NE > 0 && K < NSE) {
         constexpr int e0 = K * NE / NSE, e1 = (K + 1) * NE / NSE;
-        pb_static_for<e1 - e0>([&](auto Ec) __attribute__((always_inline)) { epi_step(std::integral_constant<int, G - 1>{}, std::integral_constant<int, e0 + decltype(Ec)::value>{}); });
+        nl_static_for<e1 - e0>([&](auto Ec) __attribute__((always_inline)) { epi_step(std::integral_constant<int, G - 1>{}, std::integral_constant<int, e0 + decltype(Ec)::value>{}); });
       }
     }
   };
@@ -344,16 +314,16 @@ __global__ __launch_bounds__(256, 1) void point_bwd_chain_kernel(const PbArgs a)
     }
 #endif
     constexpr int L = GG::layer(G), NKS = GG::nks(G), AB = G & 1, CK = GG::cumks(G);
-    pb_static_for<NKS>([&](auto Kc) __attribute__((always_inline)) {
+    nl_static_for<NKS>([&](auto Kc) __attribute__((always_inline)) {
       constexpr int ks = decltype(Kc)::value, pos = GG::rpos(CK + ks);
       if constexpr (ks == NKS - 1) {
         // chunk G+1 must have landed (only the pieces of G+2, G+3 may still fly) and every wave must be through with chunk G's slot reads
-        pb_wait_vmcnt<GG::ppw(G + 2) + GG::ppw(G + 3)>();
+        nl_wait_vmcnt<GG::ppw(G + 2) + GG::ppw(G + 3)>();
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
       }
-      const pb_u32x4 bh = frag4(Xh[(L + 1) & 1][ks]), bl = frag4(Xl[(L + 1) & 1][ks]);
-      pb_static_for<3>([&](auto Mc) __attribute__((always_inline)) {
+      const nl_u32x4 bh = frag4(Xh[(L + 1) & 1][ks]), bl = frag4(Xl[(L + 1) & 1][ks]);
+      nl_static_for<3>([&](auto Mc) __attribute__((always_inline)) {
         constexpr int m = decltype(Mc)::value, K = 3 * ks + m;
         // A fragments two k-steps ahead; the first two of the next chunk wait for the barrier of the last group
         if constexpr (ks + 2 < NKS) {
@@ -380,20 +350,20 @@ __global__ __launch_bounds__(256, 1) void point_bwd_chain_kernel(const PbArgs a)
 
   // ---------------------------------------------------------------- pipeline start
   soff = (unsigned)(GG::gkb(NC - 1) * 1024 + (GG::ppw(NC - 1) - 1) * 4096);   // the "previous piece" of the very first one
-  pb_static_for<3>([&](auto Cc) __attribute__((always_inline)) {
-    pb_static_for<GG::ppw(decltype(Cc)::value)>([&](auto Ic) __attribute__((always_inline)) { dma_piece(Cc, Ic); });
+  nl_static_for<3>([&](auto Cc) __attribute__((always_inline)) {
+    nl_static_for<GG::ppw(decltype(Cc)::value)>([&](auto Ic) __attribute__((always_inline)) { dma_piece(Cc, Ic); });
   });
   load_mask(std::integral_constant<int, 0>{}, tile);
   if constexpr (ATT) {
     set_att_off(tile, inoff, qoff, gqoff);
-    pb_static_for<4>([&](auto Hc) __attribute__((always_inline)) {
-      pb_static_for<13>([&](auto Ec) __attribute__((always_inline)) { att_event(Hc, Ec, qoff, inoff, gqoff); });
+    nl_static_for<4>([&](auto Hc) __attribute__((always_inline)) {
+      nl_static_for<13>([&](auto Ec) __attribute__((always_inline)) { att_event(Hc, Ec, qoff, inoff, gqoff); });
     });
   } else {
     inoff = row_off(tile) * 1024u + 32u * hh;
-    pb_static_for<EV>([&](auto Ec) __attribute__((always_inline)) { pro_event(Ec, inoff); });
+    nl_static_for<EV>([&](auto Ec) __attribute__((always_inline)) { pro_event(Ec, inoff); });
   }
-  pb_wait_vmcnt<GG::ppw(1) + GG::ppw(2)>();   // conservative: the prologue's own loads are younger than every piece of chunk 0
+  nl_wait_vmcnt<GG::ppw(1) + GG::ppw(2)>();   // conservative: the prologue's own loads are younger than every piece of chunk 0
   __builtin_amdgcn_s_barrier();
   read_frag(std::integral_constant<int, NC - 1>{}, std::integral_constant<int, GG::nks(NC - 1)>{}, std::integral_constant<int, 0>{});
   read_frag(std::integral_constant<int, NC - 1>{}, std::integral_constant<int, GG::nks(NC - 1) + 1>{}, std::integral_constant<int, 0>{});
@@ -403,7 +373,7 @@ __global__ __launch_bounds__(256, 1) void point_bwd_chain_kernel(const PbArgs a)
   for (;;) {
     pn_tile = tile + (int)nwg;   // rows past the end read zero: the last tile prepares a tile that is never computed
     outoff = row_off(tile) * 384u;
-    pb_static_for<NC>(region);
+    nl_static_for<NC>(region);
 #ifdef PB_TRACE
     if (blockIdx.x == 0 && wave == 0 && trace_it < 4) {
       const unsigned long long t = __builtin_readcyclecounter();
@@ -414,15 +384,8 @@ __global__ __launch_bounds__(256, 1) void point_bwd_chain_kernel(const PbArgs a)
     tile = pn_tile;
     if (tile >= a.ntiles) break;
   }
-  pb_wait_vmcnt<0>();   // LDS-DMA prefetched for a tile that does not exist must land before the LDS is handed to another workgroup
+  nl_wait_vmcnt<0>();   // LDS-DMA prefetched for a tile that does not exist must land before the LDS is handed to another workgroup
 }
-
-__device__ __forceinline__ unsigned short pb_f2bf(float x) {
-  unsigned int u = __float_as_uint(x);
-  u += 0x7fffu + ((u >> 16) & 1u);
-  return (unsigned short)(u >> 16);
-}
-__device__ __forceinline__ int pb_m(int r, int hh) { return (r & 3) + 8 * (r >> 2) + 4 * hh; }   // accumulator register -> row of the 32x32 tile
 
 // Stream: chunk (layer, rt) = [part hi/lo][k-step][lane][8 bf16] in A-fragment order (lane: out row 32 rt + (lane & 31), k-slots 8 (lane >> 5) + t).
 // Layer 0's K runs over the d kv columns in natural order (the prologue loads them so); layers 1..3 take K in ACCUMULATOR order of the layer before
@@ -446,7 +409,7 @@ __global__ void pack_point_bwd_stream_kernel(const float* __restrict__ w1, const
     const int c = 16 * ks + 8 * hh + t;
     v = c < 128 ? wk[(size_t)c * W + orow] : wv[(size_t)(c - 128) * W + orow];
   } else {
-    const int fin = 32 * (ks >> 1) + pb_m(8 * (ks & 1) + t, hh);
+    const int fin = 32 * (ks >> 1) + nl_acc_row(8 * (ks & 1) + t, hh);
     if (layer == 1) v = w3[(size_t)fin * W + orow];            // base_mlp.4.weight (H3 <- H2)
     else if (layer == 2) v = w2[(size_t)fin * W + orow];       // base_mlp.2.weight (H2 <- H1)
     else v = orow < 90 ? w1[(size_t)fin * (F + 90) + F + orow] : 0.f;   // base_mlp.0.weight's posenc | ray_diff_fc columns; 6 + 32 zero rows
@@ -455,9 +418,9 @@ __global__ void pack_point_bwd_stream_kernel(const float* __restrict__ w1, const
   if (layer == 0) base = (long long)rt * 2 * 16 * 512;
   else base = (long long)NRT * 2 * 16 * 512 + ((long long)(layer - 1) * NRT + rt) * 2 * KSL * 512;
   const long long in_part = ((long long)ks * 64 + lane) * 8 + t;
-  const unsigned short h = pb_f2bf(v);
+  const unsigned short h = nl_f2bf(v);
   out[base + in_part] = h;
-  out[base + (long long)nks * 512 + in_part] = pb_f2bf(v - __uint_as_float(((unsigned int)h) << 16));
+  out[base + (long long)nks * 512 + in_part] = nl_f2bf(v - __uint_as_float(((unsigned int)h) << 16));
 }
 
 

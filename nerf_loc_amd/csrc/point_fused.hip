@@ -18,64 +18,13 @@
 //   * Layer-1 operands are assembled in registers: pre-split bf16 feature rows are gathered with 16-B loads that
 //     are already B fragments; positional encoding / ray_diff_fc are computed per lane in fp32 and split.
 //   * One wave per SIMD (the kernel lives in the 512-register file): 128 accumulators + up to 152 operand regs.
-#include <utility>
 #include "common.h"
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
+#include "mfma.h"
 
 namespace {
 
 constexpr int L1_KSTEPS = 6;    // 4 posenc + 2 ray_diff_fc k-steps (K = 96); the 195 feature columns come from the per-frame table T
 constexpr int L1_CHUNKS = 3;
-
-// LDS-DMA of 16 B per lane; the immediate offset OFF is added to BOTH addresses, so four consecutive 1-KB pieces share one
-// scalar base and one M0 value
-template <int OFF>
-__device__ __forceinline__ void glds16(const void* g, void* l) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
-                                   (__attribute__((address_space(3))) void*)l, 16, OFF, 0);
-}
-
-template <bool X3>
-__device__ __forceinline__ void split8(const float (&v)[8], bf16x8& hi, bf16x8& lo) {
-#pragma unroll
-  for (int t = 0; t < 8; ++t) {
-    __bf16 h = (__bf16)v[t];
-    hi[t] = h;
-    if (X3) lo[t] = (__bf16)(v[t] - (float)h);
-  }
-}
-
-// branch-free sin/cos in fp64 (|x| up to ~1e5): Cody-Waite reduction to [-pi/4, pi/4] + Taylor (error < 1e-11)
-__device__ __forceinline__ void sincos_d(double x, double& s, double& c) {
-  const double kd = rint(x * 0.63661977236758134308);
-  const int k = (int)kd;
-  double r = fma(-kd, 1.5707963267948966, x);
-  r = fma(-kd, 6.123233995736766e-17, r);
-  const double r2 = r * r;
-  const double ps = r + r * r2 * (-1.0 / 6 + r2 * (1.0 / 120 + r2 * (-1.0 / 5040 + r2 * (1.0 / 362880 + r2 * (-1.0 / 39916800)))));
-  const double pc = 1.0 + r2 * (-0.5 + r2 * (1.0 / 24 + r2 * (-1.0 / 720 + r2 * (1.0 / 40320 + r2 * (-1.0 / 3628800 + r2 * (1.0 / 479001600))))));
-  const bool sw = k & 1;
-  const double ss = sw ? pc : ps, cc = sw ? ps : pc;
-  s = (k & 2) ? -ss : ss;
-  c = ((k + 1) & 2) ? -cc : cc;
-}
-
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"i"(N) : "memory");
-}
-
-template <int... Is, class F>
-__device__ __forceinline__ void static_for_impl(std::integer_sequence<int, Is...>, F&& f) {
-  (f(std::integral_constant<int, Is>{}), ...);
-}
-template <int N, class F>
-__device__ __forceinline__ void static_for(F&& f) {   // compile-time loop: every index is a constant expression
-  static_for_impl(std::make_integer_sequence<int, N>{}, static_cast<F&&>(f));
-}
 
 constexpr int NBUF = 4;   // LDS ring: chunk g lives in buffer g % 4, three chunks of LDS-DMA in flight
 
@@ -125,10 +74,10 @@ __global__ __launch_bounds__(256, 1) void point_fused_kernel(
         const int i = wave * (nkb / 4) + 4 * q4;
         const char* gp = wptr + (size_t)i * 1024 + lane * 16;
         uint4* lp = &lds[g % NBUF][i * 64];
-        glds16<0>(gp, lp);
-        if (4 * q4 + 1 < nkb / 4) glds16<1024>(gp, lp);
-        if (4 * q4 + 2 < nkb / 4) glds16<2048>(gp, lp);
-        if (4 * q4 + 3 < nkb / 4) glds16<3072>(gp, lp);
+        nl_glds16<0>(gp, lp);
+        if (4 * q4 + 1 < nkb / 4) nl_glds16<1024>(gp, lp);
+        if (4 * q4 + 2 < nkb / 4) nl_glds16<2048>(gp, lp);
+        if (4 * q4 + 3 < nkb / 4) nl_glds16<3072>(gp, lp);
       }
     }
     wptr += (size_t)4 * ort * 1024;
@@ -137,10 +86,10 @@ __global__ __launch_bounds__(256, 1) void point_fused_kernel(
   // ---------------------------------------------------------------- layer-1 operands
   // feature columns: gathered row of the per-frame table T (already W1_feat . feature + b1, accumulator order) -> acc init;
   // k-steps 0-3 positional encoding, 4-5 ray_diff_fc are assembled below
-  bf16x8 fh[2 * NRT > L1_KSTEPS ? 2 * NRT : L1_KSTEPS], fl[2 * NRT > L1_KSTEPS ? 2 * NRT : L1_KSTEPS];
+  nl_bf16x8 fh[2 * NRT > L1_KSTEPS ? 2 * NRT : L1_KSTEPS], fl[2 * NRT > L1_KSTEPS ? 2 * NRT : L1_KSTEPS];
   const bool have = live && kk < a.M && a.M > 0;   // knn_gather zero-fills k >= M (knn_utils.py:211-220)
   const int id = a.idx[(size_t)nn * 8 + kk];
-  f32x16 acc[8];
+  nl_f32x16 acc[8];
   {
     const float* trow = a.ptt + (size_t)(have ? id : a.M) * W + 16 * hh;   // row M holds the bias alone
 #pragma unroll
@@ -201,7 +150,7 @@ __global__ __launch_bounds__(256, 1) void point_fused_kernel(
           }
           v[t] = hh ? r[1] : r[0];
         }
-        split8<X3>(v, fh[4 + qs], fl[4 + qs]);
+        nl_split8_elem<X3>(v, fh[4 + qs], fl[4 + qs]);
       }
     }
     // ---- positional encoding (utils.py:5-35): sin/cos(off * 2^f), f = 0..9: k-steps 0..3.
@@ -220,7 +169,7 @@ __global__ __launch_bounds__(256, 1) void point_fused_kernel(
           float ps, pc;
           if (pi < 30) {
             const int ax = pi / 10, f = pi - 10 * ax;
-            if (f == 0) sincos_d((double)off[ax], s, c);
+            if (f == 0) nl_sincos_d((double)off[ax], s, c);
             ps = (float)s; pc = (float)c;
             const double s2 = 2.0 * s * c;
             c = fma(-2.0 * s, s, 1.0);
@@ -232,7 +181,7 @@ __global__ __launch_bounds__(256, 1) void point_fused_kernel(
         float v[8];
 #pragma unroll
         for (int t = 0; t < 8; ++t) v[t] = hh ? v1[t] : v0[t];
-        split8<X3>(v, fh[qs], fl[qs]);
+        nl_split8_elem<X3>(v, fh[qs], fl[qs]);
       }
     }
   }
@@ -251,14 +200,14 @@ __global__ __launch_bounds__(256, 1) void point_fused_kernel(
 
   // one chunk: up to 2 k-steps x ort row tiles x (3 | 1) MFMAs.  A fragments are read from LDS two row tiles
   // ahead of their MFMAs and the scheduler is fenced per row tile, so at most 3 fragment pairs are live.
-  auto compute = [&](int buf, int ort, int nks, const bf16x8 bh0, const bf16x8 bl0, const bf16x8 bh1, const bf16x8 bl1) __attribute__((always_inline)) {
+  auto compute = [&](int buf, int ort, int nks, const nl_bf16x8 bh0, const nl_bf16x8 bl0, const nl_bf16x8 bh1, const nl_bf16x8 bl1) __attribute__((always_inline)) {
     const int nt = nks * ort;   // (k-step, row tile) pairs in issue order: t = ks * ort + rt
-    auto ldA = [&](int t, bf16x8& ah, bf16x8& al) __attribute__((always_inline)) {
+    auto ldA = [&](int t, nl_bf16x8& ah, nl_bf16x8& al) __attribute__((always_inline)) {
       const int ks = t / ort, rt = t - ks * ort;
-      ah = __builtin_bit_cast(bf16x8, lds[buf][((0 * 2 + ks) * ort + rt) * 64 + lane]);
-      if (X3) al = __builtin_bit_cast(bf16x8, lds[buf][((1 * 2 + ks) * ort + rt) * 64 + lane]);
+      ah = __builtin_bit_cast(nl_bf16x8, lds[buf][((0 * 2 + ks) * ort + rt) * 64 + lane]);
+      if (X3) al = __builtin_bit_cast(nl_bf16x8, lds[buf][((1 * 2 + ks) * ort + rt) * 64 + lane]);
     };
-    bf16x8 ah[3], al[3];
+    nl_bf16x8 ah[3], al[3];
     ldA(0, ah[0], al[0]);
     if (nt > 1) ldA(1, ah[1], al[1]);
 #pragma unroll
@@ -266,8 +215,8 @@ __global__ __launch_bounds__(256, 1) void point_fused_kernel(
       if (t < nt) {
         if (t + 2 < nt) ldA(t + 2, ah[(t + 2) % 3], al[(t + 2) % 3]);
         const int ks = t / ort, rt = t - ks * ort;
-        const bf16x8 bh = ks ? bh1 : bh0;
-        const bf16x8 bl = ks ? bl1 : bl0;
+        const nl_bf16x8 bh = ks ? bh1 : bh0;
+        const nl_bf16x8 bl = ks ? bl1 : bl0;
         if (X3) {
           acc[rt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[t % 3], bh, acc[rt], 0, 0, 0);
           acc[rt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[t % 3], bl, acc[rt], 0, 0, 0);
@@ -289,21 +238,20 @@ __global__ __launch_bounds__(256, 1) void point_fused_kernel(
         for (int t = 0; t < 8; t += 2) {
           // LeakyReLU = max(x, 0.01 x): packed multiply, and a bare v_max_f32 (fmaxf() adds a canonicalising v_max x,x per
           // element, which is one instruction in six of this epilogue; NaN ordering is irrelevant here)
-          typedef float pf_f32x2 __attribute__((ext_vector_type(2)));
-          const pf_f32x2 x2 = {acc[rt][8 * s + t], acc[rt][8 * s + t + 1]};
-          const pf_f32x2 y2 = x2 * 0.01f;
+          const nl_f32x2 x2 = {acc[rt][8 * s + t], acc[rt][8 * s + t + 1]};
+          const nl_f32x2 y2 = x2 * 0.01f;
           asm("v_max_f32 %0, %1, %2" : "=v"(v[t]) : "v"(x2[0]), "v"(y2[0]));
           asm("v_max_f32 %0, %1, %2" : "=v"(v[t + 1]) : "v"(x2[1]), "v"(y2[1]));
         }
-        split8<X3>(v, fh[2 * rt + s], fl[2 * rt + s]);
+        nl_split8_elem<X3>(v, fh[2 * rt + s], fl[2 * rt + s]);
       }
   };
 
   // ---------------------------------------------------------------- the whole chain as one chunk pipeline
-  static_for<NC>([&](auto G) __attribute__((always_inline)) {
+  nl_static_for<NC>([&](auto G) __attribute__((always_inline)) {
     constexpr int g = decltype(G)::value;
     // chunk g must have landed: only the LDS-DMA of chunks g+1, g+2 (issued later) may still be in flight
-    wait_vmcnt<glds_of(g + 1) + glds_of(g + 2)>();
+    nl_wait_vmcnt<glds_of(g + 1) + glds_of(g + 2)>();
     __builtin_amdgcn_s_barrier();
     if constexpr (g + 3 < NC) stage(g + 3);   // its buffer held chunk g-1, which every wave finished before the barrier
     constexpr int layer = g < L1_CHUNKS ? 0 : (g - L1_CHUNKS) / NRT + 1;
@@ -359,12 +307,6 @@ __global__ __launch_bounds__(256, 1) void point_fused_kernel(
 }
 
 // ---------------------------------------------------------------------------------------------------- packing
-__device__ __forceinline__ unsigned short pf_f2bf(float x) {
-  unsigned int u = __float_as_uint(x);
-  u += 0x7fffu + ((u >> 16) & 1u);
-  return (unsigned short)(u >> 16);
-}
-
 // Weight stream: L1 (10 chunks) | L2 (NRT) | L3 (NRT) | KV (NRT); chunk = [hi ks0][hi ks1][lo ks0][lo ks1], each
 // ORT x 64 lanes x 8 bf16 in A-fragment order (lane: out row = 32*rt + (lane&31), k slots 8*(lane>>5) + t).
 __global__ void pack_point_stream_kernel(const float* __restrict__ w1, const float* __restrict__ w2, const float* __restrict__ w3,
@@ -407,10 +349,10 @@ __global__ void pack_point_stream_kernel(const float* __restrict__ w1, const flo
   else if (layer == 2) chunk_base = (L1_CHUNKS + NRT) * c_l + chunk * c_l;
   else chunk_base = (L1_CHUNKS + 2 * NRT) * c_l + chunk * c_kv;
   const long long in_chunk = ((long long)(ks * ort + rt) * 64 + lane) * 8 + t;
-  const unsigned short h = pf_f2bf(v);
+  const unsigned short h = nl_f2bf(v);
   const float hf = __uint_as_float(((unsigned int)h) << 16);
   out[chunk_base + in_chunk] = h;
-  out[chunk_base + (long long)2 * ort * 512 + in_chunk] = pf_f2bf(v - hf);
+  out[chunk_base + (long long)2 * ort * 512 + in_chunk] = nl_f2bf(v - hf);
 }
 
 // B operand + bias of the per-frame table GEMM  T[m][c'] = sum_k feat[m][k] * W1[f(c')][k] + b1[f(c')], where column c' =

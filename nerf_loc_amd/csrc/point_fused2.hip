@@ -25,19 +25,8 @@
 //   * ray_diff_fc (4 -> 16 -> 27) runs on the matrix pipe too (6 MFMAs) and each half-wave computes only the positional-encoding
 //     octaves of its own k-slots (half 0: octaves 0-4, half 1: 5-9; three fp64 sin/cos + four fp64 double-angle steps per axis).
 #include <string.h>
-#include <utility>
 #include "common.h"
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef int i32x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x6 __attribute__((ext_vector_type(6)));
-typedef unsigned int u32x16 __attribute__((ext_vector_type(16)));
-typedef _Float16 f16x32 __attribute__((ext_vector_type(32)));
+#include "mfma.h"
 
 namespace {
 
@@ -89,29 +78,6 @@ struct Geo {
   static_assert((PARTS * KS1I) % 4 == 0 && (PARTS * KSL) % 4 == 0, "pieces per wave");
 };
 
-template <int OFF>
-__device__ __forceinline__ void glds16(const void* g, void* l) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
-                                   (__attribute__((address_space(3))) void*)l, 16, OFF, 0);
-}
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"i"(N) : "memory");
-}
-template <int... Is, class F>
-__device__ __forceinline__ void static_for_impl(std::integer_sequence<int, Is...>, F&& f) {
-  (f(std::integral_constant<int, Is>{}), ...);
-}
-template <int N, class F>
-__device__ __forceinline__ void static_for(F&& f) {   // compile-time loop: every index is a constant expression
-  static_for_impl(std::make_integer_sequence<int, (N > 0 ? N : 0)>{}, static_cast<F&&>(f));
-}
-
-__device__ __forceinline__ unsigned cvt_pk_bf16(float a, float b) {   // low half = bf16(a), high half = bf16(b), round to nearest even
-  unsigned r;
-  asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-  return r;
-}
 __device__ __forceinline__ float vmax(float a, float b) {   // bare v_max_f32 (fmaxf adds a canonicalising v_max x,x)
   float r;
   asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
@@ -123,13 +89,6 @@ __device__ __forceinline__ unsigned lrelu_hi2(float& v0, float& v1) {
   asm("v_mul_f32 %3, 0x3c23d70a, %1\n\tv_mul_f32 %4, 0x3c23d70a, %2\n\tv_max_f32 %1, %1, %3\n\tv_max_f32 %2, %2, %4\n\tv_cvt_pk_bf16_f32 %0, %1, %2"
       : "=&v"(hi), "+v"(v0), "+v"(v1), "=&v"(t0), "=&v"(t1));
   return hi;
-}
-// lo word of a pair: bf16(v - float(hi))
-__device__ __forceinline__ unsigned lo2(float v0, float v1, unsigned hi) {
-  unsigned lo; float t0, t1;
-  asm("v_lshlrev_b32 %1, 16, %5\n\tv_and_b32 %2, 0xffff0000, %5\n\tv_sub_f32 %1, %3, %1\n\tv_sub_f32 %2, %4, %2\n\tv_cvt_pk_bf16_f32 %0, %1, %2"
-      : "=&v"(lo), "=&v"(t0), "=&v"(t1) : "v"(v0), "v"(v1), "v"(hi));
-  return lo;
 }
 // LeakyReLU of a pair + its f16 hi word (v_cvt_pk_f16_f32, saturating under MODE.FP16_OVFL)
 __device__ __forceinline__ unsigned lrelu_hi2_f16(float& v0, float& v1) {
@@ -149,10 +108,10 @@ __device__ __forceinline__ unsigned lrelu_hi2_f16_amax(float& v0, float& v1, flo
 // hi/lo split of a pair: hi = bf16(v), lo = bf16(v - float(hi))
 template <bool X3>
 __device__ __forceinline__ void split2(float v0, float v1, unsigned& hi, unsigned& lo) {
-  hi = cvt_pk_bf16(v0, v1);
+  hi = nl_cvt_pk_bf16(v0, v1);
   if (X3) {
     const float f0 = __uint_as_float(hi << 16), f1 = __uint_as_float(hi & 0xffff0000u);
-    lo = cvt_pk_bf16(v0 - f0, v1 - f1);
+    lo = nl_cvt_pk_bf16(v0 - f0, v1 - f1);
   }
 }
 
@@ -163,51 +122,12 @@ __device__ __forceinline__ unsigned lo2_f16(float v0, float v1, unsigned hi) {
       : "=&v"(lo), "=&v"(t0), "=&v"(t1) : "v"(v0), "v"(v1), "v"(hi));
   return lo;
 }
-// f16 pair of two values + the running maximum of their magnitudes (layer-1 operands of the MX-FP6 path: no activation in between)
-__device__ __forceinline__ unsigned hi2_f16_amax(float v0, float v1, float& m) {
-  unsigned hi;
-  asm("v_max3_f32 %1, |%2|, |%3|, %1\n\tv_cvt_pk_f16_f32 %0, %2, %3" : "=&v"(hi), "+v"(m) : "v"(v0), "v"(v1));
-  return hi;
-}
-// residuals of a pair as floats: v - float(hi half) (exact)
-__device__ __forceinline__ void lo2_f32(float v0, float v1, unsigned hi, float& l0, float& l1) {
-  asm("v_fma_mix_f32 %0, %4, -1.0, %2 op_sel_hi:[1,0,0]\n\tv_fma_mix_f32 %1, %4, -1.0, %3 op_sel:[1,0,0] op_sel_hi:[1,0,0]"
-      : "=&v"(l0), "=&v"(l1) : "v"(v0), "v"(v1), "v"(hi));
-}
-// The two fp6 packing conversions as asm statements with EARLY-CLOBBER results: hipcc 7.2 lets the builtins' 6-register result overlap the scale operand (seen:
-// v_cvt_scalef32_2xpk16_fp6_f32 v[206:211], v[122:137], v[138:153], v206), and the multi-pass instruction then reads a scale it has already overwritten — one slab of
-// one layer came out with garbage residuals (found with tools/mx6_debug.py: only K slab 2 of base_mlp.4 was off).
-__device__ __forceinline__ u32x6 cvt_pk32_fp6_f16(u32x16 h, float sc) {
-  u32x6 r;
-  asm("v_cvt_scalef32_pk32_fp6_f16 %0, %1, %2" : "=&v"(r) : "v"(h), "v"(sc));
-  return r;
-}
-__device__ __forceinline__ u32x6 cvt_2xpk16_fp6_f32(f32x16 a, f32x16 b, float sc) {
-  u32x6 r;
-  asm("v_cvt_scalef32_2xpk16_fp6_f32 %0, %1, %2, %3" : "=&v"(r) : "v"(a), "v"(b), "v"(sc));
-  return r;
-}
 template <bool X3, bool F16>
 __device__ __forceinline__ void split2f(float v0, float v1, unsigned& hi, unsigned& lo) {
   if constexpr (F16) {
     asm("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(hi) : "v"(v0), "v"(v1));
     lo = lo2_f16(v0, v1, hi);
   } else split2<X3>(v0, v1, hi, lo);
-}
-
-// branch-free sin/cos in fp64 (|x| up to ~1e5): Cody-Waite reduction to [-pi/4, pi/4] + Taylor (error < 1e-11)
-__device__ __forceinline__ void sincos_d(double x, double& s, double& c) {
-  const double kd = rint(x * 0.63661977236758134308);
-  const int k = (int)kd;
-  double r = fma(-kd, 1.5707963267948966, x);
-  r = fma(-kd, 6.123233995736766e-17, r);
-  const double r2 = r * r;
-  const double ps = r + r * r2 * (-1.0 / 6 + r2 * (1.0 / 120 + r2 * (-1.0 / 5040 + r2 * (1.0 / 362880 + r2 * (-1.0 / 39916800)))));
-  const double pc = 1.0 + r2 * (-0.5 + r2 * (1.0 / 24 + r2 * (-1.0 / 720 + r2 * (1.0 / 40320 + r2 * (-1.0 / 3628800 + r2 * (1.0 / 479001600))))));
-  const bool sw = k & 1;
-  const double ss = sw ? pc : ps, cc = sw ? ps : pc;
-  s = (k & 2) ? -ss : ss;
-  c = ((k + 1) & 2) ? -cc : cc;
 }
 
 struct Pf2Scalars { int dir_stride, dir_div; unsigned dir_magic; int dir_shift; unsigned dir_one; int N, M; float inv_span; int ntiles; unsigned t_bytes;
@@ -245,7 +165,7 @@ __global__ __launch_bounds__(256, 1) void point_fused2_kernel(
   lds_u4* lds_hi = (lds_u4*)lds_all + 4096 + (threadIdx.x & 63);
   asm volatile("" : "+v"(lds_hi));
   // (MX-FP6: the 8-byte tails of the fp6 images — lane stride 8 — through a second opaque base of the same kind)
-  typedef __attribute__((address_space(3))) u32x2 lds_u2;
+  typedef __attribute__((address_space(3))) nl_u32x2 lds_u2;
   lds_u2* lds_hi8 = (lds_u2*)((lds_u4*)lds_all + 4096) + (threadIdx.x & 63);
   if constexpr (MX6) asm volatile("" : "+v"(lds_hi8));
   lds_u2* lds_res8 = (lds_u2*)((lds_u4*)lds_all + NBUF * SLOT) + (threadIdx.x & 63);   // ... and the resident block behind the ring
@@ -323,17 +243,17 @@ __global__ __launch_bounds__(256, 1) void point_fused2_kernel(
   // packing kernel: byte q of the chunk's two scale dwords).  The f16 B fragments of a slab live in ONE 16-register vector (Xh16): v_cvt_scalef32_pk32_fp6_f16 packs the hi
   // image from it in one instruction, the matrix instructions read its 4-register quarters; v_cvt_scalef32_2xpk16_fp6_f32 packs the residuals of two row tiles (interleaved:
   // position 2 i <- first operand, 2 i + 1 <- second; the weights' hi image is stored in that order).
-  u32x16 Xh16[2][NRT / 2];              // [buffer][slab]: dword 4 s + d = fragment dword d of k-step 4 q + s
+  nl_u32x16 Xh16[2][NRT / 2];              // [buffer][slab]: dword 4 s + d = fragment dword d of k-step 4 q + s
   unsigned X6[2][NRT / 2][2][6];        // [buffer][slab][0 = hi6, 1 = lo6][6 dwords]: position P = bits 6 P .. 6 P + 5
-  u32x4 w6a[2][2]; u32x2 w6b[2][2];     // fp6 A operands of a slab, [slab parity][0 = w_hi6, 1 = w_lo6]: dwords 0-3 | 4-5
-  u32x2 wsc6 = {0u, 0u};                // the chunk's weight-scale dwords {w_hi6, w_lo6}: byte q = E8M0 of slab q for this lane's row and K half
+  nl_u32x4 w6a[2][2]; nl_u32x2 w6b[2][2];     // fp6 A operands of a slab, [slab parity][0 = w_hi6, 1 = w_lo6]: dwords 0-3 | 4-5
+  nl_u32x2 wsc6 = {0u, 0u};                // the chunk's weight-scale dwords {w_hi6, w_lo6}: byte q = E8M0 of slab q for this lane's row and K half
   unsigned xs6h[2] = {0u, 0u}, xs6l[2] = {0u, 0u};   // activation scale bytes [buffer]: byte q = slab q (hi image | residual image = hi - 11)
   unsigned hp6[2][8];                   // f16 pairs of the two row tiles a slab is made of (until the slab is complete)
   float lo6t[2][16];                    // their residuals
   float scf6 = 1.f;
   // layer 1 in the same arithmetic: its B operands of the tile — slab 0 = k-steps 0-3 (positional encoding + raw offsets), slab 1 = k-steps 4, 5 (ray_diff_fc outputs) + two
   // empty k-steps — as f16 fragments (P16), fp6 images (P6[slab][0 = hi, 1 = residual]) and the two scale-byte registers; pp* / plo*: pairs and residuals until a slab is complete
-  u32x16 P16[2];
+  nl_u32x16 P16[2];
   unsigned P6[2][2][6];
   unsigned pxs6h = 0u, pxs6l = 0u;
   unsigned pp0[16], pp1[8];
@@ -343,29 +263,29 @@ __global__ __launch_bounds__(256, 1) void point_fused2_kernel(
   float lmax = 0.f;   // largest |attention logit| this lane has scored: the softmax over nearly tied neighbours turns a logit error e into a weight error ~e, and the
                       // logit error is (relative product error) x |logit| — the conditioning indicator nl_frame_diagnostics reports
   unsigned Ph[GG::KS1][4], Pl[GG::KS1][4];
-  u32x4 frh[GG::RL], frl[GG::RL];         // A-fragment ring, position = (running k-step) % RL
+  nl_u32x4 frh[GG::RL], frl[GG::RL];         // A-fragment ring, position = (running k-step) % RL
   // accumulator of chunk c = acc[c & 3].  Four, because the accumulator is INITIALISED by loads that must be in flight early:
   // while region G accumulates into acc[G & 3] and the epilogue of G-1 drains acc[(G-1) & 3], the bias slice of chunk G+1
   // (LDS) and the table-row slice of layer-1 chunk G+2 (a gather from the per-frame table T) land in the other two
-  f32x16 acc[4];
-  f32x4 Qr[4];                            // query of the head being scored
+  nl_f32x16 acc[4];
+  nl_f32x4 Qr[4];                            // query of the head being scored
   float att[4] = {0.f, 0.f, 0.f, 0.f};
   float ev0 = 0.f, ev1 = 0.f, ap = 0.f, amx = 0.f, aee = 0.f, ase = 0.f;
   unsigned ehi = 0;
   float ov[4];
-  f32x4 aw[4];
+  nl_f32x4 aw[4];
   unsigned ooff_cur = 0x80000000u, ooff_prev = 0x80000000u;   // byte offset of the lane's slice of O; out of range (= dropped) for lanes that do not store
   unsigned toff = 0, qoff = 0;                                // byte offsets of the lane's table row / query slice
-  const f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  const nl_f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
   const float* sres = reinterpret_cast<const float*>(lds_all + GG::RES_BIAS);
   float* satt = reinterpret_cast<float*>(lds_all + GG::RES_ATT) + wave * 128;
 
-  auto mfma = [](const u32x4& a, const u32x4& b, const f32x16& c) __attribute__((always_inline)) {
-    if constexpr (F16) return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-    else return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
+  auto mfma = [](const nl_u32x4& a, const nl_u32x4& b, const nl_f32x16& c) __attribute__((always_inline)) {
+    if constexpr (F16) return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(nl_f16x8, a), __builtin_bit_cast(nl_f16x8, b), c, 0, 0, 0);
+    else return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(nl_bf16x8, a), __builtin_bit_cast(nl_bf16x8, b), c, 0, 0, 0);
   };
-  auto mfma_h = [](const u32x4& a, const u32x4& b, const f32x16& c) __attribute__((always_inline)) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
+  auto mfma_h = [](const nl_u32x4& a, const nl_u32x4& b, const nl_f32x16& c) __attribute__((always_inline)) {
+    return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(nl_f16x8, a), __builtin_bit_cast(nl_f16x8, b), c, 0, 0, 0);
   };
 
   // LeakyReLU + split of a finished pair -> dword `d` of the destination fragments
@@ -376,7 +296,7 @@ __global__ __launch_bounds__(256, 1) void point_fused2_kernel(
     dh = h;
     if (X3) dl = l;
   };
-  auto frag4 = [](const unsigned (&d)[4]) __attribute__((always_inline)) { return u32x4{d[0], d[1], d[2], d[3]}; };
+  auto frag4 = [](const unsigned (&d)[4]) __attribute__((always_inline)) { return nl_u32x4{d[0], d[1], d[2], d[3]}; };
 
   // ---------------------------------------------------------------- tile prologue: layer-1 operands (model.py:394-409)
   // Written as a list of micro-steps so that the NEXT tile's operands are produced in the MFMA shadow of the current tile's k / v
@@ -392,13 +312,13 @@ __global__ __launch_bounds__(256, 1) void point_fused2_kernel(
   bool pn_have = false, pn_live = false;
   float pq[3], pdv[3], pdv0[3], pp[3], pnd[3], poff[3], prd[4];
   unsigned rdbh[2] = {0, 0}, rdbl[2] = {0, 0}, hidh[4] = {0, 0, 0, 0}, hidl[4] = {0, 0, 0, 0};
-  f32x16 pa = zero16;
-  f32x4 pb[4];
+  nl_f32x16 pa = zero16;
+  nl_f32x4 pb[4];
   // the positional encoding's sin / cos recurrence of the MX-FP6 instance in fp32 (round 6): 4.5e-6 on the encoding against the 3e-5 of its fp6 cross-term image;
   // fp64 in the other precisions, whose operands carry 1e-7 (fp64 FMAs issue at the fp32 rate on this part: what fp32 returns is registers, 24 instead of 48)
   using pe_t = std::conditional_t<MX6, float, double>;
-  constexpr pe_t PE_PIO2_HI = sizeof(pe_t) == 4 ? (pe_t)1.57079637050628662 : (pe_t)1.5707963267948966;
-  constexpr pe_t PE_PIO2_LO = sizeof(pe_t) == 4 ? (pe_t)-4.37113882867379e-8 : (pe_t)6.123233995736766e-17;
+  constexpr pe_t PE_PIO2_HI = sizeof(pe_t) == 4 ? (pe_t)1.57079637050628662 : (pe_t)NL_PIO2_HI;
+  constexpr pe_t PE_PIO2_LO = sizeof(pe_t) == 4 ? (pe_t)-4.37113882867379e-8 : (pe_t)NL_PIO2_LO;
   pe_t sx[3], skd[3], sr[3], sr2[3], su[3], sw[3], ss[3], scs[3];
   int skq[3];
   constexpr int NPL = 2, NPC = MX6 ? 57 : 55, NPRO = NPL + NPC;   // load steps, compute steps (MX-FP6: + the two slabs' packing conversions)
@@ -426,13 +346,13 @@ __global__ __launch_bounds__(256, 1) void point_fused2_kernel(
       pp[0] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rSX, so * 12, 0, 0));
       pp[1] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rSX, so * 12 + 4, 0, 0));
       pp[2] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rSX, so * 12 + 8, 0, 0));
-      const f32x4 nd = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rSD, so * 16, 0, 0));
+      const nl_f32x4 nd = __builtin_bit_cast(nl_f32x4, __builtin_amdgcn_raw_buffer_load_b128(rSD, so * 16, 0, 0));
       pnd[0] = nd[0]; pnd[1] = nd[1]; pnd[2] = nd[2];
       // model.py:391-392: without a direction array the nearest neighbour's direction is used (first lane of the sample's 8)
       const int i0 = __shfl(pn_id, lane & ~7, 64);
       const bool ok0 = !p_dir && pn_live && sc.M > 0;
       const unsigned so0 = ok0 ? (unsigned)i0 * 16u : OOB;
-      const f32x4 d0 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rSD, so0, 0, 0));
+      const nl_f32x4 d0 = __builtin_bit_cast(nl_f32x4, __builtin_amdgcn_raw_buffer_load_b128(rSD, so0, 0, 0));
       pdv0[0] = d0[0]; pdv0[1] = d0[1]; pdv0[2] = d0[2];
     } else {
       constexpr int C = I - NPL;
@@ -452,18 +372,18 @@ __global__ __launch_bounds__(256, 1) void point_fused2_kernel(
         if (X3) { rdbl[0] = hh ? 0u : l0; rdbl[1] = hh ? 0u : l1; }
       } else if constexpr (C == 4 || C == 7) {   // ray_diff_fc layers on the matrix pipe (model.py:36-39)
         constexpr int l = C == 4 ? 0 : 1;
-        const u32x4 xh = l == 0 ? u32x4{rdbh[0], rdbh[1], 0u, 0u} : frag4(hidh);
-        const u32x4 xl = l == 0 ? u32x4{rdbl[0], rdbl[1], 0u, 0u} : frag4(hidl);
-        const u32x4 ah = __builtin_bit_cast(u32x4, lds_all[GG::RES_RD + (l * PARTS + 0) * 64 + lane]);
+        const nl_u32x4 xh = l == 0 ? nl_u32x4{rdbh[0], rdbh[1], 0u, 0u} : frag4(hidh);
+        const nl_u32x4 xl = l == 0 ? nl_u32x4{rdbl[0], rdbl[1], 0u, 0u} : frag4(hidl);
+        const nl_u32x4 ah = __builtin_bit_cast(nl_u32x4, lds_all[GG::RES_RD + (l * PARTS + 0) * 64 + lane]);
         if (X3) {
-          const u32x4 al = __builtin_bit_cast(u32x4, lds_all[GG::RES_RD + (l * PARTS + (PARTS - 1)) * 64 + lane]);
+          const nl_u32x4 al = __builtin_bit_cast(nl_u32x4, lds_all[GG::RES_RD + (l * PARTS + (PARTS - 1)) * 64 + lane]);
           pa = mfma(al, xh, zero16);
           pa = mfma(ah, xl, pa);
           pa = mfma(ah, xh, pa);
         } else pa = mfma(ah, xh, zero16);
-        static_for<l == 0 ? 2 : 4>([&](auto Gc) __attribute__((always_inline)) {
+        nl_static_for<l == 0 ? 2 : 4>([&](auto Gc) __attribute__((always_inline)) {
           constexpr int g = decltype(Gc)::value;
-          pb[g] = *reinterpret_cast<const f32x4*>(sres + 32 * l + 16 * hh + 4 * g);
+          pb[g] = *reinterpret_cast<const nl_f32x4*>(sres + 32 * l + 16 * hh + 4 * g);
         });
       } else if constexpr (C == 5 || C == 6) {   // hidden layer: registers 0..7 = units m(r, hh) < 16
         constexpr int g = C - 5;
@@ -475,8 +395,8 @@ __global__ __launch_bounds__(256, 1) void point_fused2_kernel(
           if constexpr (g == 0) pam1 = 0.f;
           float v0 = pa[4 * g] + pb[g][0], v1 = pa[4 * g + 1] + pb[g][1], v2 = pa[4 * g + 2] + pb[g][2], v3 = pa[4 * g + 3] + pb[g][3];
           v0 = vmax(v0, v0 * 0.01f); v1 = vmax(v1, v1 * 0.01f); v2 = vmax(v2, v2 * 0.01f); v3 = vmax(v3, v3 * 0.01f);
-          pp1[2 * g] = hi2_f16_amax(v0, v1, pam1); pp1[2 * g + 1] = hi2_f16_amax(v2, v3, pam1);
-          lo2_f32(v0, v1, pp1[2 * g], plo1[4 * g], plo1[4 * g + 1]); lo2_f32(v2, v3, pp1[2 * g + 1], plo1[4 * g + 2], plo1[4 * g + 3]);
+          pp1[2 * g] = nl_hi2_f16_amax(v0, v1, pam1); pp1[2 * g + 1] = nl_hi2_f16_amax(v2, v3, pam1);
+          nl_lo2_f32(v0, v1, pp1[2 * g], plo1[4 * g], plo1[4 * g + 1]); nl_lo2_f32(v2, v3, pp1[2 * g + 1], plo1[4 * g + 2], plo1[4 * g + 3]);
         } else {
         finish_pair(pa[4 * g] + pb[g][0], pa[4 * g + 1] + pb[g][1], Ph[4 + g / 2][(2 * g) & 3], Pl[4 + g / 2][(2 * g) & 3]);
         finish_pair(pa[4 * g + 2] + pb[g][2], pa[4 * g + 3] + pb[g][3], Ph[4 + g / 2][(2 * g + 1) & 3], Pl[4 + g / 2][(2 * g + 1) & 3]);
@@ -486,8 +406,9 @@ __global__ __launch_bounds__(256, 1) void point_fused2_kernel(
         // (comp 0 = sin, 1 = cos), then e = 30, 31 = raw (x, y) for half 0 and (z, 0) for half 1.  One accurate fp64 evaluation per
         // axis at the half's first octave (Cody-Waite to [-pi/4, pi/4] + Taylor, error < 1e-11) + the double-angle recurrence in
         // fp64 (abs error < 1e-12: correctly rounded in fp32).  Nine sub-steps per axis, the three axes interleaved.
+        // (common.h: nl_sincos_d is the same reduction and polynomials as one function; here they are fma / Horner steps spread over the fill slots, in float for MX6 — other instructions, so not a call)
         constexpr int x = (C - 12) / 3, a = (C - 12) % 3;
-        if constexpr (x == 0) { sx[a] = (pe_t)poff[a] * (hh ? (pe_t)(32.0) : (pe_t)(1.0)); skd[a] = rint(sx[a] * (pe_t)(0.63661977236758134308)); }
+        if constexpr (x == 0) { sx[a] = (pe_t)poff[a] * (hh ? (pe_t)(32.0) : (pe_t)(1.0)); skd[a] = rint(sx[a] * (pe_t)(NL_TWO_OVER_PI)); }
         else if constexpr (x == 1) { sr[a] = fma(-skd[a], PE_PIO2_HI, sx[a]); sr[a] = fma(-skd[a], PE_PIO2_LO, sr[a]); }
         else if constexpr (x == 2) { sr2[a] = sr[a] * sr[a]; skq[a] = (int)skd[a]; su[a] = fma(sr2[a], (pe_t)(-1.0 / 39916800), (pe_t)(1.0 / 362880)); }
         else if constexpr (x == 3) { su[a] = fma(sr2[a], su[a], (pe_t)(-1.0 / 5040)); su[a] = fma(sr2[a], su[a], (pe_t)(1.0 / 120)); }
@@ -506,8 +427,8 @@ __global__ __launch_bounds__(256, 1) void point_fused2_kernel(
         if constexpr (MX6) {   // pair p = dword p of slab 0
           if constexpr (C == 39) pam0 = 0.f;
           const float v0 = (float)ss[a], v1 = (float)scs[a];
-          pp0[p] = hi2_f16_amax(v0, v1, pam0);
-          lo2_f32(v0, v1, pp0[p], plo0[2 * p], plo0[2 * p + 1]);
+          pp0[p] = nl_hi2_f16_amax(v0, v1, pam0);
+          nl_lo2_f32(v0, v1, pp0[p], plo0[2 * p], plo0[2 * p + 1]);
         } else {
         unsigned h = 0, l = 0;
         split2f<X3, F16>((float)ss[a], (float)scs[a], h, l);
@@ -522,8 +443,8 @@ __global__ __launch_bounds__(256, 1) void point_fused2_kernel(
       } else if constexpr (C == 54) {
         if constexpr (MX6) {
           const float v0 = hh ? poff[2] : poff[0], v1 = hh ? 0.f : poff[1];
-          pp0[15] = hi2_f16_amax(v0, v1, pam0);
-          lo2_f32(v0, v1, pp0[15], plo0[30], plo0[31]);
+          pp0[15] = nl_hi2_f16_amax(v0, v1, pam0);
+          nl_lo2_f32(v0, v1, pp0[15], plo0[30], plo0[31]);
         } else {
         unsigned h = 0, l = 0;
         split2f<X3, F16>(hh ? poff[2] : poff[0], hh ? 0.f : poff[1], h, l);
@@ -537,19 +458,19 @@ __global__ __launch_bounds__(256, 1) void point_fused2_kernel(
         const float sf = __builtin_bit_cast(float, eb << 23);
         if constexpr (q == 0) { pxs6h = (unsigned)eb; pxs6l = (unsigned)(eb - 11); }
         else { pxs6h |= (unsigned)eb << 8; pxs6l |= (unsigned)(eb - 11) << 8; }
-        u32x16 H;
-        f32x16 l0, l1;
+        nl_u32x16 H;
+        nl_f32x16 l0, l1;
         if constexpr (q == 0) {
-          H = u32x16{pp0[0], pp0[1], pp0[2], pp0[3], pp0[4], pp0[5], pp0[6], pp0[7], pp0[8], pp0[9], pp0[10], pp0[11], pp0[12], pp0[13], pp0[14], pp0[15]};
-          l0 = f32x16{plo0[0], plo0[1], plo0[2], plo0[3], plo0[4], plo0[5], plo0[6], plo0[7], plo0[8], plo0[9], plo0[10], plo0[11], plo0[12], plo0[13], plo0[14], plo0[15]};
-          l1 = f32x16{plo0[16], plo0[17], plo0[18], plo0[19], plo0[20], plo0[21], plo0[22], plo0[23], plo0[24], plo0[25], plo0[26], plo0[27], plo0[28], plo0[29], plo0[30], plo0[31]};
+          H = nl_u32x16{pp0[0], pp0[1], pp0[2], pp0[3], pp0[4], pp0[5], pp0[6], pp0[7], pp0[8], pp0[9], pp0[10], pp0[11], pp0[12], pp0[13], pp0[14], pp0[15]};
+          l0 = nl_f32x16{plo0[0], plo0[1], plo0[2], plo0[3], plo0[4], plo0[5], plo0[6], plo0[7], plo0[8], plo0[9], plo0[10], plo0[11], plo0[12], plo0[13], plo0[14], plo0[15]};
+          l1 = nl_f32x16{plo0[16], plo0[17], plo0[18], plo0[19], plo0[20], plo0[21], plo0[22], plo0[23], plo0[24], plo0[25], plo0[26], plo0[27], plo0[28], plo0[29], plo0[30], plo0[31]};
         } else {
-          H = u32x16{pp1[0], pp1[1], pp1[2], pp1[3], pp1[4], pp1[5], pp1[6], pp1[7], 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
-          l0 = f32x16{plo1[0], plo1[1], plo1[2], plo1[3], plo1[4], plo1[5], plo1[6], plo1[7], plo1[8], plo1[9], plo1[10], plo1[11], plo1[12], plo1[13], plo1[14], plo1[15]};
+          H = nl_u32x16{pp1[0], pp1[1], pp1[2], pp1[3], pp1[4], pp1[5], pp1[6], pp1[7], 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
+          l0 = nl_f32x16{plo1[0], plo1[1], plo1[2], plo1[3], plo1[4], plo1[5], plo1[6], plo1[7], plo1[8], plo1[9], plo1[10], plo1[11], plo1[12], plo1[13], plo1[14], plo1[15]};
           l1 = zero16;
         }
         P16[q] = H;
-        const u32x6 rh = cvt_pk32_fp6_f16(H, sf), rl = cvt_2xpk16_fp6_f32(l0, l1, sf * 0.00048828125f);
+        const nl_u32x6 rh = nl_cvt_pk32_fp6_f16(H, sf), rl = nl_cvt_2xpk16_fp6_f32(l0, l1, sf * 0.00048828125f);
         P6[q][0][0] = rh[0]; P6[q][0][1] = rh[1]; P6[q][0][2] = rh[2]; P6[q][0][3] = rh[3]; P6[q][0][4] = rh[4]; P6[q][0][5] = rh[5];
         P6[q][1][0] = rl[0]; P6[q][1][1] = rl[1]; P6[q][1][2] = rl[2]; P6[q][1][3] = rl[3]; P6[q][1][4] = rl[4]; P6[q][1][5] = rl[5];
       }
@@ -561,17 +482,17 @@ __global__ __launch_bounds__(256, 1) void point_fused2_kernel(
   // unit ~64 cycles, and the four waves issue in step), one per quarter of the region two ahead rather than back to back
   auto load_Tg = [&](auto Cc, auto Gc, unsigned tof) __attribute__((always_inline)) {
     constexpr int c = decltype(Cc)::value, g = decltype(Gc)::value;
-    const f32x4 t4 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rT, tof + (32 * GG::rt(c) + 4 * g) * 4, 0, 0));
+    const nl_f32x4 t4 = __builtin_bit_cast(nl_f32x4, __builtin_amdgcn_raw_buffer_load_b128(rT, tof + (32 * GG::rt(c) + 4 * g) * 4, 0, 0));
     acc[c & 3][4 * g] = t4[0]; acc[c & 3][4 * g + 1] = t4[1]; acc[c & 3][4 * g + 2] = t4[2]; acc[c & 3][4 * g + 3] = t4[3];
   };
   auto load_T = [&](auto Cc, unsigned tof) __attribute__((always_inline)) {
-    static_for<4>([&](auto Gc) __attribute__((always_inline)) { load_Tg(Cc, Gc, tof); });
+    nl_static_for<4>([&](auto Gc) __attribute__((always_inline)) { load_Tg(Cc, Gc, tof); });
   };
   auto load_bias = [&](auto Cc) __attribute__((always_inline)) {   // bias slice of layer-2/3 chunk c = initial value of its accumulator
     constexpr int c = GG::cm(decltype(Cc)::value);
-    static_for<4>([&](auto Gc) __attribute__((always_inline)) {
+    nl_static_for<4>([&](auto Gc) __attribute__((always_inline)) {
       constexpr int g = decltype(Gc)::value;
-      const f32x4 t4 = *reinterpret_cast<const f32x4*>(sres + 64 + (GG::layer(c) - 1) * W + 32 * GG::rt(c) + 16 * hh + 4 * g);
+      const nl_f32x4 t4 = *reinterpret_cast<const nl_f32x4*>(sres + 64 + (GG::layer(c) - 1) * W + 32 * GG::rt(c) + 16 * hh + 4 * g);
       acc[c & 3][4 * g] = t4[0]; acc[c & 3][4 * g + 1] = t4[1]; acc[c & 3][4 * g + 2] = t4[2]; acc[c & 3][4 * g + 3] = t4[3];
     });
   };
@@ -582,9 +503,9 @@ __global__ __launch_bounds__(256, 1) void point_fused2_kernel(
     constexpr int c = t >= GG::nks(G) ? GG::cm(G + 1) : GG::cm(G), ks = t >= GG::nks(G) ? t - GG::nks(G) : t;
     constexpr int pos = GG::rpos(GG::cumks(GG::cm(G)) + t);
     constexpr int li = (c % NBUF) * SLOT + (part * GG::ksi(c) + ks) * 64;
-    u32x4 v;
-    if constexpr (li >= 4096 && li < 8192) v = __builtin_bit_cast(u32x4, lds_hi[li - 4096]);
-    else v = __builtin_bit_cast(u32x4, lds_all[li + lane]);
+    nl_u32x4 v;
+    if constexpr (li >= 4096 && li < 8192) v = __builtin_bit_cast(nl_u32x4, lds_hi[li - 4096]);
+    else v = __builtin_bit_cast(nl_u32x4, lds_all[li + lane]);
     if (part == 0) frh[pos] = v; else frl[pos] = v;
   };
 
@@ -594,8 +515,8 @@ __global__ __launch_bounds__(256, 1) void point_fused2_kernel(
     constexpr int lb = ((c % NBUF) * SLOT + GG::ksi(c) * 64) * 16 + q * 3072 + (i >> 1) * 1536 + (i & 1) * 1024;   // byte offset in the LDS object
     if constexpr ((i & 1) == 0) {
       constexpr int li = lb / 16;
-      if constexpr (li >= 4096 && li < 8192) w6a[q & 1][i >> 1] = __builtin_bit_cast(u32x4, lds_hi[li - 4096]);
-      else w6a[q & 1][i >> 1] = __builtin_bit_cast(u32x4, lds_all[li + lane]);
+      if constexpr (li >= 4096 && li < 8192) w6a[q & 1][i >> 1] = __builtin_bit_cast(nl_u32x4, lds_hi[li - 4096]);
+      else w6a[q & 1][i >> 1] = __builtin_bit_cast(nl_u32x4, lds_all[li + lane]);
     } else {
       constexpr int l8 = lb / 8;
       if constexpr (l8 >= 8192 && l8 < 16384) w6b[q & 1][i >> 1] = lds_hi8[l8 - 8192];
@@ -626,24 +547,24 @@ __global__ __launch_bounds__(256, 1) void point_fused2_kernel(
           ehi = lrelu_hi2_f16_amax(ev0, ev1, amax);
           hp6[par][p] = ehi;
         } else if constexpr (E < 16) {
-          lo2_f32(ev0, ev1, ehi, lo6t[par][2 * p], lo6t[par][2 * p + 1]);
+          nl_lo2_f32(ev0, ev1, ehi, lo6t[par][2 * p], lo6t[par][2 * p + 1]);
         } else if constexpr (E == 16) {   // the slab is complete: block scale 2^(ex - 3) for amax = m 2^ex, m in [0.5, 1); the hi image from the f16 fragments
           int eb = __builtin_amdgcn_frexp_expf(amax) + 124;
           eb = eb < 12 ? 12 : (eb > 254 ? 254 : eb);   // (12: the residual image's byte eb - 11 stays positive; an all-zero block takes any scale)
           scf6 = __builtin_bit_cast(float, eb << 23);
           if constexpr (q == 0) { xs6h[out] = (unsigned)eb; xs6l[out] = (unsigned)(eb - 11); }
           else { xs6h[out] |= (unsigned)eb << (8 * q); xs6l[out] |= (unsigned)(eb - 11) << (8 * q); }
-          const u32x16 H = {hp6[0][0], hp6[0][1], hp6[0][2], hp6[0][3], hp6[0][4], hp6[0][5], hp6[0][6], hp6[0][7],
+          const nl_u32x16 H = {hp6[0][0], hp6[0][1], hp6[0][2], hp6[0][3], hp6[0][4], hp6[0][5], hp6[0][6], hp6[0][7],
                             hp6[1][0], hp6[1][1], hp6[1][2], hp6[1][3], hp6[1][4], hp6[1][5], hp6[1][6], hp6[1][7]};
           Xh16[out][q] = H;
-          const u32x6 r = cvt_pk32_fp6_f16(H, scf6);
+          const nl_u32x6 r = nl_cvt_pk32_fp6_f16(H, scf6);
           X6[out][q][0][0] = r[0]; X6[out][q][0][1] = r[1]; X6[out][q][0][2] = r[2]; X6[out][q][0][3] = r[3]; X6[out][q][0][4] = r[4]; X6[out][q][0][5] = r[5];
         } else {   // the residual image: two row tiles interleaved, scale x 2^-11
-          const f32x16 l0 = {lo6t[0][0], lo6t[0][1], lo6t[0][2], lo6t[0][3], lo6t[0][4], lo6t[0][5], lo6t[0][6], lo6t[0][7],
+          const nl_f32x16 l0 = {lo6t[0][0], lo6t[0][1], lo6t[0][2], lo6t[0][3], lo6t[0][4], lo6t[0][5], lo6t[0][6], lo6t[0][7],
                              lo6t[0][8], lo6t[0][9], lo6t[0][10], lo6t[0][11], lo6t[0][12], lo6t[0][13], lo6t[0][14], lo6t[0][15]};
-          const f32x16 l1 = {lo6t[1][0], lo6t[1][1], lo6t[1][2], lo6t[1][3], lo6t[1][4], lo6t[1][5], lo6t[1][6], lo6t[1][7],
+          const nl_f32x16 l1 = {lo6t[1][0], lo6t[1][1], lo6t[1][2], lo6t[1][3], lo6t[1][4], lo6t[1][5], lo6t[1][6], lo6t[1][7],
                              lo6t[1][8], lo6t[1][9], lo6t[1][10], lo6t[1][11], lo6t[1][12], lo6t[1][13], lo6t[1][14], lo6t[1][15]};
-          const u32x6 r = cvt_2xpk16_fp6_f32(l0, l1, scf6 * 0.00048828125f);
+          const nl_u32x6 r = nl_cvt_2xpk16_fp6_f32(l0, l1, scf6 * 0.00048828125f);
           X6[out][q][1][0] = r[0]; X6[out][q][1][1] = r[1]; X6[out][q][1][2] = r[2]; X6[out][q][1][3] = r[3]; X6[out][q][1][4] = r[4]; X6[out][q][1][5] = r[5];
         }
       } else if constexpr (sub == 0) {
@@ -655,9 +576,9 @@ __global__ __launch_bounds__(256, 1) void point_fused2_kernel(
           kmask[RT >> 1] |= ((ev0 > 0.f ? 1u : 0u) | (ev1 > 0.f ? 2u : 0u)) << (16 * (RT & 1) + 2 * p);
         }
       } else {
-        Xl[out][fo][d] = F16 ? lo2_f16(ev0, ev1, ehi) : lo2(ev0, ev1, ehi);
+        Xl[out][fo][d] = F16 ? lo2_f16(ev0, ev1, ehi) : nl_lo2(ev0, ev1, ehi);
         if constexpr (KEEP && RT == NRT - 1 && p == 7)
-          __builtin_amdgcn_raw_buffer_store_b128(u32x4{kmask[0], NRT > 2 ? kmask[1] : 0u, NRT > 4 ? kmask[2] : 0u, NRT > 4 ? kmask[3] : 0u},
+          __builtin_amdgcn_raw_buffer_store_b128(nl_u32x4{kmask[0], NRT > 2 ? kmask[1] : 0u, NRT > 4 ? kmask[2] : 0u, NRT > 4 ? kmask[3] : 0u},
                                                  L == 0 ? rM0 : L == 1 ? rM1 : rM2, (unsigned)((PREV ? tile_prev : tile) * 4 + wave) * 1024u + lane * 16u, 0, 0);
       }
     } else if constexpr (RT < 4) {   // k projection of head RT: scores, softmax over the 8 neighbours (lanes) of a sample
@@ -679,7 +600,7 @@ __global__ __launch_bounds__(256, 1) void point_fused2_kernel(
         constexpr int g = E - 10;
         // (a float copy first: __builtin_bit_cast applied to an ext-vector ELEMENT reads element 0 whatever the index)
         const float k0 = acc[AB][4 * g], k1 = acc[AB][4 * g + 1], k2 = acc[AB][4 * g + 2], k3 = acc[AB][4 * g + 3];
-        __builtin_amdgcn_raw_buffer_store_b128(u32x4{__float_as_uint(k0), __float_as_uint(k1), __float_as_uint(k2), __float_as_uint(k3)},
+        __builtin_amdgcn_raw_buffer_store_b128(nl_u32x4{__float_as_uint(k0), __float_as_uint(k1), __float_as_uint(k2), __float_as_uint(k3)},
                                                rKV, kvrow + (unsigned)(32 * RT + 8 * g + 4 * hh) * 4u, 0, 0);
       }
     } else {
@@ -687,7 +608,7 @@ __global__ __launch_bounds__(256, 1) void point_fused2_kernel(
       // m(r, hh) = (r & 3) + 8 (r >> 2) + 4 hh, i.e. sample r >> 2, neighbours (r & 3) + 4 hh.  The attention-weighted sum over the
       // 8 neighbours is 4 FMAs per sample in the lane + one cross-half add, instead of a 3-step DPP reduction per value.
       constexpr int h = RT - 4;
-      if constexpr (E < 4) aw[E] = *reinterpret_cast<const f32x4*>(satt + h * 32 + 8 * E + 4 * hh);   // weights of sample E's neighbours 4 hh .. 4 hh + 3
+      if constexpr (E < 4) aw[E] = *reinterpret_cast<const nl_f32x4*>(satt + h * 32 + 8 * E + 4 * hh);   // weights of sample E's neighbours 4 hh .. 4 hh + 3
       else if constexpr (E < 8) {
         constexpr int sI = E - 4;
         float o = aw[sI][0] * acc[AB][4 * sI];
@@ -708,10 +629,10 @@ __global__ __launch_bounds__(256, 1) void point_fused2_kernel(
       } else {   // KEEP: the v values of head h: lane = dim, registers = neighbour rows m(r, hh) -> column 128 + 32 h + lane's dim of those rows
         constexpr int g = E - 10;
         const unsigned base = (PREV ? kvtile_prev : kvtile) + (unsigned)(128 + 32 * h + j) * 4u;
-        static_for<4>([&](auto Rc) __attribute__((always_inline)) {
+        nl_static_for<4>([&](auto Rc) __attribute__((always_inline)) {
           constexpr int r = 4 * g + decltype(Rc)::value;
           const float vr = acc[AB][r];
-          __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(vr), rKV, base + (unsigned)((r & 3) + 8 * (r >> 2) + 4 * hh) * 1024u, 0, 0);
+          __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(vr), rKV, base + (unsigned)nl_acc_row(r, hh) * 1024u, 0, 0);
         });
       }
     }
@@ -730,7 +651,7 @@ __global__ __launch_bounds__(256, 1) void point_fused2_kernel(
     // LDS-DMA pieces of chunk G+3 (its slot held chunk G-1, which every wave left behind at the previous barrier)
     if constexpr (K < NSD) {
       constexpr int ND = GG::ppw(G + 3), d0 = K * ND / NSD, d1 = (K + 1) * ND / NSD;
-      static_for<d1 - d0>([&](auto Ic) __attribute__((always_inline)) { dma_piece(std::integral_constant<int, G + 3>{}, std::integral_constant<int, d0 + decltype(Ic)::value>{}); });
+      nl_static_for<d1 - d0>([&](auto Ic) __attribute__((always_inline)) { dma_piece(std::integral_constant<int, G + 3>{}, std::integral_constant<int, d0 + decltype(Ic)::value>{}); });
     }
     // accumulator initial values: table rows of the layer-1 chunk two regions ahead (a gather), bias of the next layer-2/3 chunk (LDS)
     if constexpr (GG::layer(G + 2) == 0 && (K == 0 || K == NS / 4 || K == NS / 2 || K == 3 * NS / 4)) {
@@ -743,13 +664,13 @@ __global__ __launch_bounds__(256, 1) void point_fused2_kernel(
     if constexpr (K == 0 && G == 2 * NRT + NRT / 2) pro_step(std::integral_constant<int, 1>{});
     if constexpr (G >= 3 * NRT && G < 3 * NRT + 6) {
       constexpr int lo = pro_lo(G), cnt = pro_lo(G + 1) - lo, c0 = K * cnt / NS, c1 = (K + 1) * cnt / NS;
-      static_for<c1 - c0>([&](auto Ic) __attribute__((always_inline)) { pro_step(std::integral_constant<int, NPL + lo + c0 + decltype(Ic)::value>{}); });
+      nl_static_for<c1 - c0>([&](auto Ic) __attribute__((always_inline)) { pro_step(std::integral_constant<int, NPL + lo + c0 + decltype(Ic)::value>{}); });
     }
     if constexpr (K == NS / 2 && (GG::layer(G + 1) == 1 || GG::layer(G + 1) == 2)) load_bias(std::integral_constant<int, G + 1>{});
     // query slice of the head whose k projection this region computes (scored in the next region)
     if constexpr (GG::layer(G) == 3 && GG::rt(G) < 4 && K >= NS / 2 && (K - NS / 2) % (NS / 8) == 0 && (K - NS / 2) / (NS / 8) < 4) {
       constexpr int g = (K - NS / 2) / (NS / 8);
-      Qr[g] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rQ, qoff + (32 * GG::rt(G) + 8 * g) * 4, 0, 0));
+      Qr[g] = __builtin_bit_cast(nl_f32x4, __builtin_amdgcn_raw_buffer_load_b128(rQ, qoff + (32 * GG::rt(G) + 8 * g) * 4, 0, 0));
     }
     // epilogue of the previous chunk
     {
@@ -758,7 +679,7 @@ __global__ __launch_bounds__(256, 1) void point_fused2_kernel(
       constexpr int NE = GG::epi_steps(G - 1), NSE = GG::layer(G - 1) < 3 ? NSEL : NS;
       if constexpr (K < NSE) {
         constexpr int e0 = K * NE / NSE, e1 = (K + 1) * NE / NSE;
-        static_for<e1 - e0>([&](auto Ec) __attribute__((always_inline)) {
+        nl_static_for<e1 - e0>([&](auto Ec) __attribute__((always_inline)) {
           epi_step(std::integral_constant<int, G - 1>{}, std::integral_constant<int, e0 + decltype(Ec)::value>{}, std::integral_constant<bool, G == 0>{});
         });
       }
@@ -782,16 +703,16 @@ __global__ __launch_bounds__(256, 1) void point_fused2_kernel(
       // layer 1 on the same arithmetic: slab 0 = k-steps 0-3, slab 1 = k-steps 4, 5 (+ two empty ones: zero positions in both operands' images); 6 + 4 matrix instructions of
       // 8 passes; units: 0-3 | 4, 5 | 6, 7 | 8, 9, the barrier in front of unit 7
       read_wsc6(Gc);
-      static_for<2>([&](auto Qc) __attribute__((always_inline)) {
+      nl_static_for<2>([&](auto Qc) __attribute__((always_inline)) {
         constexpr int q = decltype(Qc)::value, NKQ = q == 0 ? 4 : 2;
-        static_for<NKQ>([&](auto Sc) __attribute__((always_inline)) {
+        nl_static_for<NKQ>([&](auto Sc) __attribute__((always_inline)) {
           constexpr int sI = decltype(Sc)::value, ks = 4 * q + sI, pos = GG::rpos(CK + ks);
           if constexpr (ks == NKS - 1) {
-            wait_vmcnt<GG::ppw(G + 2) + GG::ppw(G + 3)>();
+            nl_wait_vmcnt<GG::ppw(G + 2) + GG::ppw(G + 3)>();
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             __builtin_amdgcn_s_barrier();
           }
-          const u32x4 bh = __builtin_shufflevector(P16[q], P16[q], 4 * sI, 4 * sI + 1, 4 * sI + 2, 4 * sI + 3);
+          const nl_u32x4 bh = __builtin_shufflevector(P16[q], P16[q], 4 * sI, 4 * sI + 1, 4 * sI + 2, 4 * sI + 3);
           if constexpr (ks + 2 < NKS) read_frag(Gc, std::integral_constant<int, ks + 2>{}, std::integral_constant<int, 0>{});
           else if constexpr (ks == NKS - 1) {
             read_frag(Gc, std::integral_constant<int, NKS>{}, std::integral_constant<int, 0>{});
@@ -801,11 +722,11 @@ __global__ __launch_bounds__(256, 1) void point_fused2_kernel(
           fill(Gc, std::integral_constant<int, 6 * q + sI>{});
           __builtin_amdgcn_sched_barrier(0);
         });
-        static_for<2>([&](auto Ic) __attribute__((always_inline)) {
+        nl_static_for<2>([&](auto Ic) __attribute__((always_inline)) {
           constexpr int im = decltype(Ic)::value;   // 0: w_hi6 x a_lo6, 1: w_lo6 x a_hi6
-          const i32x8 wa = {(int)w6a[q & 1][im][0], (int)w6a[q & 1][im][1], (int)w6a[q & 1][im][2], (int)w6a[q & 1][im][3], (int)w6b[q & 1][im][0], (int)w6b[q & 1][im][1], 0, 0};
+          const nl_i32x8 wa = {(int)w6a[q & 1][im][0], (int)w6a[q & 1][im][1], (int)w6a[q & 1][im][2], (int)w6a[q & 1][im][3], (int)w6b[q & 1][im][0], (int)w6b[q & 1][im][1], 0, 0};
           const unsigned(&xd)[6] = P6[q][1 - im];
-          const i32x8 xb = {(int)xd[0], (int)xd[1], (int)xd[2], (int)xd[3], (int)xd[4], (int)xd[5], 0, 0};
+          const nl_i32x8 xb = {(int)xd[0], (int)xd[1], (int)xd[2], (int)xd[3], (int)xd[4], (int)xd[5], 0, 0};
           const int sw = (int)wsc6[im], sx = (int)(im == 0 ? pxs6l : pxs6h);
           acc[AB] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(wa, xb, acc[AB], 2, 2, q, sw, q, sx);
           if constexpr (q == 0) {
@@ -823,32 +744,32 @@ __global__ __launch_bounds__(256, 1) void point_fused2_kernel(
       constexpr int NSL = NKS / 4, IN = (L + 1) & 1;
       constexpr bool TR = L == 3 && GG::rt(G) >= 4;   // v heads: D = X . Wv^T (rows = neighbour rows) instead of D^T
       read_wsc6(Gc);
-      static_for<NSL>([&](auto Qc) __attribute__((always_inline)) {
+      nl_static_for<NSL>([&](auto Qc) __attribute__((always_inline)) {
         constexpr int q = decltype(Qc)::value;
-        static_for<4>([&](auto Sc) __attribute__((always_inline)) {
+        nl_static_for<4>([&](auto Sc) __attribute__((always_inline)) {
           constexpr int sI = decltype(Sc)::value, ks = 4 * q + sI, pos = GG::rpos(CK + ks);
           if constexpr (ks == NKS - 1) {
-            wait_vmcnt<GG::ppw(G + 2) + GG::ppw(G + 3)>();
+            nl_wait_vmcnt<GG::ppw(G + 2) + GG::ppw(G + 3)>();
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             __builtin_amdgcn_s_barrier();
           }
-          const u32x4 bh = __builtin_shufflevector(Xh16[IN][q], Xh16[IN][q], 4 * sI, 4 * sI + 1, 4 * sI + 2, 4 * sI + 3);
+          const nl_u32x4 bh = __builtin_shufflevector(Xh16[IN][q], Xh16[IN][q], 4 * sI, 4 * sI + 1, 4 * sI + 2, 4 * sI + 3);
           if constexpr (ks + 2 < NKS) read_frag(Gc, std::integral_constant<int, ks + 2>{}, std::integral_constant<int, 0>{});
           else if constexpr (ks == NKS - 1) {
             read_frag(Gc, std::integral_constant<int, NKS>{}, std::integral_constant<int, 0>{});
             read_frag(Gc, std::integral_constant<int, NKS + 1>{}, std::integral_constant<int, 0>{});
           }
-          const f32x16 c0 = (ZI && ks == 0) ? zero16 : acc[AB];
+          const nl_f32x16 c0 = (ZI && ks == 0) ? zero16 : acc[AB];
           acc[AB] = TR ? mfma_h(bh, frh[pos], c0) : mfma_h(frh[pos], bh, c0);
           fill(Gc, std::integral_constant<int, 6 * q + sI>{});
           __builtin_amdgcn_sched_barrier(0);
         });
         // the two cross terms, 8 passes each: w_hi6 x a_lo6, w_lo6 x a_hi6; scales: byte q of the weights' and of the activations' scale dwords
-        static_for<2>([&](auto Ic) __attribute__((always_inline)) {
+        nl_static_for<2>([&](auto Ic) __attribute__((always_inline)) {
           constexpr int im = decltype(Ic)::value;   // 0: w_hi6 x a_lo6, 1: w_lo6 x a_hi6
-          const i32x8 wa = {(int)w6a[q & 1][im][0], (int)w6a[q & 1][im][1], (int)w6a[q & 1][im][2], (int)w6a[q & 1][im][3], (int)w6b[q & 1][im][0], (int)w6b[q & 1][im][1], 0, 0};
+          const nl_i32x8 wa = {(int)w6a[q & 1][im][0], (int)w6a[q & 1][im][1], (int)w6a[q & 1][im][2], (int)w6a[q & 1][im][3], (int)w6b[q & 1][im][0], (int)w6b[q & 1][im][1], 0, 0};
           const unsigned(&xd)[6] = X6[IN][q][1 - im];
-          const i32x8 xb = {(int)xd[0], (int)xd[1], (int)xd[2], (int)xd[3], (int)xd[4], (int)xd[5], 0, 0};
+          const nl_i32x8 xb = {(int)xd[0], (int)xd[1], (int)xd[2], (int)xd[3], (int)xd[4], (int)xd[5], 0, 0};
           const int sw = (int)wsc6[im], sx = (int)(im == 0 ? xs6l[IN] : xs6h[IN]);
           if constexpr (TR) acc[AB] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(xb, wa, acc[AB], 2, 2, q, sx, q, sw);
           else acc[AB] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(wa, xb, acc[AB], 2, 2, q, sw, q, sx);
@@ -864,12 +785,12 @@ __global__ __launch_bounds__(256, 1) void point_fused2_kernel(
         });
       });
     } else
-    static_for<NKS>([&](auto Kc) __attribute__((always_inline)) {
+    nl_static_for<NKS>([&](auto Kc) __attribute__((always_inline)) {
       constexpr int ks = decltype(Kc)::value, pos = GG::rpos(CK + ks);
       if constexpr (ks == NKS - 1) {
         // chunk G+1 must have landed (only the pieces of G+2, G+3 may still fly) and every wave must be through with chunk G's
         // slot reads; its last fragments are in registers already
-        wait_vmcnt<GG::ppw(G + 2) + GG::ppw(G + 3)>();
+        nl_wait_vmcnt<GG::ppw(G + 2) + GG::ppw(G + 3)>();
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
       }
@@ -877,10 +798,10 @@ __global__ __launch_bounds__(256, 1) void point_fused2_kernel(
         if constexpr (L == 0) { if constexpr (decltype(Hi)::value) return frag4(Ph[ks]); else return frag4(Pl[ks]); }
         else { if constexpr (decltype(Hi)::value) return frag4(Xh[(L + 1) & 1][ks]); else return frag4(Xl[(L + 1) & 1][ks]); }
       };
-      const u32x4 bh = bsel(std::true_type{});
-      u32x4 bl = bh;
+      const nl_u32x4 bh = bsel(std::true_type{});
+      nl_u32x4 bl = bh;
       if constexpr (X3) bl = bsel(std::false_type{});
-      static_for<MPK>([&](auto Mc) __attribute__((always_inline)) {
+      nl_static_for<MPK>([&](auto Mc) __attribute__((always_inline)) {
         constexpr int m = decltype(Mc)::value, K = MPK * ks + m;
         // A fragments two k-steps ahead; the first two of the next chunk wait for the barrier of the last group
         if constexpr (ks + 2 < NKS) {
@@ -898,7 +819,7 @@ __global__ __launch_bounds__(256, 1) void point_fused2_kernel(
           }
         }
         constexpr bool TR = L == 3 && GG::rt(G) >= 4;   // v heads: D = X . Wv^T (rows = neighbour rows) instead of D^T
-        auto mm = [&](const u32x4& wf, const u32x4& xf, const f32x16& c) __attribute__((always_inline)) { return TR ? mfma(xf, wf, c) : mfma(wf, xf, c); };
+        auto mm = [&](const nl_u32x4& wf, const nl_u32x4& xf, const nl_f32x16& c) __attribute__((always_inline)) { return TR ? mfma(xf, wf, c) : mfma(wf, xf, c); };
         if constexpr (X3) {
           if constexpr (m == 0) acc[AB] = mm(frl[pos], bh, (ZI && ks == 0) ? zero16 : acc[AB]);
           else if constexpr (m == 1) acc[AB] = mm(frh[pos], bl, acc[AB]);
@@ -912,19 +833,19 @@ __global__ __launch_bounds__(256, 1) void point_fused2_kernel(
 
   // ---------------------------------------------------------------- pipeline start
   soff = (unsigned)(GG::gkb(NC - 1) * 1024 + ((GG::ppw(NC - 1) - 1) / 4) * 4096) + (unsigned)wave * (unsigned)(GG::ppw(NC - 1) * 1024);   // the "previous group" of the very first one
-  static_for<3>([&](auto Cc) __attribute__((always_inline)) {
-    static_for<GG::ppw(decltype(Cc)::value)>([&](auto Ic) __attribute__((always_inline)) { dma_piece(Cc, Ic); });
+  nl_static_for<3>([&](auto Cc) __attribute__((always_inline)) {
+    nl_static_for<GG::ppw(decltype(Cc)::value)>([&](auto Ic) __attribute__((always_inline)) { dma_piece(Cc, Ic); });
   });
-  static_for<NPRO>(pro_step);   // the first tile's prologue, back to back
+  nl_static_for<NPRO>(pro_step);   // the first tile's prologue, back to back
   toff = pn_toff; qoff = pn_qoff; ooff_cur = pn_ooff;
   kvtile = ((unsigned)tile * 128u + (unsigned)wave * 32u) * 1024u; kvrow = kvtile + (unsigned)j * 1024u;
   load_T(std::integral_constant<int, 0>{}, toff); load_T(std::integral_constant<int, 1>{}, toff);
-  wait_vmcnt<GG::ppw(1) + GG::ppw(2)>();   // conservative: the prologue's own loads are younger than every piece
+  nl_wait_vmcnt<GG::ppw(1) + GG::ppw(2)>();   // conservative: the prologue's own loads are younger than every piece
   __builtin_amdgcn_s_barrier();
   read_frag(std::integral_constant<int, NC - 1>{}, std::integral_constant<int, GG::nks(NC - 1)>{}, std::integral_constant<int, 0>{});
   read_frag(std::integral_constant<int, NC - 1>{}, std::integral_constant<int, GG::nks(NC - 1) + 1>{}, std::integral_constant<int, 0>{});
   if constexpr (MX6) {   // chunk 0's slab-0 images instead of its lo fragments
-    static_for<4>([&](auto Ic) __attribute__((always_inline)) { read_w6(std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{}, Ic); });
+    nl_static_for<4>([&](auto Ic) __attribute__((always_inline)) { read_w6(std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{}, Ic); });
   } else if constexpr (X3) {
     read_frag(std::integral_constant<int, NC - 1>{}, std::integral_constant<int, GG::nks(NC - 1)>{}, std::integral_constant<int, 1>{});
     read_frag(std::integral_constant<int, NC - 1>{}, std::integral_constant<int, GG::nks(NC - 1) + 1>{}, std::integral_constant<int, 1>{});
@@ -932,7 +853,7 @@ __global__ __launch_bounds__(256, 1) void point_fused2_kernel(
 
   for (;;) {
     pn_tile = tile + (int)nwg;   // rows past N are clamped inside the steps: the last tile prepares a tile that is never computed
-    static_for<NC>(region);
+    nl_static_for<NC>(region);
 #ifdef PF2_TRACE
     if (blockIdx.x == 0 && wave == 0 && trace_it < 4) {
       const unsigned long long t = __builtin_readcyclecounter();
@@ -947,8 +868,8 @@ __global__ __launch_bounds__(256, 1) void point_fused2_kernel(
     if (tile >= sc.ntiles) break;
   }
   // the last v head of the last tile
-  static_for<GG::epi_steps(NC - 1)>([&](auto Ec) __attribute__((always_inline)) { epi_step(std::integral_constant<int, NC - 1>{}, Ec, std::integral_constant<bool, true>{}); });
-  wait_vmcnt<0>();   // LDS-DMA prefetched for a tile that does not exist must land before the LDS is handed to another workgroup
+  nl_static_for<GG::epi_steps(NC - 1)>([&](auto Ec) __attribute__((always_inline)) { epi_step(std::integral_constant<int, NC - 1>{}, Ec, std::integral_constant<bool, true>{}); });
+  nl_wait_vmcnt<0>();   // LDS-DMA prefetched for a tile that does not exist must land before the LDS is handed to another workgroup
   if (sc.clk && blockIdx.x == 0 && tid == 0) { sc.clk[0] = __builtin_readcyclecounter() - clk_c0; sc.clk[1] = __builtin_amdgcn_s_memrealtime() - clk_r0; }
   if (sc.logit_amax) {
     const float m = wave_max(lmax);
@@ -957,13 +878,6 @@ __global__ __launch_bounds__(256, 1) void point_fused2_kernel(
 }
 
 // ---------------------------------------------------------------------------------------------------- packing
-__device__ __forceinline__ unsigned short pf2_f2bf(float x) {
-  unsigned int u = __float_as_uint(x);
-  u += 0x7fffu + ((u >> 16) & 1u);
-  return (unsigned short)(u >> 16);
-}
-__device__ __forceinline__ int pf2_m(int r, int hh) { return (r & 3) + 8 * (r >> 2) + 4 * hh; }   // accumulator register -> row of the 32x32 tile
-
 // Stream: chunk (layer, rt) = [part hi/lo][k-step][lane][8 bf16] in A-fragment order (lane: out row 32 rt + (lane & 31), k-slots
 // 8 (lane >> 5) + t); then the resident block: ray_diff_fc fragments [layer][part][lane][8] (4 KB) and the bias tables (floats).
 __device__ __forceinline__ unsigned short pf2_f2h(float x) { return __builtin_bit_cast(unsigned short, (_Float16)x); }
@@ -1008,10 +922,10 @@ __global__ void pack_point_stream2_kernel(const float* __restrict__ w1, const fl
         if (ee < 30) { const int a = ee / 10, rem = ee - 10 * a, f = (rem >> 1) + 5 * hh, comp = rem & 1; col = F + 3 + 6 * f + 3 * comp + a; }
         else if (ee == 30) col = hh ? F + 2 : F;
         else col = hh ? -1 : F + 1;
-      } else { const int o = pf2_m(8 * (ks - 4) + t, hh); col = o < 27 ? F + 63 + o : -1; }
+      } else { const int o = nl_acc_row(8 * (ks - 4) + t, hh); col = o < 27 ? F + 63 + o : -1; }
       if (col >= 0) v = w1[(size_t)orow * (F + 90) + col];
     } else {
-      const int fin = 32 * (ks >> 1) + pf2_m(8 * (ks & 1) + t, hh);
+      const int fin = 32 * (ks >> 1) + nl_acc_row(8 * (ks & 1) + t, hh);
       if (layer == 1) v = w2[(size_t)orow * W + fin];
       else if (layer == 2) v = w3[(size_t)orow * W + fin];
       else v = orow < 128 ? wk[(size_t)orow * W + fin] : wv[(size_t)(orow - 128) * W + fin];
@@ -1026,9 +940,9 @@ __global__ void pack_point_stream2_kernel(const float* __restrict__ w1, const fl
       out[base + in_part] = h;
       out[base + (long long)nks * 512 + in_part] = pf2_f2h(v - pf2_h2f(h));
     } else {
-      const unsigned short h = pf2_f2bf(v);
+      const unsigned short h = nl_f2bf(v);
       out[base + in_part] = h;
-      out[base + (long long)nks * 512 + in_part] = pf2_f2bf(v - __uint_as_float(((unsigned int)h) << 16));
+      out[base + (long long)nks * 512 + in_part] = nl_f2bf(v - __uint_as_float(((unsigned int)h) << 16));
     }
   }
   // resident block
@@ -1037,23 +951,23 @@ __global__ void pack_point_stream2_kernel(const float* __restrict__ w1, const fl
     const int l = (int)(e >> 9), t = (int)(e & 7), lane = (int)((e >> 3) & 63), i = lane & 31, hh = lane >> 5;
     float v = 0.f;
     if (l == 0) { if (i < 16 && hh == 0 && t < 4) v = rd_w[i * 4 + t]; }
-    else if (i < 27) v = rd_w[80 + i * 16 + pf2_m(t, hh)];
+    else if (i < 27) v = rd_w[80 + i * 16 + nl_acc_row(t, hh)];
     if (mx == 2) {
       const unsigned short h = pf2_f2h(v);
       out[res + (long long)l * 1024 + lane * 8 + t] = h;
       out[res + (long long)l * 1024 + 512 + lane * 8 + t] = pf2_f2h(v - pf2_h2f(h));
     } else {
-      const unsigned short h = pf2_f2bf(v);
+      const unsigned short h = nl_f2bf(v);
       out[res + (long long)l * 1024 + lane * 8 + t] = h;
-      out[res + (long long)l * 1024 + 512 + lane * 8 + t] = pf2_f2bf(v - __uint_as_float(((unsigned int)h) << 16));
+      out[res + (long long)l * 1024 + 512 + lane * 8 + t] = nl_f2bf(v - __uint_as_float(((unsigned int)h) << 16));
     }
   }
   if (e < 64 + 2 * W) {   // bias tables in accumulator order [rt][hh][r]
     float* bt = reinterpret_cast<float*>(out + res + 2048);
     const int i = (int)e;
     float v;
-    if (i < 64) { const int l = i >> 5, hh = (i >> 4) & 1, m = pf2_m(i & 15, hh); v = l == 0 ? (m < 16 ? rd_w[64 + m] : 0.f) : (m < 27 ? rd_w[80 + 432 + m] : 0.f); }
-    else { const int q = i - 64, l = q / W, c = q - l * W, rt = c >> 5, hh = (c >> 4) & 1, f = 32 * rt + pf2_m(c & 15, hh); v = l == 0 ? b2[f] : b3[f]; }
+    if (i < 64) { const int l = i >> 5, hh = (i >> 4) & 1, m = nl_acc_row(i & 15, hh); v = l == 0 ? (m < 16 ? rd_w[64 + m] : 0.f) : (m < 27 ? rd_w[80 + 432 + m] : 0.f); }
+    else { const int q = i - 64, l = q / W, c = q - l * W, rt = c >> 5, hh = (c >> 4) & 1, f = 32 * rt + nl_acc_row(c & 15, hh); v = l == 0 ? b2[f] : b3[f]; }
     bt[i] = v;
   }
 }
@@ -1065,14 +979,6 @@ __global__ void pack_point_stream2_kernel(const float* __restrict__ w1, const fl
 //   image 1 = w_lo6 = e2m3(w - f16(w)) meets the hi image (v_cvt_scalef32_pk32_fp6_f16: position P <- k-step 4 q + (P >> 3), element P & 7).
 // Block scale 2^(floor(log2 max) - 2) (the largest magnitude lands in [4, 8); e2m3 saturates at 7.5: at most its own half-ulp), stored as E8M0 byte q of the lane's scale dword.
 // Chunk image in the stream (32 KB): [f16 fragments 16 K][per slab: w_hi6 dwords 0-3 (1 K) | 4-5 (512) | w_lo6 dwords 0-3 | 4-5]; the scale dwords {w_hi6, w_lo6} per (wide chunk, lane): a table in the resident block
-__device__ __forceinline__ unsigned pf2_e2m3(float a) {   // a >= 0, already divided by the block scale; round to nearest even, saturating
-  if (!(a < 7.5f)) return 31u;
-  if (a < 1.f) return (unsigned)rintf(a * 8.f);   // subnormals 0 .. 0.875; 8 = the smallest normal (encodings are contiguous)
-  const int e = a < 2.f ? 0 : a < 4.f ? 1 : 2;
-  unsigned m = (unsigned)rintf(ldexpf(a, 3 - e));   // 8 .. 16
-  unsigned c = ((unsigned)(e + 1) << 3) + (m - 8u);    // m == 16 carries into the exponent
-  return c > 31u ? 31u : c;
-}
 // The layer-1 chunks too: chunk index c = 0 .. NC - 1, layer-1 chunks hold 6 k-steps = slab 0 + half of slab 1, the k-slots of k-steps 6, 7 are zero.
 __global__ void pack_point_mx6_kernel(const float* __restrict__ w1, const float* __restrict__ w2, const float* __restrict__ w3, const float* __restrict__ wk,
                                       const float* __restrict__ wv, unsigned char* __restrict__ out, int NRT, int F) {
@@ -1097,10 +1003,10 @@ __global__ void pack_point_mx6_kernel(const float* __restrict__ w1, const float*
         if (ee < 30) { const int a = ee / 10, rem = ee - 10 * a, f = (rem >> 1) + 5 * hh, comp = rem & 1; col = F + 3 + 6 * f + 3 * comp + a; }
         else if (ee == 30) col = hh ? F + 2 : F;
         else col = hh ? -1 : F + 1;
-      } else if (ks < 6) { const int o = pf2_m(8 * (ks - 4) + t, hh); col = o < 27 ? F + 63 + o : -1; }
+      } else if (ks < 6) { const int o = nl_acc_row(8 * (ks - 4) + t, hh); col = o < 27 ? F + 63 + o : -1; }
       if (col >= 0) w = w1[(size_t)orow * (F + 90) + col];
     } else {
-      const int fin = 32 * (ks >> 1) + pf2_m(8 * (ks & 1) + t, hh);
+      const int fin = 32 * (ks >> 1) + nl_acc_row(8 * (ks & 1) + t, hh);
       w = pf2_weight(w2, w3, wk, wv, layer, orow, fin, W);
     }
     const float h = pf2_h2f(pf2_f2h(w));
@@ -1114,7 +1020,7 @@ __global__ void pack_point_mx6_kernel(const float* __restrict__ w1, const float*
   const float inv = ldexpf(1.f, 127 - sb);
   unsigned d[6] = {0u, 0u, 0u, 0u, 0u, 0u};
   for (int P = 0; P < 32; ++P) {
-    const unsigned c = pf2_e2m3(fabsf(v[P]) * inv) | (v[P] < 0.f ? 32u : 0u);
+    const unsigned c = nl_e2m3(fabsf(v[P]) * inv) | (v[P] < 0.f ? 32u : 0u);
     const int b = 6 * P;
     d[b >> 5] |= c << (b & 31);
     if ((b & 31) > 26) d[(b >> 5) + 1] |= c >> (32 - (b & 31));

@@ -15,10 +15,7 @@
 // Selection: the score kernel reduces rowmax[N] / colmax[M] with unsigned atomic max on the float bits (scores are >= 0); pass 2, one wave per row, finds the FIRST j
 // with s > thr, s == rowmax[i], s == colmax[j] — the reference's rule on the scores themselves, ties included.
 #include "common.h"
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+#include "mfma.h"
 
 namespace {
 
@@ -57,12 +54,6 @@ struct S2dPackArgs {
   int C;
 };
 
-__device__ __forceinline__ unsigned short s2d_bf16(float x) {   // round to nearest even
-  unsigned u = __float_as_uint(x);
-  u += 0x7fffu + ((u >> 16) & 1u);
-  return (unsigned short)(u >> 16);
-}
-
 __global__ __launch_bounds__(256) void s2d_pack_kernel(const S2dPackArgs a) {
   const S2dLayout L = s2d_layout(a.C);
   const int C = a.C;
@@ -72,16 +63,16 @@ __global__ __launch_bounds__(256) void s2d_pack_kernel(const S2dPackArgs a) {
     if (i < n1) {   // W1, bf16 planes: fragment (s, rb), lane, slot j <-> W1[32 rb + (lane & 31)][16 s + 8 (lane >> 5) + j]
       const int j = i & 7, lane = (i >> 3) & 63, f = i >> 9, rb = f & 3, s = f >> 2;
       const float v = a.w1[(size_t)(32 * rb + (lane & 31)) * C + 16 * s + 8 * (lane >> 5) + j];
-      const unsigned short h = s2d_bf16(v);
+      const unsigned short h = nl_f2bf(v);
       ((unsigned short*)(a.img + L.w1hi))[i] = h;
-      ((unsigned short*)(a.img + L.w1lo))[i] = s2d_bf16(v - __uint_as_float((unsigned)h << 16));
+      ((unsigned short*)(a.img + L.w1lo))[i] = nl_f2bf(v - __uint_as_float((unsigned)h << 16));
     } else if (i < n1 + n2) {   // W2, bf16 planes: fragment (b, s, rb): slot j <-> hidden unit of accumulator register 8 s + j of block b
       const int e = i - n1;
       const int j = e & 7, lane = (e >> 3) & 63, f = e >> 9, rb = f & 3, s = (f >> 2) & 1, b = f >> 3;
       const float v = a.w2[(size_t)(32 * rb + (lane & 31)) * S2D_H + s2d_unit(b, 8 * s + j, lane >> 5)];
-      const unsigned short h = s2d_bf16(v);
+      const unsigned short h = nl_f2bf(v);
       ((unsigned short*)(a.img + L.w2hi))[e] = h;
-      ((unsigned short*)(a.img + L.w2lo))[e] = s2d_bf16(v - __uint_as_float((unsigned)h << 16));
+      ((unsigned short*)(a.img + L.w2lo))[e] = nl_f2bf(v - __uint_as_float((unsigned)h << 16));
     } else if (i < 2 * n1 + n2) {   // W1, fp32: fragment (g, t, rb), lane <-> W1[32 rb + (lane & 31)][8 g + 4 (lane >> 5) + t]
       const int e = i - n1 - n2;
       const int lane = e & 63, f = e >> 6, rb = f & 3, t = (f >> 2) & 3, g = f >> 4;
@@ -114,11 +105,11 @@ struct S2dArgs {
   int N, M, C;
 };
 
-__device__ __forceinline__ bf16x8 s2d_frag(const uint4 v) { return __builtin_bit_cast(bf16x8, v); }
-__device__ __forceinline__ bf16x8 s2d_frag(unsigned a, unsigned b, unsigned c, unsigned d) { return __builtin_bit_cast(bf16x8, u32x4{a, b, c, d}); }
+__device__ __forceinline__ nl_i16x8 s2d_frag(const uint4 v) { return __builtin_bit_cast(nl_i16x8, v); }
+__device__ __forceinline__ nl_i16x8 s2d_frag(unsigned a, unsigned b, unsigned c, unsigned d) { return __builtin_bit_cast(nl_i16x8, nl_u32x4{a, b, c, d}); }
 
 // bias + ReLU + last layer + sigmoid + stores + maxima, shared by the two score kernels.  acc[t][b]: tile t (row n0 + t), hidden 32-block b.
-__device__ __forceinline__ void s2d_finish(const S2dArgs& a, const float* small, const f32x16 (&acc)[2][4], int lane, int n0, bool has1, int m, unsigned& colmax) {
+__device__ __forceinline__ void s2d_finish(const S2dArgs& a, const float* small, const nl_f32x16 (&acc)[2][4], int lane, int n0, bool has1, int m, unsigned& colmax) {
   const int hh = lane >> 5;
   const float* b2p = small + 128 + 64 * hh;
   const float* w3p = small + 256 + 64 * hh;
@@ -190,7 +181,7 @@ __global__ __launch_bounds__(256) void s2d_bf16_kernel(const S2dArgs a) {
       const float* d0a = a.desc0 + (size_t)n0 * C + 8 * hh;
       const float* d0b = a.desc0 + (size_t)(has1 ? n0 + 1 : n0) * C + 8 * hh;
 
-      f32x16 acc[2][4];
+      nl_f32x16 acc[2][4];
 #pragma unroll
       for (int t = 0; t < 2; ++t)
 #pragma unroll
@@ -212,7 +203,7 @@ __global__ __launch_bounds__(256) void s2d_bf16_kernel(const S2dArgs a) {
         nl_split_bf16_pair(x0.z * yb0.z, x0.w * yb0.w, ph[1][1], pl[1][1]);
         nl_split_bf16_pair(x1.x * yb1.x, x1.y * yb1.y, ph[1][2], pl[1][2]);
         nl_split_bf16_pair(x1.z * yb1.z, x1.w * yb1.w, ph[1][3], pl[1][3]);
-        bf16x8 bh[2], bl[2];
+        nl_i16x8 bh[2], bl[2];
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
           bh[t] = s2d_frag(ph[t][0], ph[t][1], ph[t][2], ph[t][3]);
@@ -221,9 +212,9 @@ __global__ __launch_bounds__(256) void s2d_bf16_kernel(const S2dArgs a) {
 #pragma unroll
         for (int rb = 0; rb < 4; ++rb) {
           const int f = ((s << 2) + rb) * 64 + lane;
-          const bf16x8 ah = s2d_frag(w1hi[f]);
+          const nl_i16x8 ah = s2d_frag(w1hi[f]);
           if (X3) {
-            const bf16x8 al = s2d_frag(w1lo[f]);
+            const nl_i16x8 al = s2d_frag(w1lo[f]);
 #pragma unroll
             for (int t = 0; t < 2; ++t) {
               acc[t][rb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh[t], acc[t][rb], 0, 0, 0);
@@ -260,7 +251,7 @@ __global__ __launch_bounds__(256) void s2d_bf16_kernel(const S2dArgs a) {
       for (int b = 0; b < 4; ++b)
 #pragma unroll
         for (int s = 0; s < 2; ++s) {
-          bf16x8 bh[2], bl[2];
+          nl_i16x8 bh[2], bl[2];
 #pragma unroll
           for (int t = 0; t < 2; ++t) {
             bh[t] = s2d_frag(hhi[t][b][4 * s], hhi[t][b][4 * s + 1], hhi[t][b][4 * s + 2], hhi[t][b][4 * s + 3]);
@@ -269,9 +260,9 @@ __global__ __launch_bounds__(256) void s2d_bf16_kernel(const S2dArgs a) {
 #pragma unroll
           for (int rb = 0; rb < 4; ++rb) {
             const int f = (((b * 2 + s) << 2) + rb) * 64 + lane;
-            const bf16x8 ah = s2d_frag(w2hi[f]);
+            const nl_i16x8 ah = s2d_frag(w2hi[f]);
             if (X3) {
-              const bf16x8 al = s2d_frag(w2lo[f]);
+              const nl_i16x8 al = s2d_frag(w2lo[f]);
 #pragma unroll
               for (int t = 0; t < 2; ++t) {
                 acc[t][rb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh[t], acc[t][rb], 0, 0, 0);
@@ -318,7 +309,7 @@ __global__ __launch_bounds__(256) void s2d_f32_kernel(const S2dArgs a) {
       const float* d0a = a.desc0 + (size_t)n0 * C + 4 * hh;
       const float* d0b = a.desc0 + (size_t)(has1 ? n0 + 1 : n0) * C + 4 * hh;
 
-      f32x16 acc[2][4];
+      nl_f32x16 acc[2][4];
 #pragma unroll
       for (int t = 0; t < 2; ++t)
 #pragma unroll

@@ -11,59 +11,19 @@
 //   * all N <= 256 output columns of a row live in one wave's accumulators (N/32 tiles of 32x32), so X is read once.
 //   * <= 256 registers and 64 KB of LDS: two workgroups per CU, which run out of phase and hide each other's memory
 //     latency, conversion VALU and barrier time behind MFMAs; no data-dependent control flow around the MFMAs.
-#include <utility>
 #include "common.h"
-
-typedef __bf16 tg_bf16x8 __attribute__((ext_vector_type(8)));
-typedef float tg_f32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned int tg_u32x4 __attribute__((ext_vector_type(4)));
-typedef float tg_f32x4 __attribute__((ext_vector_type(4)));
+#include "mfma.h"
 
 namespace {
 
-__device__ __forceinline__ void tg_glds16(const void* g, void* l) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
-                                   (__attribute__((address_space(3))) void*)l, 16, 0, 0);
-}
-template <int N>
-__device__ __forceinline__ void tg_wait_vmcnt() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"i"(N) : "memory");
-}
-template <int... Is, class F>
-__device__ __forceinline__ void tg_static_for_impl(std::integer_sequence<int, Is...>, F&& f) {
-  (f(std::integral_constant<int, Is>{}), ...);
-}
-template <int N, class F>
-__device__ __forceinline__ void tg_static_for(F&& f) {
-  tg_static_for_impl(std::make_integer_sequence<int, N>{}, static_cast<F&&>(f));
-}
-
-template <bool X3>
-__device__ __forceinline__ void tg_split8(const float (&v)[8], tg_bf16x8& hi, tg_bf16x8& lo) {
-  unsigned h[4], l[4] = {0u, 0u, 0u, 0u};
-#pragma unroll
-  for (int t = 0; t < 4; ++t) {
-    if (X3) nl_split_bf16_pair(v[2 * t], v[2 * t + 1], h[t], l[t]);
-    else h[t] = nl_bf16_pair(v[2 * t], v[2 * t + 1]);
-  }
-  hi = __builtin_bit_cast(tg_bf16x8, tg_u32x4{h[0], h[1], h[2], h[3]});
-  if (X3) lo = __builtin_bit_cast(tg_bf16x8, tg_u32x4{l[0], l[1], l[2], l[3]});
-}
-
 // three-term split-FP16 variant (internal precision NL_PREC_F16X3_INTERNAL: the backward passes' recomputed forward): the same storage type (16-bit
 // lanes), fp16 bit patterns; products good to ~2^-22 at the speed of split-bf16
-typedef _Float16 tg_f16x8 __attribute__((ext_vector_type(8)));
-__device__ __forceinline__ void tg_split8_f16(const float (&v)[8], tg_bf16x8& hi, tg_bf16x8& lo) {
-  tg_f16x8 h, l;
+__device__ __forceinline__ void tg_split8_f16(const float (&v)[8], nl_bf16x8& hi, nl_bf16x8& lo) {
+  nl_f16x8 h, l;
 #pragma unroll
   for (int t = 0; t < 8; ++t) { const _Float16 x = (_Float16)v[t]; h[t] = x; l[t] = (_Float16)(v[t] - (float)x); }
-  hi = __builtin_bit_cast(tg_bf16x8, h);
-  lo = __builtin_bit_cast(tg_bf16x8, l);
-}
-template <bool F16>
-__device__ __forceinline__ tg_f32x16 tg_mfma(const tg_bf16x8& a, const tg_bf16x8& b, const tg_f32x16& c) {
-  if constexpr (F16) return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(tg_f16x8, a), __builtin_bit_cast(tg_f16x8, b), c, 0, 0, 0);
-  else return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
+  hi = __builtin_bit_cast(nl_bf16x8, h);
+  lo = __builtin_bit_cast(nl_bf16x8, l);
 }
 
 // chunk c (k-space [32c, 32c+32)) lies in exactly one segment (every segment is a multiple of 32 wide here);
@@ -105,7 +65,7 @@ __global__ __launch_bounds__(64 * NW, NW > 4 ? 1 : 2) void tgemm_kernel(const Nl
   constexpr int SLOT16 = PIECES * 64;       // 16-B units per LDS slot
   __shared__ uint4 lds_all[2 * SLOT16 + NRT * 8 * (EPI == NL_EPI_LNROW ? 3 : EPI == NL_EPI_LNSLAB ? 2 : 1) + (EPI == NL_EPI_LNSLAB ? 8 : 0)];
   // native vector element type everywhere (struct-typed uint4 arrays in registers do not survive SROA)
-  tg_bf16x8 (*ring)[SLOT16] = reinterpret_cast<tg_bf16x8 (*)[SLOT16]>(lds_all);
+  nl_bf16x8 (*ring)[SLOT16] = reinterpret_cast<nl_bf16x8 (*)[SLOT16]>(lds_all);
   float* sbias = reinterpret_cast<float*>(lds_all + 2 * SLOT16);
 
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -129,15 +89,15 @@ __global__ __launch_bounds__(64 * NW, NW > 4 ? 1 : 2) void tgemm_kernel(const Nl
   }
 
   // weights of chunk c: this wave's NPW pieces, 16 B per lane, fully coalesced
-  auto w_ptr = [&](int c) __attribute__((always_inline)) { return reinterpret_cast<const tg_bf16x8*>(p_bst) + (size_t)c * CH16 + wave * 64 + lane; };
+  auto w_ptr = [&](int c) __attribute__((always_inline)) { return reinterpret_cast<const nl_bf16x8*>(p_bst) + (size_t)c * CH16 + wave * 64 + lane; };
   const bool stager = NWS == NW || wave < NWS;   // (wave-uniform; a compile-time `true` for the four-wave kernels)
-  auto load_w = [&](int c, tg_bf16x8 (&w)[NPW]) __attribute__((always_inline)) {
+  auto load_w = [&](int c, nl_bf16x8 (&w)[NPW]) __attribute__((always_inline)) {
     if (!stager) return;
-    const tg_bf16x8* src = w_ptr(c);
+    const nl_bf16x8* src = w_ptr(c);
 #pragma unroll
     for (int jj = 0; jj < NPW; ++jj) w[jj] = src[NWS * jj * 64];
   };
-  auto store_w = [&](int slot, const tg_bf16x8 (&w)[NPW]) __attribute__((always_inline)) {
+  auto store_w = [&](int slot, const nl_bf16x8 (&w)[NPW]) __attribute__((always_inline)) {
     if (!stager) return;
 #pragma unroll
     for (int jj = 0; jj < NPW; ++jj) ring[slot][(wave + NWS * jj) * 64 + lane] = w[jj];
@@ -176,36 +136,36 @@ __global__ __launch_bounds__(64 * NW, NW > 4 ? 1 : 2) void tgemm_kernel(const Nl
 #pragma unroll
     for (int pc = 0; pc < 4; ++pc) raw[pc] = *(const float4*)(p + act_off(fr, pc));
   };
-  auto convert = [&](const float4 (&raw)[4], int fr, tg_bf16x8 (&bh)[2], tg_bf16x8 (&bl)[2]) __attribute__((always_inline)) {
+  auto convert = [&](const float4 (&raw)[4], int fr, nl_bf16x8 (&bh)[2], nl_bf16x8 (&bl)[2]) __attribute__((always_inline)) {
     if (fr == 1) {   // (wave-uniform branch around vector moves only: the MFMAs stay in one block)
-      bh[0] = __builtin_bit_cast(tg_bf16x8, raw[0]); bl[0] = __builtin_bit_cast(tg_bf16x8, raw[1]);
-      bh[1] = __builtin_bit_cast(tg_bf16x8, raw[2]); bl[1] = __builtin_bit_cast(tg_bf16x8, raw[3]);
+      bh[0] = __builtin_bit_cast(nl_bf16x8, raw[0]); bl[0] = __builtin_bit_cast(nl_bf16x8, raw[1]);
+      bh[1] = __builtin_bit_cast(nl_bf16x8, raw[2]); bl[1] = __builtin_bit_cast(nl_bf16x8, raw[3]);
       return;
     }
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks) {
       const float v[8] = {raw[2 * ks].x, raw[2 * ks].y, raw[2 * ks].z, raw[2 * ks].w,
                           raw[2 * ks + 1].x, raw[2 * ks + 1].y, raw[2 * ks + 1].z, raw[2 * ks + 1].w};
-      if constexpr (F16) tg_split8_f16(v, bh[ks], bl[ks]); else tg_split8<X3>(v, bh[ks], bl[ks]);
+      if constexpr (F16) tg_split8_f16(v, bh[ks], bl[ks]); else nl_split8<X3>(v, bh[ks], bl[ks]);
     }
   };
 
-  tg_f32x16 acc[NRT];
+  nl_f32x16 acc[NRT];
 #pragma unroll
   for (int rt = 0; rt < NRT; ++rt)
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[rt][r] = 0.f;
 
   // one chunk: 2 k-steps x NRT row tiles x (3 | 1) MFMAs; A fragments are read two (k-step, tile) pairs ahead
-  auto compute = [&](int slot, const tg_bf16x8 (&bh)[2], const tg_bf16x8 (&bl)[2], auto&& filler) __attribute__((always_inline)) {
-    const tg_bf16x8* L = ring[slot];
+  auto compute = [&](int slot, const nl_bf16x8 (&bh)[2], const nl_bf16x8 (&bl)[2], auto&& filler) __attribute__((always_inline)) {
+    const nl_bf16x8* L = ring[slot];
     constexpr int nt = 2 * NRT;
-    auto ldA = [&](int tt, tg_bf16x8& ah, tg_bf16x8& al) __attribute__((always_inline)) {
+    auto ldA = [&](int tt, nl_bf16x8& ah, nl_bf16x8& al) __attribute__((always_inline)) {
       const int ks = tt / NRT, rt = tt - ks * NRT;
       ah = L[((0 * 2 + ks) * NRT + rt) * 64 + lane];
       if (X3) al = L[((1 * 2 + ks) * NRT + rt) * 64 + lane];
     };
-    tg_bf16x8 ah[3], al[3];
+    nl_bf16x8 ah[3], al[3];
     ldA(0, ah[0], al[0]);
     ldA(1, ah[1], al[1]);
 #pragma unroll
@@ -213,10 +173,10 @@ __global__ __launch_bounds__(64 * NW, NW > 4 ? 1 : 2) void tgemm_kernel(const Nl
       if (tt + 2 < nt) ldA(tt + 2, ah[(tt + 2) % 3], al[(tt + 2) % 3]);
       const int ks = tt / NRT, rt = tt - ks * NRT;
       if (X3) {
-        acc[rt] = tg_mfma<F16>(al[tt % 3], bh[ks], acc[rt]);
-        acc[rt] = tg_mfma<F16>(ah[tt % 3], bl[ks], acc[rt]);
+        acc[rt] = nl_mfma<F16>(al[tt % 3], bh[ks], acc[rt]);
+        acc[rt] = nl_mfma<F16>(ah[tt % 3], bl[ks], acc[rt]);
       }
-      acc[rt] = tg_mfma<F16>(ah[tt % 3], bh[ks], acc[rt]);
+      acc[rt] = nl_mfma<F16>(ah[tt % 3], bh[ks], acc[rt]);
       filler(tt);
       __builtin_amdgcn_sched_barrier(0);
     }
@@ -228,7 +188,7 @@ __global__ __launch_bounds__(64 * NW, NW > 4 ? 1 : 2) void tgemm_kernel(const Nl
   // loop out of phase and covers this one's latencies, VALU and barrier time with its MFMAs.
   // The chunk past the end re-loads the last real chunk (never used): no data-dependent control flow around the MFMAs
   // (the accumulators must stay in AGPRs).
-  tg_bf16x8 wreg[NPW];
+  nl_bf16x8 wreg[NPW];
   float4 raw[4];
   int raw_fr = 0;   // what `raw` holds (see act_ptr)
   auto clampc = [&](int c) { return c < NC ? c : NC - 1; };
@@ -237,7 +197,7 @@ __global__ __launch_bounds__(64 * NW, NW > 4 ? 1 : 2) void tgemm_kernel(const Nl
   __syncthreads();
   for (int g = 0; g < NC; ++g) {   // one straight-line body, no control flow around the MFMAs (accumulators stay put)
     TG_T(g < 40 ? g : 40);
-    tg_bf16x8 bh[2], bl[2];
+    nl_bf16x8 bh[2], bl[2];
     convert(raw, raw_fr, bh, bl);
     // The next chunk's 4 activation loads (lane = row: ~64 cycles each in the CU's address unit) and NPW weight loads go out one at a
     // time between the MFMA groups instead of as a burst in front of them: a burst makes every wave of the workgroup wait at issue
@@ -246,7 +206,7 @@ __global__ __launch_bounds__(64 * NW, NW > 4 ? 1 : 2) void tgemm_kernel(const Nl
     if constexpr (NRT == 8) {
       int nfr = 0;
       const float* ap = act_ptr(clampc(g + 1), nfr);
-      const tg_bf16x8* wp = w_ptr(clampc(g + 1));
+      const nl_bf16x8* wp = w_ptr(clampc(g + 1));
       compute(g & 1, bh, bl, [&](int tt) __attribute__((always_inline)) {
         constexpr int NLD = 4 + NPW, nh = NRT;   // slots 0 .. NRT-1
 #pragma unroll
@@ -459,7 +419,6 @@ __global__ __launch_bounds__(64 * NW, NW > 4 ? 1 : 2) void tgemm_kernel(const Nl
   if (a.ep_maskout) *(uint4*)(a.ep_maskout + ((size_t)tile * 64 + lane) * 4) = make_uint4(mb[0], NRT > 2 ? mb[1] : 0u, NRT > 4 ? mb[2] : 0u, NRT > 4 ? mb[3] : 0u);
 }
 
-
 // ====================================================================================================================
 // conv_out in the f16mx arithmetic (round 6; NL_PREC_F16MX, W = 256, S = 128): the product of `tgemm_kernel<8, 4, true, NL_EPI_LNSLAB>` as fp16 hi.hi + two MX-FP6
 // cross terms — per K = 64 slab and 32 x 32 tile 4 x v_mfma_f32_32x32x16_f16 + 2 x v_mfma_scale_f32_32x32x64_f8f6f4 (48 matrix passes) instead of 12 bf16
@@ -475,42 +434,26 @@ __global__ __launch_bounds__(64 * NW, NW > 4 ? 1 : 2) void tgemm_kernel(const Nl
 //   * 130 KB of LDS = ONE workgroup per CU, so the workgroup is eight waves = 256 rows = two rays: the same two waves per SIMD as the two four-wave workgroups of
 //     the bf16x3 kernel, every weight byte staged once per 256 rows instead of once per 128.
 // Epilogue: LayerNorm over each ray's (128 x 256) slab + ELU + the density head, as tgemm_kernel's NL_EPI_LNSLAB.
-typedef int tg_i32x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int tg_u32x6 __attribute__((ext_vector_type(6)));
-typedef unsigned int tg_u32x16 __attribute__((ext_vector_type(16)));
 
-// f16 pair of two values + the running maximum of their magnitudes
-__device__ __forceinline__ unsigned tg_hi2_f16_amax(float v0, float v1, float& m) {
-  unsigned hi;
-  asm("v_max3_f32 %1, |%2|, |%3|, %1\n\tv_cvt_pk_f16_f32 %0, %2, %3" : "=&v"(hi), "+v"(m) : "v"(v0), "v"(v1));
-  return hi;
-}
-// residuals of a pair as floats: v - float(hi half) (exact)
-__device__ __forceinline__ void tg_lo2_f32(float v0, float v1, unsigned hi, float& l0, float& l1) {
-  asm("v_fma_mix_f32 %0, %4, -1.0, %2 op_sel_hi:[1,0,0]\n\tv_fma_mix_f32 %1, %4, -1.0, %3 op_sel:[1,0,0] op_sel_hi:[1,0,0]"
-      : "=&v"(l0), "=&v"(l1) : "v"(v0), "v"(v1), "v"(hi));
-}
 // split-FP16 of 8 values on the packed conversions (hi = f16(v), lo = f16(v - hi); 16 instructions): the chain kernel's F16FRAG rows
-__device__ __forceinline__ void tg_split8_f16_pk(const float (&v)[8], tg_bf16x8& hi, tg_bf16x8& lo) {
+__device__ __forceinline__ void tg_split8_f16_pk(const float (&v)[8], nl_bf16x8& hi, nl_bf16x8& lo) {
   unsigned h[4], l[4];
 #pragma unroll
   for (int t = 0; t < 4; ++t) {
     asm("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(h[t]) : "v"(v[2 * t]), "v"(v[2 * t + 1]));
     float l0, l1;
-    tg_lo2_f32(v[2 * t], v[2 * t + 1], h[t], l0, l1);
+    nl_lo2_f32(v[2 * t], v[2 * t + 1], h[t], l0, l1);
     asm("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(l[t]) : "v"(l0), "v"(l1));
   }
-  hi = __builtin_bit_cast(tg_bf16x8, tg_u32x4{h[0], h[1], h[2], h[3]});
-  lo = __builtin_bit_cast(tg_bf16x8, tg_u32x4{l[0], l[1], l[2], l[3]});
+  hi = __builtin_bit_cast(nl_bf16x8, nl_u32x4{h[0], h[1], h[2], h[3]});
+  lo = __builtin_bit_cast(nl_bf16x8, nl_u32x4{l[0], l[1], l[2], l[3]});
 }
 // The f16mx operand of a 64-k slab from split-FP16 fragment words (NlGemmSeg::frag == 3): the hi plane IS the f16 operand, the block maximum is an integer maximum of
 // its magnitudes, the lo plane becomes the residual fp6 image with the same instruction that makes the hi image (on the hi image's scale x 2^-11).  raw[ci][2 ks] /
 // raw[ci][2 ks + 1] = hi / lo words of chunk ci (0, 1), k-step ks: positions P = 16 ci + 8 ks + 0 .. 7.  Returns the block exponent byte eb (scale 2^(eb - 127)).
-typedef unsigned short tg_u16x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ tg_u32x6 tg_cvt_pk32_fp6_f16(tg_u32x16 h, float sc);
-__device__ __forceinline__ int tg_mx_operand_f16frag(const float4 (&raw)[2][4], tg_u32x16& H, tg_u32x6& xh6, tg_u32x6& xl6) {
-  tg_u32x16 Lw;
-  tg_u16x2 mx = {0, 0};
+__device__ __forceinline__ int tg_mx_operand_f16frag(const float4 (&raw)[2][4], nl_u32x16& H, nl_u32x6& xh6, nl_u32x6& xl6) {
+  nl_u32x16 Lw;
+  nl_u16x2 mx = {0, 0};
 #pragma unroll
   for (int ci = 0; ci < 2; ++ci)
 #pragma unroll
@@ -522,7 +465,7 @@ __device__ __forceinline__ int tg_mx_operand_f16frag(const float4 (&raw)[2][4], 
       for (int d = 0; d < 4; ++d) {
         H[8 * ci + 4 * ks + d] = uh[d];
         Lw[8 * ci + 4 * ks + d] = ul[d];
-        mx = __builtin_elementwise_max(mx, __builtin_bit_cast(tg_u16x2, uh[d] & 0x7fff7fffu));   // (f16 magnitudes order like their bit patterns)
+        mx = __builtin_elementwise_max(mx, __builtin_bit_cast(nl_u16x2, uh[d] & 0x7fff7fffu));   // (f16 magnitudes order like their bit patterns)
       }
     }
   const unsigned short m16 = mx[0] > mx[1] ? mx[0] : mx[1];
@@ -530,20 +473,9 @@ __device__ __forceinline__ int tg_mx_operand_f16frag(const float4 (&raw)[2][4], 
   int eb = __builtin_amdgcn_frexp_expf(amax) + 124;   // as tgemm_mx_kernel: the largest value lands in [4, 8)
   eb = eb < 12 ? 12 : (eb > 254 ? 254 : eb);
   const float scf = __builtin_bit_cast(float, eb << 23);
-  xh6 = tg_cvt_pk32_fp6_f16(H, scf);
-  xl6 = tg_cvt_pk32_fp6_f16(Lw, scf * 0.00048828125f);
+  xh6 = nl_cvt_pk32_fp6_f16(H, scf);
+  xl6 = nl_cvt_pk32_fp6_f16(Lw, scf * 0.00048828125f);
   return eb;
-}
-// (asm with early-clobber results: hipcc 7.2 lets the builtins' 6-register result overlap the scale operand — point_fused2.hip)
-__device__ __forceinline__ tg_u32x6 tg_cvt_pk32_fp6_f16(tg_u32x16 h, float sc) {
-  tg_u32x6 r;
-  asm("v_cvt_scalef32_pk32_fp6_f16 %0, %1, %2" : "=&v"(r) : "v"(h), "v"(sc));
-  return r;
-}
-__device__ __forceinline__ tg_u32x6 tg_cvt_2xpk16_fp6_f32(tg_f32x16 a, tg_f32x16 b, float sc) {
-  tg_u32x6 r;
-  asm("v_cvt_scalef32_2xpk16_fp6_f32 %0, %1, %2, %3" : "=&v"(r) : "v"(a), "v"(b), "v"(sc));
-  return r;
 }
 
 constexpr int TGMX_NRT = 8, TGMX_NW = 8;
@@ -614,7 +546,7 @@ __global__ __launch_bounds__(64 * TGMX_NW, 1) void tgemm_mx_kernel(const NlGemmA
     }
   };
   auto stage = [&](int sl, auto SLOTc) __attribute__((always_inline)) {
-    tg_static_for<TGMX_PPW>([&](auto Ic) __attribute__((always_inline)) { stage_piece(sl, SLOTc, Ic); });
+    nl_static_for<TGMX_PPW>([&](auto Ic) __attribute__((always_inline)) { stage_piece(sl, SLOTc, Ic); });
   };
   // ---- activations.  The layer's K structure is conv_out's (W = 256; checked by nl_tgemm_mx_supported): chunks 0 .. 23 = feature_agg (eight 32-channel blocks x three
   // taps, [block][tap]), 24 .. 26 = the three taps of x2's one block, 27 = nothing.  Everything that depends on the chunk is therefore a compile-time constant, and what
@@ -661,7 +593,7 @@ __global__ __launch_bounds__(64 * TGMX_NW, 1) void tgemm_mx_kernel(const NlGemmA
     load_chunk(std::integral_constant<int, (2 * sl + ci < 28 ? 2 * sl + ci : 27)>{}, std::integral_constant<int, ci>{}, std::integral_constant<int, (k & 3)>{});
   };
 
-  tg_f32x16 acc[NRT];
+  nl_f32x16 acc[NRT];
 #pragma unroll
   for (int rt = 0; rt < NRT; ++rt)
 #pragma unroll
@@ -669,7 +601,7 @@ __global__ __launch_bounds__(64 * TGMX_NW, 1) void tgemm_mx_kernel(const NlGemmA
 
   stage(0, std::integral_constant<int, 0>{});
   load_act(std::integral_constant<int, 0>{});
-  tg_wait_vmcnt<0>();
+  nl_wait_vmcnt<0>();
   __syncthreads();
 
   constexpr int NSC = 14;   // slabs of the layer (27 chunks)
@@ -682,8 +614,8 @@ __global__ __launch_bounds__(64 * TGMX_NW, 1) void tgemm_mx_kernel(const NlGemmA
     constexpr int g = decltype(Gc)::value, SL = g & 1;
     TGMX_T(0);
     // ---- this slab's B operand from the raw words: 32 values (position P = 8 s + t, k-step s = 2 (chunk of the slab) + ks)
-    tg_u32x16 H;
-    tg_u32x6 xh6, xl6;
+    nl_u32x16 H;
+    nl_u32x6 xh6, xl6;
     int eb;
     if (g < 12 && f16in) eb = tg_mx_operand_f16frag(raw, H, xh6, xl6);   // feature_agg's slabs from split-FP16 fragments: no sums, no conversions to f16, no residuals
     else {
@@ -725,19 +657,19 @@ __global__ __launch_bounds__(64 * TGMX_NW, 1) void tgemm_mx_kernel(const NlGemmA
     float lo[32];
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
-      H[i] = tg_hi2_f16_amax(v[2 * i], v[2 * i + 1], amax);
-      tg_lo2_f32(v[2 * i], v[2 * i + 1], H[i], lo[2 * i], lo[2 * i + 1]);
+      H[i] = nl_hi2_f16_amax(v[2 * i], v[2 * i + 1], amax);
+      nl_lo2_f32(v[2 * i], v[2 * i + 1], H[i], lo[2 * i], lo[2 * i + 1]);
     }
     eb = __builtin_amdgcn_frexp_expf(amax) + 124;   // block scale 2^(ex - 3) for amax = m 2^ex, m in [0.5, 1): the largest value lands in [4, 8)
     eb = eb < 12 ? 12 : (eb > 254 ? 254 : eb);          // (12: the residual image's byte eb - 11 stays positive; an all-zero block takes any scale)
     const float scf = __builtin_bit_cast(float, eb << 23);
-    xh6 = tg_cvt_pk32_fp6_f16(H, scf);
-    const tg_f32x16 le = {lo[0], lo[2], lo[4], lo[6], lo[8], lo[10], lo[12], lo[14], lo[16], lo[18], lo[20], lo[22], lo[24], lo[26], lo[28], lo[30]};
-    const tg_f32x16 lod = {lo[1], lo[3], lo[5], lo[7], lo[9], lo[11], lo[13], lo[15], lo[17], lo[19], lo[21], lo[23], lo[25], lo[27], lo[29], lo[31]};
-    xl6 = tg_cvt_2xpk16_fp6_f32(le, lod, scf * 0.00048828125f);   // (interleaves its operands: position 2 i <- le[i], 2 i + 1 <- lod[i] = the natural order)
+    xh6 = nl_cvt_pk32_fp6_f16(H, scf);
+    const nl_f32x16 le = {lo[0], lo[2], lo[4], lo[6], lo[8], lo[10], lo[12], lo[14], lo[16], lo[18], lo[20], lo[22], lo[24], lo[26], lo[28], lo[30]};
+    const nl_f32x16 lod = {lo[1], lo[3], lo[5], lo[7], lo[9], lo[11], lo[13], lo[15], lo[17], lo[19], lo[21], lo[23], lo[25], lo[27], lo[29], lo[31]};
+    xl6 = nl_cvt_2xpk16_fp6_f32(le, lod, scf * 0.00048828125f);   // (interleaves its operands: position 2 i <- le[i], 2 i + 1 <- lod[i] = the natural order)
     }
-    const tg_i32x8 bh6 = {(int)xh6[0], (int)xh6[1], (int)xh6[2], (int)xh6[3], (int)xh6[4], (int)xh6[5], 0, 0};
-    const tg_i32x8 bl6 = {(int)xl6[0], (int)xl6[1], (int)xl6[2], (int)xl6[3], (int)xl6[4], (int)xl6[5], 0, 0};
+    const nl_i32x8 bh6 = {(int)xh6[0], (int)xh6[1], (int)xh6[2], (int)xh6[3], (int)xh6[4], (int)xh6[5], 0, 0};
+    const nl_i32x8 bl6 = {(int)xl6[0], (int)xl6[1], (int)xl6[2], (int)xl6[3], (int)xl6[4], (int)xl6[5], 0, 0};
     const int sxh = eb, sxl = eb - 11;
     TGMX_T(1);
 
@@ -751,39 +683,39 @@ __global__ __launch_bounds__(64 * TGMX_NW, 1) void tgemm_mx_kernel(const NlGemmA
 
     // ---- the slab's product: per row tile 4 f16 k-steps + the two cross terms = 48 units; the A operand of unit u + 2 is read from LDS before the matrix instruction of
     // unit u is issued (three rotating register sets: without the read-ahead every matrix instruction waits out an LDS round trip, ~170 cycles for a 32-cycle instruction)
-    const tg_u32x4* Lf = reinterpret_cast<const tg_u32x4*>(lds_all + (SL * TGMX_SLOT) / 16);
-    const tg_u32x4* La = reinterpret_cast<const tg_u32x4*>(lds_all + (SL * TGMX_SLOT + TGMX_F16B) / 16);
-    const tg_u32x4* Lb = reinterpret_cast<const tg_u32x4*>(lds_all + (SL * TGMX_SLOT + TGMX_F16B + TGMX_IMA) / 16);
+    const nl_u32x4* Lf = reinterpret_cast<const nl_u32x4*>(lds_all + (SL * TGMX_SLOT) / 16);
+    const nl_u32x4* La = reinterpret_cast<const nl_u32x4*>(lds_all + (SL * TGMX_SLOT + TGMX_F16B) / 16);
+    const nl_u32x4* Lb = reinterpret_cast<const nl_u32x4*>(lds_all + (SL * TGMX_SLOT + TGMX_F16B + TGMX_IMA) / 16);
     // weight fragments read RD units ahead (RR rotating register sets); measured 2 / 3 / 4 units ahead: 481-483 / 475 / 472-473 us (241 / 245 registers at 3 / 4, no scratch)
     constexpr int RD = 4, RR = RD + 1;
     TGMX_T(2);
-    tg_u32x4 ra[RR], rb[RR];
+    nl_u32x4 ra[RR], rb[RR];
     auto rdA = [&](auto Uc) __attribute__((always_inline)) {
       constexpr int u = decltype(Uc)::value, rt = u / 6, k = u % 6, r = u % RR;
       if constexpr (k < 4) ra[r] = Lf[(k * NRT + rt) * 64 + lane];
       else { ra[r] = La[(rt * 2 + (k - 4)) * 64 + lane]; rb[r] = Lb[(rt * 2 + (k - 4)) * 64 + lane]; }   // rb: {dword 4, dword 5, scale byte, 0}
     };
-    tg_static_for<RD>([&](auto Uc) __attribute__((always_inline)) { rdA(Uc); });
-    tg_static_for<6 * NRT>([&](auto Uc) __attribute__((always_inline)) {
+    nl_static_for<RD>([&](auto Uc) __attribute__((always_inline)) { rdA(Uc); });
+    nl_static_for<6 * NRT>([&](auto Uc) __attribute__((always_inline)) {
       constexpr int u = decltype(Uc)::value, rt = u / 6, k = u % 6, r = u % RR;
       if constexpr (u + RD < 6 * NRT) rdA(std::integral_constant<int, u + RD>{});
       if constexpr (u % 3 == 0) mem_slot(std::integral_constant<int, u / 3>{});   // 16 slots in 48 units
       if constexpr (k < 4) {
-        const tg_f16x8 bf = __builtin_bit_cast(tg_f16x8, (tg_u32x4){H[4 * k], H[4 * k + 1], H[4 * k + 2], H[4 * k + 3]});
-        acc[rt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(tg_f16x8, ra[r]), bf, acc[rt], 0, 0, 0);
+        const nl_f16x8 bf = __builtin_bit_cast(nl_f16x8, (nl_u32x4){H[4 * k], H[4 * k + 1], H[4 * k + 2], H[4 * k + 3]});
+        acc[rt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(nl_f16x8, ra[r]), bf, acc[rt], 0, 0, 0);
       } else {
-        const tg_i32x8 w6 = {(int)ra[r][0], (int)ra[r][1], (int)ra[r][2], (int)ra[r][3], (int)rb[r][0], (int)rb[r][1], 0, 0};
+        const nl_i32x8 w6 = {(int)ra[r][0], (int)ra[r][1], (int)ra[r][2], (int)ra[r][3], (int)rb[r][0], (int)rb[r][1], 0, 0};
         if constexpr (k == 4) acc[rt] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(w6, bl6, acc[rt], 2, 2, 0, (int)rb[r][2], 0, sxl);   // w_hi6 x a_lo6
         else acc[rt] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(w6, bh6, acc[rt], 2, 2, 0, (int)rb[r][2], 0, sxh);                     // w_lo6 x a_hi6
       }
       __builtin_amdgcn_sched_barrier(0);
     });
     TGMX_T(3);
-    tg_wait_vmcnt<0>();
+    nl_wait_vmcnt<0>();
     TGMX_T(4);
     __syncthreads();
   };
-  tg_static_for<NSC>([&](auto Gc) __attribute__((always_inline)) { slab(Gc); });
+  nl_static_for<NSC>([&](auto Gc) __attribute__((always_inline)) { slab(Gc); });
 
   // ---- epilogue: LayerNorm over each ray's whole (So x N) slab (So = 128: four waves per ray, two rays per workgroup), ELU, the density head (tgemm_kernel's NL_EPI_LNSLAB)
   float* red = sbias + NRT * 32;   // [2][NW] partial sums
@@ -923,7 +855,7 @@ __global__ __launch_bounds__(64 * NW, 1) void feat_comp_mx_kernel(const float* _
     }
   };
   auto stage = [&](int sl, auto SLOTc) __attribute__((always_inline)) {
-    tg_static_for<PPW>([&](auto Ic) __attribute__((always_inline)) { stage_piece(sl, SLOTc, Ic); });
+    nl_static_for<PPW>([&](auto Ic) __attribute__((always_inline)) { stage_piece(sl, SLOTc, Ic); });
   };
   // activations: the chain kernel's fragment image — per 32-row tile 16 k-steps x 512 floats, a 32-channel block = [ks 0: hi | lo | ks 1: hi | lo] x (64 lanes x 4 floats)
   const float* P = tile_ptr(blockIdx.x);
@@ -937,7 +869,7 @@ __global__ __launch_bounds__(64 * NW, 1) void feat_comp_mx_kernel(const float* _
 
   stage(0, std::integral_constant<int, 0>{});
   load_act(P, 0);
-  tg_wait_vmcnt<0>();
+  nl_wait_vmcnt<0>();
   __syncthreads();
 
   constexpr int NSC = 4;   // slabs of the layer (K = 256)
@@ -948,7 +880,7 @@ __global__ __launch_bounds__(64 * NW, 1) void feat_comp_mx_kernel(const float* _
   const bool live = tile < ntiles;
   const int tile_c = live ? tile : ntiles - 1;
   const float* Pn = tile_ptr(grp + (int)gridDim.x);   // (past the last group: re-reads the last tile, never used)
-  tg_f32x16 acc[NRT];
+  nl_f32x16 acc[NRT];
 #pragma unroll
   for (int rt = 0; rt < NRT; ++rt)
 #pragma unroll
@@ -957,8 +889,8 @@ __global__ __launch_bounds__(64 * NW, 1) void feat_comp_mx_kernel(const float* _
     constexpr int g = decltype(Gc)::value, SL = g & 1;
     // ---- this slab's A operand from the raw words: 32 values (position P = 8 s + t, k-step s = 2 (chunk of the slab) + ks); value = bf16 hi + bf16 lo, or
     // (f16in: split-FP16 fragments) the hi plane as it stands
-    tg_u32x16 H;
-    tg_u32x6 xh6, xl6;
+    nl_u32x16 H;
+    nl_u32x6 xh6, xl6;
     int eb;
     if (f16in) eb = tg_mx_operand_f16frag(raw, H, xh6, xl6);
     else {
@@ -980,19 +912,19 @@ __global__ __launch_bounds__(64 * NW, 1) void feat_comp_mx_kernel(const float* _
     float lo[32];
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
-      H[i] = tg_hi2_f16_amax(v[2 * i], v[2 * i + 1], amax);
-      tg_lo2_f32(v[2 * i], v[2 * i + 1], H[i], lo[2 * i], lo[2 * i + 1]);
+      H[i] = nl_hi2_f16_amax(v[2 * i], v[2 * i + 1], amax);
+      nl_lo2_f32(v[2 * i], v[2 * i + 1], H[i], lo[2 * i], lo[2 * i + 1]);
     }
     eb = __builtin_amdgcn_frexp_expf(amax) + 124;   // block scale as in tgemm_mx_kernel: the largest value lands in [4, 8)
     eb = eb < 12 ? 12 : (eb > 254 ? 254 : eb);
     const float scf = __builtin_bit_cast(float, eb << 23);
-    xh6 = tg_cvt_pk32_fp6_f16(H, scf);
-    const tg_f32x16 le = {lo[0], lo[2], lo[4], lo[6], lo[8], lo[10], lo[12], lo[14], lo[16], lo[18], lo[20], lo[22], lo[24], lo[26], lo[28], lo[30]};
-    const tg_f32x16 lod = {lo[1], lo[3], lo[5], lo[7], lo[9], lo[11], lo[13], lo[15], lo[17], lo[19], lo[21], lo[23], lo[25], lo[27], lo[29], lo[31]};
-    xl6 = tg_cvt_2xpk16_fp6_f32(le, lod, scf * 0.00048828125f);
+    xh6 = nl_cvt_pk32_fp6_f16(H, scf);
+    const nl_f32x16 le = {lo[0], lo[2], lo[4], lo[6], lo[8], lo[10], lo[12], lo[14], lo[16], lo[18], lo[20], lo[22], lo[24], lo[26], lo[28], lo[30]};
+    const nl_f32x16 lod = {lo[1], lo[3], lo[5], lo[7], lo[9], lo[11], lo[13], lo[15], lo[17], lo[19], lo[21], lo[23], lo[25], lo[27], lo[29], lo[31]};
+    xl6 = nl_cvt_2xpk16_fp6_f32(le, lod, scf * 0.00048828125f);
     }
-    const tg_i32x8 bh6 = {(int)xh6[0], (int)xh6[1], (int)xh6[2], (int)xh6[3], (int)xh6[4], (int)xh6[5], 0, 0};
-    const tg_i32x8 bl6 = {(int)xl6[0], (int)xl6[1], (int)xl6[2], (int)xl6[3], (int)xl6[4], (int)xl6[5], 0, 0};
+    const nl_i32x8 bh6 = {(int)xh6[0], (int)xh6[1], (int)xh6[2], (int)xh6[3], (int)xh6[4], (int)xh6[5], 0, 0};
+    const nl_i32x8 bl6 = {(int)xl6[0], (int)xl6[1], (int)xl6[2], (int)xl6[3], (int)xl6[4], (int)xl6[5], 0, 0};
     const int sxh = eb, sxl = eb - 11;
 
     // the next slab — of this group or the first of the next: weights into the other slot (every wave left it before the barrier that ended the previous iteration;
@@ -1005,10 +937,10 @@ __global__ __launch_bounds__(64 * NW, 1) void feat_comp_mx_kernel(const float* _
     load_act(Pnx, nsl);
 
     // ---- the slab's product, weights read two units ahead (tgemm_mx_kernel); operands swapped: D[sample][channel]
-    const tg_u32x4* Lf = reinterpret_cast<const tg_u32x4*>(lds_all + (SL * TGMX_SLOT) / 16);
-    const tg_u32x4* La = reinterpret_cast<const tg_u32x4*>(lds_all + (SL * TGMX_SLOT + TGMX_F16B) / 16);
-    const tg_u32x4* Lb = reinterpret_cast<const tg_u32x4*>(lds_all + (SL * TGMX_SLOT + TGMX_F16B + TGMX_IMA) / 16);
-    tg_u32x4 ra[3], rb[3];
+    const nl_u32x4* Lf = reinterpret_cast<const nl_u32x4*>(lds_all + (SL * TGMX_SLOT) / 16);
+    const nl_u32x4* La = reinterpret_cast<const nl_u32x4*>(lds_all + (SL * TGMX_SLOT + TGMX_F16B) / 16);
+    const nl_u32x4* Lb = reinterpret_cast<const nl_u32x4*>(lds_all + (SL * TGMX_SLOT + TGMX_F16B + TGMX_IMA) / 16);
+    nl_u32x4 ra[3], rb[3];
     auto rdW = [&](auto Uc) __attribute__((always_inline)) {
       constexpr int u = decltype(Uc)::value, rt = u / 6, k = u % 6, r = u % 3;
       if constexpr (k < 4) ra[r] = Lf[(k * NRT + rt) * 64 + lane];
@@ -1016,23 +948,23 @@ __global__ __launch_bounds__(64 * NW, 1) void feat_comp_mx_kernel(const float* _
     };
     rdW(std::integral_constant<int, 0>{});
     rdW(std::integral_constant<int, 1>{});
-    tg_static_for<6 * NRT>([&](auto Uc) __attribute__((always_inline)) {
+    nl_static_for<6 * NRT>([&](auto Uc) __attribute__((always_inline)) {
       constexpr int u = decltype(Uc)::value, rt = u / 6, k = u % 6, r = u % 3;
       if constexpr (u + 2 < 6 * NRT) rdW(std::integral_constant<int, u + 2>{});
       if constexpr (k < 4) {
-        const tg_f16x8 af = __builtin_bit_cast(tg_f16x8, (tg_u32x4){H[4 * k], H[4 * k + 1], H[4 * k + 2], H[4 * k + 3]});
-        acc[rt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af, __builtin_bit_cast(tg_f16x8, ra[r]), acc[rt], 0, 0, 0);
+        const nl_f16x8 af = __builtin_bit_cast(nl_f16x8, (nl_u32x4){H[4 * k], H[4 * k + 1], H[4 * k + 2], H[4 * k + 3]});
+        acc[rt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af, __builtin_bit_cast(nl_f16x8, ra[r]), acc[rt], 0, 0, 0);
       } else {
-        const tg_i32x8 w6 = {(int)ra[r][0], (int)ra[r][1], (int)ra[r][2], (int)ra[r][3], (int)rb[r][0], (int)rb[r][1], 0, 0};
+        const nl_i32x8 w6 = {(int)ra[r][0], (int)ra[r][1], (int)ra[r][2], (int)ra[r][3], (int)rb[r][0], (int)rb[r][1], 0, 0};
         if constexpr (k == 4) acc[rt] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(bl6, w6, acc[rt], 2, 2, 0, sxl, 0, (int)rb[r][2]);   // a_lo6 x w_hi6
         else acc[rt] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(bh6, w6, acc[rt], 2, 2, 0, sxh, 0, (int)rb[r][2]);                     // a_hi6 x w_lo6
       }
       __builtin_amdgcn_sched_barrier(0);
     });
-    tg_wait_vmcnt<0>();
+    nl_wait_vmcnt<0>();
     __syncthreads();
   };
-  tg_static_for<NSC>([&](auto Gc) __attribute__((always_inline)) { slab(Gc); });
+  nl_static_for<NSC>([&](auto Gc) __attribute__((always_inline)) { slab(Gc); });
 
   // ---- epilogue.  Tile rt: lane (c, hh) holds channel 32 rt + c of the wave's rows m(r, hh) = (r & 3) + 8 (r >> 2) + 4 hh, r = 0 .. 15
   const float* wrow = wts + (size_t)tile_c * 32 + 4 * hh;
@@ -1147,7 +1079,7 @@ __global__ __launch_bounds__(64 * TGC1_NW, 4) void tgemm_conv1_kernel(const NlGe
     __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, (__attribute__((address_space(3))) void*)(lds_all + (slot * SLOTB) / 16 + pp * 64), 16, lane16, so, 0, 0);
   };
   auto stage = [&](auto Cc) __attribute__((always_inline)) {
-    tg_static_for<PPW>([&](auto Ic) __attribute__((always_inline)) { stage_piece(Cc, Ic); });
+    nl_static_for<PPW>([&](auto Ic) __attribute__((always_inline)) { stage_piece(Cc, Ic); });
   };
   // activations: three per-tap row pointers worked out once (tgemm_mx_kernel)
   const NlGemmSeg& g0 = a.seg[0];
@@ -1178,41 +1110,41 @@ __global__ __launch_bounds__(64 * TGC1_NW, 4) void tgemm_conv1_kernel(const NlGe
     raw[c % D][pc] = *(const float4*)(p + act_off(fr0, pc));
   };
 
-  tg_f32x16 acc[NRT];
+  nl_f32x16 acc[NRT];
 #pragma unroll
   for (int rt = 0; rt < NRT; ++rt)
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[rt][r] = 0.f;
 
   // prologue: chunks 0 .. D - 1 on their way
-  tg_static_for<D>([&](auto Cc) __attribute__((always_inline)) { stage(Cc); load_act(Cc); });
+  nl_static_for<D>([&](auto Cc) __attribute__((always_inline)) { stage(Cc); load_act(Cc); });
 
 #if defined(TG_TRACE) && defined(TG_TRACE_C1)   // (tools/tgmx_trace.py conv1, a -DTG_TRACE -DTG_TRACE_C1 build: phases of chunks 8 .. 13 of block 0, wave 0)
 #define TGC1_T(k) do { if (blockIdx.x == 0 && wave == 0 && g >= 8 && g < 14) { const unsigned long long t_ = __builtin_readcyclecounter(); if (lane == 0) tg_trace[5 * (g - 8) + (k)] = t_; } } while (0)
 #else
 #define TGC1_T(k)
 #endif
-  tg_static_for<NCH>([&](auto Gc) __attribute__((always_inline)) {
+  nl_static_for<NCH>([&](auto Gc) __attribute__((always_inline)) {
     constexpr int g = decltype(Gc)::value;
     TGC1_T(0);
     // chunk g has landed when at most the later chunks' operations are in flight (each chunk: PPW DMA pieces + 4 row loads per wave; vmcnt retires in order)
     constexpr int nlater = (g + D - 1 < NCH ? D - 1 : NCH - 1 - g);
     constexpr int later = nlater * (PPW + 4);
-    tg_wait_vmcnt<later>();
+    nl_wait_vmcnt<later>();
     TGC1_T(1);
     __syncthreads();   // every wave's pieces of chunk g are in LDS; every wave has left slot (g + D) % NB = (g - 1) % NB
     TGC1_T(2);
-    tg_bf16x8 bh[2], bl[2];
+    nl_bf16x8 bh[2], bl[2];
     {
       const float4 (&rw4)[4] = raw[g % D];
       if (fr0 == 1) {   // fragment image: [k-step 0: hi | lo | k-step 1: hi | lo] (wave-uniform branch around vector moves only)
-        bh[0] = __builtin_bit_cast(tg_bf16x8, rw4[0]); bl[0] = __builtin_bit_cast(tg_bf16x8, rw4[1]);
-        bh[1] = __builtin_bit_cast(tg_bf16x8, rw4[2]); bl[1] = __builtin_bit_cast(tg_bf16x8, rw4[3]);
+        bh[0] = __builtin_bit_cast(nl_bf16x8, rw4[0]); bl[0] = __builtin_bit_cast(nl_bf16x8, rw4[1]);
+        bh[1] = __builtin_bit_cast(nl_bf16x8, rw4[2]); bl[1] = __builtin_bit_cast(nl_bf16x8, rw4[3]);
       } else {
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) {
           const float v[8] = {rw4[2 * ks].x, rw4[2 * ks].y, rw4[2 * ks].z, rw4[2 * ks].w, rw4[2 * ks + 1].x, rw4[2 * ks + 1].y, rw4[2 * ks + 1].z, rw4[2 * ks + 1].w};
-          if constexpr (F16) tg_split8_f16(v, bh[ks], bl[ks]); else tg_split8<X3>(v, bh[ks], bl[ks]);
+          if constexpr (F16) tg_split8_f16(v, bh[ks], bl[ks]); else nl_split8<X3>(v, bh[ks], bl[ks]);
         }
       }
     }
@@ -1226,16 +1158,16 @@ __global__ __launch_bounds__(64 * TGC1_NW, 4) void tgemm_conv1_kernel(const NlGe
       }
     };
     TGC1_T(3);
-    const tg_bf16x8* L = reinterpret_cast<const tg_bf16x8*>(lds_all + ((g % NB) * SLOTB) / 16);
-    tg_static_for<2 * NRT>([&](auto Tc) __attribute__((always_inline)) {
+    const nl_bf16x8* L = reinterpret_cast<const nl_bf16x8*>(lds_all + ((g % NB) * SLOTB) / 16);
+    nl_static_for<2 * NRT>([&](auto Tc) __attribute__((always_inline)) {
         constexpr int tt = decltype(Tc)::value, ks = tt / NRT, rt = tt % NRT;
-        const tg_bf16x8 ah = L[((0 * 2 + ks) * NRT + rt) * 64 + lane];
+        const nl_bf16x8 ah = L[((0 * 2 + ks) * NRT + rt) * 64 + lane];
         if (X3) {
-          const tg_bf16x8 al = L[((1 * 2 + ks) * NRT + rt) * 64 + lane];
-          acc[rt] = tg_mfma<F16>(al, bh[ks], acc[rt]);
-          acc[rt] = tg_mfma<F16>(ah, bl[ks], acc[rt]);
+          const nl_bf16x8 al = L[((1 * 2 + ks) * NRT + rt) * 64 + lane];
+          acc[rt] = nl_mfma<F16>(al, bh[ks], acc[rt]);
+          acc[rt] = nl_mfma<F16>(ah, bl[ks], acc[rt]);
         }
-        acc[rt] = tg_mfma<F16>(ah, bh[ks], acc[rt]);
+        acc[rt] = nl_mfma<F16>(ah, bh[ks], acc[rt]);
         // two memory instructions behind each of the first matrix groups, then one (PPW + 4 = 5 or 6 of them over 2 NRT = 4 groups)
         mem_slot(std::integral_constant<int, (tt < 2 ? 2 * tt : 2 + tt)>{});
         if constexpr (tt < 2) mem_slot(std::integral_constant<int, 2 * tt + 1>{});
@@ -1401,7 +1333,7 @@ __global__ __launch_bounds__(256, 1) void sample_chain_kernel(const NlChainArgs 
   constexpr int NW = 4, PARTS = X3 ? 2 : 1, NCH = Geo::NCH, NB = 4;
   constexpr int SLOT16 = PARTS * 2 * 8 * 64;   // 16-B units per ring slot (sized for 8 row tiles)
   __shared__ uint4 lds_all[NB * SLOT16 + 4 * 64];
-  tg_bf16x8 (*ring)[SLOT16] = reinterpret_cast<tg_bf16x8 (*)[SLOT16]>(lds_all);
+  nl_bf16x8 (*ring)[SLOT16] = reinterpret_cast<nl_bf16x8 (*)[SLOT16]>(lds_all);
   float* stab = reinterpret_cast<float*>(lds_all + NB * SLOT16);   // gamma | beta | feat_mlp.0 bias | out_fc.2 bias
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int hh = lane >> 5, j = lane & 31;
@@ -1429,7 +1361,7 @@ __global__ __launch_bounds__(256, 1) void sample_chain_kernel(const NlChainArgs 
     constexpr int c = Geo::cm(decltype(Cc)::value), kd = Geo::kind(c), nrt = Geo::nrt(c);
     unsigned so = (kd == CK_FC ? a.off_fc : kd == CK_F0 ? a.off_f0 : kd == CK_BL ? a.off_ba : kd == CK_G2 ? a.off_g2 : a.off_q) +
                   (unsigned)(Geo::idx(c) * 4 * nrt * 1024);
-    tg_static_for<ppw(c)>([&](auto Ic) __attribute__((always_inline)) {
+    nl_static_for<ppw(c)>([&](auto Ic) __attribute__((always_inline)) {
       constexpr int i = decltype(Ic)::value;
       // (the blend projection's ring chunk = four 8-KB k-chunks [hi 4 KB | lo 4 KB]: contiguous in three-term mode; single-bf16 mode takes the four hi parts)
       //  w_qs's ring chunk = two 16-KB k-chunks [hi 8 KB | lo 8 KB]: likewise)
@@ -1439,11 +1371,11 @@ __global__ __launch_bounds__(256, 1) void sample_chain_kernel(const NlChainArgs 
     });
   };
 
-  tg_f32x16 acc[8];
-  tg_f32x16 qacc[QUERY ? 4 : 1];           // query: w_qs accumulates beside G, whose row tiles are converted while it runs
-  tg_bf16x8 Xh[16], Xl[16];
-  tg_f32x4 oraw[QUERY ? 1 : 16];           // attention output rows: fc's B operand, 8 k-steps x 8 floats per lane
-  tg_f32x4 traw[8];                        // out_fc hidden rows: out_fc.2's B operand, 4 k-steps x 8 floats per lane
+  nl_f32x16 acc[8];
+  nl_f32x16 qacc[QUERY ? 4 : 1];           // query: w_qs accumulates beside G, whose row tiles are converted while it runs
+  nl_bf16x8 Xh[16], Xl[16];
+  nl_f32x4 oraw[QUERY ? 1 : 16];           // attention output rows: fc's B operand, 8 k-steps x 8 floats per lane
+  nl_f32x4 traw[8];                        // out_fc hidden rows: out_fc.2's B operand, 4 k-steps x 8 floats per lane
   float fa[QUERY ? 4 : 8][16];             // rows waiting for their scheduled stores (chain: feature_agg, then feat_mlp.0's output; query: Q)
   auto row_of = [&](int t, int& m, int& mm, bool& mok) __attribute__((always_inline)) {
     m = t * 128 + 32 * wave + j;
@@ -1452,15 +1384,15 @@ __global__ __launch_bounds__(256, 1) void sample_chain_kernel(const NlChainArgs 
   };
   // (the indices below are compile-time constants after unrolling: every caller sits in an unrolled loop or a static_for)
   auto load_traw = [&](int i, int mm) __attribute__((always_inline)) {
-    traw[i] = *reinterpret_cast<const tg_f32x4*>(a.T64 + (size_t)mm * 64 + 8 * hh + 16 * (i >> 1) + 4 * (i & 1));
+    traw[i] = *reinterpret_cast<const nl_f32x4*>(a.T64 + (size_t)mm * 64 + 8 * hh + 16 * (i >> 1) + 4 * (i & 1));
   };
   auto load_oraw = [&](int i, int mm) __attribute__((always_inline)) {
-    oraw[i % (QUERY ? 1 : 16)] = *reinterpret_cast<const tg_f32x4*>(a.O + (size_t)mm * 128 + 8 * hh + 16 * (i >> 1) + 4 * (i & 1));
+    oraw[i % (QUERY ? 1 : 16)] = *reinterpret_cast<const nl_f32x4*>(a.O + (size_t)mm * 128 + 8 * hh + 16 * (i >> 1) + 4 * (i & 1));
   };
   // row store q (0..31 | 0..15) of `fa`: 16 B of row tile q / 4 at columns 8 (q % 4) + 4 hh
   auto store_fa = [&](int q, __amdgpu_buffer_rsrc_t rsrc, unsigned rowoff) __attribute__((always_inline)) {
     const int rt = q >> 2, gq = q & 3, rtc = rt % (QUERY ? 4 : 8);
-    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(tg_u32x4, tg_f32x4{fa[rtc][4 * gq], fa[rtc][4 * gq + 1], fa[rtc][4 * gq + 2], fa[rtc][4 * gq + 3]}), rsrc,
+    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(nl_u32x4, nl_f32x4{fa[rtc][4 * gq], fa[rtc][4 * gq + 1], fa[rtc][4 * gq + 2], fa[rtc][4 * gq + 3]}), rsrc,
                                            rowoff + (32 * rt + 8 * gq) * 4, 0, 0);
   };
 
@@ -1469,21 +1401,21 @@ __global__ __launch_bounds__(256, 1) void sample_chain_kernel(const NlChainArgs 
   auto store_FA = [&](int q, unsigned rowoff) __attribute__((always_inline)) {
     if constexpr (FRAGOUT) {
       const int rt = q >> 2, w = q & 3, sI = w & 1, part = w >> 1;
-      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(tg_u32x4, part ? Xl[2 * rt + sI] : Xh[2 * rt + sI]), rFA,
+      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(nl_u32x4, part ? Xl[2 * rt + sI] : Xh[2 * rt + sI]), rFA,
                                              fragoff + (unsigned)(((2 * rt + sI) * 2 + part) * 1024), 0, 0);
     } else store_fa(q, rFA, rowoff);
   };
   // one chunk (32 k): 2 k-steps x NRT row tiles x (3 | 1) MFMAs out of ring slot `slot`; filler(step) runs between the MFMA groups
-  auto compute = [&](auto Nc, int slot, const tg_bf16x8 (&bh)[2], const tg_bf16x8 (&bl)[2], auto& dst, auto&& filler, int sub = 0) __attribute__((always_inline)) {
+  auto compute = [&](auto Nc, int slot, const nl_bf16x8 (&bh)[2], const nl_bf16x8 (&bl)[2], auto& dst, auto&& filler, int sub = 0) __attribute__((always_inline)) {
     constexpr int NRT = decltype(Nc)::value, nt = 2 * NRT;
     constexpr bool F16 = F16FRAG && NRT == 2;   // the blend projection (the only two-row-tile product of the chain program) on the split-FP16 rows
-    const tg_bf16x8* L = ring[slot] + sub * (PARTS * 2 * NRT * 64);   // sub: the k-chunk inside a ring chunk that carries several (the blend projection's four)
-    auto ldA = [&](int tt, tg_bf16x8& ah, tg_bf16x8& al) __attribute__((always_inline)) {
+    const nl_bf16x8* L = ring[slot] + sub * (PARTS * 2 * NRT * 64);   // sub: the k-chunk inside a ring chunk that carries several (the blend projection's four)
+    auto ldA = [&](int tt, nl_bf16x8& ah, nl_bf16x8& al) __attribute__((always_inline)) {
       const int ks = tt / NRT, rt = tt - ks * NRT;
       ah = L[((0 * 2 + ks) * NRT + rt) * 64 + lane];
       if (X3) al = L[((1 * 2 + ks) * NRT + rt) * 64 + lane];
     };
-    tg_bf16x8 ah[3], al[3];
+    nl_bf16x8 ah[3], al[3];
     ldA(0, ah[0], al[0]);
     ldA(1, ah[1], al[1]);
 #pragma unroll
@@ -1491,9 +1423,9 @@ __global__ __launch_bounds__(256, 1) void sample_chain_kernel(const NlChainArgs 
       if (tt + 2 < nt) ldA(tt + 2, ah[(tt + 2) % 3], al[(tt + 2) % 3]);
       const int ks = tt / NRT, rt = tt - ks * NRT;
       if constexpr (F16) {
-        dst[rt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(tg_f16x8, al[tt % 3]), __builtin_bit_cast(tg_f16x8, bh[ks]), dst[rt], 0, 0, 0);
-        dst[rt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(tg_f16x8, ah[tt % 3]), __builtin_bit_cast(tg_f16x8, bl[ks]), dst[rt], 0, 0, 0);
-        dst[rt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(tg_f16x8, ah[tt % 3]), __builtin_bit_cast(tg_f16x8, bh[ks]), dst[rt], 0, 0, 0);
+        dst[rt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(nl_f16x8, al[tt % 3]), __builtin_bit_cast(nl_f16x8, bh[ks]), dst[rt], 0, 0, 0);
+        dst[rt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(nl_f16x8, ah[tt % 3]), __builtin_bit_cast(nl_f16x8, bl[ks]), dst[rt], 0, 0, 0);
+        dst[rt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(nl_f16x8, ah[tt % 3]), __builtin_bit_cast(nl_f16x8, bh[ks]), dst[rt], 0, 0, 0);
       } else {
       if (X3) {
         dst[rt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[tt % 3], bh[ks], dst[rt], 0, 0, 0);
@@ -1519,7 +1451,7 @@ __global__ __launch_bounds__(256, 1) void sample_chain_kernel(const NlChainArgs 
       const int sI = step - 4;
       const float u[8] = {acc[rt][8 * sI], acc[rt][8 * sI + 1], acc[rt][8 * sI + 2], acc[rt][8 * sI + 3],
                           acc[rt][8 * sI + 4], acc[rt][8 * sI + 5], acc[rt][8 * sI + 6], acc[rt][8 * sI + 7]};
-      tg_split8<X3>(u, Xh[2 * rt + sI], Xl[2 * rt + sI]);
+      nl_split8<X3>(u, Xh[2 * rt + sI], Xl[2 * rt + sI]);
     } else if (QUERY && step == 6) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[rt][r] = 0.f;
@@ -1553,7 +1485,7 @@ __global__ __launch_bounds__(256, 1) void sample_chain_kernel(const NlChainArgs 
   int trace_it = 0;
 #endif
   unsigned prev_row = DROP;   // byte offset of this lane's row in the previous tile's deferred stores
-  tg_wait_vmcnt<0>();   // the first pass of the counted waits below assumes nothing older is in flight
+  nl_wait_vmcnt<0>();   // the first pass of the counted waits below assumes nothing older is in flight
   __syncthreads();      // stab
 
   for (;;) {
@@ -1562,12 +1494,12 @@ __global__ __launch_bounds__(256, 1) void sample_chain_kernel(const NlChainArgs 
     row_of(tile_next < ntiles ? tile_next : tile, m_n, mm_n, mok_n);
     const unsigned row1k = mok_c ? (unsigned)m_c * 1024u + 16u * hh : DROP;   // this lane's row in the (N, 256) outputs
     fragoff = (unsigned)(tile * 4 + wave) * 32768u + (unsigned)lane * 16u;
-    tg_static_for<NCH>([&](auto Cc) __attribute__((always_inline)) {
+    nl_static_for<NCH>([&](auto Cc) __attribute__((always_inline)) {
       constexpr int c = decltype(Cc)::value, kd = Geo::kind(c), g = Geo::idx(c);
       // chunk c must have landed: younger operations are the pieces of chunks c+1, c+2 and the other traffic issued since chunk c-3
       constexpr int younger = ppw(c + 1) + ppw(c + 2) + Geo::post(c - 3, FEAT) + Geo::post(c - 2, FEAT) + Geo::post(c - 1, FEAT);
       CHAIN_T(0);
-      tg_wait_vmcnt<(younger < 63 ? younger : 63)>();
+      nl_wait_vmcnt<(younger < 63 ? younger : 63)>();
       __builtin_amdgcn_s_barrier();
       CHAIN_T(1);
       dma_chunk(std::integral_constant<int, c + 3>{});   // its slot held chunk c-1, which every wave has left
@@ -1603,15 +1535,15 @@ __global__ __launch_bounds__(256, 1) void sample_chain_kernel(const NlChainArgs 
       auto mem_fill = [&](int tt) __attribute__((always_inline)) { if ((tt & 3) == 1) mem_op(tt >> 2); };
       __builtin_amdgcn_sched_barrier(0);
 
-      tg_bf16x8 bh[2], bl[2];
+      nl_bf16x8 bh[2], bl[2];
       if constexpr (kd == CK_FC || kd == CK_G2) {
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) {
-          tg_f32x4 u0, u1;
+          nl_f32x4 u0, u1;
           if constexpr (kd == CK_FC) { u0 = oraw[(4 * g + 2 * ks) % (QUERY ? 1 : 16)]; u1 = oraw[(4 * g + 2 * ks + 1) % (QUERY ? 1 : 16)]; }
           else { u0 = traw[4 * g + 2 * ks]; u1 = traw[4 * g + 2 * ks + 1]; }
           const float v[8] = {u0[0], u0[1], u0[2], u0[3], u1[0], u1[1], u1[2], u1[3]};
-          tg_split8<X3>(v, bh[ks], bl[ks]);
+          nl_split8<X3>(v, bh[ks], bl[ks]);
         }
         compute(I8{}, c % NB, bh, bl, acc, mem_fill);
       } else if constexpr (kd != CK_NOP) {
@@ -1628,7 +1560,7 @@ __global__ __launch_bounds__(256, 1) void sample_chain_kernel(const NlChainArgs 
           }
         }
         else {   // w_qs: the two k-chunks of this ring chunk; k-chunk gq multiplies G's row tile gq, row tile gq + 1 is converted between its MFMAs
-          tg_static_for<2>([&](auto Sc) __attribute__((always_inline)) {
+          nl_static_for<2>([&](auto Sc) __attribute__((always_inline)) {
             constexpr int sub = decltype(Sc)::value, gq = 2 * g + sub;
             bh[0] = Xh[2 * gq]; bh[1] = Xh[2 * gq + 1]; bl[0] = Xl[2 * gq]; bl[1] = Xl[2 * gq + 1];
             compute(I4{}, c % NB, bh, bl, qacc, [&](int tt) __attribute__((always_inline)) {
@@ -1644,7 +1576,7 @@ __global__ __launch_bounds__(256, 1) void sample_chain_kernel(const NlChainArgs 
 #pragma unroll
           for (int step = 0; step < 7; ++step) g2_epilogue_step(I0{}, step);
         } else {   // G stays in the accumulators: fc continues on it (the residual of ibrnet.py:112)
-          tg_static_for<8>([&](auto Rt) __attribute__((always_inline)) {
+          nl_static_for<8>([&](auto Rt) __attribute__((always_inline)) {
 #pragma unroll
             for (int step = 0; step < 4; ++step) g2_epilogue_step(Rt, step);
             if constexpr (FEAT) store_fa(8 + decltype(Rt)::value, rFT, prev_row);
@@ -1688,7 +1620,7 @@ __global__ __launch_bounds__(256, 1) void sample_chain_kernel(const NlChainArgs 
 #pragma unroll
           for (int sI = 0; sI < 2; ++sI) {   // accumulator registers 8 s .. 8 s + 7 of row tile rt = k-step 2 rt + s in accumulator order
             const float u[8] = {v[8 * sI], v[8 * sI + 1], v[8 * sI + 2], v[8 * sI + 3], v[8 * sI + 4], v[8 * sI + 5], v[8 * sI + 6], v[8 * sI + 7]};
-            if constexpr (F16FRAG) tg_split8_f16_pk(u, Xh[2 * rt + sI], Xl[2 * rt + sI]); else tg_split8<X3>(u, Xh[2 * rt + sI], Xl[2 * rt + sI]);
+            if constexpr (F16FRAG) tg_split8_f16_pk(u, Xh[2 * rt + sI], Xl[2 * rt + sI]); else nl_split8<X3>(u, Xh[2 * rt + sI], Xl[2 * rt + sI]);
           }
 #pragma unroll
           for (int r = 0; r < 16; ++r) acc[rt][r] = 0.f;
@@ -1723,7 +1655,7 @@ __global__ __launch_bounds__(256, 1) void sample_chain_kernel(const NlChainArgs 
         const unsigned brow = mok_c ? (unsigned)m_c * 128u + 16u * hh : DROP;
 #pragma unroll
         for (int gq = 0; gq < 4; ++gq)
-          __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(tg_u32x4, tg_f32x4{acc[0][4 * gq], acc[0][4 * gq + 1], acc[0][4 * gq + 2], acc[0][4 * gq + 3]}), rBL,
+          __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(nl_u32x4, nl_f32x4{acc[0][4 * gq], acc[0][4 * gq + 1], acc[0][4 * gq + 2], acc[0][4 * gq + 3]}), rBL,
                                                  brow + 32 * gq, 0, 0);
         zero_acc(I0{}, I2{});
       }
@@ -1751,7 +1683,7 @@ __global__ __launch_bounds__(256, 1) void sample_chain_kernel(const NlChainArgs 
 #pragma unroll
     for (int q = 8; q < 32; ++q) store_fa(q, rFT, prev_row);
   }
-  tg_wait_vmcnt<0>();   // LDS-DMA prefetched past the last tile must land before the LDS goes to another workgroup
+  nl_wait_vmcnt<0>();   // LDS-DMA prefetched past the last tile must land before the LDS goes to another workgroup
 }
 
 }  // namespace

@@ -19,28 +19,10 @@
 //     form), ELU, MaxPool over neighbouring lanes (DPP), bf16 hi / lo split and the store into the next layer's planes in the epilogue.
 // Same products in the same order as the tgemm launches they replace (same weight streams, same three-term split, k ascending): the results
 // differ only by the summation order of the LayerNorm statistics.
-#include <utility>
 #include "common.h"
-
-typedef __bf16 ui_bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 ui_bf16x4 __attribute__((ext_vector_type(4)));
-typedef float ui_f32x16 __attribute__((ext_vector_type(16)));
-typedef float ui_f32x2 __attribute__((ext_vector_type(2)));
-// The epilogue's element-wise arithmetic runs on pairs (v_pk_add_f32 / v_pk_mul_f32: the same operations in the same order per element, half the instructions).
-// ELU of a pair (nl_elu_fast per element; the scale by log2(e) and the -1 packed)
-__device__ __forceinline__ ui_f32x2 ui_elu2(ui_f32x2 x) {
-  const ui_f32x2 y = x * ui_f32x2{1.4426950408889634f, 1.4426950408889634f};
-  ui_f32x2 e = {__builtin_amdgcn_exp2f(y[0]), __builtin_amdgcn_exp2f(y[1])};
-  e = e - ui_f32x2{1.f, 1.f};
-  return ui_f32x2{__builtin_amdgcn_fmed3f(x[0], e[0], 0.f), __builtin_amdgcn_fmed3f(x[1], e[1], 0.f)};
-}
+#include "mfma.h"
 
 namespace {
-
-template <int... Is, class F>
-__device__ __forceinline__ void ui_static_for_impl(std::integer_sequence<int, Is...>, F&& f) { (f(std::integral_constant<int, Is>{}), ...); }
-template <int N, class F>
-__device__ __forceinline__ void ui_static_for(F&& f) { ui_static_for_impl(std::make_integer_sequence<int, N>{}, static_cast<F&&>(f)); }
 
 // ---- LDS map (bytes).  Geometry A: 64 channels, 64 positions (c1, x1); geometry B: 128 channels, 32 positions (c2, x0); c3: 128 channels, 16 positions.
 constexpr int STR64 = 2 * 64 + 16, STR128 = 2 * 128 + 16;
@@ -140,31 +122,31 @@ __global__ __launch_bounds__(512, 1) void unet_inner_kernel(const NlUnetInnerArg
     const float f[4] = {v.x, v.y, v.z, v.w};
     unsigned hw[2], lw[2];
     nl_split_bf16_pair(f[0], f[1], hw[0], lw[0]); nl_split_bf16_pair(f[2], f[3], hw[1], lw[1]);
-    const ui_bf16x4 h = __builtin_bit_cast(ui_bf16x4, make_uint2(hw[0], hw[1])), l = __builtin_bit_cast(ui_bf16x4, make_uint2(lw[0], lw[1]));
+    const nl_bf16x4 h = __builtin_bit_cast(nl_bf16x4, make_uint2(hw[0], hw[1])), l = __builtin_bit_cast(nl_bf16x4, make_uint2(lw[0], lw[1]));
     char* dst = lds + OFF_C1 + (ray * 2) * PL_C1 + (row + 1) * STR64 + 8 * c4;
-    *reinterpret_cast<ui_bf16x4*>(dst) = h;
-    if (X3) *reinterpret_cast<ui_bf16x4*>(dst + PL_C1) = l;
+    *reinterpret_cast<nl_bf16x4*>(dst) = h;
+    if (X3) *reinterpret_cast<nl_bf16x4*>(dst + PL_C1) = l;
   }
 
   float* const red = reinterpret_cast<float*>(lds + OFF_RED);   // [2 statistics][8 waves][2 rays]
 
-  ui_bf16x8 wreg[DEPTH][4];   // [ring slot][hi ks0, hi ks1, lo ks0, lo ks1]
+  nl_bf16x8 wreg[DEPTH][4];   // [ring slot][hi ks0, hi ks1, lo ks0, lo ks1]
   // weight fragments of chunk c of layer LT for this wave's column tile
-  auto load_w = [&](auto LT, int c, int ct, ui_bf16x8 (&w)[4]) __attribute__((always_inline)) {
+  auto load_w = [&](auto LT, int c, int ct, nl_bf16x8 (&w)[4]) __attribute__((always_inline)) {
     using L = Lyr<decltype(LT)::value>;
-    const ui_bf16x8* src = reinterpret_cast<const ui_bf16x8*>(a.w[decltype(LT)::value]) + (size_t)c * (4 * L::NRT * 64) + ct * 64 + lane;
+    const nl_bf16x8* src = reinterpret_cast<const nl_bf16x8*>(a.w[decltype(LT)::value]) + (size_t)c * (4 * L::NRT * 64) + ct * 64 + lane;
     w[0] = src[(0 * 2 + 0) * L::NRT * 64];
     w[1] = src[(0 * 2 + 1) * L::NRT * 64];
     if (X3) { w[2] = src[(1 * 2 + 0) * L::NRT * 64]; w[3] = src[(1 * 2 + 1) * L::NRT * 64]; }
   };
   {   // the first layer's first chunks are on their way while c1 is staged
     const int ct0 = wave % Lyr<0>::NRT;
-    ui_static_for<DEPTH>([&](auto C) __attribute__((always_inline)) { load_w(std::integral_constant<int, 0>{}, decltype(C)::value, ct0, wreg[decltype(C)::value]); });
+    nl_static_for<DEPTH>([&](auto C) __attribute__((always_inline)) { load_w(std::integral_constant<int, 0>{}, decltype(C)::value, ct0, wreg[decltype(C)::value]); });
   }
   __syncthreads();
   UI_T(1);
 
-  ui_static_for<5>([&](auto LT) __attribute__((always_inline)) {
+  nl_static_for<5>([&](auto LT) __attribute__((always_inline)) {
     constexpr int ID = decltype(LT)::value;
     using L = Lyr<ID>;
     constexpr int RTP = 2 * L::LI / 32;          // row tiles of the pair
@@ -182,7 +164,7 @@ __global__ __launch_bounds__(512, 1) void unet_inner_kernel(const NlUnetInnerArg
       rayl[ti] = p / L::LI; tl[ti] = p % L::LI;
       rowbase[ti] = (unsigned)(rayl[ti] * 2 * slab_pl(s0) + (tl[ti] + 1) * slab_str(s0) + 16 * hh);
     }
-    ui_f32x16 acc[TPW];
+    nl_f32x16 acc[TPW];
 #pragma unroll
     for (int ti = 0; ti < TPW; ++ti)
 #pragma unroll
@@ -201,8 +183,8 @@ __global__ __launch_bounds__(512, 1) void unet_inner_kernel(const NlUnetInnerArg
       for (int gq = 0; gq < 4; ++gq) { gpre[ti][gq] = *reinterpret_cast<const float4*>(gp + gq * 256); bpre[ti][gq] = *reinterpret_cast<const float4*>(bp + gq * 256); }
     }
     // ---- the product: chunk by chunk, the weight ring DEPTH chunks ahead, the B fragments one chunk ahead
-    ui_bf16x8 bfr[2][2][TPW][2];   // [buffer][k-step][tile][hi | lo]
-    auto load_b = [&](auto C, ui_bf16x8 (&dst)[2][TPW][2]) __attribute__((always_inline)) {
+    nl_bf16x8 bfr[2][2][TPW][2];   // [buffer][k-step][tile][hi | lo]
+    auto load_b = [&](auto C, nl_bf16x8 (&dst)[2][TPW][2]) __attribute__((always_inline)) {
       constexpr int c = decltype(C)::value;
       constexpr int s = L::src(c);
       static_assert(slab_str(s) == slab_str(s0) && slab_pl(s) == slab_pl(s0), "the slabs of one layer share a geometry");
@@ -212,17 +194,17 @@ __global__ __launch_bounds__(512, 1) void unet_inner_kernel(const NlUnetInnerArg
 #pragma unroll
         for (int ti = 0; ti < TPW; ++ti) {
           const char* bp = lds + rowbase[ti] + (cbase + 32 * ks);
-          dst[ks][ti][0] = *reinterpret_cast<const ui_bf16x8*>(bp);
-          if (X3) dst[ks][ti][1] = *reinterpret_cast<const ui_bf16x8*>(bp + slab_pl(s));
+          dst[ks][ti][0] = *reinterpret_cast<const nl_bf16x8*>(bp);
+          if (X3) dst[ks][ti][1] = *reinterpret_cast<const nl_bf16x8*>(bp + slab_pl(s));
         }
     };
     load_b(std::integral_constant<int, 0>{}, bfr[0]);
-    ui_static_for<L::NCH>([&](auto C) __attribute__((always_inline)) {
+    nl_static_for<L::NCH>([&](auto C) __attribute__((always_inline)) {
       constexpr int c = decltype(C)::value;
       constexpr int slot = (c + ring_phase(ID)) % DEPTH;
-      const ui_bf16x8 (&w)[4] = wreg[slot];
+      const nl_bf16x8 (&w)[4] = wreg[slot];
       if constexpr (c + 1 < L::NCH) load_b(std::integral_constant<int, c + 1>{}, bfr[(c + 1) & 1]);
-      const ui_bf16x8 (&b)[2][TPW][2] = bfr[c & 1];
+      const nl_bf16x8 (&b)[2][TPW][2] = bfr[c & 1];
 #pragma unroll
       for (int ks = 0; ks < 2; ++ks) {
 #pragma unroll
@@ -254,10 +236,10 @@ __global__ __launch_bounds__(512, 1) void unet_inner_kernel(const NlUnetInnerArg
 #pragma unroll
       for (int gq = 0; gq < 4; ++gq) {
         const float4 b4 = bias4[gq];
-        const ui_f32x2 p0 = ui_f32x2{acc[ti][4 * gq + 0], acc[ti][4 * gq + 1]} + ui_f32x2{b4.x, b4.y};
-        const ui_f32x2 p1 = ui_f32x2{acc[ti][4 * gq + 2], acc[ti][4 * gq + 3]} + ui_f32x2{b4.z, b4.w};
+        const nl_f32x2 p0 = nl_f32x2{acc[ti][4 * gq + 0], acc[ti][4 * gq + 1]} + nl_f32x2{b4.x, b4.y};
+        const nl_f32x2 p1 = nl_f32x2{acc[ti][4 * gq + 2], acc[ti][4 * gq + 3]} + nl_f32x2{b4.z, b4.w};
         acc[ti][4 * gq + 0] = p0[0]; acc[ti][4 * gq + 1] = p0[1]; acc[ti][4 * gq + 2] = p1[0]; acc[ti][4 * gq + 3] = p1[1];
-        const ui_f32x2 q = p0 + p1;
+        const nl_f32x2 q = p0 + p1;
         s += q[0] + q[1];
       }
       s1[0] += rayl[ti] == 0 ? s : 0.f;
@@ -276,10 +258,10 @@ __global__ __launch_bounds__(512, 1) void unet_inner_kernel(const NlUnetInnerArg
 #pragma unroll
     for (int ti = 0; ti < TPW; ++ti) {
       const float m = rayl[ti] == 0 ? mean[0] : mean[1];
-      ui_f32x2 sp = {0.f, 0.f};
-      const ui_f32x2 mm = {m, m};
+      nl_f32x2 sp = {0.f, 0.f};
+      const nl_f32x2 mm = {m, m};
 #pragma unroll
-      for (int r = 0; r < 16; r += 2) { const ui_f32x2 d = ui_f32x2{acc[ti][r], acc[ti][r + 1]} - mm; sp += d * d; }
+      for (int r = 0; r < 16; r += 2) { const nl_f32x2 d = nl_f32x2{acc[ti][r], acc[ti][r + 1]} - mm; sp += d * d; }
       const float s = sp[0] + sp[1];
       s2[0] += rayl[ti] == 0 ? s : 0.f;
       s2[1] += rayl[ti] == 0 ? 0.f : s;
@@ -305,9 +287,9 @@ __global__ __launch_bounds__(512, 1) void unet_inner_kernel(const NlUnetInnerArg
 #pragma unroll
       for (int gq = 0; gq < 4; ++gq) {
         const float4 g4 = gpre[ti][gq], be4 = bpre[ti][gq];
-        const ui_f32x2 mm = {m, m}, rr = {rs, rs};
-        const ui_f32x2 p0 = ui_elu2((ui_f32x2{acc[ti][4 * gq + 0], acc[ti][4 * gq + 1]} - mm) * rr * ui_f32x2{g4.x, g4.y} + ui_f32x2{be4.x, be4.y});
-        const ui_f32x2 p1 = ui_elu2((ui_f32x2{acc[ti][4 * gq + 2], acc[ti][4 * gq + 3]} - mm) * rr * ui_f32x2{g4.z, g4.w} + ui_f32x2{be4.z, be4.w});
+        const nl_f32x2 mm = {m, m}, rr = {rs, rs};
+        const nl_f32x2 p0 = nl_elu_fast2((nl_f32x2{acc[ti][4 * gq + 0], acc[ti][4 * gq + 1]} - mm) * rr * nl_f32x2{g4.x, g4.y} + nl_f32x2{be4.x, be4.y});
+        const nl_f32x2 p1 = nl_elu_fast2((nl_f32x2{acc[ti][4 * gq + 2], acc[ti][4 * gq + 3]} - mm) * rr * nl_f32x2{g4.z, g4.w} + nl_f32x2{be4.z, be4.w});
         float v[4] = {p0[0], p0[1], p1[0], p1[1]};
         if constexpr (L::POOL) {   // positions 2 p, 2 p + 1 are neighbouring lanes
 #pragma unroll
@@ -325,11 +307,11 @@ __global__ __launch_bounds__(512, 1) void unet_inner_kernel(const NlUnetInnerArg
           if (!L::POOL || !(j & 1)) {
             unsigned hw[2], lw[2];
             nl_split_bf16_pair(v[0], v[1], hw[0], lw[0]); nl_split_bf16_pair(v[2], v[3], hw[1], lw[1]);
-            const ui_bf16x4 h = __builtin_bit_cast(ui_bf16x4, make_uint2(hw[0], hw[1])), l = __builtin_bit_cast(ui_bf16x4, make_uint2(lw[0], lw[1]));
+            const nl_bf16x4 h = __builtin_bit_cast(nl_bf16x4, make_uint2(hw[0], hw[1])), l = __builtin_bit_cast(nl_bf16x4, make_uint2(lw[0], lw[1]));
             constexpr int so = L::OUT >= 0 ? L::OUT : 0;
             char* dst = lds + slab_off(so) + (rayl[ti] * 2) * slab_pl(so) + (pos + 1) * slab_str(so) + 2 * ch;
-            *reinterpret_cast<ui_bf16x4*>(dst) = h;
-            if (X3) *reinterpret_cast<ui_bf16x4*>(dst + slab_pl(so)) = l;
+            *reinterpret_cast<nl_bf16x4*>(dst) = h;
+            if (X3) *reinterpret_cast<nl_bf16x4*>(dst + slab_pl(so)) = l;
           }
         }
       }

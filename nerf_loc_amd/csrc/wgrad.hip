@@ -19,9 +19,7 @@
 // Convolutions over the samples of a ray (k = 3) are three such products with X shifted by -1 / 0 / +1 rows inside each ray
 // (`shift`, `period`: rows whose neighbour falls outside the ray read zero) and an output stride (gW[m][n * cs + co]).
 #include "common.h"
-
-typedef __bf16 wg_bf16x8 __attribute__((ext_vector_type(8)));
-typedef float wg_f32x16 __attribute__((ext_vector_type(16)));
+#include "mfma.h"
 
 namespace {
 
@@ -42,9 +40,8 @@ struct WgArgs {
 };
 
 __device__ __forceinline__ void wg_split(const float (&v)[8], uint4& hi, uint4& lo) {
-  wg_bf16x8 h, l;
-#pragma unroll
-  for (int t = 0; t < 8; ++t) { const __bf16 b = (__bf16)v[t]; h[t] = b; l[t] = (__bf16)(v[t] - (float)b); }
+  nl_bf16x8 h, l;
+  nl_split8_elem(v, h, l);
   hi = __builtin_bit_cast(uint4, h); lo = __builtin_bit_cast(uint4, l);
 }
 
@@ -101,10 +98,10 @@ __global__ __launch_bounds__(256) void wgrad_kernel(const WgArgs a) {
   };
   // fragment of LDS column `col` (0..255), k-group kgi
   auto frag = [&](int col, int kgi, int plane) {
-    return __builtin_bit_cast(wg_bf16x8, *(const uint4*)(lds + plane * WG_PLANE + kgi * WG_KG + (col & 3) * WG_S + (col >> 2) * 16));
+    return __builtin_bit_cast(nl_bf16x8, *(const uint4*)(lds + plane * WG_PLANE + kgi * WG_KG + (col & 3) * WG_S + (col >> 2) * 16));
   };
   const int wm = wave >> 1, wn = wave & 1, hh = lane >> 5, i = lane & 31;
-  wg_f32x16 acc[2][2];
+  nl_f32x16 acc[2][2];
 #pragma unroll
   for (int x = 0; x < 2; ++x)
 #pragma unroll
@@ -120,7 +117,7 @@ __global__ __launch_bounds__(256) void wgrad_kernel(const WgArgs a) {
     if (r0 + 32 < r_end) fetch(r0 + 32);
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
-      wg_bf16x8 ah[2], al[2], bh[2], bl[2];
+      nl_bf16x8 ah[2], al[2], bh[2], bl[2];
 #pragma unroll
       for (int x = 0; x < 2; ++x) {
         ah[x] = frag(wm * 64 + x * 32 + i, 2 * s + hh, 0); al[x] = frag(wm * 64 + x * 32 + i, 2 * s + hh, 1);
@@ -212,10 +209,10 @@ __global__ __launch_bounds__(256) void wgrad_small_kernel(const WgArgs a) {
     }
   };
   auto frag = [&](int col, int kgi, int plane) {
-    return __builtin_bit_cast(wg_bf16x8, *(const uint4*)(lds + plane * WS_PLANE + kgi * WS_KG + (col & 3) * WS_S + (col >> 2) * 16));
+    return __builtin_bit_cast(nl_bf16x8, *(const uint4*)(lds + plane * WS_PLANE + kgi * WS_KG + (col & 3) * WS_S + (col >> 2) * 16));
   };
   const int hh = lane >> 5, i = lane & 31;
-  wg_f32x16 acc;
+  nl_f32x16 acc;
 #pragma unroll
   for (int r = 0; r < 16; ++r) acc[r] = 0.f;
   if (r_begin < r_end) fetch(r_begin);
@@ -227,7 +224,7 @@ __global__ __launch_bounds__(256) void wgrad_small_kernel(const WgArgs a) {
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
       const int kgi = 4 * wave + 2 * s + hh;
-      const wg_bf16x8 ah = frag(i, kgi, 0), al = frag(i, kgi, 1), bh = frag(32 + i, kgi, 0), bl = frag(32 + i, kgi, 1);
+      const nl_bf16x8 ah = frag(i, kgi, 0), al = frag(i, kgi, 1), bh = frag(32 + i, kgi, 0), bl = frag(32 + i, kgi, 1);
       acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, acc, 0, 0, 0);
       acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl, acc, 0, 0, 0);
       acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, acc, 0, 0, 0);

@@ -42,7 +42,8 @@ def test_fp6_packing_conversions_go_through_the_early_clobber_wrappers():
     (v_cvt_scalef32_2xpk16_fp6_f32 v[206:211], v[122:137], v[138:153], v206): the multi-pass instruction then reads a scale it has already
     overwritten and one K slab of one layer of the fused neural-point kernel carried garbage residuals (5e-4 instead of 1.5e-5 on the
     goldens; found with tools/mx6_debug.py).  The kernel sources must issue these conversions only through asm statements whose result
-    is an early-clobber operand."""
+    is an early-clobber operand.  The single definition of the two wrappers is csrc/mfma.h (nl_cvt_pk32_fp6_f16, nl_cvt_2xpk16_fp6_f32);
+    every source file is still searched, so a second copy with a plain result would be caught too."""
     for fn in os.listdir(CSRC):
         if not fn.endswith((".hip", ".h")):
             continue
