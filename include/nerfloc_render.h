@@ -43,9 +43,10 @@ extern "C" {
 #pragma GCC visibility push(default)
 #endif
 
-#define NL_ABI_VERSION 8   /* 2: nl_render_rays_ex / nl_render_opts (early termination, per-ray query centres); 3: nl_render_opts.flags,
+#define NL_ABI_VERSION 9   /* 2: nl_render_rays_ex / nl_render_opts (early termination, per-ray query centres); 3: nl_render_opts.flags,
                             * reserved fields validated, side stream owned by the nl_frame; 5: NL_PREC_F16MX; 6: nl_frame_diagnostics;
-                            * 7: NL_RENDER_PRECISION_GUARD (the precision guard at the boundary), NL_DIAG_GUARD_*; 8: nl_s2d_* (the coarse matcher) */
+                            * 7: NL_RENDER_PRECISION_GUARD (the precision guard at the boundary), NL_DIAG_GUARD_*; 8: nl_s2d_* (the coarse matcher);
+                            * 9: nl_fine_* (the fine matcher) */
 #define NL_MAX_VIEWS 16
 #define NL_KNN_MAX_K 8
 
@@ -500,6 +501,32 @@ int nl_s2d_pack_weights(int C, const float* w1, const float* b1, const float* w2
 size_t nl_s2d_min_workspace_bytes(int64_t N, int64_t M, int C, int want_scores);
 int nl_s2d_match(const void* packed, int C, int precision, const float* desc0, int64_t N, const float* desc1, int64_t M, float thr, float* scores_out,
                  int32_t* match_j, float* match_score, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- localisation head: the fine matcher ------------------------------------------------------------------------------------------------
+ * The two stages behind the coarse matches (matcher.py:101-124), models/matching/fine_matching.py.  No workspace: both calls are one launch that writes its
+ * outputs only.  Cf, Cout, C: multiples of 32, 32..256.  precision as for nl_s2d_match (NL_PREC_F16MX: NL_ERR_UNSUPPORTED).  Null pointers, M < 0, unsupported
+ * widths and stride < 1 are NL_ERR_BAD_ARG before anything is dereferenced; M == 0 is NL_OK with nothing launched.  packed images and the feature tensors must be
+ * 16-byte aligned.
+ *
+ * nl_fine_windows: FinePreprocess.forward with fine_concat_coarse_feat = False (fine_matching.py:35-76): out (M,49,Cout) = proj(window), where window m is the 7 x 7
+ * window l = j_ids[m] of image b_ids[m] as F.unfold(kernel 7, stride, padding 3) + 'n (c ww) l -> n l ww c' define it: Ly = (Hf-1)/stride + 1, Lx = (Wf-1)/stride + 1,
+ * (ly, lx) = (l / Lx, l % Lx), cell ww = wy*7 + wx reads pixel (ly*stride + wy - 3, lx*stride + wx - 3); a pixel outside the map is a row of zeros (the output is
+ * the bias).  feat_nhwc is the fine map as (B,Hf,Wf,Cf); b_ids, j_ids are int64 DEVICE arrays whose range the CALLER has checked (b in [0,B), l in [0,Ly*Lx)).
+ * The packed image holds proj.weight (Cout,Cf) and proj.bias (DEVICE pointers, fp32, torch layout) for every precision.  The unfolded map is never formed.
+ *
+ * nl_fine_match: FineMatching.forward in eval mode (fine_matching.py:94-143, get_fine_match :145-153): for every match m the 49 logits mlps(feat_f0[m] * feat_f1[m,r])
+ * (mlps = C -> 128 -> ReLU -> 128 -> ReLU -> 1, packed by nl_s2d_pack_weights: the coarse matcher's image format), heatmap = softmax(logits / sqrt(C)),
+ * coords = its expectation over linspace(-1,1,7)^2 (x along the fast axis), std = sum over x, y of sqrt(max(sum(g^2 h) - coords^2, 1e-10)).
+ * expec_f (M,3) = (x, y, std); mkps2d_f (M,2) = mkps2d_c + 3 * coords; heatmap (M,49) may be NULL.  Products, hidden activations and logits are never written.
+ * NL_PREC_BF16X3 here is three-term split-FP16 (hi = f16(v), lo = f16(v - hi); 2^-22 per product, still three matrix instructions; the image carries fp16 planes
+ * for it): the softmax multiplies a logit's error by the logit's size, and split-bf16's 2^-17 misses 1e-4 on nearly one-hot heat-maps.  RANGE of that mode: products
+ * feat_f0 * feat_f1 and hidden activations saturate at 65504 (MODE.FP16_OVFL) instead of overflowing; NL_PREC_F32 and NL_PREC_BF16 have no such limit. */
+size_t nl_fine_proj_packed_bytes(int Cf, int Cout);
+int nl_fine_pack_proj(int Cf, int Cout, const float* w, const float* b, void* packed, size_t packed_bytes, void* stream);
+int nl_fine_windows(const void* packed, int Cf, int Cout, int precision, const float* feat_nhwc, int B, int Hf, int Wf, const int64_t* b_ids, const int64_t* j_ids,
+                    int64_t M, int stride, float* out, void* stream);
+int nl_fine_match(const void* packed_mlp, int C, int precision, const float* feat_f0, const float* feat_f1, int64_t M, const float* mkps2d_c, float* expec_f,
+                  float* mkps2d_f, float* heatmap, void* stream);
 
 #if defined(__GNUC__) || defined(__clang__)
 #pragma GCC visibility pop

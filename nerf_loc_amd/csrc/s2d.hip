@@ -16,36 +16,11 @@
 // with s > thr, s == rowmax[i], s == colmax[j] — the reference's rule on the scores themselves, ties included.
 #include "common.h"
 #include "mfma.h"
+#include "s2d.h"
 
 namespace {
 
-constexpr int S2D_H = 128;                 // hidden width (fixed, as the reference)
-constexpr int S2D_SMALL_BYTES = 2048;      // b1p[2][64], b2p[2][64], w3p[2][64], b3
-constexpr int S2D_W2_BYTES = 32 * 1024;    // one bf16 plane of W2: 32 fragments
-constexpr int S2D_F32_LDS = 4 * 128 * 64 * 4;   // fp32 kernel: the hidden activations of 4 waves x 2 tiles, lane-private columns
 constexpr int S2D_NROWS = 32;              // rows n of one work item (4 waves x 2 rows x 4 iterations)
-
-struct S2dLayout {
-  size_t w1hi, w2hi, w2lo, small, w1lo, f32w1, f32w2, total;
-  size_t lds_bytes;   // the prefix [0, lds_bytes) is what the bf16 kernels keep in LDS
-};
-__host__ __device__ inline S2dLayout s2d_layout(int C) {
-  S2dLayout l;
-  const size_t w1 = (size_t)C * S2D_H * 2;   // one bf16 plane of W1
-  l.w1hi = 0;
-  l.w2hi = l.w1hi + w1;
-  l.w2lo = l.w2hi + S2D_W2_BYTES;
-  l.small = l.w2lo + S2D_W2_BYTES;
-  l.lds_bytes = l.small + S2D_SMALL_BYTES;
-  l.w1lo = l.lds_bytes;
-  l.f32w1 = l.w1lo + w1;
-  l.f32w2 = l.f32w1 + (size_t)C * S2D_H * 4;
-  l.total = l.f32w2 + (size_t)S2D_H * S2D_H * 4;
-  return l;
-}
-
-// hidden unit held by accumulator register r of 32-block b in half-wave hh (C/D layout of the 32x32 MFMAs: row = (r & 3) + 8 (r >> 2) + 4 hh)
-__host__ __device__ inline int s2d_unit(int b, int r, int hh) { return 32 * b + 8 * (r >> 2) + 4 * hh + (r & 3); }
 
 // ------------------------------------------------------------------------------------------ packing
 struct S2dPackArgs {
@@ -58,7 +33,7 @@ __global__ __launch_bounds__(256) void s2d_pack_kernel(const S2dPackArgs a) {
   const S2dLayout L = s2d_layout(a.C);
   const int C = a.C;
   const int n1 = C * S2D_H, n2 = S2D_H * S2D_H;
-  const int total = 2 * n1 + 2 * n2 + 512;
+  const int total = 2 * n1 + 2 * n2 + 512 + n1 + n2;
   for (int i = blockIdx.x * 256 + threadIdx.x; i < total; i += gridDim.x * 256) {
     if (i < n1) {   // W1, bf16 planes: fragment (s, rb), lane, slot j <-> W1[32 rb + (lane & 31)][16 s + 8 (lane >> 5) + j]
       const int j = i & 7, lane = (i >> 3) & 63, f = i >> 9, rb = f & 3, s = f >> 2;
@@ -81,6 +56,23 @@ __global__ __launch_bounds__(256) void s2d_pack_kernel(const S2dPackArgs a) {
       const int e = i - 2 * n1 - n2;
       const int lane = e & 63, f = e >> 6, rb = f & 3, t = (f >> 2) & 15, b = f >> 6;
       ((float*)(a.img + L.f32w2))[e] = a.w2[(size_t)(32 * rb + (lane & 31)) * S2D_H + s2d_unit(b, t, lane >> 5)];
+    } else if (i >= 2 * n1 + 2 * n2 + 512) {   // the two bf16 images again as split-FP16, same fragment order (fine.hip's parity mode)
+      const int e = i - (2 * n1 + 2 * n2 + 512);
+      float v;
+      unsigned short *hi, *lo;
+      if (e < n1) {
+        const int j = e & 7, lane = (e >> 3) & 63, f = e >> 9, rb = f & 3, s = f >> 2;
+        v = a.w1[(size_t)(32 * rb + (lane & 31)) * C + 16 * s + 8 * (lane >> 5) + j];
+        hi = (unsigned short*)(a.img + L.h1hi) + e; lo = (unsigned short*)(a.img + L.h1lo) + e;
+      } else {
+        const int q = e - n1;
+        const int j = q & 7, lane = (q >> 3) & 63, f = q >> 9, rb = f & 3, s = (f >> 2) & 1, b = f >> 3;
+        v = a.w2[(size_t)(32 * rb + (lane & 31)) * S2D_H + s2d_unit(b, 8 * s + j, lane >> 5)];
+        hi = (unsigned short*)(a.img + L.h2hi) + q; lo = (unsigned short*)(a.img + L.h2lo) + q;
+      }
+      const _Float16 h = (_Float16)v, l = (_Float16)(v - (float)h);
+      *hi = __builtin_bit_cast(unsigned short, h);
+      *lo = __builtin_bit_cast(unsigned short, l);
     } else {   // b1p / b2p / w3p [hh][16 b + r] in accumulator order, then b3 and zero padding
       const int e = i - 2 * n1 - 2 * n2;
       float v = 0.f;
@@ -105,33 +97,12 @@ struct S2dArgs {
   int N, M, C;
 };
 
-__device__ __forceinline__ nl_i16x8 s2d_frag(const uint4 v) { return __builtin_bit_cast(nl_i16x8, v); }
-__device__ __forceinline__ nl_i16x8 s2d_frag(unsigned a, unsigned b, unsigned c, unsigned d) { return __builtin_bit_cast(nl_i16x8, nl_u32x4{a, b, c, d}); }
-
 // bias + ReLU + last layer + sigmoid + stores + maxima, shared by the two score kernels.  acc[t][b]: tile t (row n0 + t), hidden 32-block b.
 __device__ __forceinline__ void s2d_finish(const S2dArgs& a, const float* small, const nl_f32x16 (&acc)[2][4], int lane, int n0, bool has1, int m, unsigned& colmax) {
   const int hh = lane >> 5;
-  const float* b2p = small + 128 + 64 * hh;
-  const float* w3p = small + 256 + 64 * hh;
-  float dot[2] = {0.f, 0.f};
-#pragma unroll
-  for (int b = 0; b < 4; ++b)
-#pragma unroll
-    for (int r4 = 0; r4 < 4; ++r4) {
-      const float4 bb = *(const float4*)(b2p + 16 * b + 4 * r4), ww = *(const float4*)(w3p + 16 * b + 4 * r4);
-      const float bv[4] = {bb.x, bb.y, bb.z, bb.w}, wv[4] = {ww.x, ww.y, ww.z, ww.w};
-#pragma unroll
-      for (int e = 0; e < 4; ++e)
-#pragma unroll
-        for (int t = 0; t < 2; ++t) dot[t] += fmaxf(acc[t][b][4 * r4 + e] + bv[e], 0.f) * wv[e];
-    }
-  const float b3 = small[384];
-  float sc[2];
-#pragma unroll
-  for (int t = 0; t < 2; ++t) {
-    const float tot = dot[t] + __shfl_xor(dot[t], 32);   // the two half-waves' 64 units each: a + b == b + a, both halves hold the same bits
-    sc[t] = nl_sigmoid(tot + b3);
-  }
+  float logit[2];
+  s2d_logits(acc, small, hh, logit);
+  const float sc[2] = {nl_sigmoid(logit[0]), nl_sigmoid(logit[1])};
   const bool mok = m < a.M;
   const bool ok0 = mok, ok1 = mok && has1;
   const unsigned u0 = ok0 ? __float_as_uint(sc[0]) : 0u, u1 = ok1 ? __float_as_uint(sc[1]) : 0u;
@@ -182,12 +153,7 @@ __global__ __launch_bounds__(256) void s2d_bf16_kernel(const S2dArgs a) {
       const float* d0b = a.desc0 + (size_t)(has1 ? n0 + 1 : n0) * C + 8 * hh;
 
       nl_f32x16 acc[2][4];
-#pragma unroll
-      for (int t = 0; t < 2; ++t)
-#pragma unroll
-        for (int b = 0; b < 4; ++b)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) acc[t][b][r] = 0.f;
+      s2d_zero(acc);
 
       // ---- layer 1: K = C, the B operand built per k-step from desc1 (shared by both tiles) and the two desc0 rows
       for (int s = 0; s < nk1; ++s) {
@@ -203,76 +169,9 @@ __global__ __launch_bounds__(256) void s2d_bf16_kernel(const S2dArgs a) {
         nl_split_bf16_pair(x0.z * yb0.z, x0.w * yb0.w, ph[1][1], pl[1][1]);
         nl_split_bf16_pair(x1.x * yb1.x, x1.y * yb1.y, ph[1][2], pl[1][2]);
         nl_split_bf16_pair(x1.z * yb1.z, x1.w * yb1.w, ph[1][3], pl[1][3]);
-        nl_i16x8 bh[2], bl[2];
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-          bh[t] = s2d_frag(ph[t][0], ph[t][1], ph[t][2], ph[t][3]);
-          bl[t] = s2d_frag(pl[t][0], pl[t][1], pl[t][2], pl[t][3]);
-        }
-#pragma unroll
-        for (int rb = 0; rb < 4; ++rb) {
-          const int f = ((s << 2) + rb) * 64 + lane;
-          const nl_i16x8 ah = s2d_frag(w1hi[f]);
-          if (X3) {
-            const nl_i16x8 al = s2d_frag(w1lo[f]);
-#pragma unroll
-            for (int t = 0; t < 2; ++t) {
-              acc[t][rb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh[t], acc[t][rb], 0, 0, 0);
-              acc[t][rb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl[t], acc[t][rb], 0, 0, 0);
-            }
-          }
-#pragma unroll
-          for (int t = 0; t < 2; ++t) acc[t][rb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh[t], acc[t][rb], 0, 0, 0);
-        }
+        s2d_layer1_step<X3>(acc, w1hi, w1lo, s, lane, ph, pl);
       }
-
-      // ---- bias + ReLU + split: layer 2's B operand, k-step (b, s) = accumulator registers 8 s .. 8 s + 7 of block b
-      unsigned hhi[2][4][8], hlo[2][4][8];
-#pragma unroll
-      for (int b = 0; b < 4; ++b)
-#pragma unroll
-        for (int r4 = 0; r4 < 4; ++r4) {
-          const float4 bb = *(const float4*)(b1p + 16 * b + 4 * r4);
-#pragma unroll
-          for (int t = 0; t < 2; ++t) {
-            nl_split_bf16_pair(fmaxf(acc[t][b][4 * r4 + 0] + bb.x, 0.f), fmaxf(acc[t][b][4 * r4 + 1] + bb.y, 0.f), hhi[t][b][2 * r4], hlo[t][b][2 * r4]);
-            nl_split_bf16_pair(fmaxf(acc[t][b][4 * r4 + 2] + bb.z, 0.f), fmaxf(acc[t][b][4 * r4 + 3] + bb.w, 0.f), hhi[t][b][2 * r4 + 1], hlo[t][b][2 * r4 + 1]);
-          }
-        }
-
-      // ---- layer 2: K = 128
-#pragma unroll
-      for (int t = 0; t < 2; ++t)
-#pragma unroll
-        for (int b = 0; b < 4; ++b)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) acc[t][b][r] = 0.f;
-#pragma unroll
-      for (int b = 0; b < 4; ++b)
-#pragma unroll
-        for (int s = 0; s < 2; ++s) {
-          nl_i16x8 bh[2], bl[2];
-#pragma unroll
-          for (int t = 0; t < 2; ++t) {
-            bh[t] = s2d_frag(hhi[t][b][4 * s], hhi[t][b][4 * s + 1], hhi[t][b][4 * s + 2], hhi[t][b][4 * s + 3]);
-            bl[t] = s2d_frag(hlo[t][b][4 * s], hlo[t][b][4 * s + 1], hlo[t][b][4 * s + 2], hlo[t][b][4 * s + 3]);
-          }
-#pragma unroll
-          for (int rb = 0; rb < 4; ++rb) {
-            const int f = (((b * 2 + s) << 2) + rb) * 64 + lane;
-            const nl_i16x8 ah = s2d_frag(w2hi[f]);
-            if (X3) {
-              const nl_i16x8 al = s2d_frag(w2lo[f]);
-#pragma unroll
-              for (int t = 0; t < 2; ++t) {
-                acc[t][rb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh[t], acc[t][rb], 0, 0, 0);
-                acc[t][rb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl[t], acc[t][rb], 0, 0, 0);
-              }
-            }
-#pragma unroll
-            for (int t = 0; t < 2; ++t) acc[t][rb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh[t], acc[t][rb], 0, 0, 0);
-          }
-        }
+      s2d_layer2<X3>(acc, b1p, w2hi, w2lo, lane);
 
       s2d_finish(a, small, acc, lane, n0, has1, m, colmax);
     }
@@ -310,56 +209,15 @@ __global__ __launch_bounds__(256) void s2d_f32_kernel(const S2dArgs a) {
       const float* d0b = a.desc0 + (size_t)(has1 ? n0 + 1 : n0) * C + 4 * hh;
 
       nl_f32x16 acc[2][4];
-#pragma unroll
-      for (int t = 0; t < 2; ++t)
-#pragma unroll
-        for (int b = 0; b < 4; ++b)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) acc[t][b][r] = 0.f;
+      s2d_zero(acc);
 
       for (int g = 0; g < ng; ++g) {
         const float4 x = *(const float4*)(d1p + 8 * g), ya = *(const float4*)(d0a + 8 * g), yb = *(const float4*)(d0b + 8 * g);
         const float pa[4] = {x.x * ya.x, x.y * ya.y, x.z * ya.z, x.w * ya.w};
         const float pb[4] = {x.x * yb.x, x.y * yb.y, x.z * yb.z, x.w * yb.w};
-#pragma unroll
-        for (int t = 0; t < 4; ++t)
-#pragma unroll
-          for (int rb = 0; rb < 4; ++rb) {
-            const float w = w1f[(((g * 4 + t) << 2) + rb) * 64 + lane];
-            acc[0][rb] = __builtin_amdgcn_mfma_f32_32x32x2f32(w, pa[t], acc[0][rb], 0, 0, 0);
-            acc[1][rb] = __builtin_amdgcn_mfma_f32_32x32x2f32(w, pb[t], acc[1][rb], 0, 0, 0);
-          }
+        s2d_f32_layer1_group(acc, w1f, g, lane, pa, pb);
       }
-
-      // bias + ReLU; the 128 values per lane are parked in a lane-private LDS column so that layer 2 can be a rolled loop (fully unrolled, its 256 fragment
-      // loads are hoisted and the kernel spills)
-#pragma unroll
-      for (int b = 0; b < 4; ++b)
-#pragma unroll
-        for (int r4 = 0; r4 < 4; ++r4) {
-          const float4 bb = *(const float4*)(b1p + 16 * b + 4 * r4);
-          const float bv[4] = {bb.x, bb.y, bb.z, bb.w};
-#pragma unroll
-          for (int e = 0; e < 4; ++e)
-#pragma unroll
-            for (int t = 0; t < 2; ++t) hbuf[(t * 64 + 16 * b + 4 * r4 + e) * 64] = fmaxf(acc[t][b][4 * r4 + e] + bv[e], 0.f);
-        }
-#pragma unroll
-      for (int t = 0; t < 2; ++t)
-#pragma unroll
-        for (int b = 0; b < 4; ++b)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) acc[t][b][r] = 0.f;
-#pragma unroll 2
-      for (int k = 0; k < 64; ++k) {   // k = 16 b + t: step t of block b takes accumulator register t
-        const float h0 = hbuf[k * 64], h1 = hbuf[(64 + k) * 64];
-#pragma unroll
-        for (int rb = 0; rb < 4; ++rb) {
-          const float w = w2f[((k << 2) + rb) * 64 + lane];
-          acc[0][rb] = __builtin_amdgcn_mfma_f32_32x32x2f32(w, h0, acc[0][rb], 0, 0, 0);
-          acc[1][rb] = __builtin_amdgcn_mfma_f32_32x32x2f32(w, h1, acc[1][rb], 0, 0, 0);
-        }
-      }
+      s2d_f32_layer2(acc, b1p, hbuf, w2f, lane);
 
       s2d_finish(a, small, acc, lane, n0, has1, m, colmax);
     }
@@ -394,8 +252,6 @@ __global__ __launch_bounds__(256) void s2d_select_kernel(const float* scores, co
     match_score[n] = found >= 0 ? __uint_as_float(rm) : 0.f;
   }
 }
-
-bool s2d_c_ok(int C) { return C >= 32 && C <= 256 && (C & 31) == 0; }
 
 struct S2dWs { size_t rowmax, colmax, scores, total; };
 S2dWs s2d_ws(int64_t N, int64_t M, bool want_scores) {
