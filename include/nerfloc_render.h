@@ -43,10 +43,10 @@ extern "C" {
 #pragma GCC visibility push(default)
 #endif
 
-#define NL_ABI_VERSION 9   /* 2: nl_render_rays_ex / nl_render_opts (early termination, per-ray query centres); 3: nl_render_opts.flags,
+#define NL_ABI_VERSION 10  /* 2: nl_render_rays_ex / nl_render_opts (early termination, per-ray query centres); 3: nl_render_opts.flags,
                             * reserved fields validated, side stream owned by the nl_frame; 5: NL_PREC_F16MX; 6: nl_frame_diagnostics;
                             * 7: NL_RENDER_PRECISION_GUARD (the precision guard at the boundary), NL_DIAG_GUARD_*; 8: nl_s2d_* (the coarse matcher);
-                            * 9: nl_fine_* (the fine matcher) */
+                            * 9: nl_fine_* (the fine matcher); 10: nl_sct_* (the matcher's SelfCrossTransformer) */
 #define NL_MAX_VIEWS 16
 #define NL_KNN_MAX_K 8
 
@@ -527,6 +527,30 @@ int nl_fine_windows(const void* packed, int Cf, int Cout, int precision, const f
                     int64_t M, int stride, float* out, void* stream);
 int nl_fine_match(const void* packed_mlp, int C, int precision, const float* feat_f0, const float* feat_f1, int64_t M, const float* mkps2d_c, float* expec_f,
                   float* mkps2d_f, float* heatmap, void* stream);
+
+/* ---- localisation head: SelfCrossTransformer ------------------------------------------------------------------------------------------
+ * models/COTR/transformer.py:17-64 in eval mode (matcher.py:68-72, :120-124): four post-norm layers on v0 (B,N0,C) and v1 (B,N1,C), batch first, fp32 —
+ * layer 0: self-attention of v0 (q = k = x + pos, value = x), layer 1: the same for v1, layer 2: v0 attends to layer 1's output (q = x + pos0, k = mem + pos1,
+ * value = mem), layer 3: v1 attends to layer 2's OUTPUT.  Each layer: in_proj, 8-head softmax attention (scores * (C/8)^-0.5), out_proj, + residual, LayerNorm
+ * (eps 1e-5), linear2(relu(linear1)), + residual, LayerNorm.  The attention is flash-style: no Nq x Nk value is written to memory in any mode, and the F-wide hidden
+ * rows stay on chip.  Every Nq, Nk >= 1.
+ * Supported: nhead == 8, C in {64, 128, 192, 256}, F a multiple of 32 in 32..512 (nl_sct_packed_bytes returns 0 otherwise, the calls NL_ERR_UNSUPPORTED);
+ * B * max(N0, N1) <= 2^24.  precision: NL_PREC_F32 (exact fp32 products), NL_PREC_BF16X3 (three-term split-FP16 as nl_fine_match, operands saturate at 65504),
+ * NL_PREC_BF16 (throughput, no bar); NL_PREC_F16MX is NL_ERR_UNSUPPORTED.
+ * nl_sct_pack_weights: `tensors` is a HOST array of the module's 52 state-dict tensors in state-dict order (DEVICE pointers, fp32, torch layout: two encoder
+ * layers of 12, two decoder layers of 14 — the decoder layers' norm1 pair is taken and ignored, as the reference never applies it); one image for all modes.
+ * Nothing is allocated; work is enqueued on `stream`.  Negative or zero extents, null or not 16-byte aligned pointers are NL_ERR_BAD_ARG, a missing, short or not
+ * 256-byte aligned workspace NL_ERR_WORKSPACE, all before anything is dereferenced; B == 0 is NL_OK with nothing launched.
+ * nl_sct_layer: one layer (0..3 in forward order) of the image, so that a deviation can be attributed: out (B,Nq,C) from x, x_pos (B,Nq,C) and, for layers 2 / 3,
+ * mem, mem_pos (B,Nk,C); for layers 0 / 1 mem and mem_pos are NULL or x and x_pos, and Nk == Nq.  out may be x.
+ * nl_sct_forward: the four layers; out0 (B,N0,C), out1 (B,N1,C) are distinct buffers that alias neither input of the other side (out0 may be v0, out1 may be v1). */
+size_t nl_sct_packed_bytes(int C, int nhead, int F);
+int nl_sct_pack_weights(int C, int nhead, int F, const float* const* tensors, int n_tensors, void* packed, size_t packed_bytes, void* stream);
+size_t nl_sct_workspace_bytes(int64_t B, int64_t N0, int64_t N1, int C, int F);
+int nl_sct_layer(const void* packed, int C, int nhead, int F, int layer, int precision, const float* x, const float* x_pos, int64_t Nq, const float* mem,
+                 const float* mem_pos, int64_t Nk, int64_t B, float* out, void* ws, size_t ws_bytes, void* stream);
+int nl_sct_forward(const void* packed, int C, int nhead, int F, int precision, const float* v0, const float* pos0, int64_t N0, const float* v1, const float* pos1,
+                   int64_t N1, int64_t B, float* out0, float* out1, void* ws, size_t ws_bytes, void* stream);
 
 #if defined(__GNUC__) || defined(__clang__)
 #pragma GCC visibility pop

@@ -29,7 +29,7 @@ GUARD_LOGIT_LIMIT = {"f16mx": 50.0, "bf16x3": 500.0}   # include/nerfloc_render.
 PRECISION_NAMES = {PREC_F32: "fp32", PREC_BF16X3: "bf16x3", PREC_BF16: "bf16", PREC_F16MX: "f16mx"}
 GUARD_DENSITY_LIMIT = {"f16mx": 32.0}  # include/nerfloc_render.h: NL_GUARD_DENSITY_LIMIT_F16MX (the guard's second indicator: the largest density of the frame's guarded batches; bf16x3 has no such limit)
 DIAG_COUNT = 6
-ABI_VERSION = 9   # include/nerfloc_render.h: NL_ABI_VERSION
+ABI_VERSION = 10  # include/nerfloc_render.h: NL_ABI_VERSION
 
 
 class NlConfig(C.Structure):
@@ -151,6 +151,11 @@ SYMBOLS = [
     ("nl_fine_pack_proj", _I, [_I, _I, _P, _P, _P, _Z, _P]),
     ("nl_fine_windows", _I, [_P, _I, _I, _I, _P, _I, _I, _I, _P, _P, _L, _I, _P, _P]),
     ("nl_fine_match", _I, [_P, _I, _I, _P, _P, _L, _P, _P, _P, _P, _P]),
+    ("nl_sct_packed_bytes", _Z, [_I, _I, _I]),
+    ("nl_sct_pack_weights", _I, [_I, _I, _I, C.POINTER(_P), _I, _P, _Z, _P]),
+    ("nl_sct_workspace_bytes", _Z, [_L, _L, _L, _I, _I]),
+    ("nl_sct_layer", _I, [_P, _I, _I, _I, _I, _I, _P, _P, _L, _P, _P, _L, _L, _P, _P, _Z, _P]),
+    ("nl_sct_forward", _I, [_P, _I, _I, _I, _I, _P, _P, _L, _P, _P, _L, _L, _P, _P, _P, _Z, _P]),
     ("nl_backproject_support", _I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _L, _P, _P, _P, _P, C.POINTER(_L), _P, _Z, _P]),
 ]
 

@@ -1,0 +1,715 @@
+// SelfCrossTransformer (reference: models/COTR/transformer.py:17-64, 171-250) in eval mode: four post-norm layers (self v0, self v1, cross v0 <- v1, cross v1 <- new v0),
+// each three kernels on rows flattened over the batch ([B * N][C] fp32, batch first):
+//
+// sct_proj_kernel   q / k / v = (x [+ pos]) . W^T + b.  A workgroup owns 32 rows: x and x + pos are formed once while the tile is loaded into LDS (no x + pos tensor),
+//   the four waves share the 32-column output blocks of in_proj_weight; [q; k] blocks multiply the x + pos tile, v blocks the x tile.  Cross layers launch it twice
+//   (q from the target side, k and v once from the memory side).
+// sct_attn_kernel   flash-style attention: a wave owns (batch item, head, 32-query tile, key range).  S^T = K . Q^T on the 32x32 MFMAs puts a query in a lane's
+//   COLUMN, so a row's running maximum and sum are in-lane reductions over the 16 accumulator registers plus one exchange between the half-waves, and the probabilities
+//   are already the B operand of O^T = V^T . P^T (k slot (hh, j) of step s = accumulator register 8 s + j; the V fragment is gathered in that key order).  Keys beyond Nk
+//   get -inf before the maximum; their loads are clamped to the last key.  The next key tile's K / V values are fetched before the current tile's arithmetic.  A long
+//   key sequence is cut into 2 or 4 ranges (>= 4 / >= 16 tiles) held by neighbouring waves of the workgroup, whose (maximum, sum, accumulator) meet in 18 KB of LDS and
+//   are added in range order by the first of them: with one range per item the 4800 x 4800 layer is 1200 waves for 1024 SIMDs, each waiting on its own loads.
+//   No Nq x Nk value ever reaches memory.  The head dimension (8 / 16 / 24 / 32) is padded with zero k slots to 16 / 32; fp32 mode needs no padding (k step 2).
+//   The same kernel serves every Nq, also Nq == 1 (the fine shape: B x 8 waves with one live column each, four (batch item, head) pairs to a workgroup): a row's bits
+//   must not depend on how many rows or batch items the call holds (tests/test_gpu_sct.py), which rules out a second kernel chosen by Nq or B; the number of key
+//   ranges depends on Nk alone.
+// sct_chain_kernel  out_proj, + residual, LayerNorm, linear1, ReLU, linear2, + residual, LayerNorm for 32 rows that stay in LDS from the attention output to the layer
+//   output; the F-wide hidden rows live in LDS only.  The four waves split the output blocks of each product, so every weight fragment is read by exactly ONE wave
+//   of the workgroup, straight from L2 in 1-KB coalesced pieces (fragment order): a copy through LDS would add a barrier pair per chunk and no reuse.
+//   Measured: the kernel takes ~90 us per launch whatever the row count — it waits on these loads, which are not requested ahead of use; not yet changed.
+//
+// Precision: NL_PREC_F32 = v_mfma_f32_32x32x2_f32 on fp32 operands; NL_PREC_BF16X3 = three-term split-FP16 (s2d.h: hi = f16(v), lo = f16(v - hi)) for every product —
+//   the logits feed a softmax (as in fine.hip) and one format keeps one code path; NL_PREC_BF16 = one bf16 product.  LayerNorm, softmax and residuals are fp32 everywhere.
+// Every output row depends on its own row, the memory side, the weights and the mode only: fixed reduction orders, no atomics.
+#include <atomic>
+#include "common.h"
+#include "mfma.h"
+#include "s2d.h"
+
+namespace {
+
+constexpr int SCT_HEADS = 8, SCT_LAYERS = 4, SCT_TENSORS = 52;
+constexpr int SCT_PAD = 4;   // floats between LDS rows
+constexpr float SCT_EPS = 1e-5f;
+enum { SCT_F32 = 0, SCT_X3 = 1, SCT_BF = 2 };   // = NL_PREC_F32 / NL_PREC_BF16X3 / NL_PREC_BF16
+
+// ------------------------------------------------------------------------------------------ packed image
+// per layer: in_proj_weight (3C x C), out_proj.weight (C x C), linear1.weight (F x C), linear2.weight (C x F), each as four planes — fp16 hi, fp16 lo, bf16 (fragment
+// (s, rb), lane, slot j <-> W[32 rb + (lane & 31)][16 s + 8 (lane >> 5) + j]) and fp32 (fragment (g, t, rb), lane <-> W[32 rb + (lane & 31)][8 g + 4 (lane >> 5) + t]) —
+// then the vectors: in_proj_bias (3C), out_proj.bias (C), linear1.bias (F), linear2.bias (C), first norm weight / bias, second norm weight / bias (C each).
+struct SctW { const uint4* hi; const uint4* lo; const uint4* bf; const float* f32; int nrb; };
+struct SctMatOff { size_t hi, lo, bf, f32; };
+struct SctLayerOff { SctMatOff m[4]; size_t vec; };
+struct SctLayout { SctLayerOff l[SCT_LAYERS]; size_t total; };
+
+inline SctLayout sct_layout(int C, int F) {
+  SctLayout L;
+  size_t o = 0;
+  for (int i = 0; i < SCT_LAYERS; ++i) {
+    const size_t n[4] = {(size_t)3 * C * C, (size_t)C * C, (size_t)F * C, (size_t)C * F};
+    for (int k = 0; k < 4; ++k) {
+      L.l[i].m[k].hi = o; o += n[k] * 2;
+      L.l[i].m[k].lo = o; o += n[k] * 2;
+      L.l[i].m[k].bf = o; o += n[k] * 2;
+      L.l[i].m[k].f32 = o; o += n[k] * 4;
+    }
+    L.l[i].vec = o; o += (size_t)(9 * C + F) * 4;
+  }
+  L.total = o;
+  return L;
+}
+inline SctW sct_mat(const unsigned char* img, const SctMatOff& m, int N) {
+  return SctW{(const uint4*)(img + m.hi), (const uint4*)(img + m.lo), (const uint4*)(img + m.bf), (const float*)(img + m.f32), N >> 5};
+}
+
+struct SctPackArgs { const float* w; unsigned char* img; SctMatOff m; int N, K; };
+
+__global__ __launch_bounds__(256) void sct_pack_mat_kernel(const SctPackArgs a) {
+  const int K = a.K, nrb = a.N >> 5, n = a.N * a.K;
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < 2 * n; i += gridDim.x * 256) {
+    if (i < n) {
+      const int j = i & 7, lane = (i >> 3) & 63, f = i >> 9, rb = f % nrb, s = f / nrb;
+      const float v = a.w[(size_t)(32 * rb + (lane & 31)) * K + 16 * s + 8 * (lane >> 5) + j];
+      const _Float16 h = (_Float16)v;
+      ((unsigned short*)(a.img + a.m.hi))[i] = __builtin_bit_cast(unsigned short, h);
+      ((unsigned short*)(a.img + a.m.lo))[i] = __builtin_bit_cast(unsigned short, (_Float16)(v - (float)h));
+      ((unsigned short*)(a.img + a.m.bf))[i] = nl_f2bf(v);
+    } else {
+      const int e = i - n;
+      const int lane = e & 63, f = e >> 6, rb = f % nrb, t = (f / nrb) & 3, g = f / (4 * nrb);
+      ((float*)(a.img + a.m.f32))[e] = a.w[(size_t)(32 * rb + (lane & 31)) * K + 8 * g + 4 * (lane >> 5) + t];
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------------ operand helpers
+__device__ __forceinline__ void sct_load8(const float* p, float (&v)[8]) {
+  const float4 a = *(const float4*)p, b = *(const float4*)(p + 4);
+  v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
+}
+// 8 values -> the 16-bit fragment(s) of the mode: split-FP16 hi / lo (SCT_X3) or bf16 (SCT_BF; lo unused)
+template <int MODE>
+__device__ __forceinline__ void sct_split8(const float (&v)[8], nl_i16x8& hi, nl_i16x8& lo) {
+  unsigned h[4], l[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+  for (int t = 0; t < 4; ++t) {
+    if constexpr (MODE == SCT_X3) s2d_split_pair<true>(v[2 * t], v[2 * t + 1], h[t], l[t]);
+    else h[t] = nl_bf16_pair(v[2 * t], v[2 * t + 1]);
+  }
+  hi = s2d_frag(h[0], h[1], h[2], h[3]);
+  lo = s2d_frag(l[0], l[1], l[2], l[3]);
+}
+// acc += a . b: three terms, small ones first (SCT_X3), or the one bf16 product
+template <int MODE>
+__device__ __forceinline__ nl_f32x16 sct_mfma(const nl_i16x8 ah, const nl_i16x8 al, const nl_i16x8 bh, const nl_i16x8 bl, nl_f32x16 acc) {
+  if constexpr (MODE == SCT_X3) {
+    acc = s2d_mfma<true>(al, bh, acc);
+    acc = s2d_mfma<true>(ah, bl, acc);
+  }
+  return s2d_mfma<MODE == SCT_X3>(ah, bh, acc);
+}
+template <int NB>
+__device__ __forceinline__ void sct_zero(nl_f32x16 (&acc)[NB]) {
+#pragma unroll
+  for (int i = 0; i < NB; ++i)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[i][r] = 0.f;
+}
+
+// acc[i] += X[32 rows][K] . W[rows 32 rb .. 32 rb + 31][K]^T for the wave's output blocks rb = rbs + 4 i < rbe.  xrow: the lane's row (lane & 31) of the LDS tile.
+// Accumulator register r of half-wave hh is row nl_acc_row(r, hh); the lane's column is output 32 rb + (lane & 31).
+template <int MODE, int NB>
+__device__ __forceinline__ void sct_gemm(nl_f32x16 (&acc)[NB], const float* xrow, int K, const SctW& w, int rbs, int rbe, int lane) {
+  const int hh = lane >> 5;
+  if constexpr (MODE == SCT_F32) {
+    for (int g = 0; g < (K >> 3); ++g) {
+      const float4 v = *(const float4*)(xrow + 8 * g + 4 * hh);
+      const float x[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+      for (int t = 0; t < 4; ++t)
+#pragma unroll
+        for (int i = 0; i < NB; ++i) {
+          const int rb = rbs + 4 * i;
+          if (rb < rbe) acc[i] = __builtin_amdgcn_mfma_f32_32x32x2f32(x[t], w.f32[((size_t)(g * 4 + t) * w.nrb + rb) * 64 + lane], acc[i], 0, 0, 0);
+        }
+    }
+  } else {
+    const uint4* whi = MODE == SCT_X3 ? w.hi : w.bf;
+    for (int s = 0; s < (K >> 4); ++s) {
+      float v[8];
+      sct_load8(xrow + 16 * s + 8 * hh, v);
+      nl_i16x8 ah, al;
+      sct_split8<MODE>(v, ah, al);
+#pragma unroll
+      for (int i = 0; i < NB; ++i) {
+        const int rb = rbs + 4 * i;
+        if (rb < rbe) {
+          const size_t f = ((size_t)s * w.nrb + rb) * 64 + lane;
+          const nl_i16x8 bh = s2d_frag(whi[f]);
+          nl_i16x8 bl = bh;
+          if constexpr (MODE == SCT_X3) bl = s2d_frag(w.lo[f]);
+          acc[i] = sct_mfma<MODE>(ah, al, bh, bl, acc[i]);
+        }
+      }
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------------ q / k / v projections
+struct SctProjArgs {
+  const float* x; const float* pos;
+  float* out[3];        // q, k, v rows ([rows][C]); only the parts inside [rb_lo, rb_hi) are written
+  SctW w; const float* bias;
+  long long rows;
+  int C, rb_lo, rb_hi;  // output blocks of in_proj_weight: [0, C/32) = q, [C/32, 2C/32) = k, [2C/32, 3C/32) = v
+};
+
+template <int MODE, int NB>
+__device__ __forceinline__ void sct_proj_pass(const SctProjArgs& a, const float* tile, int lo, int hi, long long row0, int lane, int wave) {
+  if (lo + wave >= hi) return;   // wave-uniform
+  const int C = a.C, nc = C >> 5, hh = lane >> 5, col = lane & 31;
+  nl_f32x16 acc[NB];
+  sct_zero(acc);
+  sct_gemm<MODE, NB>(acc, tile + col * (C + SCT_PAD), C, a.w, lo + wave, hi, lane);
+#pragma unroll
+  for (int i = 0; i < NB; ++i) {
+    const int rb = lo + wave + 4 * i;
+    if (rb >= hi) break;
+    const int part = rb / nc, n = 32 * (rb - part * nc) + col;
+    const float bv = a.bias[32 * rb + col];
+    float* o = a.out[part];
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const long long row = row0 + nl_acc_row(r, hh);
+      if (row < a.rows) o[(size_t)row * C + n] = acc[i][r] + bv;
+    }
+  }
+}
+
+template <int MODE>
+__global__ __launch_bounds__(256) void sct_proj_kernel(const SctProjArgs a) {
+  if constexpr (MODE == SCT_X3) __builtin_amdgcn_s_setreg(1473, 1);   // MODE.FP16_OVFL: conversions to f16 saturate at 65504 (as fine.hip)
+  extern __shared__ __attribute__((aligned(16))) float sct_smem[];
+  const int C = a.C, ld = C + SCT_PAD, c4n = C >> 2, nc = C >> 5;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const long long row0 = (long long)blockIdx.x * 32;
+  float* xp = sct_smem;             // x + pos
+  float* xs = sct_smem + 32 * ld;   // x
+  const bool need_p = a.rb_lo < 2 * nc, need_x = a.rb_hi > 2 * nc;   // the q-only launch of a cross layer has no v block: it neither stages nor reads the x tile
+  for (int i = threadIdx.x; i < 32 * c4n; i += 256) {
+    const int r = i / c4n, c = 4 * (i - r * c4n);
+    const long long row = row0 + r < a.rows ? row0 + r : a.rows - 1;   // rows past the end repeat the last one and are not stored
+    const float4 v = *(const float4*)(a.x + (size_t)row * C + c);
+    if (need_x) *(float4*)(xs + r * ld + c) = v;
+    if (need_p) {
+      const float4 p = *(const float4*)(a.pos + (size_t)row * C + c);
+      *(float4*)(xp + r * ld + c) = make_float4(v.x + p.x, v.y + p.y, v.z + p.z, v.w + p.w);
+    }
+  }
+  __syncthreads();
+  sct_proj_pass<MODE, 4>(a, xp, a.rb_lo, a.rb_hi < 2 * nc ? a.rb_hi : 2 * nc, row0, lane, wave);
+  sct_proj_pass<MODE, 2>(a, xs, a.rb_lo > 2 * nc ? a.rb_lo : 2 * nc, a.rb_hi, row0, lane, wave);
+}
+
+// ------------------------------------------------------------------------------------------ attention
+struct SctAttnArgs {
+  const float* q; const float* k; const float* v; float* out;   // [B][Nq | Nk][C]
+  long long Nq, Nk, items;   // items = B * 8 * ceil(Nq / 32)
+  int nqt, nkt;              // 32-row query / key tiles
+  int lg, tps;               // a workgroup's four waves are (4 >> lg) items x (1 << lg) key ranges of tps tiles each
+  float scale;
+};
+
+// A wave's operands of one key tile as they come from memory: K row (k0 + column) of the head — fp32: the half-wave's DH / 2 dimensions, else the 8-wide groups
+// 16 s + 8 hh (zeros where the group is padding) — and V[key of accumulator register r][the lane's channel].  Keys past Nk repeat the last one.
+template <int MODE, int DH>
+__device__ __forceinline__ void sct_attn_load(const float* kbase, const float* vbase, long long k0, long long Nk, int hh, int col,
+                                              float (&kr)[MODE == SCT_F32 ? DH / 2 : (DH <= 16 ? 8 : 16)], float (&vr)[16]) {
+  constexpr int C = 8 * DH;
+  const long long krow = k0 + col < Nk ? k0 + col : Nk - 1;
+  const float* kp = kbase + (size_t)krow * C;
+  if constexpr (MODE == SCT_F32) {
+#pragma unroll
+    for (int t = 0; t < DH / 2; t += 4) {
+      const float4 v = *(const float4*)(kp + hh * (DH / 2) + t);
+      kr[t] = v.x; kr[t + 1] = v.y; kr[t + 2] = v.z; kr[t + 3] = v.w;
+    }
+  } else {
+#pragma unroll
+    for (int s = 0; s < (DH <= 16 ? 1 : 2); ++s) {
+      float v[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+      if (16 * s + 8 * hh < DH) sct_load8(kp + 16 * s + 8 * hh, v);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) kr[8 * s + j] = v[j];
+    }
+  }
+  if (k0 + 32 <= Nk) {   // wave-uniform: a full tile needs no clamp, and its 16 rows sit at constant offsets
+    const float* vp = vbase + (size_t)(k0 + 4 * hh) * C;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) vr[r] = vp[((r & 3) + 8 * (r >> 2)) * C];
+  } else {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const long long key = k0 + nl_acc_row(r, hh);
+      vr[r] = vbase[(size_t)(key < Nk ? key : Nk - 1) * C];   // the probability is 0 there
+    }
+  }
+}
+
+template <int MODE, int DH>
+__global__ __launch_bounds__(256) void sct_attn_kernel(const SctAttnArgs a) {
+  if constexpr (MODE == SCT_X3) __builtin_amdgcn_s_setreg(1473, 1);
+  __shared__ float part[4][18][64];   // per wave: running maximum, sum, and the 16 accumulator registers, lane-major
+  constexpr int C = 8 * DH;
+  constexpr int KS = DH <= 16 ? 1 : 2;   // 16-wide k steps of the (zero-padded) head dimension
+  constexpr int HD = DH / 2;             // fp32: half-wave hh multiplies dimensions hh * HD .. hh * HD + HD - 1
+  constexpr int KF = MODE == SCT_F32 ? HD : 8 * KS;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, hh = lane >> 5, col = lane & 31;
+  const long long item = (long long)blockIdx.x * (4 >> a.lg) + (wave >> a.lg), Nq = a.Nq, Nk = a.Nk;
+  const int sp = wave & ((1 << a.lg) - 1);
+  const bool valid = item < a.items;   // wave-uniform
+
+  float m = -INFINITY, l = 0.f;
+  nl_f32x16 o;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) o[r] = 0.f;
+  long long b = 0, q0 = 0;
+  int h = 0;
+
+  if (valid) {
+    const long long bh = item / a.nqt;
+    h = (int)(bh & 7); b = bh >> 3; q0 = (item - bh * a.nqt) * 32;
+    const long long qrow = q0 + col < Nq ? q0 + col : Nq - 1;
+    const float* qp = a.q + ((size_t)b * Nq + qrow) * C + h * DH;
+    const float* kbase = a.k + (size_t)b * Nk * C + h * DH;
+    const float* vbase = a.v + (size_t)b * Nk * C + h * DH + (col < DH ? col : DH - 1);   // channel rows >= DH of O^T repeat the last one and are not stored
+
+    nl_i16x8 qh[KS], ql[KS];
+    float qf[HD];
+    if constexpr (MODE == SCT_F32) {
+#pragma unroll
+      for (int t = 0; t < HD; t += 4) {
+        const float4 v = *(const float4*)(qp + hh * HD + t);
+        qf[t] = v.x * a.scale; qf[t + 1] = v.y * a.scale; qf[t + 2] = v.z * a.scale; qf[t + 3] = v.w * a.scale;
+      }
+    } else {
+#pragma unroll
+      for (int s = 0; s < KS; ++s) {
+        float v[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        if (16 * s + 8 * hh < DH) sct_load8(qp + 16 * s + 8 * hh, v);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) v[j] *= a.scale;
+        sct_split8<MODE>(v, qh[s], ql[s]);
+      }
+    }
+
+    const int t0 = sp * a.tps, t1 = t0 + a.tps < a.nkt ? t0 + a.tps : a.nkt;
+    float kr[KF], vr[16];
+    if (t0 < t1) sct_attn_load<MODE, DH>(kbase, vbase, (long long)t0 * 32, Nk, hh, col, kr, vr);
+    for (int t = t0; t < t1; ++t) {
+      const long long k0 = (long long)t * 32;
+      // the next tile's operands are fetched before this tile's arithmetic
+      float kn[KF], vn[16];
+      if (t + 1 < t1) {   // wave-uniform
+        sct_attn_load<MODE, DH>(kbase, vbase, k0 + 32, Nk, hh, col, kn, vn);
+      } else {
+#pragma unroll
+        for (int j = 0; j < KF; ++j) kn[j] = kr[j];
+#pragma unroll
+        for (int r = 0; r < 16; ++r) vn[r] = vr[r];
+      }
+      // ---- S^T[key][query] of this tile
+      nl_f32x16 st;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) st[r] = 0.f;
+      if constexpr (MODE == SCT_F32) {
+#pragma unroll
+        for (int t2 = 0; t2 < HD; ++t2) st = __builtin_amdgcn_mfma_f32_32x32x2f32(kr[t2], qf[t2], st, 0, 0, 0);
+      } else {
+#pragma unroll
+        for (int s = 0; s < KS; ++s) {
+          float v[8];
+#pragma unroll
+          for (int j = 0; j < 8; ++j) v[j] = kr[8 * s + j];
+          nl_i16x8 kh, kl;
+          sct_split8<MODE>(v, kh, kl);
+          st = sct_mfma<MODE>(kh, kl, qh[s], ql[s], st);
+        }
+      }
+      // ---- online softmax of the lane's query: keys past Nk leave the maximum and the sum
+      if (k0 + 32 > Nk) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r)
+          if (k0 + nl_acc_row(r, hh) >= Nk) st[r] = -INFINITY;
+      }
+      float mx = st[0];
+#pragma unroll
+      for (int r = 1; r < 16; ++r) mx = fmaxf(mx, st[r]);
+      mx = fmaxf(mx, __shfl_xor(mx, 32));
+      const float mnew = fmaxf(m, mx);   // finite: key k0 is valid
+      const float alpha = __expf(m - mnew);
+      float p[16], ps = 0.f;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        p[r] = __expf(st[r] - mnew);
+        ps += p[r];
+      }
+      ps += __shfl_xor(ps, 32);
+      l = l * alpha + ps;
+      m = mnew;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) o[r] *= alpha;
+      // ---- O^T[channel][query] += V^T . P^T; k slot (hh, j) of step s is accumulator register 8 s + j, i.e. key k0 + nl_acc_row(8 s + j, hh)
+      if constexpr (MODE == SCT_F32) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) o = __builtin_amdgcn_mfma_f32_32x32x2f32(vr[r], p[r], o, 0, 0, 0);
+      } else {
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+          float v[8], pv[8];
+#pragma unroll
+          for (int j = 0; j < 8; ++j) { v[j] = vr[8 * s + j]; pv[j] = p[8 * s + j]; }
+          nl_i16x8 vh, vl, ph, pl;
+          sct_split8<MODE>(v, vh, vl);
+          sct_split8<MODE>(pv, ph, pl);
+          o = sct_mfma<MODE>(vh, vl, ph, pl, o);
+        }
+      }
+#pragma unroll
+      for (int j = 0; j < KF; ++j) kr[j] = kn[j];
+#pragma unroll
+      for (int r = 0; r < 16; ++r) vr[r] = vn[r];
+    }
+  }
+
+  // ---- the key ranges of an item meet in LDS; its first wave adds them in range order (one range: the factor is exp(0) = 1, the sum the wave's own)
+  part[wave][0][lane] = m;
+  part[wave][1][lane] = l;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) part[wave][2 + r][lane] = o[r];
+  __syncthreads();
+  if (valid && sp == 0 && q0 + col < Nq) {
+    const int ns = 1 << a.lg;
+    float mt = m;
+    for (int s = 1; s < ns; ++s) mt = fmaxf(mt, part[wave + s][0][lane]);
+    float lt = 0.f, ot[16];
+#pragma unroll
+    for (int r = 0; r < 16; ++r) ot[r] = 0.f;
+    for (int s = 0; s < ns; ++s) {
+      const float f = __expf(part[wave + s][0][lane] - mt);   // an empty range: exp(-inf) = 0 times its zeros
+      lt += part[wave + s][1][lane] * f;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) ot[r] += part[wave + s][2 + r][lane] * f;
+    }
+    float* op = a.out + ((size_t)b * Nq + q0 + col) * C + h * DH;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int c = nl_acc_row(r, hh);
+      if (c < DH) op[c] = ot[r] / lt;
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------------ post-attention row chain
+struct SctChainArgs {
+  const float* attn; const float* x; float* out;   // out may be x: a workgroup reads its 32 rows of x before it writes them
+  SctW wo, w1, w2;
+  const float* vec;   // the layer's vectors (layout above)
+  long long rows;
+  int C, F;
+};
+
+// LayerNorm of the wave's 8 rows of the LDS tile: in place, or (dst) to the output rows
+__device__ __forceinline__ void sct_layernorm(float* y, int ld, int C, const float* g, const float* bta, int lane, int wave, float* dst, long long row0, long long rows) {
+  const int nci = C >> 6;
+  for (int rr = 0; rr < 8; ++rr) {
+    const int row = 8 * wave + rr;
+    float v[4] = {0.f, 0.f, 0.f, 0.f}, s = 0.f;
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+      if (i < nci) { v[i] = y[row * ld + lane + 64 * i]; s += v[i]; }
+    const float mean = wave_sum(s) / (float)C;
+    float sq = 0.f;
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+      if (i < nci) { v[i] -= mean; sq += v[i] * v[i]; }
+    const float rstd = 1.f / sqrtf(wave_sum(sq) / (float)C + SCT_EPS);
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+      if (i < nci) {
+        const int c = lane + 64 * i;
+        const float r = v[i] * rstd * g[c] + bta[c];
+        if (!dst) y[row * ld + c] = r;
+        else if (row0 + row < rows) dst[(size_t)(row0 + row) * C + c] = r;
+      }
+  }
+}
+
+template <int MODE>
+__global__ __launch_bounds__(256) void sct_chain_kernel(const SctChainArgs a) {
+  if constexpr (MODE == SCT_X3) __builtin_amdgcn_s_setreg(1473, 1);
+  extern __shared__ __attribute__((aligned(16))) float sct_smem[];
+  const int C = a.C, F = a.F, ldc = C + SCT_PAD, ldf = F + SCT_PAD, c4n = C >> 2, nc = C >> 5, nf = F >> 5;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, hh = lane >> 5, col = lane & 31;
+  const long long row0 = (long long)blockIdx.x * 32;
+  float* y = sct_smem;               // [32][ldc]: the running rows
+  float* hb = sct_smem + 32 * ldc;   // [32][ldc] attention output, then [32][ldf] hidden rows
+  const float* bo = a.vec + 3 * C;
+  const float* b1 = a.vec + 4 * C;
+  const float* b2 = b1 + F;
+  const float* lnp = b2 + C;   // weight A, bias A, weight B, bias B
+
+  for (int i = threadIdx.x; i < 32 * c4n; i += 256) {
+    const int r = i / c4n, c = 4 * (i - r * c4n);
+    const long long row = row0 + r < a.rows ? row0 + r : a.rows - 1;
+    *(float4*)(hb + r * ldc + c) = *(const float4*)(a.attn + (size_t)row * C + c);
+  }
+  __syncthreads();
+  {   // out_proj + bias + residual
+    nl_f32x16 acc[2];
+    sct_zero(acc);
+    sct_gemm<MODE, 2>(acc, hb + col * ldc, C, a.wo, wave, nc, lane);
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      const int rb = wave + 4 * i;
+      if (rb >= nc) break;
+      const int n = 32 * rb + col;
+      const float bv = bo[n];
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int row = nl_acc_row(r, hh);
+        const long long grow = row0 + row < a.rows ? row0 + row : a.rows - 1;
+        y[row * ldc + n] = a.x[(size_t)grow * C + n] + (acc[i][r] + bv);
+      }
+    }
+  }
+  __syncthreads();
+  sct_layernorm(y, ldc, C, lnp, lnp + C, lane, wave, nullptr, 0, 0);
+  __syncthreads();
+  {   // linear1 + bias + ReLU -> hidden rows (the attention tile is dead)
+    nl_f32x16 acc[4];
+    sct_zero(acc);
+    sct_gemm<MODE, 4>(acc, y + col * ldc, C, a.w1, wave, nf, lane);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int rb = wave + 4 * i;
+      if (rb >= nf) break;
+      const int n = 32 * rb + col;
+      const float bv = b1[n];
+#pragma unroll
+      for (int r = 0; r < 16; ++r) hb[nl_acc_row(r, hh) * ldf + n] = fmaxf(acc[i][r] + bv, 0.f);
+    }
+  }
+  __syncthreads();
+  {   // linear2 + bias + residual
+    nl_f32x16 acc[2];
+    sct_zero(acc);
+    sct_gemm<MODE, 2>(acc, hb + col * ldf, F, a.w2, wave, nc, lane);
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      const int rb = wave + 4 * i;
+      if (rb >= nc) break;
+      const int n = 32 * rb + col;
+      const float bv = b2[n];
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int row = nl_acc_row(r, hh);
+        y[row * ldc + n] = y[row * ldc + n] + (acc[i][r] + bv);
+      }
+    }
+  }
+  __syncthreads();
+  sct_layernorm(y, ldc, C, lnp + 2 * C, lnp + 3 * C, lane, wave, a.out, row0, a.rows);
+}
+
+// ------------------------------------------------------------------------------------------ host side
+bool sct_cfg_ok(int C, int nhead, int F) {
+  return nhead == SCT_HEADS && (C == 64 || C == 128 || C == 192 || C == 256) && F >= 32 && F <= 512 && (F & 31) == 0;
+}
+constexpr int64_t SCT_MAX_ROWS = (int64_t)1 << 24;   // B * max(N0, N1): keeps every grid and the attention's work-item count far inside 32 bits
+int sct_prec_status(int precision) {
+  if (precision == NL_PREC_F16MX) return NL_ERR_UNSUPPORTED;
+  if (precision != NL_PREC_F32 && precision != NL_PREC_BF16X3 && precision != NL_PREC_BF16) return NL_ERR_BAD_ARG;
+  return NL_OK;
+}
+size_t sct_ws_part(int64_t B, int64_t N0, int64_t N1, int C) { return nl_align_up((size_t)B * (size_t)(N0 > N1 ? N0 : N1) * C * 4, 256); }
+size_t sct_proj_lds(int C) { return (size_t)2 * 32 * (C + SCT_PAD) * 4; }
+size_t sct_chain_lds(int C, int F) { return (size_t)32 * ((C + SCT_PAD) + (C > F ? C : F) + SCT_PAD) * 4; }
+
+// The kernels' dynamic LDS exceeds the 64 KB a kernel may use unasked: raise the limit to the largest supported configuration's need, once per device and kernel
+// (bit d of `done`: device d; two threads that race both set the same value)
+int sct_allow_lds(const void* kernel, size_t bytes, std::atomic<unsigned long long>& done) {
+  int dev = 0;
+  NL_CHECK_HIP(hipGetDevice(&dev));
+  const unsigned long long bit = 1ull << (dev & 63);
+  if (dev < 64 && (done.load(std::memory_order_acquire) & bit)) return NL_OK;
+  NL_CHECK_HIP(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+  if (dev < 64) done.fetch_or(bit, std::memory_order_release);
+  return NL_OK;
+}
+
+struct SctRun {
+  const unsigned char* img; int C, F, layer;
+  const float* x; const float* xpos; int64_t Nq;
+  const float* mem; const float* mpos; int64_t Nk;
+  int64_t B; float* out; unsigned char* ws; size_t part;
+};
+
+template <int MODE, int DH>
+void sct_launch_attn(const SctAttnArgs& a, hipStream_t st) {
+  hipLaunchKernelGGL((sct_attn_kernel<MODE, DH>), dim3((unsigned)nl_cdiv(a.items, 4 >> a.lg)), dim3(256), 0, st, a);
+}
+
+template <int MODE>
+int sct_run_layer(const SctRun& r, hipStream_t st) {
+  const int C = r.C, F = r.F, nc = C >> 5;
+  const SctLayout L = sct_layout(C, F);
+  const SctLayerOff& lo = L.l[r.layer];
+  const float* vec = (const float*)(r.img + lo.vec);
+  float* qb = (float*)r.ws;
+  float* kb = (float*)(r.ws + r.part);
+  float* vb = (float*)(r.ws + 2 * r.part);
+  float* ab = (float*)(r.ws + 3 * r.part);
+  const long long rowsq = r.B * r.Nq, rowsk = r.B * r.Nk;
+  const bool cross = r.layer >= 2;
+
+  static std::atomic<unsigned long long> proj_set{0}, chain_set{0};   // per mode: one pair per instantiation of this function
+  if (const int e = sct_allow_lds((const void*)sct_proj_kernel<MODE>, sct_proj_lds(256), proj_set)) return e;
+  if (const int e = sct_allow_lds((const void*)sct_chain_kernel<MODE>, sct_chain_lds(256, 512), chain_set)) return e;
+  SctProjArgs p;
+  p.x = r.x; p.pos = r.xpos;
+  p.out[0] = qb; p.out[1] = kb; p.out[2] = vb;
+  p.w = sct_mat(r.img, lo.m[0], 3 * C); p.bias = vec;
+  p.rows = rowsq; p.C = C; p.rb_lo = 0; p.rb_hi = cross ? nc : 3 * nc;
+  hipLaunchKernelGGL(sct_proj_kernel<MODE>, dim3((unsigned)nl_cdiv(rowsq, 32)), dim3(256), sct_proj_lds(C), st, p);
+  if (cross) {   // k and v of the memory side, once
+    p.x = r.mem; p.pos = r.mpos; p.rows = rowsk; p.rb_lo = nc; p.rb_hi = 3 * nc;
+    hipLaunchKernelGGL(sct_proj_kernel<MODE>, dim3((unsigned)nl_cdiv(rowsk, 32)), dim3(256), sct_proj_lds(C), st, p);
+  }
+
+  SctAttnArgs t;
+  t.q = qb; t.k = kb; t.v = vb; t.out = ab;
+  t.Nq = r.Nq; t.Nk = r.Nk; t.nqt = (int)nl_cdiv(r.Nq, 32); t.nkt = (int)nl_cdiv(r.Nk, 32); t.items = r.B * SCT_HEADS * t.nqt;
+  t.lg = t.nkt >= 16 ? 2 : t.nkt >= 4 ? 1 : 0;   // long key sequences are cut into 2 or 4 ranges: enough waves per SIMD to hide the loads; a function of Nk alone
+  t.tps = (int)nl_cdiv(t.nkt, 1 << t.lg);
+  t.scale = (float)(1.0 / sqrt((double)(C / SCT_HEADS)));
+  switch (C) {
+    case 64: sct_launch_attn<MODE, 8>(t, st); break;
+    case 128: sct_launch_attn<MODE, 16>(t, st); break;
+    case 192: sct_launch_attn<MODE, 24>(t, st); break;
+    default: sct_launch_attn<MODE, 32>(t, st); break;
+  }
+
+  SctChainArgs c;
+  c.attn = ab; c.x = r.x; c.out = r.out;
+  c.wo = sct_mat(r.img, lo.m[1], C); c.w1 = sct_mat(r.img, lo.m[2], F); c.w2 = sct_mat(r.img, lo.m[3], C);
+  c.vec = vec; c.rows = rowsq; c.C = C; c.F = F;
+  hipLaunchKernelGGL(sct_chain_kernel<MODE>, dim3((unsigned)nl_cdiv(rowsq, 32)), dim3(256), sct_chain_lds(C, F), st, c);
+  NL_LAUNCH_CHECK();
+  return NL_OK;
+}
+
+int sct_run(const SctRun& r, int precision, hipStream_t st) {
+  if (precision == NL_PREC_F32) return sct_run_layer<SCT_F32>(r, st);
+  if (precision == NL_PREC_BF16X3) return sct_run_layer<SCT_X3>(r, st);
+  return sct_run_layer<SCT_BF>(r, st);
+}
+
+// everything that can be refused without touching a pointer's target; NL_OK + *empty for B == 0
+int sct_check(const void* packed, int C, int nhead, int F, int precision, int64_t B, int64_t N0, int64_t N1, const void* const* ptrs, int nptr, const void* ws,
+              size_t ws_bytes, bool* empty) {
+  *empty = false;
+  if (B < 0 || N0 < 1 || N1 < 1) return NL_ERR_BAD_ARG;
+  if (!sct_cfg_ok(C, nhead, F)) return NL_ERR_UNSUPPORTED;
+  if (const int ps = sct_prec_status(precision)) return ps;
+  if (N0 > SCT_MAX_ROWS || N1 > SCT_MAX_ROWS || B > SCT_MAX_ROWS || B * (N0 > N1 ? N0 : N1) > SCT_MAX_ROWS) return NL_ERR_UNSUPPORTED;
+  if (B == 0) { *empty = true; return NL_OK; }
+  if (!packed || ((uintptr_t)packed & 15) != 0) return NL_ERR_BAD_ARG;
+  for (int i = 0; i < nptr; ++i)
+    if (!ptrs[i] || ((uintptr_t)ptrs[i] & 15) != 0) return NL_ERR_BAD_ARG;   // rows are read and written as 16-byte pieces
+  if (!ws || ((uintptr_t)ws & 255) != 0 || ws_bytes < 4 * sct_ws_part(B, N0, N1, C)) return NL_ERR_WORKSPACE;
+  return NL_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t nl_sct_packed_bytes(int C, int nhead, int F) { return sct_cfg_ok(C, nhead, F) ? nl_align_up(sct_layout(C, F).total, 256) : 0; }
+
+int nl_sct_pack_weights(int C, int nhead, int F, const float* const* tensors, int n_tensors, void* packed, size_t packed_bytes, void* stream) {
+  if (!sct_cfg_ok(C, nhead, F)) return NL_ERR_UNSUPPORTED;
+  if (!tensors || n_tensors != SCT_TENSORS || !packed || ((uintptr_t)packed & 15) != 0) return NL_ERR_BAD_ARG;
+  for (int i = 0; i < SCT_TENSORS; ++i)
+    if (!tensors[i]) return NL_ERR_BAD_ARG;
+  if (packed_bytes < nl_sct_packed_bytes(C, nhead, F)) return NL_ERR_WORKSPACE;
+  const SctLayout L = sct_layout(C, F);
+  hipStream_t st = (hipStream_t)stream;
+  unsigned char* img = (unsigned char*)packed;
+  // state-dict order: two encoder layers of 12 tensors (in_proj w/b, out_proj w/b, linear1 w/b, linear2 w/b, norm1 w/b, norm2 w/b), two decoder layers of 14
+  // (.., norm1 w/b [constructed, never applied], norm2 w/b, norm3 w/b)
+  const int base[SCT_LAYERS] = {0, 12, 24, 38};
+  for (int l = 0; l < SCT_LAYERS; ++l) {
+    const float* const* t = tensors + base[l];
+    const int ln = l < 2 ? 8 : 10;   // first of the four LayerNorm tensors the layer applies
+    const int N[4] = {3 * C, C, F, C}, K[4] = {C, C, C, F};
+    for (int k = 0; k < 4; ++k) {
+      SctPackArgs a{t[2 * k], img, L.l[l].m[k], N[k], K[k]};
+      hipLaunchKernelGGL(sct_pack_mat_kernel, dim3(128), dim3(256), 0, st, a);
+    }
+    float* vec = (float*)(img + L.l[l].vec);
+    const float* src[8] = {t[1], t[3], t[5], t[7], t[ln], t[ln + 1], t[ln + 2], t[ln + 3]};
+    const int cnt[8] = {3 * C, C, F, C, C, C, C, C};
+    for (int k = 0; k < 8; ++k) {
+      NL_CHECK_HIP(hipMemcpyAsync(vec, src[k], (size_t)cnt[k] * 4, hipMemcpyDeviceToDevice, st));
+      vec += cnt[k];
+    }
+  }
+  NL_LAUNCH_CHECK();
+  return NL_OK;
+}
+
+size_t nl_sct_workspace_bytes(int64_t B, int64_t N0, int64_t N1, int C, int F) {
+  (void)F;   // the hidden rows never leave LDS
+  if (B < 0 || N0 < 1 || N1 < 1 || C < 1 || B > SCT_MAX_ROWS || N0 > SCT_MAX_ROWS || N1 > SCT_MAX_ROWS || B * (N0 > N1 ? N0 : N1) > SCT_MAX_ROWS) return 0;
+  return 4 * sct_ws_part(B ? B : 1, N0, N1, C);
+}
+
+int nl_sct_layer(const void* packed, int C, int nhead, int F, int layer, int precision, const float* x, const float* x_pos, int64_t Nq, const float* mem,
+                 const float* mem_pos, int64_t Nk, int64_t B, float* out, void* ws, size_t ws_bytes, void* stream) {
+  if (layer < 0 || layer >= SCT_LAYERS) return NL_ERR_BAD_ARG;
+  if (layer < 2) {   // self layers: the memory side is the target side
+    if ((mem && mem != x) || (mem_pos && mem_pos != x_pos) || Nk != Nq) return NL_ERR_BAD_ARG;
+    mem = x; mem_pos = x_pos;
+  }
+  const void* ptrs[5] = {x, x_pos, mem, mem_pos, out};
+  bool empty;
+  if (const int s = sct_check(packed, C, nhead, F, precision, B, Nq, Nk, ptrs, 5, ws, ws_bytes, &empty)) return s;
+  if (empty) return NL_OK;
+  const SctRun r{(const unsigned char*)packed, C, F, layer, x, x_pos, Nq, mem, mem_pos, Nk, B, out, (unsigned char*)ws, sct_ws_part(B, Nq, Nk, C)};
+  return sct_run(r, precision, (hipStream_t)stream);
+}
+
+int nl_sct_forward(const void* packed, int C, int nhead, int F, int precision, const float* v0, const float* pos0, int64_t N0, const float* v1, const float* pos1,
+                   int64_t N1, int64_t B, float* out0, float* out1, void* ws, size_t ws_bytes, void* stream) {
+  const void* ptrs[6] = {v0, pos0, v1, pos1, out0, out1};
+  bool empty;
+  if (const int s = sct_check(packed, C, nhead, F, precision, B, N0, N1, ptrs, 6, ws, ws_bytes, &empty)) return s;
+  if (empty) return NL_OK;
+  if (out0 == out1) return NL_ERR_BAD_ARG;
+  const unsigned char* img = (const unsigned char*)packed;
+  unsigned char* w = (unsigned char*)ws;
+  const size_t part = sct_ws_part(B, N0, N1, C);
+  hipStream_t st = (hipStream_t)stream;
+  // out0 / out1 carry the self layers' results; the cross layers then work in place (transformer.py:57-61: layer 3 reads the OUTPUT of layer 2)
+  const SctRun r[SCT_LAYERS] = {{img, C, F, 0, v0, pos0, N0, v0, pos0, N0, B, out0, w, part},
+                                {img, C, F, 1, v1, pos1, N1, v1, pos1, N1, B, out1, w, part},
+                                {img, C, F, 2, out0, pos0, N0, out1, pos1, N1, B, out0, w, part},
+                                {img, C, F, 3, out1, pos1, N1, out0, pos0, N0, B, out1, w, part}};
+  for (int l = 0; l < SCT_LAYERS; ++l)
+    if (const int s = sct_run(r[l], precision, st)) return s;
+  return NL_OK;
+}
+
+}  // extern "C"
