@@ -8,7 +8,7 @@
 // nl_fine_match (FineMatching.forward, fine_matching.py:94-143): one wave per match.  The 49 product rows feat_f0[m] * feat_f1[m, r] are the two 32-column tiles of
 //   s2d.h's MLP (cell = 32 t + column); the logit of cell `lane` ends up in lane `lane`, and softmax (temperature 1 / sqrt C), expectation over linspace(-1, 1, 7)
 //   and the standard deviation are DPP reductions of that one wave.  Neither the products nor the hidden activations nor the logits reach memory.
-//   NL_PREC_BF16X3 multiplies as three-term split-FP16 here (s2d.h; the image's fp16 planes): the softmax multiplies a logit's error by the logit's size, and
+//   NL_PREC_BF16X3 multiplies as three-term split-FP16 here (mfma.h: nl_split_pair<true>; the image's fp16 planes): the softmax multiplies a logit's error by the logit's size, and
 //   split-bf16's 2^-17 per product missed the 1e-4 bar on nearly one-hot heat-maps.  nl_fine_windows stays split-bf16.
 // Weights come from L2 in both kernels, not from LDS as in the coarse matcher: a wave uses every fragment once per match (there the same fragments serve 32 rows x
 // 4 iterations per work item), and with the grid sized by M <= a few thousand a workgroup would fill 100 - 256 KiB of LDS to score four matches.
@@ -16,12 +16,14 @@
 #include "common.h"
 #include "mfma.h"
 #include "s2d.h"
+#include "host.h"
 
 namespace {
 
 constexpr int FINE_W = 7, FINE_WW = 49;
 
-// ------------------------------------------------------------------------------------------ proj: layout + packing
+// ------------------------------------------------------------------------------------------ proj: layout
+// bf16 hi / lo and fp32 planes of proj.weight (Cout x Cf) in mfma.h's fragment maps (written by pack.hip's nl_launch_frag_pack), then the bias
 struct FineProjLayout { size_t hi, lo, f32, bias, total; };
 __host__ __device__ inline FineProjLayout fine_proj_layout(int Cf, int Cout) {
   FineProjLayout l;
@@ -32,28 +34,6 @@ __host__ __device__ inline FineProjLayout fine_proj_layout(int Cf, int Cout) {
   l.bias = n * 8;
   l.total = l.bias + (size_t)Cout * 4;
   return l;
-}
-
-struct FinePackArgs { const float* w; const float* b; unsigned char* img; int Cf, Cout; };
-
-__global__ __launch_bounds__(256) void fine_pack_kernel(const FinePackArgs a) {
-  const FineProjLayout L = fine_proj_layout(a.Cf, a.Cout);
-  const int Cf = a.Cf, nrb = a.Cout >> 5, n = a.Cf * a.Cout;
-  for (int i = blockIdx.x * 256 + threadIdx.x; i < 2 * n + a.Cout; i += gridDim.x * 256) {
-    if (i < n) {   // bf16 planes: fragment (s, rb), lane, slot j <-> W[32 rb + (lane & 31)][16 s + 8 (lane >> 5) + j]
-      const int j = i & 7, lane = (i >> 3) & 63, f = i >> 9, rb = f % nrb, s = f / nrb;
-      const float v = a.w[(size_t)(32 * rb + (lane & 31)) * Cf + 16 * s + 8 * (lane >> 5) + j];
-      const unsigned short h = nl_f2bf(v);
-      ((unsigned short*)(a.img + L.hi))[i] = h;
-      ((unsigned short*)(a.img + L.lo))[i] = nl_f2bf(v - __uint_as_float((unsigned)h << 16));
-    } else if (i < 2 * n) {   // fp32: fragment (g, t, rb), lane <-> W[32 rb + (lane & 31)][8 g + 4 (lane >> 5) + t]
-      const int e = i - n;
-      const int lane = e & 63, f = e >> 6, rb = f % nrb, t = (f / nrb) & 3, g = f / (4 * nrb);
-      ((float*)(a.img + L.f32))[e] = a.w[(size_t)(32 * rb + (lane & 31)) * Cf + 8 * g + 4 * (lane >> 5) + t];
-    } else {
-      ((float*)(a.img + L.bias))[i - 2 * n] = a.b[i - 2 * n];
-    }
-  }
 }
 
 // ------------------------------------------------------------------------------------------ windows
@@ -108,7 +88,7 @@ __global__ __launch_bounds__(256) void fine_win_bf16_kernel(const FineWinArgs a)
 
   nl_f32x16 acc[2][2];
 #pragma unroll
-  for (int t = 0; t < 2; ++t)
+  for (int t = 0; t < 2; ++t)   // (written out: with nl_acc_zero this kernel compiles to other code)
 #pragma unroll
     for (int j = 0; j < 2; ++j)
 #pragma unroll
@@ -128,16 +108,16 @@ __global__ __launch_bounds__(256) void fine_win_bf16_kernel(const FineWinArgs a)
       nl_split_bf16_pair(x0.z, x0.w, ph[1], pl[1]);
       nl_split_bf16_pair(x1.x, x1.y, ph[2], pl[2]);
       nl_split_bf16_pair(x1.z, x1.w, ph[3], pl[3]);
-      ah[t] = s2d_frag(ph[0], ph[1], ph[2], ph[3]);
-      al[t] = s2d_frag(pl[0], pl[1], pl[2], pl[3]);
+      ah[t] = nl_frag(ph[0], ph[1], ph[2], ph[3]);
+      al[t] = nl_frag(pl[0], pl[1], pl[2], pl[3]);
     }
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
       if (j == 1 && !has1) break;
       const int f = (s * nrb + rb0 + j) * 64 + lane;
-      const nl_i16x8 bh = s2d_frag(whi[f]);
+      const nl_i16x8 bh = nl_frag(whi[f]);
       if (X3) {
-        const nl_i16x8 bl = s2d_frag(wlo[f]);
+        const nl_i16x8 bl = nl_frag(wlo[f]);
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
           acc[t][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[t], bh, acc[t][j], 0, 0, 0);
@@ -163,12 +143,7 @@ __global__ __launch_bounds__(256) void fine_win_f32_kernel(const FineWinArgs a) 
   const float* row[2] = {fine_cell_row(a, m, col), fine_cell_row(a, m, 32 + col)};
 
   nl_f32x16 acc[2][2];
-#pragma unroll
-  for (int t = 0; t < 2; ++t)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[t][j][r] = 0.f;
+  nl_acc_zero(acc);
 
   for (int g = 0; g < ng; ++g) {
     float x[2][4];
@@ -219,7 +194,7 @@ __device__ __forceinline__ void fine_finish(const FineMatchArgs& a, const float 
   }
 }
 
-// F16: the parity mode multiplies as three-term split-FP16 (s2d.h), from the image's fp16 planes
+// F16: the parity mode multiplies as three-term split-FP16 (mfma.h), from the image's fp16 planes
 template <bool X3, bool F16>
 __global__ __launch_bounds__(256) void fine_match_bf16_kernel(const FineMatchArgs a) {
   if constexpr (F16) __builtin_amdgcn_s_setreg(1473, 1);   // MODE.FP16_OVFL: conversions to f16 saturate at 65504 instead of producing inf (as tgemm.hip's split-FP16 rows)
@@ -238,20 +213,20 @@ __global__ __launch_bounds__(256) void fine_match_bf16_kernel(const FineMatchArg
   const float* yb = a.f1 + ((size_t)m * FINE_WW + min(32 + col, FINE_WW - 1)) * C + 8 * hh;   // columns 49 .. 63 repeat cell 48; their logits are dropped
 
   nl_f32x16 acc[2][4];
-  s2d_zero(acc);
+  nl_acc_zero(acc);
   for (int s = 0; s < nk1; ++s) {
     const float4 x0 = *(const float4*)(xp + 16 * s), x1 = *(const float4*)(xp + 16 * s + 4);
     const float4 ya0 = *(const float4*)(ya + 16 * s), ya1 = *(const float4*)(ya + 16 * s + 4);
     const float4 yb0 = *(const float4*)(yb + 16 * s), yb1 = *(const float4*)(yb + 16 * s + 4);
     unsigned ph[2][4], pl[2][4];
-    s2d_split_pair<F16>(x0.x * ya0.x, x0.y * ya0.y, ph[0][0], pl[0][0]);
-    s2d_split_pair<F16>(x0.z * ya0.z, x0.w * ya0.w, ph[0][1], pl[0][1]);
-    s2d_split_pair<F16>(x1.x * ya1.x, x1.y * ya1.y, ph[0][2], pl[0][2]);
-    s2d_split_pair<F16>(x1.z * ya1.z, x1.w * ya1.w, ph[0][3], pl[0][3]);
-    s2d_split_pair<F16>(x0.x * yb0.x, x0.y * yb0.y, ph[1][0], pl[1][0]);
-    s2d_split_pair<F16>(x0.z * yb0.z, x0.w * yb0.w, ph[1][1], pl[1][1]);
-    s2d_split_pair<F16>(x1.x * yb1.x, x1.y * yb1.y, ph[1][2], pl[1][2]);
-    s2d_split_pair<F16>(x1.z * yb1.z, x1.w * yb1.w, ph[1][3], pl[1][3]);
+    nl_split_pair<F16>(x0.x * ya0.x, x0.y * ya0.y, ph[0][0], pl[0][0]);
+    nl_split_pair<F16>(x0.z * ya0.z, x0.w * ya0.w, ph[0][1], pl[0][1]);
+    nl_split_pair<F16>(x1.x * ya1.x, x1.y * ya1.y, ph[0][2], pl[0][2]);
+    nl_split_pair<F16>(x1.z * ya1.z, x1.w * ya1.w, ph[0][3], pl[0][3]);
+    nl_split_pair<F16>(x0.x * yb0.x, x0.y * yb0.y, ph[1][0], pl[1][0]);
+    nl_split_pair<F16>(x0.z * yb0.z, x0.w * yb0.w, ph[1][1], pl[1][1]);
+    nl_split_pair<F16>(x1.x * yb1.x, x1.y * yb1.y, ph[1][2], pl[1][2]);
+    nl_split_pair<F16>(x1.z * yb1.z, x1.w * yb1.w, ph[1][3], pl[1][3]);
     s2d_layer1_step<X3, F16>(acc, w1hi, w1lo, s, lane, ph, pl);
   }
   s2d_layer2<X3, F16>(acc, small + 64 * hh, w2hi, w2lo, lane);
@@ -276,7 +251,7 @@ __global__ __launch_bounds__(256) void fine_match_f32_kernel(const FineMatchArgs
   const float* yb = a.f1 + ((size_t)m * FINE_WW + min(32 + col, FINE_WW - 1)) * C + 4 * hh;
 
   nl_f32x16 acc[2][4];
-  s2d_zero(acc);
+  nl_acc_zero(acc);
   for (int g = 0; g < ng; ++g) {
     const float4 x = *(const float4*)(xp + 8 * g), va = *(const float4*)(ya + 8 * g), vb = *(const float4*)(yb + 8 * g);
     const float pa[4] = {x.x * va.x, x.y * va.y, x.z * va.z, x.w * va.w};
@@ -291,12 +266,6 @@ __global__ __launch_bounds__(256) void fine_match_f32_kernel(const FineMatchArgs
 
 bool fine_c_ok(int C) { return s2d_c_ok(C); }
 constexpr int64_t FINE_MAX_M = 1 << 24;
-// BAD_ARG / UNSUPPORTED / OK for a precision argument (as nl_s2d_match)
-int fine_prec_status(int precision) {
-  if (precision == NL_PREC_F16MX) return NL_ERR_UNSUPPORTED;
-  if (precision != NL_PREC_F32 && precision != NL_PREC_BF16X3 && precision != NL_PREC_BF16) return NL_ERR_BAD_ARG;
-  return NL_OK;
-}
 
 }  // namespace
 
@@ -308,16 +277,19 @@ int nl_fine_pack_proj(int Cf, int Cout, const float* w, const float* b, void* pa
   if (!fine_c_ok(Cf) || !fine_c_ok(Cout)) return NL_ERR_BAD_ARG;
   if (!w || !b || !packed || ((uintptr_t)packed & 15) != 0) return NL_ERR_BAD_ARG;
   if (packed_bytes < nl_fine_proj_packed_bytes(Cf, Cout)) return NL_ERR_WORKSPACE;
-  FinePackArgs a{w, b, (unsigned char*)packed, Cf, Cout};
-  hipLaunchKernelGGL(fine_pack_kernel, dim3(128), dim3(256), 0, (hipStream_t)stream, a);
-  NL_LAUNCH_CHECK();
+  const FineProjLayout L = fine_proj_layout(Cf, Cout);
+  unsigned char* img = (unsigned char*)packed;
+  hipStream_t st = (hipStream_t)stream;
+  if (const int e = nl_launch_frag_pack(w, Cout, Cf, (unsigned short*)(img + L.hi), (unsigned short*)(img + L.lo), nullptr, nullptr, (float*)(img + L.f32), false, st))
+    return e;
+  NL_CHECK_HIP(hipMemcpyAsync(img + L.bias, b, (size_t)Cout * 4, hipMemcpyDeviceToDevice, st));
   return NL_OK;
 }
 
 int nl_fine_windows(const void* packed, int Cf, int Cout, int precision, const float* feat_nhwc, int B, int Hf, int Wf, const int64_t* b_ids, const int64_t* j_ids,
                     int64_t M, int stride, float* out, void* stream) {
   if (M < 0 || stride < 1 || B < 1 || Hf < 1 || Wf < 1 || !fine_c_ok(Cf) || !fine_c_ok(Cout)) return NL_ERR_BAD_ARG;
-  if (const int ps = fine_prec_status(precision)) return ps;
+  if (const int ps = nl_prec_status_no_mx(precision)) return ps;
   if (M > FINE_MAX_M || (int64_t)B * Hf * Wf > ((int64_t)1 << 40)) return NL_ERR_UNSUPPORTED;
   if (M == 0) return NL_OK;
   if (!packed || !feat_nhwc || !b_ids || !j_ids || !out) return NL_ERR_BAD_ARG;
@@ -343,7 +315,7 @@ int nl_fine_windows(const void* packed, int Cf, int Cout, int precision, const f
 int nl_fine_match(const void* packed_mlp, int C, int precision, const float* feat_f0, const float* feat_f1, int64_t M, const float* mkps2d_c, float* expec_f,
                   float* mkps2d_f, float* heatmap, void* stream) {
   if (M < 0 || !fine_c_ok(C)) return NL_ERR_BAD_ARG;
-  if (const int ps = fine_prec_status(precision)) return ps;
+  if (const int ps = nl_prec_status_no_mx(precision)) return ps;
   if (M > FINE_MAX_M) return NL_ERR_UNSUPPORTED;
   if (M == 0) return NL_OK;
   if (!packed_mlp || !feat_f0 || !feat_f1 || !mkps2d_c || !expec_f || !mkps2d_f) return NL_ERR_BAD_ARG;
@@ -358,7 +330,8 @@ int nl_fine_match(const void* packed_mlp, int C, int precision, const float* fea
   hipStream_t st = (hipStream_t)stream;
   const unsigned grid = (unsigned)nl_cdiv(M, 4);
   if (precision == NL_PREC_F32) {
-    NL_CHECK_HIP(hipFuncSetAttribute((const void*)fine_match_f32_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, S2D_F32_LDS));
+    static std::atomic<unsigned long long> lds_set{0};
+    if (const int e = nl_allow_dynamic_lds((const void*)fine_match_f32_kernel, S2D_F32_LDS, lds_set)) return e;
     hipLaunchKernelGGL(fine_match_f32_kernel, dim3(grid), dim3(256), S2D_F32_LDS, st, a);
   } else if (precision == NL_PREC_BF16X3) {
     hipLaunchKernelGGL((fine_match_bf16_kernel<true, true>), dim3(grid), dim3(256), 0, st, a);

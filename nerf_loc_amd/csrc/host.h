@@ -1,11 +1,32 @@
-// Shared header of the HOST units of libnerfloc_render.so — abi.hip, pack.hip, render.hip and render_bwd.hip — and of those only: no kernel file includes it and
-// common.h does not.  It holds the types the drivers hand to each other (packed-blob layout, per-stage buffer sets, GEMM descriptors, the frame) and ONE
-// declaration of every host function that one of the four units defines and another calls, grouped by the defining file (default arguments live here only),
-// all in namespace nlhost (hidden visibility like everything else; exports.map lists the C-ABI alone).  The defining unit includes it too, so a definition
-// that drifts from its declaration is an ambiguous call / a redefined default argument at compile time or an undefined symbol at link time (-Wl,--no-undefined).
-// What only one unit uses stays static / in an anonymous namespace of that unit.  Kernel launchers shared with the kernel files: launch.h.
+// Shared header of the HOST units of libnerfloc_render.so — abi.hip, pack.hip, render.hip and render_bwd.hip.  common.h does not include it, and of the kernel
+// files only the localisation head's (s2d.hip, fine.hip, sct.hip) do, for the two entry-point helpers at its top (nl_prec_status_no_mx, nl_allow_dynamic_lds).
+// It holds the types the drivers hand to each other (packed-blob layout, per-stage buffer sets, GEMM descriptors, the frame) and ONE declaration of every host
+// function that one of the four units defines and another calls, grouped by the defining file (default arguments live here only), all in namespace nlhost
+// (hidden visibility like everything else; exports.map lists the C-ABI alone).  The defining unit includes it too, so a definition that drifts from its
+// declaration is an ambiguous call / a redefined default argument at compile time or an undefined symbol at link time (-Wl,--no-undefined). What only one unit
+// uses stays static / in an anonymous namespace of that unit.  Kernel launchers shared with the kernel files: launch.h.
 #pragma once
+#include <atomic>
 #include "common.h"
+
+// ---- entry-point helpers of the units whose kernels have no NL_PREC_F16MX form (s2d.hip, fine.hip, sct.hip) -------------------------------------------
+// NL_OK / NL_ERR_UNSUPPORTED (F16MX) / NL_ERR_BAD_ARG (no precision at all) for a precision argument
+inline int nl_prec_status_no_mx(int precision) {
+  if (precision == NL_PREC_F16MX) return NL_ERR_UNSUPPORTED;
+  if (precision != NL_PREC_F32 && precision != NL_PREC_BF16X3 && precision != NL_PREC_BF16) return NL_ERR_BAD_ARG;
+  return NL_OK;
+}
+// A kernel whose dynamic LDS may exceed the 64 KB a kernel can use unasked: raise its limit to `bytes`, the largest supported configuration's need, once per device
+// and kernel (`done`: one static per kernel; bit d = device d; two threads that race both set the same value).  Each launch still asks for its own size.
+inline int nl_allow_dynamic_lds(const void* kernel, size_t bytes, std::atomic<unsigned long long>& done) {
+  int dev = 0;
+  NL_CHECK_HIP(hipGetDevice(&dev));
+  const unsigned long long bit = 1ull << (dev & 63);
+  if (dev < 64 && (done.load(std::memory_order_acquire) & bit)) return NL_OK;
+  NL_CHECK_HIP(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+  if (dev < 64) done.fetch_or(bit, std::memory_order_release);
+  return NL_OK;
+}
 
 struct nl_frame {
   NlViews views;

@@ -10,6 +10,13 @@
 // — a process may drive several GPUs through several HipRenderers.  < 0: NL_ERR_HIP
 int nl_persistent_cus();
 
+// ---- pack.hip --------------------------------------------------------------------------------------------
+// An N x K row-major fp32 matrix (device) into fragment planes of N * K elements each (mfma.h: nl_frag16_src for the four 16-bit planes — acc_order: its
+// permuted form — and nl_frag32_src for the fp32 plane); a null plane is not stored (the maps are walked all the same).  N a multiple of 32, K of 16.
+// The weight images of s2d.hip, fine.hip and sct.hip.
+int nl_launch_frag_pack(const float* w, int N, int K, unsigned short* bf_hi, unsigned short* bf_lo, unsigned short* f16_hi, unsigned short* f16_lo, float* f32,
+                        bool acc_order, hipStream_t st);
+
 // ---- gemm.hip --------------------------------------------------------------------------------------------
 int nl_gemm_launch(const NlGemmArgs& a, int precision, hipStream_t stream);
 

@@ -1,5 +1,7 @@
-// Device helpers shared by the units that use MFMA, LDS-DMA or split precision (gfx950 only): ONE definition of what the kernel files used to copy.
-// Include after common.h.  Everything here is __device__ __forceinline__ (no emitted symbol) and carries the nl_ prefix; kernels, argument structs and
+// Device helpers shared by the units that use MFMA, LDS-DMA or split precision (gfx950 only): ONE definition of what the kernel files used to copy —
+// vector types, pair conversions, the 16-bit operand helpers of the 32x32x16 MFMAs (nl_frag, nl_split_pair, nl_mfma, nl_acc_zero) and the two fragment maps of a
+// packed weight matrix (nl_frag16_src, nl_frag32_src: what pack.hip's frag_pack_kernel writes and what s2d.h, fine.hip and sct.hip read).
+// Include after common.h.  Everything here is __device__ __forceinline__ or inline (no emitted symbol) and carries the nl_ prefix; kernels, argument structs and
 // per-kernel geometry stay in their files.
 #pragma once
 #include <utility>
@@ -9,7 +11,8 @@
 typedef __bf16 nl_bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 nl_bf16x4 __attribute__((ext_vector_type(4)));
 typedef _Float16 nl_f16x8 __attribute__((ext_vector_type(8)));
-typedef short nl_i16x8 __attribute__((ext_vector_type(8)));   // 8 bf16 as raw 16-bit lanes (gemm.hip, s2d.hip)
+typedef _Float16 nl_f16x2 __attribute__((ext_vector_type(2)));
+typedef short nl_i16x8 __attribute__((ext_vector_type(8)));   // 8 bf16 / fp16 as raw 16-bit lanes (gemm.hip, s2d.h, fine.hip, sct.hip)
 typedef unsigned short nl_u16x2 __attribute__((ext_vector_type(2)));
 typedef int nl_i32x8 __attribute__((ext_vector_type(8)));
 typedef float nl_f32x4 __attribute__((ext_vector_type(4)));
@@ -109,8 +112,68 @@ __device__ __forceinline__ nl_f32x16 nl_mfma(const nl_bf16x8& a, const nl_bf16x8
   if constexpr (F16) return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(nl_f16x8, a), __builtin_bit_cast(nl_f16x8, b), c, 0, 0, 0);
   else return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
 }
+template <bool F16>
+__device__ __forceinline__ nl_f32x16 nl_mfma(const nl_i16x8 a, const nl_i16x8 b, const nl_f32x16 c) {   // the same on raw 16-bit lanes
+  if constexpr (F16) return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(nl_f16x8, a), __builtin_bit_cast(nl_f16x8, b), c, 0, 0, 0);
+  else return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
+}
 // accumulator register r of half-wave hh -> row of the 32x32 tile (C/D layout of the 32x32 MFMAs)
 __device__ __forceinline__ int nl_acc_row(int r, int hh) { return (r & 3) + 8 * (r >> 2) + 4 * hh; }
+template <int NB>
+__device__ __forceinline__ void nl_acc_zero(nl_f32x16 (&acc)[NB]) {
+#pragma unroll
+  for (int i = 0; i < NB; ++i)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[i][r] = 0.f;
+}
+template <int A, int B>
+__device__ __forceinline__ void nl_acc_zero(nl_f32x16 (&acc)[A][B]) {
+#pragma unroll
+  for (int t = 0; t < A; ++t) nl_acc_zero(acc[t]);
+}
+
+// A 16-bit operand from raw dwords.  The operands are split-bf16 (hi = bf16(v), lo = bf16(v - hi): 2^-17 per product, any magnitude) or, F16, split-FP16
+// (hi = f16(v), lo = f16(v - hi): 2^-22 per product while |v| < 65504; the parity mode of the units whose logits feed a softmax, which multiplies a logit's error
+// by the logit's size).  Same storage, same fragment order.
+__device__ __forceinline__ nl_i16x8 nl_frag(const uint4 v) { return __builtin_bit_cast(nl_i16x8, v); }
+__device__ __forceinline__ nl_i16x8 nl_frag(unsigned a, unsigned b, unsigned c, unsigned d) { return __builtin_bit_cast(nl_i16x8, nl_u32x4{a, b, c, d}); }
+template <bool F16>
+__device__ __forceinline__ void nl_split_pair(float a, float b, unsigned& hi, unsigned& lo) {
+  if constexpr (F16) {
+    const nl_f32x2 v = {a, b};
+    const nl_f16x2 h = __builtin_convertvector(v, nl_f16x2);
+    hi = __builtin_bit_cast(unsigned, h);
+    lo = __builtin_bit_cast(unsigned, __builtin_convertvector(v - __builtin_convertvector(h, nl_f32x2), nl_f16x2));
+  } else {
+    nl_split_bf16_pair(a, b, hi, lo);
+  }
+}
+
+// ------------------------------------------------------------------ fragment maps of a packed N x K weight matrix (row-major source, nrb = N / 32 row blocks)
+// The source offset of element i of a plane; a plane is N * K elements, 64 lanes per fragment, so that a wave reads a fragment as one coalesced piece.
+// 16-bit planes: fragment (s, rb), lane, slot j <-> W[32 rb + (lane & 31)][16 s + 8 (lane >> 5) + j], 8 slots (16 B) per lane.  acc_order: the 8 columns a lane
+// holds of k-step s are the hidden units of accumulator registers 8 (s & 1) + j of 32-block s >> 1 — 16 s + 8 (j >> 2) + 4 (lane >> 5) + (j & 3) — for a layer whose
+// B operand is the previous layer's accumulators (s2d.h: layer 2).
+__host__ __device__ inline size_t nl_frag16_src(int i, int nrb, int K, bool acc_order) {
+  const int j = i & 7, lane = (i >> 3) & 63, f = i >> 9, rb = f % nrb, s = f / nrb, hh = lane >> 5;
+  return (size_t)(32 * rb + (lane & 31)) * K + 16 * s + (acc_order ? 8 * (j >> 2) + 4 * hh + (j & 3) : 8 * hh + j);
+}
+// fp32 plane (v_mfma_f32_32x32x2_f32: half-wave hh supplies k slot hh): fragment (g, t, rb), lane <-> W[32 rb + (lane & 31)][8 g + 4 (lane >> 5) + t], t < 4.
+// Read with g = 4 b + (t' >> 2), t = t' & 3 this is already the accumulator order: column 32 b + 8 (t' >> 2) + 4 hh + (t' & 3) = register t' of 32-block b.
+__host__ __device__ inline size_t nl_frag32_src(int i, int nrb, int K) {
+  const int lane = i & 63, f = i >> 6, rb = f % nrb, q = f / nrb;   // q = 4 g + t
+  return (size_t)(32 * rb + (lane & 31)) * K + 8 * (q >> 2) + 4 * (lane >> 5) + (q & 3);
+}
+// one value into the 16-bit planes that exist: bf16 hi / lo (round to nearest even, lo = bf16(v - float(hi))) and fp16 hi / lo (lo = f16(v - float(hi))).
+// All four conversions are computed; only the store of a null plane is skipped.
+__device__ __forceinline__ void nl_store_split(float v, size_t i, unsigned short* bf_hi, unsigned short* bf_lo, unsigned short* f16_hi, unsigned short* f16_lo) {
+  const unsigned short h = nl_f2bf(v);
+  if (bf_hi) bf_hi[i] = h;
+  if (bf_lo) bf_lo[i] = nl_f2bf(v - __uint_as_float((unsigned)h << 16));
+  const _Float16 g = (_Float16)v;
+  if (f16_hi) f16_hi[i] = __builtin_bit_cast(unsigned short, g);
+  if (f16_lo) f16_lo[i] = __builtin_bit_cast(unsigned short, (_Float16)(v - (float)g));
+}
 
 // ------------------------------------------------------------------ e2m3 (fp6) encoder of the weight-packing kernels
 __device__ __forceinline__ unsigned nl_e2m3(float a) {   // a >= 0, already divided by the block scale; round to nearest even, saturating at 7.5

@@ -1,4 +1,5 @@
-// The packed weight blob of libnerfloc_render.so: the weight table, the blob's layout (make_layout), the kernels that write its images and nl_pack_weights.
+// The packed weight blob of libnerfloc_render.so: the weight table, the blob's layout (make_layout), the kernels that write its images and nl_pack_weights —
+// and the fragment packer of the localisation head's images (nl_launch_frag_pack: s2d.hip, fine.hip, sct.hip).
 #include <stddef.h>
 #include <stdlib.h>
 #include <string.h>
@@ -264,6 +265,22 @@ __global__ void copy_kernel(const float* __restrict__ src, float* __restrict__ d
   if (i < n) dst[i] = src[i];
 }
 
+// An N x K row-major fp32 matrix into up to five planes of N * K elements each, in mfma.h's fragment maps: bf16 hi / lo and fp16 hi / lo (nl_frag16_src; acc_order:
+// its permuted form) and fp32 (nl_frag32_src).  A null plane is not stored; both maps are walked whatever planes exist.
+struct FragPackArgs {
+  const float* w;
+  unsigned short *bf_hi, *bf_lo, *f16_hi, *f16_lo;
+  float* f32;
+  int N, K, acc_order;
+};
+__global__ __launch_bounds__(256) void frag_pack_kernel(const FragPackArgs a) {
+  const int nrb = a.N >> 5, n = a.N * a.K;
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
+    nl_store_split(a.w[nl_frag16_src(i, nrb, a.K, a.acc_order != 0)], i, a.bf_hi, a.bf_lo, a.f16_hi, a.f16_lo);
+    if (a.f32) a.f32[i] = a.w[nl_frag32_src(i, nrb, a.K)];
+  }
+}
+
 struct Packer {
   const float* const* t;
   char* base;
@@ -394,6 +411,15 @@ PackInfo pack_info(const void* pk) {
 }
 
 }  // namespace nlhost
+
+int nl_launch_frag_pack(const float* w, int N, int K, unsigned short* bf_hi, unsigned short* bf_lo, unsigned short* f16_hi, unsigned short* f16_lo, float* f32,
+                        bool acc_order, hipStream_t st) {
+  if (!w || N < 32 || (N & 31) != 0 || K < 16 || (K & 15) != 0 || (int64_t)N * K > (1 << 30)) return NL_ERR_BAD_ARG;   // whole fragments; element indices are ints
+  const FragPackArgs a{w, bf_hi, bf_lo, f16_hi, f16_lo, f32, N, K, acc_order ? 1 : 0};
+  hipLaunchKernelGGL(frag_pack_kernel, dim3(128), dim3(256), 0, st, a);
+  NL_LAUNCH_CHECK();
+  return NL_OK;
+}
 
 extern "C" {
 

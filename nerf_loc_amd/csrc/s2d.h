@@ -1,7 +1,8 @@
 // What the two users of the matcher MLP (C -> 128 -> ReLU -> 128 -> ReLU -> 1) share: s2d.hip (coarse: every 3-D row against every 2-D column) and fine.hip (fine: a
-// match's centre descriptor against its 49 window cells).  ONE packed image (nl_s2d_pack_weights), one fragment / accumulator convention, one copy of the layer
-// bodies.  Everything here is __device__ __forceinline__ or constexpr; how the B operand of layer 1 is built, where the weights live (LDS or L2) and what happens to
-// the 128 -> 1 output stay in the kernel files.  Include after common.h and mfma.h.
+// match's centre descriptor against its 49 window cells).  ONE packed image (nl_s2d_pack_weights: s2d_layout), the accumulator convention (s2d_unit) and one copy
+// of the layer bodies and of the last layer (s2d_logits) — nothing else: the 16-bit operand helpers (nl_frag, nl_split_pair, nl_mfma, nl_acc_zero) and the fragment
+// maps of the image's planes are mfma.h's.  Everything here is __device__ __forceinline__ or constexpr; how the B operand of layer 1 is built, where the weights live
+// (LDS or L2) and what happens to the 128 -> 1 output stay in the kernel files.  Include after common.h and mfma.h.
 #pragma once
 #include "common.h"
 #include "mfma.h"
@@ -38,39 +39,7 @@ inline bool s2d_c_ok(int C) { return C >= 32 && C <= 256 && (C & 31) == 0; }
 // hidden unit held by accumulator register r of 32-block b in half-wave hh (C/D layout of the 32x32 MFMAs: row = (r & 3) + 8 (r >> 2) + 4 hh)
 __host__ __device__ inline int s2d_unit(int b, int r, int hh) { return 32 * b + 8 * (r >> 2) + 4 * hh + (r & 3); }
 
-__device__ __forceinline__ nl_i16x8 s2d_frag(const uint4 v) { return __builtin_bit_cast(nl_i16x8, v); }
-__device__ __forceinline__ nl_i16x8 s2d_frag(unsigned a, unsigned b, unsigned c, unsigned d) { return __builtin_bit_cast(nl_i16x8, nl_u32x4{a, b, c, d}); }
-
-// The 16-bit operands are split-bf16 (hi = bf16(v), lo = bf16(v - hi): 2^-17 per product, any magnitude) or, F16, split-FP16 (hi = f16(v), lo = f16(v - hi): 2^-22
-// per product while |v| < 65504; the fine matcher's parity mode, whose softmax multiplies a logit error by the logit's size).  Same storage, same fragment order.
-typedef _Float16 s2d_f16x2 __attribute__((ext_vector_type(2)));
-template <bool F16>
-__device__ __forceinline__ void s2d_split_pair(float a, float b, unsigned& hi, unsigned& lo) {
-  if constexpr (F16) {
-    const nl_f32x2 v = {a, b};
-    const s2d_f16x2 h = __builtin_convertvector(v, s2d_f16x2);
-    hi = __builtin_bit_cast(unsigned, h);
-    lo = __builtin_bit_cast(unsigned, __builtin_convertvector(v - __builtin_convertvector(h, nl_f32x2), s2d_f16x2));
-  } else {
-    nl_split_bf16_pair(a, b, hi, lo);
-  }
-}
-template <bool F16>
-__device__ __forceinline__ nl_f32x16 s2d_mfma(const nl_i16x8 a, const nl_i16x8 b, const nl_f32x16 c) {
-  if constexpr (F16) return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(nl_f16x8, a), __builtin_bit_cast(nl_f16x8, b), c, 0, 0, 0);
-  else return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-}
-
-__device__ __forceinline__ void s2d_zero(nl_f32x16 (&acc)[2][4]) {
-#pragma unroll
-  for (int t = 0; t < 2; ++t)
-#pragma unroll
-    for (int b = 0; b < 4; ++b)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[t][b][r] = 0.f;
-}
-
-// ---- split-bf16 path.  acc[t][b]: column tile t (32 pairs), hidden 32-block b.
+// ---- 16-bit path (split-bf16 or, F16, split-FP16: mfma.h).  acc[t][b]: column tile t (32 pairs), hidden 32-block b.
 // k-step s of layer 1: the four row blocks of W1 against the two tiles' B operands (hi / lo words of 8 products per lane)
 template <bool X3, bool F16 = false>
 __device__ __forceinline__ void s2d_layer1_step(nl_f32x16 (&acc)[2][4], const uint4* w1hi, const uint4* w1lo, int s, int lane, const unsigned (&ph)[2][4],
@@ -78,23 +47,23 @@ __device__ __forceinline__ void s2d_layer1_step(nl_f32x16 (&acc)[2][4], const ui
   nl_i16x8 bh[2], bl[2];
 #pragma unroll
   for (int t = 0; t < 2; ++t) {
-    bh[t] = s2d_frag(ph[t][0], ph[t][1], ph[t][2], ph[t][3]);
-    bl[t] = s2d_frag(pl[t][0], pl[t][1], pl[t][2], pl[t][3]);
+    bh[t] = nl_frag(ph[t][0], ph[t][1], ph[t][2], ph[t][3]);
+    bl[t] = nl_frag(pl[t][0], pl[t][1], pl[t][2], pl[t][3]);
   }
 #pragma unroll
   for (int rb = 0; rb < 4; ++rb) {
     const int f = ((s << 2) + rb) * 64 + lane;
-    const nl_i16x8 ah = s2d_frag(w1hi[f]);
+    const nl_i16x8 ah = nl_frag(w1hi[f]);
     if (X3) {
-      const nl_i16x8 al = s2d_frag(w1lo[f]);
+      const nl_i16x8 al = nl_frag(w1lo[f]);
 #pragma unroll
       for (int t = 0; t < 2; ++t) {
-        acc[t][rb] = s2d_mfma<F16>(al, bh[t], acc[t][rb]);
-        acc[t][rb] = s2d_mfma<F16>(ah, bl[t], acc[t][rb]);
+        acc[t][rb] = nl_mfma<F16>(al, bh[t], acc[t][rb]);
+        acc[t][rb] = nl_mfma<F16>(ah, bl[t], acc[t][rb]);
       }
     }
 #pragma unroll
-    for (int t = 0; t < 2; ++t) acc[t][rb] = s2d_mfma<F16>(ah, bh[t], acc[t][rb]);
+    for (int t = 0; t < 2; ++t) acc[t][rb] = nl_mfma<F16>(ah, bh[t], acc[t][rb]);
   }
 }
 
@@ -110,11 +79,11 @@ __device__ __forceinline__ void s2d_layer2(nl_f32x16 (&acc)[2][4], const float* 
       const float4 bb = *(const float4*)(b1p + 16 * b + 4 * r4);
 #pragma unroll
       for (int t = 0; t < 2; ++t) {
-        s2d_split_pair<F16>(fmaxf(acc[t][b][4 * r4 + 0] + bb.x, 0.f), fmaxf(acc[t][b][4 * r4 + 1] + bb.y, 0.f), hhi[t][b][2 * r4], hlo[t][b][2 * r4]);
-        s2d_split_pair<F16>(fmaxf(acc[t][b][4 * r4 + 2] + bb.z, 0.f), fmaxf(acc[t][b][4 * r4 + 3] + bb.w, 0.f), hhi[t][b][2 * r4 + 1], hlo[t][b][2 * r4 + 1]);
+        nl_split_pair<F16>(fmaxf(acc[t][b][4 * r4 + 0] + bb.x, 0.f), fmaxf(acc[t][b][4 * r4 + 1] + bb.y, 0.f), hhi[t][b][2 * r4], hlo[t][b][2 * r4]);
+        nl_split_pair<F16>(fmaxf(acc[t][b][4 * r4 + 2] + bb.z, 0.f), fmaxf(acc[t][b][4 * r4 + 3] + bb.w, 0.f), hhi[t][b][2 * r4 + 1], hlo[t][b][2 * r4 + 1]);
       }
     }
-  s2d_zero(acc);
+  nl_acc_zero(acc);
 #pragma unroll
   for (int b = 0; b < 4; ++b)
 #pragma unroll
@@ -122,23 +91,23 @@ __device__ __forceinline__ void s2d_layer2(nl_f32x16 (&acc)[2][4], const float* 
       nl_i16x8 bh[2], bl[2];
 #pragma unroll
       for (int t = 0; t < 2; ++t) {
-        bh[t] = s2d_frag(hhi[t][b][4 * s], hhi[t][b][4 * s + 1], hhi[t][b][4 * s + 2], hhi[t][b][4 * s + 3]);
-        bl[t] = s2d_frag(hlo[t][b][4 * s], hlo[t][b][4 * s + 1], hlo[t][b][4 * s + 2], hlo[t][b][4 * s + 3]);
+        bh[t] = nl_frag(hhi[t][b][4 * s], hhi[t][b][4 * s + 1], hhi[t][b][4 * s + 2], hhi[t][b][4 * s + 3]);
+        bl[t] = nl_frag(hlo[t][b][4 * s], hlo[t][b][4 * s + 1], hlo[t][b][4 * s + 2], hlo[t][b][4 * s + 3]);
       }
 #pragma unroll
       for (int rb = 0; rb < 4; ++rb) {
         const int f = (((b * 2 + s) << 2) + rb) * 64 + lane;
-        const nl_i16x8 ah = s2d_frag(w2hi[f]);
+        const nl_i16x8 ah = nl_frag(w2hi[f]);
         if (X3) {
-          const nl_i16x8 al = s2d_frag(w2lo[f]);
+          const nl_i16x8 al = nl_frag(w2lo[f]);
 #pragma unroll
           for (int t = 0; t < 2; ++t) {
-            acc[t][rb] = s2d_mfma<F16>(al, bh[t], acc[t][rb]);
-            acc[t][rb] = s2d_mfma<F16>(ah, bl[t], acc[t][rb]);
+            acc[t][rb] = nl_mfma<F16>(al, bh[t], acc[t][rb]);
+            acc[t][rb] = nl_mfma<F16>(ah, bl[t], acc[t][rb]);
           }
         }
 #pragma unroll
-        for (int t = 0; t < 2; ++t) acc[t][rb] = s2d_mfma<F16>(ah, bh[t], acc[t][rb]);
+        for (int t = 0; t < 2; ++t) acc[t][rb] = nl_mfma<F16>(ah, bh[t], acc[t][rb]);
       }
     }
 }
@@ -169,7 +138,7 @@ __device__ __forceinline__ void s2d_f32_layer2(nl_f32x16 (&acc)[2][4], const flo
 #pragma unroll
         for (int t = 0; t < 2; ++t) hbuf[(t * 64 + 16 * b + 4 * r4 + e) * 64] = fmaxf(acc[t][b][4 * r4 + e] + bv[e], 0.f);
     }
-  s2d_zero(acc);
+  nl_acc_zero(acc);
 #pragma unroll 2
   for (int k = 0; k < 64; ++k) {
     const float h0 = hbuf[k * 64], h1 = hbuf[(64 + k) * 64];

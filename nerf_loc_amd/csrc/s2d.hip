@@ -7,7 +7,7 @@
 // accumulators (4 x 32 hidden units x 32 pairs per tile) become layer 2's B operand without leaving the lane: layer 2's K order inside every 32-block is the
 // accumulator order (k-step s of block b takes accumulator registers 8 s .. 8 s + 7), the weights are packed to match.  The last 128 -> 1 layer is an in-lane dot
 // over the lane's 64 hidden units plus the other half-wave's 64.
-// Weights: one packed image (nl_s2d_pack_weights) of A fragments in lane order (16 B per lane, 1 KiB per fragment).  The hi planes of W1 and W2, the lo plane of W2
+// Weights: one packed image (nl_s2d_pack_weights; s2d.h: s2d_layout) of A fragments in lane order (mfma.h's fragment maps: 16 B per lane, 1 KiB per fragment).  The hi planes of W1 and W2, the lo plane of W2
 // and the bias / W3 tables are copied to LDS once per workgroup (112 KiB at C = 192, 128 KiB at C = 256) by a persistent grid; the lo plane of W1 (48 .. 64 KiB) does
 // not fit next to them and is read from L2, where every workgroup reads the same bytes.  NL_PREC_F32 reads a second, fp32 fragment image (v_mfma_f32_32x32x2_f32) from L2.
 // The value of a pair depends on its two descriptor rows, the weights and the mode only: each output column of an MFMA is an independent dot product in a fixed
@@ -17,75 +17,26 @@
 #include "common.h"
 #include "mfma.h"
 #include "s2d.h"
+#include "host.h"
 
 namespace {
 
 constexpr int S2D_NROWS = 32;              // rows n of one work item (4 waves x 2 rows x 4 iterations)
 
 // ------------------------------------------------------------------------------------------ packing
-struct S2dPackArgs {
-  const float* w1; const float* b1; const float* w2; const float* b2; const float* w3; const float* b3;
-  unsigned char* img;
-  int C;
-};
-
-__global__ __launch_bounds__(256) void s2d_pack_kernel(const S2dPackArgs a) {
-  const S2dLayout L = s2d_layout(a.C);
-  const int C = a.C;
-  const int n1 = C * S2D_H, n2 = S2D_H * S2D_H;
-  const int total = 2 * n1 + 2 * n2 + 512 + n1 + n2;
-  for (int i = blockIdx.x * 256 + threadIdx.x; i < total; i += gridDim.x * 256) {
-    if (i < n1) {   // W1, bf16 planes: fragment (s, rb), lane, slot j <-> W1[32 rb + (lane & 31)][16 s + 8 (lane >> 5) + j]
-      const int j = i & 7, lane = (i >> 3) & 63, f = i >> 9, rb = f & 3, s = f >> 2;
-      const float v = a.w1[(size_t)(32 * rb + (lane & 31)) * C + 16 * s + 8 * (lane >> 5) + j];
-      const unsigned short h = nl_f2bf(v);
-      ((unsigned short*)(a.img + L.w1hi))[i] = h;
-      ((unsigned short*)(a.img + L.w1lo))[i] = nl_f2bf(v - __uint_as_float((unsigned)h << 16));
-    } else if (i < n1 + n2) {   // W2, bf16 planes: fragment (b, s, rb): slot j <-> hidden unit of accumulator register 8 s + j of block b
-      const int e = i - n1;
-      const int j = e & 7, lane = (e >> 3) & 63, f = e >> 9, rb = f & 3, s = (f >> 2) & 1, b = f >> 3;
-      const float v = a.w2[(size_t)(32 * rb + (lane & 31)) * S2D_H + s2d_unit(b, 8 * s + j, lane >> 5)];
-      const unsigned short h = nl_f2bf(v);
-      ((unsigned short*)(a.img + L.w2hi))[e] = h;
-      ((unsigned short*)(a.img + L.w2lo))[e] = nl_f2bf(v - __uint_as_float((unsigned)h << 16));
-    } else if (i < 2 * n1 + n2) {   // W1, fp32: fragment (g, t, rb), lane <-> W1[32 rb + (lane & 31)][8 g + 4 (lane >> 5) + t]
-      const int e = i - n1 - n2;
-      const int lane = e & 63, f = e >> 6, rb = f & 3, t = (f >> 2) & 3, g = f >> 4;
-      ((float*)(a.img + L.f32w1))[e] = a.w1[(size_t)(32 * rb + (lane & 31)) * C + 8 * g + 4 * (lane >> 5) + t];
-    } else if (i < 2 * n1 + 2 * n2) {   // W2, fp32: fragment (b, t, rb), lane <-> W2[32 rb + (lane & 31)][unit of accumulator register t of block b]
-      const int e = i - 2 * n1 - n2;
-      const int lane = e & 63, f = e >> 6, rb = f & 3, t = (f >> 2) & 15, b = f >> 6;
-      ((float*)(a.img + L.f32w2))[e] = a.w2[(size_t)(32 * rb + (lane & 31)) * S2D_H + s2d_unit(b, t, lane >> 5)];
-    } else if (i >= 2 * n1 + 2 * n2 + 512) {   // the two bf16 images again as split-FP16, same fragment order (fine.hip's parity mode)
-      const int e = i - (2 * n1 + 2 * n2 + 512);
-      float v;
-      unsigned short *hi, *lo;
-      if (e < n1) {
-        const int j = e & 7, lane = (e >> 3) & 63, f = e >> 9, rb = f & 3, s = f >> 2;
-        v = a.w1[(size_t)(32 * rb + (lane & 31)) * C + 16 * s + 8 * (lane >> 5) + j];
-        hi = (unsigned short*)(a.img + L.h1hi) + e; lo = (unsigned short*)(a.img + L.h1lo) + e;
-      } else {
-        const int q = e - n1;
-        const int j = q & 7, lane = (q >> 3) & 63, f = q >> 9, rb = f & 3, s = (f >> 2) & 1, b = f >> 3;
-        v = a.w2[(size_t)(32 * rb + (lane & 31)) * S2D_H + s2d_unit(b, 8 * s + j, lane >> 5)];
-        hi = (unsigned short*)(a.img + L.h2hi) + q; lo = (unsigned short*)(a.img + L.h2lo) + q;
-      }
-      const _Float16 h = (_Float16)v, l = (_Float16)(v - (float)h);
-      *hi = __builtin_bit_cast(unsigned short, h);
-      *lo = __builtin_bit_cast(unsigned short, l);
-    } else {   // b1p / b2p / w3p [hh][16 b + r] in accumulator order, then b3 and zero padding
-      const int e = i - 2 * n1 - 2 * n2;
-      float v = 0.f;
-      if (e < 384) {
-        const int which = e >> 7, q = e & 127, hh = q >> 6, b = (q >> 4) & 3, r = q & 15;
-        const float* src = which == 0 ? a.b1 : (which == 1 ? a.b2 : a.w3);
-        v = src[s2d_unit(b, r, hh)];
-      } else if (e == 384) {
-        v = a.b3[0];
-      }
-      ((float*)(a.img + L.small))[e] = v;
-    }
+// The image's matrices are packed by pack.hip's nl_launch_frag_pack (W2's 16-bit planes in accumulator order); what is left is the 2-KB table of the last
+// layers: b1p / b2p / w3p [hh][16 b + r] in accumulator order, then b3 and zero padding
+__global__ __launch_bounds__(256) void s2d_pack_small_kernel(const float* b1, const float* b2, const float* w3, const float* b3, float* small) {
+  const int e = blockIdx.x * 256 + threadIdx.x;   // < S2D_SMALL_BYTES / 4: the launch is two blocks
+  float v = 0.f;
+  if (e < 384) {
+    const int which = e >> 7, q = e & 127, hh = q >> 6, b = (q >> 4) & 3, r = q & 15;
+    const float* src = which == 0 ? b1 : (which == 1 ? b2 : w3);
+    v = src[s2d_unit(b, r, hh)];
+  } else if (e == 384) {
+    v = b3[0];
   }
+  small[e] = v;
 }
 
 // ------------------------------------------------------------------------------------------ scores
@@ -153,7 +104,7 @@ __global__ __launch_bounds__(256) void s2d_bf16_kernel(const S2dArgs a) {
       const float* d0b = a.desc0 + (size_t)(has1 ? n0 + 1 : n0) * C + 8 * hh;
 
       nl_f32x16 acc[2][4];
-      s2d_zero(acc);
+      nl_acc_zero(acc);
 
       // ---- layer 1: K = C, the B operand built per k-step from desc1 (shared by both tiles) and the two desc0 rows
       for (int s = 0; s < nk1; ++s) {
@@ -209,7 +160,7 @@ __global__ __launch_bounds__(256) void s2d_f32_kernel(const S2dArgs a) {
       const float* d0b = a.desc0 + (size_t)(has1 ? n0 + 1 : n0) * C + 4 * hh;
 
       nl_f32x16 acc[2][4];
-      s2d_zero(acc);
+      nl_acc_zero(acc);
 
       for (int g = 0; g < ng; ++g) {
         const float4 x = *(const float4*)(d1p + 8 * g), ya = *(const float4*)(d0a + 8 * g), yb = *(const float4*)(d0b + 8 * g);
@@ -276,8 +227,13 @@ int nl_s2d_pack_weights(int C, const float* w1, const float* b1, const float* w2
   if (!w1 || !b1 || !w2 || !b2 || !w3 || !b3 || !packed) return NL_ERR_BAD_ARG;
   if (((uintptr_t)packed & 15) != 0) return NL_ERR_BAD_ARG;
   if (packed_bytes < s2d_layout(C).total) return NL_ERR_WORKSPACE;
-  S2dPackArgs a{w1, b1, w2, b2, w3, b3, (unsigned char*)packed, C};
-  hipLaunchKernelGGL(s2d_pack_kernel, dim3(128), dim3(256), 0, (hipStream_t)stream, a);
+  const S2dLayout L = s2d_layout(C);
+  unsigned char* img = (unsigned char*)packed;
+  hipStream_t st = (hipStream_t)stream;
+  auto u16 = [&](size_t off) { return (unsigned short*)(img + off); };
+  if (const int e = nl_launch_frag_pack(w1, S2D_H, C, u16(L.w1hi), u16(L.w1lo), u16(L.h1hi), u16(L.h1lo), (float*)(img + L.f32w1), false, st)) return e;
+  if (const int e = nl_launch_frag_pack(w2, S2D_H, S2D_H, u16(L.w2hi), u16(L.w2lo), u16(L.h2hi), u16(L.h2lo), (float*)(img + L.f32w2), true, st)) return e;
+  hipLaunchKernelGGL(s2d_pack_small_kernel, dim3(S2D_SMALL_BYTES / 4 / 256), dim3(256), 0, st, b1, b2, w3, b3, (float*)(img + L.small));
   NL_LAUNCH_CHECK();
   return NL_OK;
 }
@@ -291,8 +247,7 @@ int nl_s2d_match(const void* packed, int C, int precision, const float* desc0, i
                  int32_t* match_j, float* match_score, void* workspace, size_t workspace_bytes, void* stream) {
   if (N < 1 || M < 1 || C < 1) return NL_ERR_BAD_ARG;
   if (!s2d_c_ok(C) || !s2d_shape_ok(N, M)) return NL_ERR_UNSUPPORTED;
-  if (precision == NL_PREC_F16MX) return NL_ERR_UNSUPPORTED;
-  if (precision != NL_PREC_F32 && precision != NL_PREC_BF16X3 && precision != NL_PREC_BF16) return NL_ERR_BAD_ARG;
+  if (const int ps = nl_prec_status_no_mx(precision)) return ps;
   if (!packed || !desc0 || !desc1 || !match_j || !match_score) return NL_ERR_BAD_ARG;
   if ((((uintptr_t)packed | (uintptr_t)desc0 | (uintptr_t)desc1) & 15) != 0) return NL_ERR_BAD_ARG;   // read as 16-byte pieces
   if ((((uintptr_t)scores_out | (uintptr_t)match_j | (uintptr_t)match_score) & 3) != 0) return NL_ERR_BAD_ARG;
@@ -312,16 +267,18 @@ int nl_s2d_match(const void* packed, int C, int precision, const float* desc0, i
   NL_CHECK_HIP(hipMemsetAsync(ws, 0, w.scores, st));
   const int64_t items = nl_cdiv(M, 32) * nl_cdiv(N, S2D_NROWS);
   const unsigned grid = (unsigned)(items < cus ? items : cus);
+  // dynamic LDS beyond 64 KB: each kernel's limit is raised once per device to what the largest supported C needs; a launch asks for its own size
+  static std::atomic<unsigned long long> f32_set{0}, x3_set{0}, bf_set{0};
   if (precision == NL_PREC_F32) {
-    NL_CHECK_HIP(hipFuncSetAttribute((const void*)s2d_f32_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, S2D_F32_LDS));
+    if (const int e = nl_allow_dynamic_lds((const void*)s2d_f32_kernel, S2D_F32_LDS, f32_set)) return e;
     hipLaunchKernelGGL(s2d_f32_kernel, dim3(grid), dim3(256), S2D_F32_LDS, st, a);
   } else {
-    const size_t lds = s2d_layout(C).lds_bytes;
+    const size_t lds = s2d_layout(C).lds_bytes, lds_max = s2d_layout(256).lds_bytes;
     if (precision == NL_PREC_BF16X3) {
-      NL_CHECK_HIP(hipFuncSetAttribute((const void*)s2d_bf16_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+      if (const int e = nl_allow_dynamic_lds((const void*)s2d_bf16_kernel<true>, lds_max, x3_set)) return e;
       hipLaunchKernelGGL(s2d_bf16_kernel<true>, dim3(grid), dim3(256), lds, st, a);
     } else {
-      NL_CHECK_HIP(hipFuncSetAttribute((const void*)s2d_bf16_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+      if (const int e = nl_allow_dynamic_lds((const void*)s2d_bf16_kernel<false>, lds_max, bf_set)) return e;
       hipLaunchKernelGGL(s2d_bf16_kernel<false>, dim3(grid), dim3(256), lds, st, a);
     }
   }

@@ -19,13 +19,12 @@
 //   of the workgroup, straight from L2 in 1-KB coalesced pieces (fragment order): a copy through LDS would add a barrier pair per chunk and no reuse.
 //   Measured: the kernel takes ~90 us per launch whatever the row count — it waits on these loads, which are not requested ahead of use; not yet changed.
 //
-// Precision: NL_PREC_F32 = v_mfma_f32_32x32x2_f32 on fp32 operands; NL_PREC_BF16X3 = three-term split-FP16 (s2d.h: hi = f16(v), lo = f16(v - hi)) for every product —
+// Precision: NL_PREC_F32 = v_mfma_f32_32x32x2_f32 on fp32 operands; NL_PREC_BF16X3 = three-term split-FP16 (mfma.h: hi = f16(v), lo = f16(v - hi)) for every product —
 //   the logits feed a softmax (as in fine.hip) and one format keeps one code path; NL_PREC_BF16 = one bf16 product.  LayerNorm, softmax and residuals are fp32 everywhere.
 // Every output row depends on its own row, the memory side, the weights and the mode only: fixed reduction orders, no atomics.
-#include <atomic>
 #include "common.h"
 #include "mfma.h"
-#include "s2d.h"
+#include "host.h"
 
 namespace {
 
@@ -35,9 +34,8 @@ constexpr float SCT_EPS = 1e-5f;
 enum { SCT_F32 = 0, SCT_X3 = 1, SCT_BF = 2 };   // = NL_PREC_F32 / NL_PREC_BF16X3 / NL_PREC_BF16
 
 // ------------------------------------------------------------------------------------------ packed image
-// per layer: in_proj_weight (3C x C), out_proj.weight (C x C), linear1.weight (F x C), linear2.weight (C x F), each as four planes — fp16 hi, fp16 lo, bf16 (fragment
-// (s, rb), lane, slot j <-> W[32 rb + (lane & 31)][16 s + 8 (lane >> 5) + j]) and fp32 (fragment (g, t, rb), lane <-> W[32 rb + (lane & 31)][8 g + 4 (lane >> 5) + t]) —
-// then the vectors: in_proj_bias (3C), out_proj.bias (C), linear1.bias (F), linear2.bias (C), first norm weight / bias, second norm weight / bias (C each).
+// per layer: in_proj_weight (3C x C), out_proj.weight (C x C), linear1.weight (F x C), linear2.weight (C x F), each as four planes — fp16 hi, fp16 lo, bf16 and fp32,
+// in mfma.h's fragment maps (nl_frag16_src / nl_frag32_src; written by pack.hip's nl_launch_frag_pack) — then the vectors: in_proj_bias (3C), out_proj.bias (C), linear1.bias (F), linear2.bias (C), first norm weight / bias, second norm weight / bias (C each).
 struct SctW { const uint4* hi; const uint4* lo; const uint4* bf; const float* f32; int nrb; };
 struct SctMatOff { size_t hi, lo, bf, f32; };
 struct SctLayerOff { SctMatOff m[4]; size_t vec; };
@@ -63,26 +61,6 @@ inline SctW sct_mat(const unsigned char* img, const SctMatOff& m, int N) {
   return SctW{(const uint4*)(img + m.hi), (const uint4*)(img + m.lo), (const uint4*)(img + m.bf), (const float*)(img + m.f32), N >> 5};
 }
 
-struct SctPackArgs { const float* w; unsigned char* img; SctMatOff m; int N, K; };
-
-__global__ __launch_bounds__(256) void sct_pack_mat_kernel(const SctPackArgs a) {
-  const int K = a.K, nrb = a.N >> 5, n = a.N * a.K;
-  for (int i = blockIdx.x * 256 + threadIdx.x; i < 2 * n; i += gridDim.x * 256) {
-    if (i < n) {
-      const int j = i & 7, lane = (i >> 3) & 63, f = i >> 9, rb = f % nrb, s = f / nrb;
-      const float v = a.w[(size_t)(32 * rb + (lane & 31)) * K + 16 * s + 8 * (lane >> 5) + j];
-      const _Float16 h = (_Float16)v;
-      ((unsigned short*)(a.img + a.m.hi))[i] = __builtin_bit_cast(unsigned short, h);
-      ((unsigned short*)(a.img + a.m.lo))[i] = __builtin_bit_cast(unsigned short, (_Float16)(v - (float)h));
-      ((unsigned short*)(a.img + a.m.bf))[i] = nl_f2bf(v);
-    } else {
-      const int e = i - n;
-      const int lane = e & 63, f = e >> 6, rb = f % nrb, t = (f / nrb) & 3, g = f / (4 * nrb);
-      ((float*)(a.img + a.m.f32))[e] = a.w[(size_t)(32 * rb + (lane & 31)) * K + 8 * g + 4 * (lane >> 5) + t];
-    }
-  }
-}
-
 // ------------------------------------------------------------------------------------------ operand helpers
 __device__ __forceinline__ void sct_load8(const float* p, float (&v)[8]) {
   const float4 a = *(const float4*)p, b = *(const float4*)(p + 4);
@@ -94,27 +72,20 @@ __device__ __forceinline__ void sct_split8(const float (&v)[8], nl_i16x8& hi, nl
   unsigned h[4], l[4] = {0u, 0u, 0u, 0u};
 #pragma unroll
   for (int t = 0; t < 4; ++t) {
-    if constexpr (MODE == SCT_X3) s2d_split_pair<true>(v[2 * t], v[2 * t + 1], h[t], l[t]);
+    if constexpr (MODE == SCT_X3) nl_split_pair<true>(v[2 * t], v[2 * t + 1], h[t], l[t]);
     else h[t] = nl_bf16_pair(v[2 * t], v[2 * t + 1]);
   }
-  hi = s2d_frag(h[0], h[1], h[2], h[3]);
-  lo = s2d_frag(l[0], l[1], l[2], l[3]);
+  hi = nl_frag(h[0], h[1], h[2], h[3]);
+  lo = nl_frag(l[0], l[1], l[2], l[3]);
 }
 // acc += a . b: three terms, small ones first (SCT_X3), or the one bf16 product
 template <int MODE>
 __device__ __forceinline__ nl_f32x16 sct_mfma(const nl_i16x8 ah, const nl_i16x8 al, const nl_i16x8 bh, const nl_i16x8 bl, nl_f32x16 acc) {
   if constexpr (MODE == SCT_X3) {
-    acc = s2d_mfma<true>(al, bh, acc);
-    acc = s2d_mfma<true>(ah, bl, acc);
+    acc = nl_mfma<true>(al, bh, acc);
+    acc = nl_mfma<true>(ah, bl, acc);
   }
-  return s2d_mfma<MODE == SCT_X3>(ah, bh, acc);
-}
-template <int NB>
-__device__ __forceinline__ void sct_zero(nl_f32x16 (&acc)[NB]) {
-#pragma unroll
-  for (int i = 0; i < NB; ++i)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[i][r] = 0.f;
+  return nl_mfma<MODE == SCT_X3>(ah, bh, acc);
 }
 
 // acc[i] += X[32 rows][K] . W[rows 32 rb .. 32 rb + 31][K]^T for the wave's output blocks rb = rbs + 4 i < rbe.  xrow: the lane's row (lane & 31) of the LDS tile.
@@ -146,9 +117,9 @@ __device__ __forceinline__ void sct_gemm(nl_f32x16 (&acc)[NB], const float* xrow
         const int rb = rbs + 4 * i;
         if (rb < rbe) {
           const size_t f = ((size_t)s * w.nrb + rb) * 64 + lane;
-          const nl_i16x8 bh = s2d_frag(whi[f]);
+          const nl_i16x8 bh = nl_frag(whi[f]);
           nl_i16x8 bl = bh;
-          if constexpr (MODE == SCT_X3) bl = s2d_frag(w.lo[f]);
+          if constexpr (MODE == SCT_X3) bl = nl_frag(w.lo[f]);
           acc[i] = sct_mfma<MODE>(ah, al, bh, bl, acc[i]);
         }
       }
@@ -170,7 +141,7 @@ __device__ __forceinline__ void sct_proj_pass(const SctProjArgs& a, const float*
   if (lo + wave >= hi) return;   // wave-uniform
   const int C = a.C, nc = C >> 5, hh = lane >> 5, col = lane & 31;
   nl_f32x16 acc[NB];
-  sct_zero(acc);
+  nl_acc_zero(acc);
   sct_gemm<MODE, NB>(acc, tile + col * (C + SCT_PAD), C, a.w, lo + wave, hi, lane);
 #pragma unroll
   for (int i = 0; i < NB; ++i) {
@@ -468,7 +439,7 @@ __global__ __launch_bounds__(256) void sct_chain_kernel(const SctChainArgs a) {
   __syncthreads();
   {   // out_proj + bias + residual
     nl_f32x16 acc[2];
-    sct_zero(acc);
+    nl_acc_zero(acc);
     sct_gemm<MODE, 2>(acc, hb + col * ldc, C, a.wo, wave, nc, lane);
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
@@ -489,7 +460,7 @@ __global__ __launch_bounds__(256) void sct_chain_kernel(const SctChainArgs a) {
   __syncthreads();
   {   // linear1 + bias + ReLU -> hidden rows (the attention tile is dead)
     nl_f32x16 acc[4];
-    sct_zero(acc);
+    nl_acc_zero(acc);
     sct_gemm<MODE, 4>(acc, y + col * ldc, C, a.w1, wave, nf, lane);
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
@@ -504,7 +475,7 @@ __global__ __launch_bounds__(256) void sct_chain_kernel(const SctChainArgs a) {
   __syncthreads();
   {   // linear2 + bias + residual
     nl_f32x16 acc[2];
-    sct_zero(acc);
+    nl_acc_zero(acc);
     sct_gemm<MODE, 2>(acc, hb + col * ldf, F, a.w2, wave, nc, lane);
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
@@ -528,26 +499,9 @@ bool sct_cfg_ok(int C, int nhead, int F) {
   return nhead == SCT_HEADS && (C == 64 || C == 128 || C == 192 || C == 256) && F >= 32 && F <= 512 && (F & 31) == 0;
 }
 constexpr int64_t SCT_MAX_ROWS = (int64_t)1 << 24;   // B * max(N0, N1): keeps every grid and the attention's work-item count far inside 32 bits
-int sct_prec_status(int precision) {
-  if (precision == NL_PREC_F16MX) return NL_ERR_UNSUPPORTED;
-  if (precision != NL_PREC_F32 && precision != NL_PREC_BF16X3 && precision != NL_PREC_BF16) return NL_ERR_BAD_ARG;
-  return NL_OK;
-}
 size_t sct_ws_part(int64_t B, int64_t N0, int64_t N1, int C) { return nl_align_up((size_t)B * (size_t)(N0 > N1 ? N0 : N1) * C * 4, 256); }
 size_t sct_proj_lds(int C) { return (size_t)2 * 32 * (C + SCT_PAD) * 4; }
 size_t sct_chain_lds(int C, int F) { return (size_t)32 * ((C + SCT_PAD) + (C > F ? C : F) + SCT_PAD) * 4; }
-
-// The kernels' dynamic LDS exceeds the 64 KB a kernel may use unasked: raise the limit to the largest supported configuration's need, once per device and kernel
-// (bit d of `done`: device d; two threads that race both set the same value)
-int sct_allow_lds(const void* kernel, size_t bytes, std::atomic<unsigned long long>& done) {
-  int dev = 0;
-  NL_CHECK_HIP(hipGetDevice(&dev));
-  const unsigned long long bit = 1ull << (dev & 63);
-  if (dev < 64 && (done.load(std::memory_order_acquire) & bit)) return NL_OK;
-  NL_CHECK_HIP(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-  if (dev < 64) done.fetch_or(bit, std::memory_order_release);
-  return NL_OK;
-}
 
 struct SctRun {
   const unsigned char* img; int C, F, layer;
@@ -574,9 +528,10 @@ int sct_run_layer(const SctRun& r, hipStream_t st) {
   const long long rowsq = r.B * r.Nq, rowsk = r.B * r.Nk;
   const bool cross = r.layer >= 2;
 
-  static std::atomic<unsigned long long> proj_set{0}, chain_set{0};   // per mode: one pair per instantiation of this function
-  if (const int e = sct_allow_lds((const void*)sct_proj_kernel<MODE>, sct_proj_lds(256), proj_set)) return e;
-  if (const int e = sct_allow_lds((const void*)sct_chain_kernel<MODE>, sct_chain_lds(256, 512), chain_set)) return e;
+  // the two kernels' dynamic LDS exceeds 64 KB at the larger configurations (per mode: one pair of flags per instantiation of this function)
+  static std::atomic<unsigned long long> proj_set{0}, chain_set{0};
+  if (const int e = nl_allow_dynamic_lds((const void*)sct_proj_kernel<MODE>, sct_proj_lds(256), proj_set)) return e;
+  if (const int e = nl_allow_dynamic_lds((const void*)sct_chain_kernel<MODE>, sct_chain_lds(256, 512), chain_set)) return e;
   SctProjArgs p;
   p.x = r.x; p.pos = r.xpos;
   p.out[0] = qb; p.out[1] = kb; p.out[2] = vb;
@@ -622,7 +577,7 @@ int sct_check(const void* packed, int C, int nhead, int F, int precision, int64_
   *empty = false;
   if (B < 0 || N0 < 1 || N1 < 1) return NL_ERR_BAD_ARG;
   if (!sct_cfg_ok(C, nhead, F)) return NL_ERR_UNSUPPORTED;
-  if (const int ps = sct_prec_status(precision)) return ps;
+  if (const int ps = nl_prec_status_no_mx(precision)) return ps;
   if (N0 > SCT_MAX_ROWS || N1 > SCT_MAX_ROWS || B > SCT_MAX_ROWS || B * (N0 > N1 ? N0 : N1) > SCT_MAX_ROWS) return NL_ERR_UNSUPPORTED;
   if (B == 0) { *empty = true; return NL_OK; }
   if (!packed || ((uintptr_t)packed & 15) != 0) return NL_ERR_BAD_ARG;
@@ -655,8 +610,10 @@ int nl_sct_pack_weights(int C, int nhead, int F, const float* const* tensors, in
     const int ln = l < 2 ? 8 : 10;   // first of the four LayerNorm tensors the layer applies
     const int N[4] = {3 * C, C, F, C}, K[4] = {C, C, C, F};
     for (int k = 0; k < 4; ++k) {
-      SctPackArgs a{t[2 * k], img, L.l[l].m[k], N[k], K[k]};
-      hipLaunchKernelGGL(sct_pack_mat_kernel, dim3(128), dim3(256), 0, st, a);
+      const SctMatOff& m = L.l[l].m[k];
+      if (const int e = nl_launch_frag_pack(t[2 * k], N[k], K[k], (unsigned short*)(img + m.bf), nullptr, (unsigned short*)(img + m.hi), (unsigned short*)(img + m.lo),
+                                            (float*)(img + m.f32), false, st))
+        return e;
     }
     float* vec = (float*)(img + L.l[l].vec);
     const float* src[8] = {t[1], t[3], t[5], t[7], t[ln], t[ln + 1], t[ln + 2], t[ln + 3]};

@@ -15,35 +15,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _lib
-
-_HIDDEN = 128
-_MLP_PARAMS = ("mlps.0.weight", "mlps.0.bias", "mlps.2.weight", "mlps.2.bias", "mlps.4.weight", "mlps.4.bias")
-
-
-def _check_precision(precision):
-    if precision not in _lib.PRECISIONS:
-        raise ValueError(f"unknown precision {precision!r}")
-    return precision
-
-
-class _PackedCache:
-    """Packed weights keyed like S2DMatching._packed_weights: device + (storage, version, dtype) of every parameter."""
-
-    def _cache_init(self):
-        self._packed = None
-        self._packed_key = None
-        self.pack_count = 0   # how often the weights were packed (tests watch the cache)
-
-    def _cached(self, device, names, pack):
-        ps = [self.get_parameter(n) for n in names]
-        key = (str(device),) + tuple((p.data_ptr(), p._version, p.dtype) for p in ps)
-        if self._packed is None or key != self._packed_key:
-            ts = [p.detach().to(device=device, dtype=torch.float32).contiguous() for p in ps]
-            self._packed, self._packed_key = pack(ts), key
-            self._pack_sources = ts   # alive until the stream has consumed them
-            self.pack_count += 1
-        return self._packed
-
+from ._packing import MATCHER_HIDDEN, PackedCache, check_precision, pack_matcher_mlp, require_device
 
 def gather_windows(feat_f1, b_ids, j_ids, stride, window=7):
     """(M, window^2, C): rows [b_ids, j_ids] of `rearrange(F.unfold(feat_f1, window, stride=stride, padding=window // 2), 'n (c ww) l -> n l ww c')` without
@@ -59,7 +31,7 @@ def gather_windows(feat_f1, b_ids, j_ids, stride, window=7):
     return fp[b_ids.long()[:, None], :, py, px]
 
 
-class FinePreprocess(nn.Module, _PackedCache):
+class FinePreprocess(nn.Module, PackedCache):
     """`FinePreprocess(config)` with the reference's config keys and parameter names (`proj.*`, or `down_proj.*` / `merge_feat.*` with
     fine_concat_coarse_feat), so `matcher.fine_preprocess.*` of a NeRF-Loc checkpoint loads with strict=True.
 
@@ -79,7 +51,7 @@ class FinePreprocess(nn.Module, _PackedCache):
             self.merge_feat = nn.Linear(2 * in_channels_fine, self.out_channels, bias=True)
         else:
             self.proj = nn.Linear(in_channels_fine, self.out_channels, bias=True)
-        self.precision = _check_precision(precision)
+        self.precision = check_precision(precision)
         self._cache_init()
         self._reset_parameters()
 
@@ -111,12 +83,11 @@ class FinePreprocess(nn.Module, _PackedCache):
             _lib.check(lib.nl_fine_pack_proj(self.in_channels_fine, self.out_channels, ts[0].data_ptr(), ts[1].data_ptr(), packed.data_ptr(), need, st),
                        "nl_fine_pack_proj")
             return packed
-        return self._cached(device, ("proj.weight", "proj.bias"), pack)
+        return self._cached(device, [self.proj.weight, self.proj.bias], pack)
 
     def windows(self, feat_f1, b_ids, j_ids, stride):
         """The library call: (M, 49, out_channels) from feat_f1 (B, C, Hf, Wf) — a permuted view of an NHWC tensor is used as it is."""
-        if not feat_f1.is_cuda:
-            raise RuntimeError("FinePreprocess's eval path runs only on a HIP device (no CPU fallback); move the module and its inputs to cuda")
+        require_device("FinePreprocess", feat_f1)
         if self.W != 7:
             raise RuntimeError("FinePreprocess: the HIP kernel is built for fine_window_size 7")
         if feat_f1.dim() != 4 or feat_f1.shape[1] != self.in_channels_fine:
@@ -154,7 +125,7 @@ class FinePreprocess(nn.Module, _PackedCache):
         return self.windows(feat_f1, data["b_ids"], data["j_ids"], stride)
 
 
-class FineMatching(nn.Module, _PackedCache):
+class FineMatching(nn.Module, PackedCache):
     """`FineMatching(config)` ("FineMatching with s2d paradigm") with the reference's config keys and parameter names (`mlps.{0,2,4}.*`), so
     `matcher.fine_matcher.*` of a NeRF-Loc checkpoint loads with strict=True.  precision as for FinePreprocess."""
 
@@ -163,29 +134,18 @@ class FineMatching(nn.Module, _PackedCache):
         self.correct_thr = config["correct_thr"]
         self.loss_type = config["loss_type"]
         self.feat_dim = int(config["feat_dim"])
-        self.mlps = nn.Sequential(nn.Linear(self.feat_dim, _HIDDEN), nn.ReLU(inplace=True), nn.Linear(_HIDDEN, _HIDDEN), nn.ReLU(inplace=True),
-                                  nn.Linear(_HIDDEN, 1))
-        self.precision = _check_precision(precision)
+        self.mlps = nn.Sequential(nn.Linear(self.feat_dim, MATCHER_HIDDEN), nn.ReLU(inplace=True), nn.Linear(MATCHER_HIDDEN, MATCHER_HIDDEN), nn.ReLU(inplace=True),
+                                  nn.Linear(MATCHER_HIDDEN, 1))
+        self.precision = check_precision(precision)
         self._cache_init()
 
     # ------------------------------------------------------------------ library path
     def _pack(self, device):
-        lib = _lib.load()
-        need = lib.nl_s2d_packed_weights_bytes(self.feat_dim)
-        if need == 0:
-            raise RuntimeError(f"FineMatching: feat_dim {self.feat_dim} is not supported by the HIP kernel (a multiple of 32, 32..256)")
-
-        def pack(ts):
-            packed = torch.empty(need, dtype=torch.uint8, device=device)
-            st = torch.cuda.current_stream(device).cuda_stream
-            _lib.check(lib.nl_s2d_pack_weights(self.feat_dim, *[t.data_ptr() for t in ts], packed.data_ptr(), need, st), "nl_s2d_pack_weights")
-            return packed
-        return self._cached(device, _MLP_PARAMS, pack)
+        return pack_matcher_mlp("FineMatching", self, device)
 
     def match(self, feat_f0, feat_f1, mkps2d_c, want_heatmap=False):
         """The library call: (expec_f (M, 3), mkps2d_f (M, 2), heatmap (M, 49) or None)."""
-        if not (feat_f0.is_cuda and feat_f1.is_cuda):
-            raise RuntimeError("FineMatching's eval path runs only on a HIP device (no CPU fallback); move the module and its inputs to cuda")
+        require_device("FineMatching", feat_f0, feat_f1)
         M = feat_f0.shape[0]
         if feat_f0.dim() != 2 or feat_f0.shape[1] != self.feat_dim or tuple(feat_f1.shape) != (M, 49, self.feat_dim):
             raise ValueError(f"FineMatching: features must be (M, {self.feat_dim}) and (M, 49, {self.feat_dim})")

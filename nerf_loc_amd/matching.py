@@ -12,9 +12,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-
-_HIDDEN = 128
-_PARAMS = ("mlps.0.weight", "mlps.0.bias", "mlps.2.weight", "mlps.2.bias", "mlps.4.weight", "mlps.4.bias")
+from ._packing import MATCHER_HIDDEN, PackedCache, check_precision, pack_matcher_mlp, require_device
 
 
 def sigmoid_focal_loss(logits: torch.Tensor, target: torch.Tensor, alpha: float = 0.25, gamma: float = 2.0) -> torch.Tensor:
@@ -34,7 +32,7 @@ def select_mutual_nearest(score: torch.Tensor, thr: float):
     return i_ids, all_j[i_ids]
 
 
-class S2DMatching(nn.Module):
+class S2DMatching(nn.Module, PackedCache):
     """`S2DMatching(feat_dim, thr)` with the reference's parameter names, so `matcher.coarse_matcher.*` of a NeRF-Loc checkpoint loads with strict=True.
 
     precision: "bf16x3" (default: three-term split-bf16 MFMA, within 1e-4 of the fp32 reference), "fp32" (exact fp32 products) or "bf16" (throughput, not
@@ -44,18 +42,14 @@ class S2DMatching(nn.Module):
 
     def __init__(self, feat_dim, thr=0.1, precision: str = "bf16x3", want_score_matrix: bool = True, eager_chunk_rows: int = 32):
         super().__init__()
-        self.mlps = nn.Sequential(nn.Linear(feat_dim, _HIDDEN), nn.ReLU(inplace=True), nn.Linear(_HIDDEN, _HIDDEN), nn.ReLU(inplace=True),
-                                  nn.Linear(_HIDDEN, 1))
+        self.mlps = nn.Sequential(nn.Linear(feat_dim, MATCHER_HIDDEN), nn.ReLU(inplace=True), nn.Linear(MATCHER_HIDDEN, MATCHER_HIDDEN), nn.ReLU(inplace=True),
+                                  nn.Linear(MATCHER_HIDDEN, 1))
         self.feat_dim = int(feat_dim)
         self.thr = thr
-        if precision not in _lib.PRECISIONS:
-            raise ValueError(f"unknown precision {precision!r}")
-        self.precision = precision
+        self.precision = check_precision(precision)
         self.want_score_matrix = bool(want_score_matrix)
         self.eager_chunk_rows = int(eager_chunk_rows)
-        self._packed = None
-        self._packed_key = None
-        self.pack_count = 0   # how often the weights were packed (tests watch the cache)
+        self._cache_init()
 
     # ------------------------------------------------------------------ eager path (training / autograd)
     def get_loss(self, conf, conf_gt):
@@ -70,26 +64,11 @@ class S2DMatching(nn.Module):
 
     # ------------------------------------------------------------------ library path
     def _packed_weights(self, device):
-        ps = [self.get_parameter(n) for n in _PARAMS]
-        key = (str(device),) + tuple((p.data_ptr(), p._version, p.dtype) for p in ps)
-        if self._packed is None or key != self._packed_key:
-            lib = _lib.load()
-            need = lib.nl_s2d_packed_weights_bytes(self.feat_dim)
-            if need == 0:
-                raise RuntimeError(f"S2DMatching: feat_dim {self.feat_dim} is not supported by the HIP kernel (a multiple of 32, 32..256)")
-            ts = [p.detach().to(device=device, dtype=torch.float32).contiguous() for p in ps]
-            packed = torch.empty(need, dtype=torch.uint8, device=device)
-            st = torch.cuda.current_stream(device).cuda_stream
-            _lib.check(lib.nl_s2d_pack_weights(self.feat_dim, *[t.data_ptr() for t in ts], packed.data_ptr(), need, st), "nl_s2d_pack_weights")
-            self._packed, self._packed_key = packed, key
-            self._pack_sources = ts   # alive until the stream has consumed them
-            self.pack_count += 1
-        return self._packed
+        return pack_matcher_mlp("S2DMatching", self, device)
 
     def match(self, desc0, desc1, want_scores=None):
         """The library call: (score_matrix or None, match_j (N) int32 with -1 = unmatched, match_score (N))."""
-        if not (desc0.is_cuda and desc1.is_cuda):
-            raise RuntimeError("S2DMatching's eval path runs only on a HIP device (no CPU fallback); move the module and its inputs to cuda")
+        require_device("S2DMatching", desc0, desc1)
         if desc0.dim() != 2 or desc1.dim() != 2 or desc0.shape[1] != self.feat_dim or desc1.shape[1] != self.feat_dim:
             raise ValueError(f"S2DMatching: descriptors must be (N, {self.feat_dim}) and (M, {self.feat_dim})")
         want = self.want_score_matrix if want_scores is None else bool(want_scores)

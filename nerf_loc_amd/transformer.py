@@ -18,7 +18,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _lib
-from .fine_matching import _check_precision
+from ._packing import PackedCache, check_precision, require_device
 
 _LIMITS = "nhead == 8, d_model in {64, 128, 192, 256}, dim_feedforward a multiple of 32 in 32..512, activation 'relu'"
 
@@ -54,7 +54,7 @@ class _Layer(nn.Module):
         return norm_b(x + self.dropout_b(f))
 
 
-class SelfCrossTransformer(nn.Module):
+class SelfCrossTransformer(nn.Module, PackedCache):
     """`SelfCrossTransformer(d_model, nhead, ..., dim_feedforward, dropout, activation)` with the reference's signature.
 
     precision: "bf16x3" (default: three-term split products on the matrix pipe, within 1e-4 of the fp32 reference), "fp32" (exact fp32 products) or
@@ -74,10 +74,8 @@ class SelfCrossTransformer(nn.Module):
             if p.dim() > 1:
                 nn.init.xavier_uniform_(p)
         self.d_model, self.nhead, self.dim_feedforward = int(d_model), int(nhead), int(dim_feedforward)
-        self.precision = _check_precision(precision)
-        self._packed = None
-        self._packed_key = None
-        self.pack_count = 0   # how often the weights were packed (tests watch the cache)
+        self.precision = check_precision(precision)
+        self._cache_init()
 
     # ------------------------------------------------------------------ eager path (training / autograd)
     def _eager(self, v0, pos0, v1, pos1):
@@ -98,23 +96,19 @@ class SelfCrossTransformer(nn.Module):
         ps = list(self.parameters())   # registration order = state-dict order (the module has no buffers); cheaper per call than building the state dict
         if len(ps) != 52:
             raise RuntimeError("SelfCrossTransformer: expected the reference's 52 tensors")
-        key = (str(device),) + tuple((p.data_ptr(), p._version, p.dtype) for p in ps)
-        if self._packed is None or key != self._packed_key:
-            ts = [p.detach().to(device=device, dtype=torch.float32).contiguous() for p in ps]
+
+        def pack(ts):
             arr = (ctypes.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
             packed = torch.empty(need, dtype=torch.uint8, device=device)
             st = torch.cuda.current_stream(device).cuda_stream
             _lib.check(lib.nl_sct_pack_weights(self.d_model, self.nhead, self.dim_feedforward, arr, len(ts), packed.data_ptr(), need, st), "nl_sct_pack_weights")
-            self._packed, self._packed_key = packed, key
-            self._pack_sources = ts   # alive until the stream has consumed them
-            self.pack_count += 1
-        return self._packed
+            return packed
+        return self._cached(device, ps, pack)
 
     def transform(self, v0, pos0, v1, pos1):
         """The library call: (out0 (B, N0, C), out1 (B, N1, C))."""
         ts = (v0, pos0, v1, pos1)
-        if not all(t.is_cuda for t in ts):
-            raise RuntimeError("SelfCrossTransformer's eval path runs only on a HIP device (no CPU fallback); move the module and its inputs to cuda")
+        require_device("SelfCrossTransformer", *ts)
         C = self.d_model
         if v0.dim() != 3 or v1.dim() != 3 or v0.shape[2] != C or v1.shape[2] != C or v0.shape[0] != v1.shape[0] or pos0.shape != v0.shape or pos1.shape != v1.shape:
             raise ValueError(f"SelfCrossTransformer: inputs must be (B, N0, {C}) and (B, N1, {C}) with position encodings of the same shapes")

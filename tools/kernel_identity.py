@@ -5,7 +5,8 @@
 
 For every .hip in the Makefile's SRCS, in both trees: compile with the Makefile's FLAGS plus `--cuda-device-only -c`, unbundle the gfx950
 code object, and take every kernel (a function symbol F with a 64-byte descriptor F.kd): its name, size, the sha256 of its code bytes and of
-its descriptor.  One line per kernel; exit status 1 if any kernel differs, is missing or is new.  The __hip_cuid_* marker is not a kernel
+its descriptor — without the descriptor's kernel_code_entry_byte_offset (bytes 16-23), the distance from the descriptor to the code: it says where the unit's
+layout put the kernel and moves for every kernel of a unit when another one is added or removed.  One line per kernel; exit status 1 if any kernel differs, is missing or is new.  The __hip_cuid_* marker is not a kernel
 and is not looked at.  Nothing is disassembled: a refactor that claims "the same device code" is checked by hashes alone.
 
 Each tree needs its include/ two levels up (csrc includes ../../include/nerfloc_render.h): for the parent, e.g.
@@ -84,7 +85,8 @@ def kernels(path):
         if typ != 2 or kd is None:   # STT_FUNC with a descriptor
             continue
         assert kd[3] == 64, (path, name)
-        out[name] = (size, hashlib.sha256(data(shndx, value, size)).hexdigest(), hashlib.sha256(data(*kd[1:])).hexdigest())
+        desc = data(*kd[1:])
+        out[name] = (size, hashlib.sha256(data(shndx, value, size)).hexdigest(), hashlib.sha256(desc[:16] + bytes(8) + desc[24:]).hexdigest())
     return out
 
 
