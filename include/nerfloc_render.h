@@ -43,10 +43,11 @@ extern "C" {
 #pragma GCC visibility push(default)
 #endif
 
-#define NL_ABI_VERSION 10  /* 2: nl_render_rays_ex / nl_render_opts (early termination, per-ray query centres); 3: nl_render_opts.flags,
+#define NL_ABI_VERSION 11  /* 2: nl_render_rays_ex / nl_render_opts (early termination, per-ray query centres); 3: nl_render_opts.flags,
                             * reserved fields validated, side stream owned by the nl_frame; 5: NL_PREC_F16MX; 6: nl_frame_diagnostics;
                             * 7: NL_RENDER_PRECISION_GUARD (the precision guard at the boundary), NL_DIAG_GUARD_*; 8: nl_s2d_* (the coarse matcher);
-                            * 9: nl_fine_* (the fine matcher); 10: nl_sct_* (the matcher's SelfCrossTransformer) */
+                            * 9: nl_fine_* (the fine matcher); 10: nl_sct_* (the matcher's SelfCrossTransformer);
+                            * 11: nl_s2d_*_train (the coarse matcher's training step) */
 #define NL_MAX_VIEWS 16
 #define NL_KNN_MAX_K 8
 
@@ -501,6 +502,31 @@ int nl_s2d_pack_weights(int C, const float* w1, const float* b1, const float* w2
 size_t nl_s2d_min_workspace_bytes(int64_t N, int64_t M, int C, int want_scores);
 int nl_s2d_match(const void* packed, int C, int precision, const float* desc0, int64_t N, const float* desc1, int64_t M, float thr, float* scores_out,
                  int32_t* match_j, float* match_score, void* workspace, size_t workspace_bytes, void* stream);
+
+/* The coarse matcher's training step (S2DMatching.forward in train mode and its autograd backward, sparse_to_dense.py:14-78, 112-151).
+ * nl_s2d_forward_train is nl_s2d_match (the same kernels, scores and selection) that also keeps the fp32 logits (N,M) and, with target (N,M) != NULL, writes the
+ * reference's sigmoid focal loss (alpha 0.25, gamma 2, unit anchor weights, mean over N*M, float targets) to the DEVICE scalar loss_out, summed in a fixed order.
+ * target and loss_out are given together or both NULL (no loss); scores_out and logits_out are required.
+ * nl_s2d_backward_train: from the descriptors, the saved logits, the target, the loss's cotangent g_loss (a pointer to a DEVICE scalar: no host read) and an
+ * optional cotangent g_score (N,M) of the scores (NULL: zero) it writes (overwrites) g_desc0 (N,C), g_desc1 (M,C) and the parameter gradients g_w1 (128,C),
+ * g_b1 (128), g_w2 (128,128), g_b2 (128), g_w3 (1,128), g_b3 (1).  Each parameter-gradient pointer may be NULL (frozen weights: with all six NULL only the
+ * descriptor gradients are computed, with the same bits).  target and g_loss are given together or both NULL (only g_score flows).
+ * The hidden activations are recomputed from the descriptors in row chunks; the workspace holds one chunk and does not grow with N.  Sums run in a fixed
+ * order and no float atomic touches a result: a call is bit-reproducible.  Gradient products are split-bf16 MFMA: three terms under NL_PREC_F32 and
+ * NL_PREC_BF16X3 (parity), one under NL_PREC_BF16 (throughput); NL_PREC_F16MX is NL_ERR_UNSUPPORTED.
+ * The backward pass reads the inference image (nl_s2d_pack_weights) and a second, training image with the transposed weights (nl_s2d_pack_train_weights from
+ * mlps.0.weight and mlps.2.weight, DEVICE pointers).  C, alignment and error conventions as for nl_s2d_match; N * M < 2^31 and M <= 2^20
+ * (NL_ERR_UNSUPPORTED / a size query of 0 otherwise).  Arguments are validated before anything is dereferenced. */
+size_t nl_s2d_forward_train_workspace_bytes(int64_t N, int64_t M, int C);
+int nl_s2d_forward_train(const void* packed, int C, int precision, const float* desc0, int64_t N, const float* desc1, int64_t M, float thr, const float* target,
+                         float* scores_out, float* logits_out, float* loss_out, int32_t* match_j, float* match_score, void* workspace, size_t workspace_bytes,
+                         void* stream);
+size_t nl_s2d_train_weights_bytes(int C);
+int nl_s2d_pack_train_weights(int C, const float* w1, const float* w2, void* packed, size_t packed_bytes, void* stream);
+size_t nl_s2d_backward_train_workspace_bytes(int64_t N, int64_t M, int C);
+int nl_s2d_backward_train(const void* packed, const void* train_packed, int C, int precision, const float* desc0, int64_t N, const float* desc1, int64_t M,
+                          const float* logits, const float* target, const float* g_loss, const float* g_score, float* g_desc0, float* g_desc1, float* g_w1,
+                          float* g_b1, float* g_w2, float* g_b2, float* g_w3, float* g_b3, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- localisation head: the fine matcher ------------------------------------------------------------------------------------------------
  * The two stages behind the coarse matches (matcher.py:101-124), models/matching/fine_matching.py.  No workspace: both calls are one launch that writes its

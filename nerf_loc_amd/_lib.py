@@ -29,7 +29,7 @@ GUARD_LOGIT_LIMIT = {"f16mx": 50.0, "bf16x3": 500.0}   # include/nerfloc_render.
 PRECISION_NAMES = {PREC_F32: "fp32", PREC_BF16X3: "bf16x3", PREC_BF16: "bf16", PREC_F16MX: "f16mx"}
 GUARD_DENSITY_LIMIT = {"f16mx": 32.0}  # include/nerfloc_render.h: NL_GUARD_DENSITY_LIMIT_F16MX (the guard's second indicator: the largest density of the frame's guarded batches; bf16x3 has no such limit)
 DIAG_COUNT = 6
-ABI_VERSION = 10  # include/nerfloc_render.h: NL_ABI_VERSION
+ABI_VERSION = 11  # include/nerfloc_render.h: NL_ABI_VERSION
 
 
 class NlConfig(C.Structure):
@@ -147,6 +147,12 @@ SYMBOLS = [
     ("nl_s2d_pack_weights", _I, [_I, _P, _P, _P, _P, _P, _P, _P, _Z, _P]),
     ("nl_s2d_min_workspace_bytes", _Z, [_L, _L, _I, _I]),
     ("nl_s2d_match", _I, [_P, _I, _I, _P, _L, _P, _L, _F, _P, _P, _P, _P, _Z, _P]),
+    ("nl_s2d_forward_train_workspace_bytes", _Z, [_L, _L, _I]),
+    ("nl_s2d_forward_train", _I, [_P, _I, _I, _P, _L, _P, _L, _F, _P, _P, _P, _P, _P, _P, _P, _Z, _P]),
+    ("nl_s2d_train_weights_bytes", _Z, [_I]),
+    ("nl_s2d_pack_train_weights", _I, [_I, _P, _P, _P, _Z, _P]),
+    ("nl_s2d_backward_train_workspace_bytes", _Z, [_L, _L, _I]),
+    ("nl_s2d_backward_train", _I, [_P, _P, _I, _I, _P, _L, _P, _L] + [_P] * 13 + [_Z, _P]),
     ("nl_fine_proj_packed_bytes", _Z, [_I, _I]),
     ("nl_fine_pack_proj", _I, [_I, _I, _P, _P, _P, _Z, _P]),
     ("nl_fine_windows", _I, [_P, _I, _I, _I, _P, _I, _I, _I, _P, _P, _L, _I, _P, _P]),

@@ -172,3 +172,36 @@ __device__ __forceinline__ void s2d_logits(const nl_f32x16 (&acc)[2][4], const f
 #pragma unroll
   for (int t = 0; t < 2; ++t) logit[t] = dot[t] + __shfl_xor(dot[t], 32) + b3;
 }
+
+// ---- training (s2d.hip: the loss of nl_s2d_forward_train; s2d_bwd.hip: its derivative).  The reference's sigmoid focal loss of one pair with unit anchor weight
+// (sparse_to_dense.py:14-78: alpha 0.25, gamma 2) from the logit z and a float target y, before the mean over N * M:
+//   L = (y a + (1 - y)(1 - a)) pt^2 bce,   pt = y (1 - p) + (1 - y) p,   bce = max(z, 0) - z y + log1p(exp(-|z|)),   dL/dz = aw (2 pt (1 - 2 y) p (1 - p) bce + pt^2 (p - y))
+// p and 1 - p both come from e = exp(-|z|), so neither cancels in saturation (z large: p == 1.0f, 1 - p == e); dsig = p (1 - p) is also the score's derivative.
+constexpr float S2D_FOCAL_ALPHA = 0.25f;
+__device__ __forceinline__ void s2d_focal(float z, float y, float& loss, float& dz, float& dsig) {
+  const float e = expf(-fabsf(z)), r = 1.f / (1.f + e);
+  const float big = r, small = e * r;   // sigmoid(|z|), sigmoid(-|z|)
+  const float p = z >= 0.f ? big : small, q = z >= 0.f ? small : big;
+  const float aw = y * S2D_FOCAL_ALPHA + (1.f - y) * (1.f - S2D_FOCAL_ALPHA);
+  const float pt = y * q + (1.f - y) * p;
+  const float bce = fmaxf(z, 0.f) - z * y + log1pf(e);
+  dsig = p * q;
+  loss = aw * pt * pt * bce;
+  dz = aw * (2.f * pt * (1.f - 2.f * y) * dsig * bce + pt * pt * (p - y));
+}
+
+// The training image (nl_s2d_pack_train_weights): the transposed weights as A fragments whose K order is the accumulator order (nl_frag16_src, acc_order), so that a
+// gradient held in layer accumulators is the B operand of the transposed product without leaving the lane.  The fp32 transposes are the packer's source rows.
+struct S2dTrainLayout { size_t w2t_hi, w2t_lo, w1t_hi, w1t_lo, f32w2t, f32w1t, total; };
+__host__ __device__ inline S2dTrainLayout s2d_train_layout(int C) {
+  S2dTrainLayout l;
+  const size_t w1 = (size_t)C * S2D_H * 2;
+  l.w2t_hi = 0;
+  l.w2t_lo = l.w2t_hi + S2D_W2_BYTES;
+  l.w1t_hi = l.w2t_lo + S2D_W2_BYTES;
+  l.w1t_lo = l.w1t_hi + w1;
+  l.f32w2t = l.w1t_lo + w1;
+  l.f32w1t = l.f32w2t + (size_t)S2D_H * S2D_H * 4;
+  l.total = l.f32w1t + (size_t)C * S2D_H * 4;
+  return l;
+}

@@ -14,6 +14,7 @@
 // order, the cross-half sum of the last layer is commutative, and no float atomic touches a value.
 // Selection: the score kernel reduces rowmax[N] / colmax[M] with unsigned atomic max on the float bits (scores are >= 0); pass 2, one wave per row, finds the FIRST j
 // with s > thr, s == rowmax[i], s == colmax[j] — the reference's rule on the scores themselves, ties included.
+#include <algorithm>
 #include "common.h"
 #include "mfma.h"
 #include "s2d.h"
@@ -44,6 +45,7 @@ struct S2dArgs {
   const unsigned char* img;
   const float* desc0; const float* desc1;
   float* scores;
+  float* logits;   // (N,M) or null: the training forward keeps them for the loss and the backward pass (s2d_bwd.hip)
   unsigned* rowmax; unsigned* colmax;
   int N, M, C;
 };
@@ -63,6 +65,7 @@ __device__ __forceinline__ void s2d_finish(const S2dArgs& a, const float* small,
   const float mine = hh ? sc[1] : sc[0];
   const int nm = n0 + hh;
   if (okm) a.scores[(size_t)nm * a.M + m] = mine;
+  if (a.logits && okm) a.logits[(size_t)nm * a.M + m] = hh ? logit[1] : logit[0];
   unsigned rm = okm ? __float_as_uint(mine) : 0u;   // scores are >= 0: the order of the bits is the order of the values
 #pragma unroll
   for (int o = 16; o >= 1; o >>= 1) rm = max(rm, (unsigned)__shfl_xor((int)rm, o));
@@ -204,6 +207,41 @@ __global__ __launch_bounds__(256) void s2d_select_kernel(const float* scores, co
   }
 }
 
+
+// ------------------------------------------------------------------------------------------ loss (training forward)
+// mean sigmoid focal loss over N * M logits in a fixed order: block b adds elements b * 256 + tid + k * nblk * 256 in-thread, then a tree over the block; a second, single
+// block adds the nblk partials the same way.  nblk depends on N * M only, so the order does not depend on the device.
+constexpr int S2D_LOSS_MAX_BLOCKS = 1024;
+__device__ __forceinline__ float s2d_block_sum(float v, float* red) {
+  const int tid = threadIdx.x;
+  red[tid] = v;
+  __syncthreads();
+#pragma unroll
+  for (int o = 128; o >= 1; o >>= 1) {
+    if (tid < o) red[tid] += red[tid + o];
+    __syncthreads();
+  }
+  return red[0];
+}
+__global__ __launch_bounds__(256) void s2d_loss_part_kernel(const float* logits, const float* target, long long total, float* part) {
+  __shared__ float red[256];
+  float s = 0.f;
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
+    float l, dz, ds;
+    s2d_focal(logits[i], target[i], l, dz, ds);
+    s += l;
+  }
+  const float v = s2d_block_sum(s, red);
+  if (threadIdx.x == 0) part[blockIdx.x] = v;
+}
+__global__ __launch_bounds__(256) void s2d_loss_final_kernel(const float* part, int nblk, float inv_total, float* loss) {
+  __shared__ float red[256];
+  float s = 0.f;
+  for (int i = threadIdx.x; i < nblk; i += 256) s += part[i];
+  const float v = s2d_block_sum(s, red);
+  if (threadIdx.x == 0) loss[0] = v * inv_total;
+}
+
 struct S2dWs { size_t rowmax, colmax, scores, total; };
 S2dWs s2d_ws(int64_t N, int64_t M, bool want_scores) {
   S2dWs w;
@@ -216,6 +254,53 @@ S2dWs s2d_ws(int64_t N, int64_t M, bool want_scores) {
 bool s2d_shape_ok(int64_t N, int64_t M) { return N >= 1 && M >= 1 && N <= (1 << 30) && M <= (1 << 30); }
 
 }  // namespace
+
+// nl_s2d_match, and with logits_out the first half of nl_s2d_forward_train: the same kernels, scores and selection
+static int s2d_run(const void* packed, int C, int precision, const float* desc0, int64_t N, const float* desc1, int64_t M, float thr, float* scores_out,
+                   float* logits_out, int32_t* match_j, float* match_score, void* workspace, size_t workspace_bytes, void* stream) {
+  if (N < 1 || M < 1 || C < 1) return NL_ERR_BAD_ARG;
+  if (!s2d_c_ok(C) || !s2d_shape_ok(N, M)) return NL_ERR_UNSUPPORTED;
+  if (const int ps = nl_prec_status_no_mx(precision)) return ps;
+  if (!packed || !desc0 || !desc1 || !match_j || !match_score) return NL_ERR_BAD_ARG;
+  if ((((uintptr_t)packed | (uintptr_t)desc0 | (uintptr_t)desc1) & 15) != 0) return NL_ERR_BAD_ARG;   // read as 16-byte pieces
+  if ((((uintptr_t)scores_out | (uintptr_t)logits_out | (uintptr_t)match_j | (uintptr_t)match_score) & 3) != 0) return NL_ERR_BAD_ARG;
+  const S2dWs w = s2d_ws(N, M, scores_out != nullptr);
+  if (!workspace || workspace_bytes < w.total || ((uintptr_t)workspace & 15) != 0) return NL_ERR_WORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  unsigned char* ws = (unsigned char*)workspace;
+  S2dArgs a;
+  a.img = (const unsigned char*)packed;
+  a.desc0 = desc0; a.desc1 = desc1;
+  a.scores = scores_out ? scores_out : (float*)(ws + w.scores);
+  a.logits = logits_out;
+  a.rowmax = (unsigned*)(ws + w.rowmax);
+  a.colmax = (unsigned*)(ws + w.colmax);
+  a.N = (int)N; a.M = (int)M; a.C = C;
+  const int cus = nl_persistent_cus();
+  if (cus < 0) return cus;
+  NL_CHECK_HIP(hipMemsetAsync(ws, 0, w.scores, st));
+  const int64_t items = nl_cdiv(M, 32) * nl_cdiv(N, S2D_NROWS);
+  const unsigned grid = (unsigned)(items < cus ? items : cus);
+  // dynamic LDS beyond 64 KB: each kernel's limit is raised once per device to what the largest supported C needs; a launch asks for its own size
+  static std::atomic<unsigned long long> f32_set{0}, x3_set{0}, bf_set{0};
+  if (precision == NL_PREC_F32) {
+    if (const int e = nl_allow_dynamic_lds((const void*)s2d_f32_kernel, S2D_F32_LDS, f32_set)) return e;
+    hipLaunchKernelGGL(s2d_f32_kernel, dim3(grid), dim3(256), S2D_F32_LDS, st, a);
+  } else {
+    const size_t lds = s2d_layout(C).lds_bytes, lds_max = s2d_layout(256).lds_bytes;
+    if (precision == NL_PREC_BF16X3) {
+      if (const int e = nl_allow_dynamic_lds((const void*)s2d_bf16_kernel<true>, lds_max, x3_set)) return e;
+      hipLaunchKernelGGL(s2d_bf16_kernel<true>, dim3(grid), dim3(256), lds, st, a);
+    } else {
+      if (const int e = nl_allow_dynamic_lds((const void*)s2d_bf16_kernel<false>, lds_max, bf_set)) return e;
+      hipLaunchKernelGGL(s2d_bf16_kernel<false>, dim3(grid), dim3(256), lds, st, a);
+    }
+  }
+  NL_LAUNCH_CHECK();
+  hipLaunchKernelGGL(s2d_select_kernel, dim3((unsigned)nl_cdiv(N, 4)), dim3(256), 0, st, a.scores, a.rowmax, a.colmax, (int)N, (int)M, thr, match_j, match_score);
+  NL_LAUNCH_CHECK();
+  return NL_OK;
+}
 
 extern "C" {
 
@@ -245,46 +330,35 @@ size_t nl_s2d_min_workspace_bytes(int64_t N, int64_t M, int C, int want_scores) 
 
 int nl_s2d_match(const void* packed, int C, int precision, const float* desc0, int64_t N, const float* desc1, int64_t M, float thr, float* scores_out,
                  int32_t* match_j, float* match_score, void* workspace, size_t workspace_bytes, void* stream) {
+  return s2d_run(packed, C, precision, desc0, N, desc1, M, thr, scores_out, nullptr, match_j, match_score, workspace, workspace_bytes, stream);
+}
+
+size_t nl_s2d_forward_train_workspace_bytes(int64_t N, int64_t M, int C) {
+  if (!s2d_c_ok(C) || !s2d_shape_ok(N, M)) return 0;
+  return s2d_ws(N, M, true).total + S2D_LOSS_MAX_BLOCKS * sizeof(float);
+}
+
+int nl_s2d_forward_train(const void* packed, int C, int precision, const float* desc0, int64_t N, const float* desc1, int64_t M, float thr, const float* target,
+                         float* scores_out, float* logits_out, float* loss_out, int32_t* match_j, float* match_score, void* workspace, size_t workspace_bytes,
+                         void* stream) {
   if (N < 1 || M < 1 || C < 1) return NL_ERR_BAD_ARG;
   if (!s2d_c_ok(C) || !s2d_shape_ok(N, M)) return NL_ERR_UNSUPPORTED;
   if (const int ps = nl_prec_status_no_mx(precision)) return ps;
-  if (!packed || !desc0 || !desc1 || !match_j || !match_score) return NL_ERR_BAD_ARG;
-  if ((((uintptr_t)packed | (uintptr_t)desc0 | (uintptr_t)desc1) & 15) != 0) return NL_ERR_BAD_ARG;   // read as 16-byte pieces
-  if ((((uintptr_t)scores_out | (uintptr_t)match_j | (uintptr_t)match_score) & 3) != 0) return NL_ERR_BAD_ARG;
-  const S2dWs w = s2d_ws(N, M, scores_out != nullptr);
-  if (!workspace || workspace_bytes < w.total || ((uintptr_t)workspace & 15) != 0) return NL_ERR_WORKSPACE;
-  hipStream_t st = (hipStream_t)stream;
-  unsigned char* ws = (unsigned char*)workspace;
-  S2dArgs a;
-  a.img = (const unsigned char*)packed;
-  a.desc0 = desc0; a.desc1 = desc1;
-  a.scores = scores_out ? scores_out : (float*)(ws + w.scores);
-  a.rowmax = (unsigned*)(ws + w.rowmax);
-  a.colmax = (unsigned*)(ws + w.colmax);
-  a.N = (int)N; a.M = (int)M; a.C = C;
-  const int cus = nl_persistent_cus();
-  if (cus < 0) return cus;
-  NL_CHECK_HIP(hipMemsetAsync(ws, 0, w.scores, st));
-  const int64_t items = nl_cdiv(M, 32) * nl_cdiv(N, S2D_NROWS);
-  const unsigned grid = (unsigned)(items < cus ? items : cus);
-  // dynamic LDS beyond 64 KB: each kernel's limit is raised once per device to what the largest supported C needs; a launch asks for its own size
-  static std::atomic<unsigned long long> f32_set{0}, x3_set{0}, bf_set{0};
-  if (precision == NL_PREC_F32) {
-    if (const int e = nl_allow_dynamic_lds((const void*)s2d_f32_kernel, S2D_F32_LDS, f32_set)) return e;
-    hipLaunchKernelGGL(s2d_f32_kernel, dim3(grid), dim3(256), S2D_F32_LDS, st, a);
-  } else {
-    const size_t lds = s2d_layout(C).lds_bytes, lds_max = s2d_layout(256).lds_bytes;
-    if (precision == NL_PREC_BF16X3) {
-      if (const int e = nl_allow_dynamic_lds((const void*)s2d_bf16_kernel<true>, lds_max, x3_set)) return e;
-      hipLaunchKernelGGL(s2d_bf16_kernel<true>, dim3(grid), dim3(256), lds, st, a);
-    } else {
-      if (const int e = nl_allow_dynamic_lds((const void*)s2d_bf16_kernel<false>, lds_max, bf_set)) return e;
-      hipLaunchKernelGGL(s2d_bf16_kernel<false>, dim3(grid), dim3(256), lds, st, a);
-    }
+  if (!packed || !desc0 || !desc1 || !match_j || !match_score || !scores_out || !logits_out || (target != nullptr) != (loss_out != nullptr)) return NL_ERR_BAD_ARG;
+  if ((((uintptr_t)target | (uintptr_t)loss_out) & 3) != 0) return NL_ERR_BAD_ARG;
+  const size_t match_bytes = s2d_ws(N, M, true).total;
+  if (!workspace || workspace_bytes < match_bytes + S2D_LOSS_MAX_BLOCKS * sizeof(float) || ((uintptr_t)workspace & 15) != 0) return NL_ERR_WORKSPACE;
+  if (const int e = s2d_run(packed, C, precision, desc0, N, desc1, M, thr, scores_out, logits_out, match_j, match_score, workspace, match_bytes, stream)) return e;
+  if (target) {
+    hipStream_t st = (hipStream_t)stream;
+    float* part = (float*)((unsigned char*)workspace + match_bytes);
+    const long long total = (long long)N * M;
+    const int nblk = (int)std::min<int64_t>(S2D_LOSS_MAX_BLOCKS, nl_cdiv(total, 1024));
+    hipLaunchKernelGGL(s2d_loss_part_kernel, dim3(nblk), dim3(256), 0, st, logits_out, target, total, part);
+    NL_LAUNCH_CHECK();
+    hipLaunchKernelGGL(s2d_loss_final_kernel, dim3(1), dim3(256), 0, st, part, nblk, (float)(1.0 / (double)total), loss_out);
+    NL_LAUNCH_CHECK();
   }
-  NL_LAUNCH_CHECK();
-  hipLaunchKernelGGL(s2d_select_kernel, dim3((unsigned)nl_cdiv(N, 4)), dim3(256), 0, st, a.scores, a.rowmax, a.colmax, (int)N, (int)M, thr, match_j, match_score);
-  NL_LAUNCH_CHECK();
   return NL_OK;
 }
 

@@ -1,0 +1,579 @@
+// Training step of the sparse-to-dense coarse matcher (s2d.hip is the forward: nl_s2d_forward_train keeps the N x M logits and the focal loss): the gradients of
+//   loss = mean focal(logit, target),  score = sigmoid(logit),  logit[n, m] = W3 . relu( W2 . relu( W1 . (desc0[n] * desc1[m]) + b1 ) + b2 ) + b3
+// with respect to both descriptor sets and the six parameters, from the saved logits alone: the hidden activations are recomputed, never kept.
+//
+// The rows n are walked in chunks of about S2D_BWD_PAIRS pairs (half of that for small problems); the buffers below hold one chunk and are reused by the next, so the workspace does not grow with N.
+// Per chunk:
+//   1. s2d_bwd_kernel, one wave per (32 columns m) x (two rows n), the tile shape and the layer bodies of the score kernel (s2d.h), weight fragments from L2:
+//      layer 1 and 2 again (exact fp32 in the parity modes: see the kernel); g_logit = g_loss / (N M) focal'(logit) + g_score s (1 - s); g_a2 = g_logit w3 [h2 > 0] in the accumulators of layer 2, which are at once
+//      the B operand of W2^T (the training image holds the transposed weights with their K in accumulator order): g_a1 = (W2^T g_a2) [h1 > 0], and the same again with
+//      W1^T, one 32-channel block at a time: g_x = W1^T g_a1.  Stored per pair (row-major chunk matrices): x, h1, g_a2, g_a1 (the operands of the weight gradients;
+//      skipped when the parameter pointers are null) and g_x.  gW3 / gb3: the lane's sums over its two pairs, added across the 32 lanes of a half-wave by a halving
+//      exchange (62 adds for 64 values), one partial row per wave.
+//   2. gW2 += g_a2^T h1, gb2, gW1 += g_a1^T x, gb1: the split-K kernel of wgrad.hip on the chunk's rows (partials added in a fixed order, += over the chunks).
+//   3. g_desc0[n] = sum_m g_x[n, m] * desc1[m] (256-column segments, four interleaved sub-sums each, then the segments in order), g_desc1[m] += sum_n g_x[n, m] * desc0[n]
+//      (one thread per (m, 4 channels), rows in order), gW3 / gb3 += the waves' partials in order.
+// Every sum has a fixed order that depends on the shape alone and no float atomic touches a result: two calls give the same bits.
+// Gradient products are split-bf16 (three terms under NL_PREC_F32 and NL_PREC_BF16X3, one under NL_PREC_BF16) as in wgrad.hip: a gradient's scale is arbitrary.
+// The recomputation of the activations is exact fp32 in both parity modes (the ReLU masks hang on it) and one-term bf16 under NL_PREC_BF16.
+#include <algorithm>
+#include "common.h"
+#include "mfma.h"
+#include "s2d.h"
+#include "host.h"
+
+namespace {
+
+// pairs of one chunk (rounded to an even number of rows, at least two): 64 pairs per wave, so 65 536 pairs are one workgroup on each of 256 CUs; problems below
+// 2^20 pairs take half of that, which keeps the workspace under half the product tensor down to a quarter of a million pairs
+constexpr int64_t S2D_BWD_PAIRS = 65536, S2D_BWD_PAIRS_SMALL = 32768, S2D_BWD_SMALL_BELOW = 1 << 20;
+constexpr int S2D_W3P_LD = 132;            // floats of a wave's gW3 / gb3 partial row: [hh][64 accumulator slots], gb3, padding
+
+struct BwdArgs {
+  const unsigned char* img; const unsigned char* timg;
+  const float* desc0; const float* desc1;
+  const float* logits; const float* target; const float* g_loss; const float* g_score;
+  float *x, *h1, *ga2, *ga1, *gx;   // the chunk's matrices, row (n - r0) * M + m; x, h1, ga2, ga1 may be null
+  float* w3part;                    // [items][S2D_W3P_LD] or null
+  int N, M, C, r0, r1;              // the chunk's rows [r0, r1)
+  float inv_total;
+};
+
+__device__ __forceinline__ void bwd_store4(float* p, const nl_f32x16& v, int r4) { *(float4*)p = make_float4(v[4 * r4], v[4 * r4 + 1], v[4 * r4 + 2], v[4 * r4 + 3]); }
+
+// accumulators (final values) -> the split B operands of the next product: k-step (b, s) = words 4 s .. 4 s + 3 of block b (accumulator registers 8 s .. 8 s + 7)
+__device__ __forceinline__ void bwd_split(const nl_f32x16 (&acc)[2][4], unsigned (&hi)[2][4][8], unsigned (&lo)[2][4][8]) {
+#pragma unroll
+  for (int t = 0; t < 2; ++t)
+#pragma unroll
+    for (int b = 0; b < 4; ++b)
+#pragma unroll
+      for (int r4 = 0; r4 < 4; ++r4) {
+        nl_split_bf16_pair(acc[t][b][4 * r4 + 0], acc[t][b][4 * r4 + 1], hi[t][b][2 * r4], lo[t][b][2 * r4]);
+        nl_split_bf16_pair(acc[t][b][4 * r4 + 2], acc[t][b][4 * r4 + 3], hi[t][b][2 * r4 + 1], lo[t][b][2 * r4 + 1]);
+      }
+}
+// row block rb of a transposed product (K = 128 in accumulator order, nrb row blocks in the image) into o0 / o1 (tile 0 / 1)
+template <bool X3>
+__device__ __forceinline__ void bwd_mult(nl_f32x16& o0, nl_f32x16& o1, const unsigned (&hi)[2][4][8], const unsigned (&lo)[2][4][8], const uint4* whi, const uint4* wlo,
+                                         int nrb, int rb, int lane) {
+#pragma unroll
+  for (int b = 0; b < 4; ++b)
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+      const nl_i16x8 bh0 = nl_frag(hi[0][b][4 * s], hi[0][b][4 * s + 1], hi[0][b][4 * s + 2], hi[0][b][4 * s + 3]);
+      const nl_i16x8 bh1 = nl_frag(hi[1][b][4 * s], hi[1][b][4 * s + 1], hi[1][b][4 * s + 2], hi[1][b][4 * s + 3]);
+      const int f = ((b * 2 + s) * nrb + rb) * 64 + lane;
+      const nl_i16x8 ah = nl_frag(whi[f]);
+      if (X3) {
+        const nl_i16x8 bl0 = nl_frag(lo[0][b][4 * s], lo[0][b][4 * s + 1], lo[0][b][4 * s + 2], lo[0][b][4 * s + 3]);
+        const nl_i16x8 bl1 = nl_frag(lo[1][b][4 * s], lo[1][b][4 * s + 1], lo[1][b][4 * s + 2], lo[1][b][4 * s + 3]);
+        const nl_i16x8 al = nl_frag(wlo[f]);
+        o0 = nl_mfma<false>(al, bh0, o0); o1 = nl_mfma<false>(al, bh1, o1);
+        o0 = nl_mfma<false>(ah, bl0, o0); o1 = nl_mfma<false>(ah, bl1, o1);
+      }
+      o0 = nl_mfma<false>(ah, bh0, o0); o1 = nl_mfma<false>(ah, bh1, o1);
+    }
+}
+// one step of the halving exchange over the 32 lanes of a half-wave: lanes with bit O keep the upper NH values, the others the lower NH, plus the partner's
+template <int NH, int O>
+__device__ __forceinline__ void bwd_halve(float (&v)[64], int lane) {
+  const bool up = (lane & O) != 0;
+#pragma unroll
+  for (int i = 0; i < NH; ++i) {
+    const float send = up ? v[i] : v[i + NH], keep = up ? v[i + NH] : v[i];
+    v[i] = keep + __shfl_xor(send, O);
+  }
+}
+
+// index into a bias table of the image's `small` block (accumulator order: [hh][16 b + r]) of hidden unit u
+__device__ __forceinline__ int bwd_small_index(int u) { const int w = u & 31; return 64 * ((w >> 2) & 1) + 16 * (u >> 5) + 4 * (w >> 3) + (w & 3); }
+// the lane's 64 mask bits (bit 16 b + r) out of the two ballots over the hidden units 0..63 / 64..127
+__device__ __forceinline__ unsigned long long bwd_mask_from_units(unsigned long long lo, unsigned long long hi, int hh) {
+  unsigned long long mk = 0ull;
+#pragma unroll
+  for (int b = 0; b < 4; ++b)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int u = 32 * b + 8 * (r >> 2) + 4 * hh + (r & 3);
+      mk |= (((b < 2 ? lo : hi) >> (u & 63)) & 1ull) << (16 * b + r);
+    }
+  return mk;
+}
+// The signs of both layers' pre-activations of ONE pair in fp64, by the whole wave: lane l evaluates hidden units l and l + 64 (w1t: W1^T [C][128], w2t: W2^T
+// [128 k][128 j], fp32; small: the image's bias tables), h1 goes round by shuffles, the signs come back as ballots over units 0..63 / 64..127.  Its own function so
+// that the rare path reads as one; the register pressure it puts on the kernel (116 spilled VGPRs; DESIGN.md section 5.32 has the A/B) is the same inlined or not.
+__device__ __attribute__((noinline)) void bwd_fp64_signs(const float* pd0, const float* pd1, int C, const float* w1t, const float* w2t, const float* small, int lane,
+                                                         unsigned long long& m1lo, unsigned long long& m1hi, unsigned long long& m2lo, unsigned long long& m2hi) {
+  const int i0 = bwd_small_index(lane), i1 = bwd_small_index(lane + 64);
+  double s0 = 0.0, s1 = 0.0;
+#pragma unroll 8
+  for (int k = 0; k < C; ++k) {
+    const double xv = (double)pd0[k] * (double)pd1[k];
+    s0 += xv * (double)w1t[k * S2D_H + lane];
+    s1 += xv * (double)w1t[k * S2D_H + 64 + lane];
+  }
+  s0 += (double)small[i0]; s1 += (double)small[i1];
+  m1lo = __ballot(s0 > 0.0); m1hi = __ballot(s1 > 0.0);
+  s0 = s0 > 0.0 ? s0 : 0.0; s1 = s1 > 0.0 ? s1 : 0.0;
+  double t0 = 0.0, t1 = 0.0;
+#pragma unroll 8
+  for (int k = 0; k < 64; ++k) {
+    const double hk = __shfl(s0, k);
+    t0 += hk * (double)w2t[k * S2D_H + lane];
+    t1 += hk * (double)w2t[k * S2D_H + 64 + lane];
+  }
+#pragma unroll 8
+  for (int k = 0; k < 64; ++k) {
+    const double hk = __shfl(s1, k);
+    t0 += hk * (double)w2t[(64 + k) * S2D_H + lane];
+    t1 += hk * (double)w2t[(64 + k) * S2D_H + 64 + lane];
+  }
+  t0 += (double)small[128 + i0]; t1 += (double)small[128 + i1];
+  m2lo = __ballot(t0 > 0.0); m2hi = __ballot(t1 > 0.0);
+}
+// relative width of the band around zero inside which a pre-activation's sign is decided again in fp64 (of the lane's largest |pre-activation| of the layer):
+// some forty times the typical error of the fp32 chains, so that the masks are those of the fp64 evaluation; 1.6e-6 of the units fall inside (one pair in 2400)
+constexpr float S2D_BWD_BAND = 1e-6f;
+
+// EXACT (NL_PREC_F32, NL_PREC_BF16X3): layers 1 and 2 are recomputed with the exact fp32 bodies (v_mfma_f32_32x32x2_f32) and the gradient products are three-term
+// split-bf16; otherwise (NL_PREC_BF16) both are one-term bf16.  The recomputation decides the ReLU masks, and a mask is not a smooth function of its input: a
+// pre-activation within the recomputation's error of zero flips its unit's gradient between g and 0.  With the three-term bodies (5e-6 of the row's scale) about
+// one unit in 10^5 flipped, a planted pair among them every other case, each worth 5e-3 of max |gradient|.  Exact fp32 still flipped one unit in 10^7 — as the fp32
+// reference does against fp64 — which a random cotangent of the scores shows as 1e-3 in gW2, so the pairs that have a pre-activation inside a narrow band around zero
+// get their masks from an fp64 evaluation of that pair by the whole wave (two hidden units per lane; fp32 transposes of the training image).
+template <bool EXACT>
+__global__ __launch_bounds__(256) void s2d_bwd_kernel(const BwdArgs a) {
+  constexpr bool X3 = EXACT;
+  extern __shared__ __attribute__((aligned(16))) float s2d_bwd_hidden[];   // EXACT: S2D_F32_LDS bytes, lane-private columns (s2d.h: s2d_f32_layer2)
+  const int tid = threadIdx.x, lane = tid & 63, hh = lane >> 5;
+  const int C = a.C, M = a.M, nrb1 = C >> 5;
+  const int MT = (M + 31) >> 5, RP = (a.r1 - a.r0 + 1) >> 1;
+  const int item = blockIdx.x * 4 + (tid >> 6);
+  if (item >= MT * RP) return;   // wave-uniform; the kernel has no barrier
+  const int rp = item / MT, mt = item - rp * MT;
+  const S2dLayout L = s2d_layout(C);
+  const S2dTrainLayout T = s2d_train_layout(C);
+  const uint4* w1hi = (const uint4*)(a.img + L.w1hi);
+  const uint4* w1lo = (const uint4*)(a.img + L.w1lo);
+  const uint4* w2hi = (const uint4*)(a.img + L.w2hi);
+  const uint4* w2lo = (const uint4*)(a.img + L.w2lo);
+  const float* small = (const float*)(a.img + L.small);
+  const float* b1p = small + 64 * hh;
+
+  const int m = mt * 32 + (lane & 31), n0 = a.r0 + 2 * rp;
+  const bool has1 = n0 + 1 < a.r1;
+  const bool ok[2] = {m < M, m < M && has1};
+  const size_t prow[2] = {(size_t)(n0 - a.r0) * M + m, (size_t)(n0 + 1 - a.r0) * M + m};
+  nl_f32x16 acc[2][4];
+  nl_acc_zero(acc);
+  // ---- layer 1 again (s2d.hip's walks); the products are also the X operand of gW1
+  if constexpr (EXACT) {
+    const float* w1f = (const float*)(a.img + L.f32w1);
+    const float* d1p = a.desc1 + (size_t)min(m, M - 1) * C + 4 * hh;
+    const float* d0a = a.desc0 + (size_t)n0 * C + 4 * hh;
+    const float* d0b = a.desc0 + (size_t)(has1 ? n0 + 1 : n0) * C + 4 * hh;
+    for (int g = 0; g < (C >> 3); ++g) {
+      const float4 x = *(const float4*)(d1p + 8 * g), ya = *(const float4*)(d0a + 8 * g), yb = *(const float4*)(d0b + 8 * g);
+      const float pa[4] = {x.x * ya.x, x.y * ya.y, x.z * ya.z, x.w * ya.w};
+      const float pb[4] = {x.x * yb.x, x.y * yb.y, x.z * yb.z, x.w * yb.w};
+      if (a.x) {
+        if (ok[0]) *(float4*)(a.x + prow[0] * C + 8 * g + 4 * hh) = make_float4(pa[0], pa[1], pa[2], pa[3]);
+        if (ok[1]) *(float4*)(a.x + prow[1] * C + 8 * g + 4 * hh) = make_float4(pb[0], pb[1], pb[2], pb[3]);
+      }
+      s2d_f32_layer1_group(acc, w1f, g, lane, pa, pb);
+    }
+  } else {
+    const float* d1p = a.desc1 + (size_t)min(m, M - 1) * C + 8 * hh;
+    const float* d0a = a.desc0 + (size_t)n0 * C + 8 * hh;
+    const float* d0b = a.desc0 + (size_t)(has1 ? n0 + 1 : n0) * C + 8 * hh;
+    for (int s = 0; s < (C >> 4); ++s) {
+      const float4 x0 = *(const float4*)(d1p + 16 * s), x1 = *(const float4*)(d1p + 16 * s + 4);
+      const float4 ya0 = *(const float4*)(d0a + 16 * s), ya1 = *(const float4*)(d0a + 16 * s + 4);
+      const float4 yb0 = *(const float4*)(d0b + 16 * s), yb1 = *(const float4*)(d0b + 16 * s + 4);
+      const float4 pa0 = make_float4(x0.x * ya0.x, x0.y * ya0.y, x0.z * ya0.z, x0.w * ya0.w), pa1 = make_float4(x1.x * ya1.x, x1.y * ya1.y, x1.z * ya1.z, x1.w * ya1.w);
+      const float4 pb0 = make_float4(x0.x * yb0.x, x0.y * yb0.y, x0.z * yb0.z, x0.w * yb0.w), pb1 = make_float4(x1.x * yb1.x, x1.y * yb1.y, x1.z * yb1.z, x1.w * yb1.w);
+      if (a.x) {
+        if (ok[0]) { float* p = a.x + prow[0] * C + 16 * s + 8 * hh; *(float4*)p = pa0; *(float4*)(p + 4) = pa1; }
+        if (ok[1]) { float* p = a.x + prow[1] * C + 16 * s + 8 * hh; *(float4*)p = pb0; *(float4*)(p + 4) = pb1; }
+      }
+      unsigned ph[2][4], pl[2][4];
+      nl_split_bf16_pair(pa0.x, pa0.y, ph[0][0], pl[0][0]);
+      nl_split_bf16_pair(pa0.z, pa0.w, ph[0][1], pl[0][1]);
+      nl_split_bf16_pair(pa1.x, pa1.y, ph[0][2], pl[0][2]);
+      nl_split_bf16_pair(pa1.z, pa1.w, ph[0][3], pl[0][3]);
+      nl_split_bf16_pair(pb0.x, pb0.y, ph[1][0], pl[1][0]);
+      nl_split_bf16_pair(pb0.z, pb0.w, ph[1][1], pl[1][1]);
+      nl_split_bf16_pair(pb1.x, pb1.y, ph[1][2], pl[1][2]);
+      nl_split_bf16_pair(pb1.z, pb1.w, ph[1][3], pl[1][3]);
+      s2d_layer1_step<X3>(acc, w1hi, w1lo, s, lane, ph, pl);
+    }
+  }
+  // h1 = relu(a1 + b1): its sign bits (bit 16 b + r of the tile's word) and, for gW2, its values
+  unsigned long long mask1[2] = {0ull, 0ull};
+#pragma unroll
+  for (int b = 0; b < 4; ++b)
+#pragma unroll
+    for (int r4 = 0; r4 < 4; ++r4) {
+      const float4 bb = *(const float4*)(b1p + 16 * b + 4 * r4);
+      const float bv[4] = {bb.x, bb.y, bb.z, bb.w};
+#pragma unroll
+      for (int t = 0; t < 2; ++t) {
+        float h[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          h[e] = fmaxf(acc[t][b][4 * r4 + e] + bv[e], 0.f);
+          if (h[e] > 0.f) mask1[t] |= 1ull << (16 * b + 4 * r4 + e);
+        }
+        if (a.h1 && ok[t]) *(float4*)(a.h1 + prow[t] * S2D_H + 32 * b + 8 * r4 + 4 * hh) = make_float4(h[0], h[1], h[2], h[3]);
+      }
+    }
+  bool amb[2] = {false, false};   // EXACT: a pre-activation of the pair lies inside the band
+  if constexpr (EXACT) {
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+      float amax = 0.f, amin = 3.4e38f;
+#pragma unroll
+      for (int b = 0; b < 4; ++b)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const float v = fabsf(acc[t][b][r] + b1p[16 * b + r]);
+          amax = fmaxf(amax, v); amin = fminf(amin, v);
+        }
+      amb[t] = amin < S2D_BWD_BAND * amax;
+    }
+  }
+  if constexpr (EXACT) s2d_f32_layer2(acc, b1p, s2d_bwd_hidden + (tid >> 6) * (128 * 64) + lane, (const float*)(a.img + L.f32w2), lane);
+  else s2d_layer2<false>(acc, b1p, w2hi, w2lo, lane);
+
+  // ---- sign bits of h2 (bit 16 b + r); EXACT: the pairs with a pre-activation inside the band get the masks of both layers from an fp64 evaluation by the whole wave
+  unsigned long long mask2[2] = {0ull, 0ull};
+  {
+    const float* b2p = small + 128 + 64 * hh;
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+      float amax = 0.f, amin = 3.4e38f;
+#pragma unroll
+      for (int b = 0; b < 4; ++b)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const float v = acc[t][b][r] + b2p[16 * b + r];
+          if (v > 0.f) mask2[t] |= 1ull << (16 * b + r);
+          amax = fmaxf(amax, fabsf(v)); amin = fminf(amin, fabsf(v));
+        }
+      if (EXACT) amb[t] = amb[t] || amin < S2D_BWD_BAND * amax;
+    }
+  }
+  if constexpr (EXACT) {
+    const float* w1t = (const float*)(a.timg + T.f32w1t);   // [C][128]
+    const float* w2t = (const float*)(a.timg + T.f32w2t);   // [128 k][128 j]
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+      const unsigned long long bal = __ballot(amb[t] && ok[t]);
+      unsigned pairs = (unsigned)(bal | (bal >> 32));   // wave-uniform: either half-wave of a pair may have flagged it
+      while (pairs) {
+        const int c = __builtin_ctz(pairs);
+        pairs &= pairs - 1;
+        unsigned long long m1lo, m1hi, m2lo, m2hi;
+        bwd_fp64_signs(a.desc0 + (size_t)(n0 + t) * C, a.desc1 + (size_t)(mt * 32 + c) * C, C, w1t, w2t, small, lane, m1lo, m1hi, m2lo, m2hi);
+        if ((lane & 31) == c) {
+          mask1[t] = bwd_mask_from_units(m1lo, m1hi, hh);
+          mask2[t] = bwd_mask_from_units(m2lo, m2hi, hh);
+        }
+      }
+    }
+  }
+
+  // ---- the logit's gradient of the lane's two pairs (both half-waves hold both)
+  float gl[2];
+  {
+    const float gloss = a.g_loss ? a.g_loss[0] * a.inv_total : 0.f;
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+      gl[t] = 0.f;
+      if (ok[t]) {
+        const size_t i = (size_t)(n0 + t) * M + m;
+        float l, dz, ds;
+        s2d_focal(a.logits[i], a.target ? a.target[i] : 0.f, l, dz, ds);
+        if (a.target) gl[t] = gloss * dz;
+        if (a.g_score) gl[t] += a.g_score[i] * ds;
+      }
+    }
+  }
+  // ---- g_a2 = g_logit w3 [h2 > 0] in place; the lane's share of gW3
+  {
+    const float* b2p = small + 128 + 64 * hh;
+    const float* w3p = small + 256 + 64 * hh;
+    float gw3[64];
+#pragma unroll
+    for (int b = 0; b < 4; ++b)
+#pragma unroll
+      for (int r4 = 0; r4 < 4; ++r4) {
+        const float4 bb = *(const float4*)(b2p + 16 * b + 4 * r4), ww = *(const float4*)(w3p + 16 * b + 4 * r4);
+        const float bv[4] = {bb.x, bb.y, bb.z, bb.w}, wv[4] = {ww.x, ww.y, ww.z, ww.w};
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const int r = 4 * r4 + e;
+          const float h0 = fmaxf(acc[0][b][r] + bv[e], 0.f), h1 = fmaxf(acc[1][b][r] + bv[e], 0.f);
+          gw3[16 * b + r] = gl[0] * h0 + gl[1] * h1;
+          acc[0][b][r] = ((mask2[0] >> (16 * b + r)) & 1ull) ? gl[0] * wv[e] : 0.f;
+          acc[1][b][r] = ((mask2[1] >> (16 * b + r)) & 1ull) ? gl[1] * wv[e] : 0.f;
+        }
+#pragma unroll
+        for (int t = 0; t < 2; ++t)
+          if (a.ga2 && ok[t]) bwd_store4(a.ga2 + prow[t] * S2D_H + 32 * b + 8 * r4 + 4 * hh, acc[t][b], r4);
+      }
+    if (a.w3part) {
+      bwd_halve<32, 16>(gw3, lane);
+      bwd_halve<16, 8>(gw3, lane);
+      bwd_halve<8, 4>(gw3, lane);
+      bwd_halve<4, 2>(gw3, lane);
+      bwd_halve<2, 1>(gw3, lane);   // the lane now holds slots 2 (lane & 31) and + 1 of its half-wave
+      float* row = a.w3part + (size_t)item * S2D_W3P_LD;
+      *(float2*)(row + 64 * hh + 2 * (lane & 31)) = make_float2(gw3[0], gw3[1]);
+      float g = gl[0] + gl[1];
+#pragma unroll
+      for (int o = 16; o >= 1; o >>= 1) g += __shfl_xor(g, o);
+      if (lane == 0) row[128] = g;
+    }
+  }
+  // ---- g_a1 = (W2^T g_a2) [h1 > 0]
+  unsigned hi[2][4][8], lo[2][4][8];
+  bwd_split(acc, hi, lo);
+  nl_acc_zero(acc);
+  {
+    const uint4* w2thi = (const uint4*)(a.timg + T.w2t_hi);
+    const uint4* w2tlo = (const uint4*)(a.timg + T.w2t_lo);
+#pragma unroll
+    for (int rb = 0; rb < 4; ++rb) bwd_mult<X3>(acc[0][rb], acc[1][rb], hi, lo, w2thi, w2tlo, 4, rb, lane);
+  }
+#pragma unroll
+  for (int t = 0; t < 2; ++t)
+#pragma unroll
+    for (int b = 0; b < 4; ++b) {
+#pragma unroll
+      for (int r = 0; r < 16; ++r)
+        if (!((mask1[t] >> (16 * b + r)) & 1ull)) acc[t][b][r] = 0.f;
+#pragma unroll
+      for (int r4 = 0; r4 < 4; ++r4)
+        if (a.ga1 && ok[t]) bwd_store4(a.ga1 + prow[t] * S2D_H + 32 * b + 8 * r4 + 4 * hh, acc[t][b], r4);
+    }
+  // ---- g_x = W1^T g_a1, 32 channels at a time
+  bwd_split(acc, hi, lo);
+  {
+    const uint4* w1thi = (const uint4*)(a.timg + T.w1t_hi);
+    const uint4* w1tlo = (const uint4*)(a.timg + T.w1t_lo);
+    for (int rb = 0; rb < nrb1; ++rb) {
+      nl_f32x16 o[2];
+      nl_acc_zero(o);
+      bwd_mult<X3>(o[0], o[1], hi, lo, w1thi, w1tlo, nrb1, rb, lane);
+#pragma unroll
+      for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int r4 = 0; r4 < 4; ++r4)
+          if (ok[t]) bwd_store4(a.gx + prow[t] * C + 32 * rb + 8 * r4 + 4 * hh, o[t], r4);
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------------ reductions of a chunk
+// g_desc0: partial sums of row `blockIdx.x` over the 256-column segment blockIdx.y; thread (c4, sub) adds columns sub, sub + 4, .. of the segment
+__global__ __launch_bounds__(256) void s2d_gd0_part_kernel(const float* gx, const float* desc1, int M, int C, int nseg, float* part) {
+  __shared__ float4 red[4][64];
+  const int c4 = threadIdx.x & 63, sub = threadIdx.x >> 6, row = blockIdx.x, seg = blockIdx.y;
+  float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
+  if (4 * c4 < C) {
+    const int m_end = min(M, seg * 256 + 256);
+    for (int m = seg * 256 + sub; m < m_end; m += 4) {
+      const float4 g = *(const float4*)(gx + ((size_t)row * M + m) * C + 4 * c4), d = *(const float4*)(desc1 + (size_t)m * C + 4 * c4);
+      s.x += g.x * d.x; s.y += g.y * d.y; s.z += g.z * d.z; s.w += g.w * d.w;
+    }
+  }
+  red[sub][c4] = s;
+  __syncthreads();
+  if (sub == 0 && 4 * c4 < C) {
+    const float4 p = red[0][c4], q = red[1][c4], u = red[2][c4], v = red[3][c4];
+    *(float4*)(part + ((size_t)row * nseg + seg) * C + 4 * c4) = make_float4((p.x + q.x) + (u.x + v.x), (p.y + q.y) + (u.y + v.y), (p.z + q.z) + (u.z + v.z), (p.w + q.w) + (u.w + v.w));
+  }
+}
+__global__ __launch_bounds__(256) void s2d_gd0_final_kernel(const float* part, int rows, int C, int nseg, float* g_desc0) {
+  const int e = blockIdx.x * 256 + threadIdx.x;
+  if (e >= rows * C) return;
+  const int row = e / C, c = e - row * C;
+  float s = 0.f;
+  for (int g = 0; g < nseg; ++g) s += part[((size_t)row * nseg + g) * C + c];
+  g_desc0[e] = s;
+}
+// g_desc1[m] += sum over the chunk's rows, in order
+__global__ __launch_bounds__(256) void s2d_gd1_kernel(const float* gx, const float* desc0, int rows, int M, int C, float* g_desc1) {
+  const int c4n = C >> 2;
+  const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (e >= (long long)M * c4n) return;
+  const int m = (int)(e / c4n), c4 = (int)(e - (long long)m * c4n);
+  float4 s = *(float4*)(g_desc1 + (size_t)m * C + 4 * c4);
+  for (int r = 0; r < rows; ++r) {
+    const float4 g = *(const float4*)(gx + ((size_t)r * M + m) * C + 4 * c4), d = *(const float4*)(desc0 + (size_t)r * C + 4 * c4);
+    s.x += g.x * d.x; s.y += g.y * d.y; s.z += g.z * d.z; s.w += g.w * d.w;
+  }
+  *(float4*)(g_desc1 + (size_t)m * C + 4 * c4) = s;
+}
+// gW3[unit] += the waves' partials, block j = one output (128: gb3): 256 interleaved in-thread sums, then a tree in a fixed order
+__global__ __launch_bounds__(256) void s2d_w3_reduce_kernel(const float* part, int items, float* gw3, float* gb3) {
+  __shared__ float red[256];
+  const int j = blockIdx.x, tid = threadIdx.x;
+  float s = 0.f;
+  for (int i = tid; i < items; i += 256) s += part[(size_t)i * S2D_W3P_LD + j];
+  red[tid] = s;
+  __syncthreads();
+#pragma unroll
+  for (int o = 128; o >= 1; o >>= 1) {
+    if (tid < o) red[tid] += red[tid + o];
+    __syncthreads();
+  }
+  if (tid != 0) return;
+  if (j == 128) { if (gb3) gb3[0] += red[0]; }
+  else if (gw3) { const int q = j & 63; gw3[s2d_unit(q >> 4, q & 15, j >> 6)] += red[0]; }
+}
+__global__ __launch_bounds__(256) void s2d_transpose_kernel(const float* w, int rows, int cols, float* wt) {   // wt[c][r] = w[r][c]
+  const int e = blockIdx.x * 256 + threadIdx.x;
+  if (e >= rows * cols) return;
+  const int c = e / rows, r = e - c * rows;
+  wt[e] = w[(size_t)r * cols + c];
+}
+
+bool bwd_shape_ok(int64_t N, int64_t M) { return N >= 1 && M >= 1 && M <= (1 << 20) && N <= (1 << 30) && N * M < (1ll << 31); }
+int64_t bwd_chunk_rows(int64_t N, int64_t M) {
+  const int64_t pairs = N * M < S2D_BWD_SMALL_BELOW ? S2D_BWD_PAIRS_SMALL : S2D_BWD_PAIRS;
+  const int64_t r = std::max<int64_t>(2, (pairs / M) & ~(int64_t)1);
+  return std::min<int64_t>(r, (N + 1) & ~(int64_t)1);
+}
+struct BwdWs { size_t x, h1, ga2, ga1, gx, w3part, gd0part, wg, dummy, total; size_t wg_floats; int64_t rows; int nseg; };
+BwdWs bwd_ws(int64_t N, int64_t M, int C) {
+  BwdWs w;
+  w.rows = bwd_chunk_rows(N, M);
+  w.nseg = (int)nl_cdiv(M, 256);
+  const size_t P = (size_t)w.rows * (size_t)M;
+  const size_t items = (size_t)nl_cdiv(M, 32) * (size_t)(w.rows / 2);
+  size_t o = 0;
+  auto take = [&](size_t bytes) { const size_t at = o; o += nl_align_up(bytes, 256); return at; };
+  w.x = take(P * C * 4);
+  w.h1 = take(P * S2D_H * 4);
+  w.ga2 = take(P * S2D_H * 4);
+  w.ga1 = take(P * S2D_H * 4);
+  w.gx = take(P * C * 4);
+  w.w3part = take(items * S2D_W3P_LD * 4);
+  w.gd0part = take((size_t)w.rows * w.nseg * C * 4);
+  w.wg_floats = std::max(nl_wgrad_scratch_floats((int64_t)P, S2D_H, C), nl_wgrad_scratch_floats((int64_t)P, S2D_H, S2D_H));
+  w.wg = take(w.wg_floats * 4);
+  w.dummy = take((size_t)S2D_H * 256 * 4);
+  w.total = o;
+  return w;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t nl_s2d_train_weights_bytes(int C) { return s2d_c_ok(C) ? s2d_train_layout(C).total : 0; }
+
+int nl_s2d_pack_train_weights(int C, const float* w1, const float* w2, void* packed, size_t packed_bytes, void* stream) {
+  if (!s2d_c_ok(C)) return C > 0 ? NL_ERR_UNSUPPORTED : NL_ERR_BAD_ARG;
+  if (!w1 || !w2 || !packed) return NL_ERR_BAD_ARG;
+  if (((uintptr_t)packed & 15) != 0 || (((uintptr_t)w1 | (uintptr_t)w2) & 3) != 0) return NL_ERR_BAD_ARG;
+  const S2dTrainLayout T = s2d_train_layout(C);
+  if (packed_bytes < T.total) return NL_ERR_WORKSPACE;
+  unsigned char* img = (unsigned char*)packed;
+  hipStream_t st = (hipStream_t)stream;
+  float* w2t = (float*)(img + T.f32w2t);
+  float* w1t = (float*)(img + T.f32w1t);
+  hipLaunchKernelGGL(s2d_transpose_kernel, dim3((unsigned)nl_cdiv(S2D_H * S2D_H, 256)), dim3(256), 0, st, w2, S2D_H, S2D_H, w2t);
+  NL_LAUNCH_CHECK();
+  hipLaunchKernelGGL(s2d_transpose_kernel, dim3((unsigned)nl_cdiv(S2D_H * C, 256)), dim3(256), 0, st, w1, S2D_H, C, w1t);
+  NL_LAUNCH_CHECK();
+  auto u16 = [&](size_t off) { return (unsigned short*)(img + off); };
+  if (const int e = nl_launch_frag_pack(w2t, S2D_H, S2D_H, u16(T.w2t_hi), u16(T.w2t_lo), nullptr, nullptr, nullptr, true, st)) return e;
+  if (const int e = nl_launch_frag_pack(w1t, C, S2D_H, u16(T.w1t_hi), u16(T.w1t_lo), nullptr, nullptr, nullptr, true, st)) return e;
+  return NL_OK;
+}
+
+size_t nl_s2d_backward_train_workspace_bytes(int64_t N, int64_t M, int C) {
+  if (!s2d_c_ok(C) || !bwd_shape_ok(N, M)) return 0;
+  return bwd_ws(N, M, C).total;
+}
+
+int nl_s2d_backward_train(const void* packed, const void* train_packed, int C, int precision, const float* desc0, int64_t N, const float* desc1, int64_t M,
+                          const float* logits, const float* target, const float* g_loss, const float* g_score, float* g_desc0, float* g_desc1, float* g_w1,
+                          float* g_b1, float* g_w2, float* g_b2, float* g_w3, float* g_b3, void* workspace, size_t workspace_bytes, void* stream) {
+  if (N < 1 || M < 1 || C < 1) return NL_ERR_BAD_ARG;
+  if (!s2d_c_ok(C) || !bwd_shape_ok(N, M)) return NL_ERR_UNSUPPORTED;
+  if (const int ps = nl_prec_status_no_mx(precision)) return ps;
+  if (!packed || !train_packed || !desc0 || !desc1 || !logits || !g_desc0 || !g_desc1) return NL_ERR_BAD_ARG;
+  if ((target != nullptr) != (g_loss != nullptr)) return NL_ERR_BAD_ARG;
+  if ((((uintptr_t)packed | (uintptr_t)train_packed | (uintptr_t)desc0 | (uintptr_t)desc1 | (uintptr_t)g_desc0 | (uintptr_t)g_desc1) & 15) != 0) return NL_ERR_BAD_ARG;
+  if ((((uintptr_t)logits | (uintptr_t)target | (uintptr_t)g_loss | (uintptr_t)g_score | (uintptr_t)g_w1 | (uintptr_t)g_b1 | (uintptr_t)g_w2 | (uintptr_t)g_b2 |
+        (uintptr_t)g_w3 | (uintptr_t)g_b3) & 3) != 0)
+    return NL_ERR_BAD_ARG;
+  const BwdWs w = bwd_ws(N, M, C);
+  if (!workspace || workspace_bytes < w.total || ((uintptr_t)workspace & 15) != 0) return NL_ERR_WORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  unsigned char* ws = (unsigned char*)workspace;
+  const bool want1 = g_w1 || g_b1, want2 = g_w2 || g_b2, want3 = g_w3 || g_b3;
+
+  NL_CHECK_HIP(hipMemsetAsync(g_desc1, 0, (size_t)M * C * 4, st));
+  if (g_w1) NL_CHECK_HIP(hipMemsetAsync(g_w1, 0, (size_t)S2D_H * C * 4, st));
+  if (g_b1) NL_CHECK_HIP(hipMemsetAsync(g_b1, 0, S2D_H * 4, st));
+  if (g_w2) NL_CHECK_HIP(hipMemsetAsync(g_w2, 0, (size_t)S2D_H * S2D_H * 4, st));
+  if (g_b2) NL_CHECK_HIP(hipMemsetAsync(g_b2, 0, S2D_H * 4, st));
+  if (g_w3) NL_CHECK_HIP(hipMemsetAsync(g_w3, 0, S2D_H * 4, st));
+  if (g_b3) NL_CHECK_HIP(hipMemsetAsync(g_b3, 0, 4, st));
+
+  BwdArgs a;
+  a.img = (const unsigned char*)packed; a.timg = (const unsigned char*)train_packed;
+  a.desc0 = desc0; a.desc1 = desc1;
+  a.logits = logits; a.target = target; a.g_loss = g_loss; a.g_score = g_score;
+  a.x = want1 ? (float*)(ws + w.x) : nullptr;
+  a.ga1 = want1 ? (float*)(ws + w.ga1) : nullptr;
+  a.h1 = want2 ? (float*)(ws + w.h1) : nullptr;
+  a.ga2 = want2 ? (float*)(ws + w.ga2) : nullptr;
+  a.gx = (float*)(ws + w.gx);
+  a.w3part = want3 ? (float*)(ws + w.w3part) : nullptr;
+  a.N = (int)N; a.M = (int)M; a.C = C;
+  a.inv_total = (float)(1.0 / ((double)N * (double)M));
+  float* wg = (float*)(ws + w.wg);
+  float* dummy = (float*)(ws + w.dummy);
+  float* gd0part = (float*)(ws + w.gd0part);
+  const int MT = (int)nl_cdiv(M, 32);
+
+  static std::atomic<unsigned long long> lds_set{0};   // the exact kernel's dynamic LDS is beyond the 64 KB a kernel gets unasked
+  if (precision != NL_PREC_BF16)
+    if (const int e = nl_allow_dynamic_lds((const void*)s2d_bwd_kernel<true>, S2D_F32_LDS, lds_set)) return e;
+
+  for (int64_t r0 = 0; r0 < N; r0 += w.rows) {
+    const int64_t r1 = std::min(N, r0 + w.rows);
+    const int rows = (int)(r1 - r0);
+    const int64_t P = (int64_t)rows * M;
+    a.r0 = (int)r0; a.r1 = (int)r1;
+    const int items = MT * ((rows + 1) / 2);
+    const dim3 grid((unsigned)nl_cdiv(items, 4));
+    if (precision == NL_PREC_BF16) hipLaunchKernelGGL(s2d_bwd_kernel<false>, grid, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL(s2d_bwd_kernel<true>, grid, dim3(256), S2D_F32_LDS, st, a);
+    NL_LAUNCH_CHECK();
+    if (want2)
+      if (const int e = nl_launch_wgrad(a.ga2, S2D_H, S2D_H, a.h1, S2D_H, S2D_H, P, 0, 0, g_w2 ? g_w2 : dummy, S2D_H, 1, 0, g_b2, wg, w.wg_floats, st)) return e;
+    if (want1)
+      if (const int e = nl_launch_wgrad(a.ga1, S2D_H, S2D_H, a.x, C, C, P, 0, 0, g_w1 ? g_w1 : dummy, C, 1, 0, g_b1, wg, w.wg_floats, st)) return e;
+    if (want3) {
+      hipLaunchKernelGGL(s2d_w3_reduce_kernel, dim3(129), dim3(256), 0, st, a.w3part, items, g_w3, g_b3);
+      NL_LAUNCH_CHECK();
+    }
+    hipLaunchKernelGGL(s2d_gd0_part_kernel, dim3(rows, w.nseg), dim3(256), 0, st, a.gx, desc1, (int)M, C, w.nseg, gd0part);
+    NL_LAUNCH_CHECK();
+    hipLaunchKernelGGL(s2d_gd0_final_kernel, dim3((unsigned)nl_cdiv((int64_t)rows * C, 256)), dim3(256), 0, st, gd0part, rows, C, w.nseg, g_desc0 + (size_t)r0 * C);
+    NL_LAUNCH_CHECK();
+    hipLaunchKernelGGL(s2d_gd1_kernel, dim3((unsigned)nl_cdiv(M * (C >> 2), 256)), dim3(256), 0, st, a.gx, desc0 + (size_t)r0 * C, rows, (int)M, C, g_desc1);
+    NL_LAUNCH_CHECK();
+  }
+  return NL_OK;
+}
+
+}  // extern "C"

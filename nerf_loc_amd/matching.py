@@ -1,8 +1,9 @@
 """Drop-in for the reference's coarse matcher, `S2DMatching` (models/matching/sparse_to_dense.py:80-151, used by matcher.py:22,72).
 
 Eval mode on a HIP device is one library call (nl_s2d_match, csrc/s2d.hip): the N x M x C outer product and the two hidden tensors of the reference's
-formulation are never materialised.  Training mode, or an input that requires grad, runs the reference's formulation in eager PyTorch in row chunks (plumbing
-so that swapping the class does not break a training script; there is no gradient kernel).  Eval mode on CPU tensors is refused: no CPU fallback.
+formulation are never materialised.  Training mode, or an input that requires grad, is the library's training step on a HIP device (nl_s2d_forward_train keeps
+the logits and writes the focal loss, nl_s2d_backward_train recomputes the hidden activations in row chunks: csrc/s2d_bwd.hip) as one autograd Function;
+hip_training = False, or CPU tensors, run the reference's formulation in eager PyTorch in row chunks.  Eval mode on CPU tensors is refused: no CPU fallback.
 """
 from __future__ import annotations
 
@@ -12,7 +13,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from ._packing import MATCHER_HIDDEN, PackedCache, check_precision, pack_matcher_mlp, require_device
+from ._packing import MATCHER_HIDDEN, MATCHER_MLP_PARAMS, PackedCache, check_precision, pack_matcher_mlp, require_device
 
 
 def sigmoid_focal_loss(logits: torch.Tensor, target: torch.Tensor, alpha: float = 0.25, gamma: float = 2.0) -> torch.Tensor:
@@ -32,13 +33,90 @@ def select_mutual_nearest(score: torch.Tensor, thr: float):
     return i_ids, all_j[i_ids]
 
 
+class _S2DTrainFn(torch.autograd.Function):
+    """(desc0, desc1, six parameters) -> (coarse_loss, score_matrix, match_j): the library pair nl_s2d_forward_train / nl_s2d_backward_train.
+
+    target is None in eval mode (no loss: the first output is a zero that carries no gradient).  Parameters that do not require grad get a NULL gradient
+    pointer.  The backward pass is not differentiable: a second-order backward raises.
+    """
+
+    @staticmethod
+    def forward(ctx, mod, target, desc0, desc1, *params):
+        lib = _lib.load()
+        dev = desc0.device
+        d0 = desc0.detach().to(torch.float32).contiguous()
+        d1 = desc1.detach().to(torch.float32).contiguous()
+        N, M, Cf = d0.shape[0], d1.shape[0], mod.feat_dim
+        with torch.cuda.device(dev):
+            packed = mod._packed_weights(dev)
+            ws_bytes = lib.nl_s2d_forward_train_workspace_bytes(N, M, Cf)
+            if ws_bytes == 0:
+                raise RuntimeError("S2DMatching: unsupported shape")
+            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+            scores = torch.empty((N, M), dtype=torch.float32, device=dev)
+            logits = torch.empty((N, M), dtype=torch.float32, device=dev)
+            loss = torch.zeros((), dtype=torch.float32, device=dev)
+            match_j = torch.empty(N, dtype=torch.int32, device=dev)
+            match_s = torch.empty(N, dtype=torch.float32, device=dev)
+            tgt = None if target is None else target.detach().to(device=dev, dtype=torch.float32).contiguous()
+            if tgt is not None and tuple(tgt.shape) != (N, M):
+                raise ValueError(f"S2DMatching: conf_matrix_gt must be ({N}, {M})")
+            st = torch.cuda.current_stream(dev).cuda_stream
+            _lib.check(lib.nl_s2d_forward_train(packed.data_ptr(), Cf, _lib.PRECISIONS[mod.precision], d0.data_ptr(), N, d1.data_ptr(), M, C.c_float(float(mod.thr)),
+                                                None if tgt is None else tgt.data_ptr(), scores.data_ptr(), logits.data_ptr(),
+                                                None if tgt is None else loss.data_ptr(), match_j.data_ptr(), match_s.data_ptr(), ws.data_ptr(), ws_bytes, st),
+                       "nl_s2d_forward_train")
+        ctx.mod, ctx.has_target = mod, tgt is not None
+        # the images of the weights this forward ran on: a parameter changed in place before backward() must not meet the saved logits
+        ctx.packed, ctx.tpacked = packed, mod._packed_train_weights(dev) if any(ctx.needs_input_grad) else None
+        ctx.in_dtypes = (desc0.dtype, desc1.dtype)
+        ctx.save_for_backward(d0, d1, logits, *([tgt] if tgt is not None else []))
+        ctx.mark_non_differentiable(match_j)
+        return loss, scores, match_j
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_loss, g_score, _g_match):
+        mod = ctx.mod
+        saved = ctx.saved_tensors
+        d0, d1, logits = saved[0], saved[1], saved[2]
+        tgt = saved[3] if ctx.has_target else None
+        lib = _lib.load()
+        dev = d0.device
+        N, M, Cf = d0.shape[0], d1.shape[0], mod.feat_dim
+        with torch.cuda.device(dev):
+            packed, tpacked = ctx.packed, ctx.tpacked
+            ws_bytes = lib.nl_s2d_backward_train_workspace_bytes(N, M, Cf)
+            if ws_bytes == 0:
+                raise RuntimeError("S2DMatching: shape not supported by the training kernels")
+            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+            g_d0 = torch.empty_like(d0)
+            g_d1 = torch.empty_like(d1)
+            params = [mod.get_parameter(n) for n in MATCHER_MLP_PARAMS]
+            g_params = [torch.empty(p.shape, dtype=torch.float32, device=dev) if ctx.needs_input_grad[4 + i] else None for i, p in enumerate(params)]
+            gl = None
+            if tgt is not None:
+                gl = (torch.zeros((), dtype=torch.float32, device=dev) if g_loss is None else g_loss.detach().to(torch.float32)).reshape(1).contiguous()
+            gs = None if g_score is None else g_score.detach().to(torch.float32).contiguous()
+            st = torch.cuda.current_stream(dev).cuda_stream
+            ptr = lambda t: None if t is None else t.data_ptr()
+            _lib.check(lib.nl_s2d_backward_train(packed.data_ptr(), tpacked.data_ptr(), Cf, _lib.PRECISIONS[mod.precision], d0.data_ptr(), N, d1.data_ptr(), M,
+                                                 logits.data_ptr(), ptr(tgt), ptr(gl), ptr(gs), g_d0.data_ptr(), g_d1.data_ptr(), *[ptr(g) for g in g_params],
+                                                 ws.data_ptr(), ws_bytes, st), "nl_s2d_backward_train")
+        out_params = [None if g is None else g.to(p.dtype) for g, p in zip(g_params, params)]
+        return (None, None, g_d0.to(ctx.in_dtypes[0]) if ctx.needs_input_grad[2] else None, g_d1.to(ctx.in_dtypes[1]) if ctx.needs_input_grad[3] else None, *out_params)
+
+
 class S2DMatching(nn.Module, PackedCache):
     """`S2DMatching(feat_dim, thr)` with the reference's parameter names, so `matcher.coarse_matcher.*` of a NeRF-Loc checkpoint loads with strict=True.
 
     precision: "bf16x3" (default: three-term split-bf16 MFMA, within 1e-4 of the fp32 reference), "fp32" (exact fp32 products) or "bf16" (throughput, not
     held to the parity bar).  want_score_matrix=False leaves data['score_matrix'] = None and skips the N x M output tensor.
     eager_chunk_rows: rows of desc0 per chunk of the eager (training) path.
+    hip_training (attribute, default True): on HIP tensors, training mode or a descriptor that requires grad runs the library's training step; False selects the
+    eager path (as ConditionalNeRF.hip_training).  CPU tensors always take the eager path there.
     """
+    hip_training = True
 
     def __init__(self, feat_dim, thr=0.1, precision: str = "bf16x3", want_score_matrix: bool = True, eager_chunk_rows: int = 32):
         super().__init__()
@@ -50,6 +128,8 @@ class S2DMatching(nn.Module, PackedCache):
         self.want_score_matrix = bool(want_score_matrix)
         self.eager_chunk_rows = int(eager_chunk_rows)
         self._cache_init()
+        self._train_cache = PackedCache()
+        self._train_cache._cache_init()
 
     # ------------------------------------------------------------------ eager path (training / autograd)
     def get_loss(self, conf, conf_gt):
@@ -65,6 +145,19 @@ class S2DMatching(nn.Module, PackedCache):
     # ------------------------------------------------------------------ library path
     def _packed_weights(self, device):
         return pack_matcher_mlp("S2DMatching", self, device)
+
+    def _packed_train_weights(self, device):
+        """The training image (the transposed weights of nl_s2d_pack_train_weights), cached like the inference image."""
+        def pack(ts):
+            lib = _lib.load()
+            need = lib.nl_s2d_train_weights_bytes(self.feat_dim)
+            if need == 0:
+                raise RuntimeError(f"S2DMatching: feat_dim {self.feat_dim} is not supported by the HIP kernel (a multiple of 32, 32..256)")
+            packed = torch.empty(need, dtype=torch.uint8, device=device)
+            st = torch.cuda.current_stream(device).cuda_stream
+            _lib.check(lib.nl_s2d_pack_train_weights(self.feat_dim, ts[0].data_ptr(), ts[1].data_ptr(), packed.data_ptr(), need, st), "nl_s2d_pack_train_weights")
+            return packed
+        return self._train_cache._cached(device, [self.mlps[0].weight, self.mlps[2].weight], pack)
 
     def match(self, desc0, desc1, want_scores=None):
         """The library call: (score_matrix or None, match_j (N) int32 with -1 = unmatched, match_score (N))."""
@@ -95,6 +188,18 @@ class S2DMatching(nn.Module, PackedCache):
     def forward(self, desc0, desc1, data):
         assert (desc0.shape[0] > 0) and (desc1.shape[0] > 0)
         if self.training or (torch.is_grad_enabled() and (desc0.requires_grad or desc1.requires_grad)):
+            if self.hip_training and desc0.is_cuda and desc1.is_cuda:
+                if desc0.dim() != 2 or desc1.dim() != 2 or desc0.shape[1] != self.feat_dim or desc1.shape[1] != self.feat_dim:
+                    raise ValueError(f"S2DMatching: descriptors must be (N, {self.feat_dim}) and (M, {self.feat_dim})")
+                target = data["conf_matrix_gt"] if self.training else None
+                # eval mode differentiates the scores with respect to the descriptors only: detached parameters are NULL gradient pointers in the backward call
+                params = [self.get_parameter(n) if self.training else self.get_parameter(n).detach() for n in MATCHER_MLP_PARAMS]
+                loss, score, match_j = _S2DTrainFn.apply(self, target, desc0, desc1, *params)
+                i_ids = torch.nonzero(match_j >= 0).squeeze(1)
+                data.update({"i_ids": i_ids, "j_ids": match_j[i_ids].to(torch.int64), "score_matrix": score})
+                if self.training:
+                    data["coarse_loss"] = loss
+                return data
             conf = self._eager_logits(desc0, desc1)
             score = torch.sigmoid(conf)
             i_ids, j_ids = select_mutual_nearest(score, self.thr)
