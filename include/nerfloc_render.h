@@ -43,11 +43,12 @@ extern "C" {
 #pragma GCC visibility push(default)
 #endif
 
-#define NL_ABI_VERSION 11  /* 2: nl_render_rays_ex / nl_render_opts (early termination, per-ray query centres); 3: nl_render_opts.flags,
+#define NL_ABI_VERSION 12  /* 2: nl_render_rays_ex / nl_render_opts (early termination, per-ray query centres); 3: nl_render_opts.flags,
                             * reserved fields validated, side stream owned by the nl_frame; 5: NL_PREC_F16MX; 6: nl_frame_diagnostics;
                             * 7: NL_RENDER_PRECISION_GUARD (the precision guard at the boundary), NL_DIAG_GUARD_*; 8: nl_s2d_* (the coarse matcher);
                             * 9: nl_fine_* (the fine matcher); 10: nl_sct_* (the matcher's SelfCrossTransformer);
-                            * 11: nl_s2d_*_train (the coarse matcher's training step) */
+                            * 11: nl_s2d_*_train (the coarse matcher's training step);
+                            * 12: nl_fine_*_backward, nl_fine_pack_proj_train (the fine matcher's training step) */
 #define NL_MAX_VIEWS 16
 #define NL_KNN_MAX_K 8
 
@@ -553,6 +554,45 @@ int nl_fine_windows(const void* packed, int Cf, int Cout, int precision, const f
                     int64_t M, int stride, float* out, void* stream);
 int nl_fine_match(const void* packed_mlp, int C, int precision, const float* feat_f0, const float* feat_f1, int64_t M, const float* mkps2d_c, float* expec_f,
                   float* mkps2d_f, float* heatmap, void* stream);
+
+/* The fine matcher's training step (ABI 12).  The training forward is nl_fine_windows, and nl_fine_match with the heat-map requested; nothing else is kept.
+ * Widths, alignment, precision and the order of the argument checks as for the forward calls; M <= NL_FINE_BACKWARD_MAX_M (NL_ERR_UNSUPPORTED / a size query
+ * of 0 above): nl_fine_windows_backward places each match at its rank among the earlier matches of its window, one thread per match over all earlier ones,
+ * which is quadratic in M (nothing at a frame's few thousand matches, 2 * 10^9 key reads at the limit), and both workspaces grow linearly with M.
+ * A training forward should compute the window rows with NL_PREC_F32 also when the rest runs in NL_PREC_BF16X3 (as the FinePreprocess drop-in does): every
+ * gradient is taken at those rows, and split-bf16's 2^-17 there shows as up to 2e-3 in the gradients (softmax gain, ReLU units near their kink).
+ * Gradient products are split-bf16 MFMA: three terms under NL_PREC_F32 and NL_PREC_BF16X3, one under NL_PREC_BF16.  The hidden activations are recomputed — exact
+ * fp32 in the two parity modes, with the ReLU masks of pre-activations near zero decided in fp64 as in nl_s2d_backward_train.  Every sum runs in an order that
+ * depends on the shapes and the ids alone and no float atomic touches a result: two calls give the same bits.  All outputs are overwritten.
+ *
+ * nl_fine_match_backward: from feat_f0 (M,C), feat_f1 (M,49,C), the heatmap (M,49) nl_fine_match wrote and the cotangent g_expec (M,3) of expec_f it writes
+ * g_feat_f0 (M,C), g_feat_f1 (M,49,C) and the six parameter gradients (shapes as nl_s2d_backward_train).  Each of the eight output pointers may be NULL; a NULL
+ * parameter pointer (frozen weights) skips that weight-gradient work and leaves the other results' bits unchanged.  With t[r] = g_x gx[r] + g_y gy[r] +
+ * g_std dstd/dh[r], dstd/dh[r] = sum over the axes with var >= 1e-10 (the clamp passes its gradient at equality, as torch's) of (g[r]^2 - 2 coord g[r]) /
+ * (2 sqrt(var)), the logit's gradient is h[r] (t[r] - sum h t) / sqrt(C); a zero g_std contributes exactly nothing whatever the variance, and a match whose
+ * g_expec row is zero yields exact zeros.  g_b3 is written as an exact zero: a softmax ignores a common shift of its logits, so expec_f does not depend on
+ * mlps.4.bias (autograd leaves rounding noise around zero there).  packed_mlp: nl_s2d_pack_weights; train_packed: nl_s2d_pack_train_weights.  M == 0: NL_OK, nothing launched.
+ * Workspace (the size query; 0 for an unsupported C or M): the operands of the weight gradients, M*49 rows of C + 3*128 floats, M*132 floats of gW3 / gb3
+ * partial rows, 256 * 128 * (max(C,128) + 1) floats of split-K partial tiles and 128*256 floats — about M * 49 * (C + 384) * 4 bytes.
+ *
+ * nl_fine_windows_backward: from the cotangent g_out (M,49,Cout) of nl_fine_windows' output it writes g_w (Cout,Cf), g_b (Cout) and g_feat_nhwc (B,Hf,Wf,Cf);
+ * each may be NULL.  g_b sums all M*49 rows (a padded cell's output is the bias), g_w sees zeros for padded cells; a pixel's gradient is the sum of
+ * g_out[m,ww] . W over the matches whose window covers it, in ascending m (repeated j_ids, overlapping windows and B > 1 follow from that), and a pixel no window
+ * covers is written as zero.  packed: nl_fine_pack_proj; train_packed: nl_fine_pack_proj_train (proj.weight^T in the same fragment format,
+ * nl_fine_proj_train_bytes bytes, from the DEVICE pointer w).  M == 0: NL_OK, zeros are written to the pointers given.  ids as for nl_fine_windows.
+ * Workspace: two (M*49,Cf) fp32 matrices (the gathered windows, the window-gradient rows), 256 * (Cout*Cf + Cout) floats of split-K partial tiles, Cout*Cf floats,
+ * and (2 M + B*Ly*Lx + 1) int32 of window lists — about M * 49 * Cf * 8 bytes. */
+#define NL_FINE_BACKWARD_MAX_M 65536
+size_t nl_fine_proj_train_bytes(int Cf, int Cout);
+int nl_fine_pack_proj_train(int Cf, int Cout, const float* w, void* packed, size_t packed_bytes, void* stream);
+size_t nl_fine_match_backward_workspace_bytes(int64_t M, int C);
+int nl_fine_match_backward(const void* packed_mlp, const void* train_packed, int C, int precision, const float* feat_f0, const float* feat_f1, int64_t M,
+                           const float* heatmap, const float* g_expec, float* g_feat_f0, float* g_feat_f1, float* g_w1, float* g_b1, float* g_w2, float* g_b2,
+                           float* g_w3, float* g_b3, void* workspace, size_t workspace_bytes, void* stream);
+size_t nl_fine_windows_backward_workspace_bytes(int Cf, int Cout, int B, int Hf, int Wf, int stride, int64_t M);
+int nl_fine_windows_backward(const void* packed, const void* train_packed, int Cf, int Cout, int precision, const float* feat_nhwc, int B, int Hf, int Wf,
+                             const int64_t* b_ids, const int64_t* j_ids, int64_t M, int stride, const float* g_out, float* g_w, float* g_b, float* g_feat_nhwc,
+                             void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- localisation head: SelfCrossTransformer ------------------------------------------------------------------------------------------
  * models/COTR/transformer.py:17-64 in eval mode (matcher.py:68-72, :120-124): four post-norm layers on v0 (B,N0,C) and v1 (B,N1,C), batch first, fp32 —

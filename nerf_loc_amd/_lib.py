@@ -29,7 +29,8 @@ GUARD_LOGIT_LIMIT = {"f16mx": 50.0, "bf16x3": 500.0}   # include/nerfloc_render.
 PRECISION_NAMES = {PREC_F32: "fp32", PREC_BF16X3: "bf16x3", PREC_BF16: "bf16", PREC_F16MX: "f16mx"}
 GUARD_DENSITY_LIMIT = {"f16mx": 32.0}  # include/nerfloc_render.h: NL_GUARD_DENSITY_LIMIT_F16MX (the guard's second indicator: the largest density of the frame's guarded batches; bf16x3 has no such limit)
 DIAG_COUNT = 6
-ABI_VERSION = 11  # include/nerfloc_render.h: NL_ABI_VERSION
+FINE_BACKWARD_MAX_M = 65536  # include/nerfloc_render.h: NL_FINE_BACKWARD_MAX_M (above it the fine matcher's modules train on the eager path)
+ABI_VERSION = 12  # include/nerfloc_render.h: NL_ABI_VERSION
 
 
 class NlConfig(C.Structure):
@@ -157,6 +158,12 @@ SYMBOLS = [
     ("nl_fine_pack_proj", _I, [_I, _I, _P, _P, _P, _Z, _P]),
     ("nl_fine_windows", _I, [_P, _I, _I, _I, _P, _I, _I, _I, _P, _P, _L, _I, _P, _P]),
     ("nl_fine_match", _I, [_P, _I, _I, _P, _P, _L, _P, _P, _P, _P, _P]),
+    ("nl_fine_proj_train_bytes", _Z, [_I, _I]),
+    ("nl_fine_pack_proj_train", _I, [_I, _I, _P, _P, _Z, _P]),
+    ("nl_fine_match_backward_workspace_bytes", _Z, [_L, _I]),
+    ("nl_fine_match_backward", _I, [_P, _P, _I, _I, _P, _P, _L] + [_P] * 11 + [_Z, _P]),
+    ("nl_fine_windows_backward_workspace_bytes", _Z, [_I, _I, _I, _I, _I, _I, _L]),
+    ("nl_fine_windows_backward", _I, [_P, _P, _I, _I, _I, _P, _I, _I, _I, _P, _P, _L, _I, _P, _P, _P, _P, _P, _Z, _P]),
     ("nl_sct_packed_bytes", _Z, [_I, _I, _I]),
     ("nl_sct_pack_weights", _I, [_I, _I, _I, C.POINTER(_P), _I, _P, _Z, _P]),
     ("nl_sct_workspace_bytes", _Z, [_L, _L, _L, _I, _I]),

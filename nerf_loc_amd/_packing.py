@@ -41,6 +41,27 @@ class PackedCache:
         return self._packed
 
 
+def pack_matcher_mlp_train(who, module, device):
+    """The training image of module.mlps (the transposed weights of nl_s2d_pack_train_weights, read by the backward calls of both matchers), cached in
+    module._train_cache like the inference image."""
+    def pack(ts):
+        lib = _lib.load()
+        need = lib.nl_s2d_train_weights_bytes(module.feat_dim)
+        if need == 0:
+            raise RuntimeError(f"{who}: feat_dim {module.feat_dim} is not supported by the HIP kernel (a multiple of 32, 32..256)")
+        packed = torch.empty(need, dtype=torch.uint8, device=device)
+        st = torch.cuda.current_stream(device).cuda_stream
+        _lib.check(lib.nl_s2d_pack_train_weights(module.feat_dim, ts[0].data_ptr(), ts[1].data_ptr(), packed.data_ptr(), need, st), "nl_s2d_pack_train_weights")
+        return packed
+    return module._train_cache._cached(device, [module.mlps[0].weight, module.mlps[2].weight], pack)
+
+
+def new_train_cache():
+    cache = PackedCache()
+    cache._cache_init()
+    return cache
+
+
 def pack_matcher_mlp(who, module, device):
     """The packed image of module.mlps (a PackedCache module with feat_dim; who: its name in error messages), packed on the current stream when the cache misses."""
     def pack(ts):

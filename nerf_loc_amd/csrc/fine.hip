@@ -16,44 +16,10 @@
 #include "common.h"
 #include "mfma.h"
 #include "s2d.h"
+#include "fine.h"
 #include "host.h"
 
 namespace {
-
-constexpr int FINE_W = 7, FINE_WW = 49;
-
-// ------------------------------------------------------------------------------------------ proj: layout
-// bf16 hi / lo and fp32 planes of proj.weight (Cout x Cf) in mfma.h's fragment maps (written by pack.hip's nl_launch_frag_pack), then the bias
-struct FineProjLayout { size_t hi, lo, f32, bias, total; };
-__host__ __device__ inline FineProjLayout fine_proj_layout(int Cf, int Cout) {
-  FineProjLayout l;
-  const size_t n = (size_t)Cf * Cout;
-  l.hi = 0;
-  l.lo = n * 2;
-  l.f32 = n * 4;
-  l.bias = n * 8;
-  l.total = l.bias + (size_t)Cout * 4;
-  return l;
-}
-
-// ------------------------------------------------------------------------------------------ windows
-struct FineWinArgs {
-  const unsigned char* img;
-  const float* feat;
-  const long long* b_ids; const long long* j_ids;
-  float* out;
-  int B, Hf, Wf, Cf, Cout, M, stride, Lx, L, Q;   // L = Ly * Lx windows per image, Q = work items per match (pairs of 32-channel blocks)
-};
-
-// the lane's pixel row for tile t (cell 32 t + column), or null: outside the map, a padding row, or ids the host check should have refused
-__device__ __forceinline__ const float* fine_cell_row(const FineWinArgs& a, int m, int cell) {
-  const long long b = a.b_ids[m], l = a.j_ids[m];
-  if (cell >= FINE_WW || b < 0 || b >= a.B || l < 0 || l >= a.L) return nullptr;
-  const int ly = (int)(l / a.Lx), lx = (int)(l - (long long)ly * a.Lx);
-  const int py = ly * a.stride + cell / FINE_W - FINE_W / 2, px = lx * a.stride + cell % FINE_W - FINE_W / 2;
-  if (py < 0 || py >= a.Hf || px < 0 || px >= a.Wf) return nullptr;
-  return a.feat + (((size_t)b * a.Hf + py) * a.Wf + px) * a.Cf;
-}
 
 __device__ __forceinline__ void fine_win_store(const FineWinArgs& a, const nl_f32x16 (&acc)[2][2], int m, int rb0, bool has1, int lane) {
   const int hh = lane >> 5, col = lane & 31;
@@ -264,10 +230,26 @@ __global__ __launch_bounds__(256) void fine_match_f32_kernel(const FineMatchArgs
   fine_finish(a, logit, m, lane);
 }
 
-bool fine_c_ok(int C) { return s2d_c_ok(C); }
-constexpr int64_t FINE_MAX_M = 1 << 24;
-
 }  // namespace
+
+// out (M * 49, Cout) = rows (M * 49, Cin) . W^T with `img` a proj image of W (Cout x Cin) — the window kernels on dense rows (the backward's g_out . proj.weight,
+// with the training image of proj.weight^T, whose bias is zero); split-bf16, three terms with x3.  There is no exact-fp32 form on purpose: fine_win_f32_kernel
+// must never run on a training image, whose fp32 plane holds the plain transpose (the packer's staging), not fragment order
+int nl_launch_fine_rows(const void* img, int Cin, int Cout, bool x3, const float* rows, int64_t M, float* out, hipStream_t st) {
+  FineWinArgs a;
+  a.img = (const unsigned char*)img;
+  a.feat = rows;
+  a.b_ids = nullptr; a.j_ids = nullptr;
+  a.out = out;
+  a.B = 1; a.Hf = 1; a.Wf = 1; a.Cf = Cin; a.Cout = Cout; a.M = (int)M; a.stride = 1; a.Lx = 1; a.L = 1;
+  a.Q = ((Cout >> 5) + 1) >> 1;
+  a.dense = 1;
+  const unsigned grid = (unsigned)nl_cdiv(M * a.Q, 4);
+  if (x3) hipLaunchKernelGGL(fine_win_bf16_kernel<true>, dim3(grid), dim3(256), 0, st, a);
+  else hipLaunchKernelGGL(fine_win_bf16_kernel<false>, dim3(grid), dim3(256), 0, st, a);
+  NL_LAUNCH_CHECK();
+  return NL_OK;
+}
 
 extern "C" {
 
@@ -303,6 +285,7 @@ int nl_fine_windows(const void* packed, int Cf, int Cout, int precision, const f
   a.Lx = (Wf - 1) / stride + 1;
   a.L = ((Hf - 1) / stride + 1) * a.Lx;
   a.Q = ((Cout >> 5) + 1) >> 1;
+  a.dense = 0;
   hipStream_t st = (hipStream_t)stream;
   const unsigned grid = (unsigned)nl_cdiv(M * a.Q, 4);   // sized by M: a device-wide persistent grid would idle at a few thousand tiles
   if (precision == NL_PREC_F32) hipLaunchKernelGGL(fine_win_f32_kernel, dim3(grid), dim3(256), 0, st, a);

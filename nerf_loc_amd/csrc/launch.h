@@ -178,3 +178,13 @@ int nl_launch_wgrad(const float* dY, int ldy, int M, const float* X, int ldx, in
 size_t nl_wgrad_scratch_floats(int64_t rows, int M, int N);
 int nl_launch_wgrad_multi(int nsub, const float* const* dY, int ldy, int M, const float* const* X, int ldx, int N, int64_t rows, const int* shift, int period,
                           float* gW, int ldc, int cs, const int* co, float* gb, int bias_sub, float* scratch, size_t scratch_floats, hipStream_t st);
+
+// ---- s2d_bwd.hip -----------------------------------------------------------------------------------------
+// gw3[unit] += / gb3[0] += the waves' partial rows ([items][S2D_W3P_LD], s2d_bwd.h) in a fixed order; either output may be null
+int nl_launch_s2d_w3_reduce(const float* part, int items, float* gw3, float* gb3, hipStream_t st);
+// wt (cols, rows) = w (rows, cols)^T
+int nl_launch_transpose(const float* w, int rows, int cols, float* wt, hipStream_t st);
+
+// ---- fine.hip --------------------------------------------------------------------------------------------
+// out (M * 49, Cout) = rows (M * 49, Cin) . W^T for a proj image of W (Cout x Cin): the window kernels on dense rows, split-bf16 (three terms with x3)
+int nl_launch_fine_rows(const void* img, int Cin, int Cout, bool x3, const float* rows, int64_t M, float* out, hipStream_t st);

@@ -13,7 +13,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from ._packing import MATCHER_HIDDEN, MATCHER_MLP_PARAMS, PackedCache, check_precision, pack_matcher_mlp, require_device
+from ._packing import MATCHER_HIDDEN, MATCHER_MLP_PARAMS, PackedCache, check_precision, pack_matcher_mlp, pack_matcher_mlp_train, require_device
 
 
 def sigmoid_focal_loss(logits: torch.Tensor, target: torch.Tensor, alpha: float = 0.25, gamma: float = 2.0) -> torch.Tensor:
@@ -148,16 +148,7 @@ class S2DMatching(nn.Module, PackedCache):
 
     def _packed_train_weights(self, device):
         """The training image (the transposed weights of nl_s2d_pack_train_weights), cached like the inference image."""
-        def pack(ts):
-            lib = _lib.load()
-            need = lib.nl_s2d_train_weights_bytes(self.feat_dim)
-            if need == 0:
-                raise RuntimeError(f"S2DMatching: feat_dim {self.feat_dim} is not supported by the HIP kernel (a multiple of 32, 32..256)")
-            packed = torch.empty(need, dtype=torch.uint8, device=device)
-            st = torch.cuda.current_stream(device).cuda_stream
-            _lib.check(lib.nl_s2d_pack_train_weights(self.feat_dim, ts[0].data_ptr(), ts[1].data_ptr(), packed.data_ptr(), need, st), "nl_s2d_pack_train_weights")
-            return packed
-        return self._train_cache._cached(device, [self.mlps[0].weight, self.mlps[2].weight], pack)
+        return pack_matcher_mlp_train("S2DMatching", self, device)
 
     def match(self, desc0, desc1, want_scores=None):
         """The library call: (score_matrix or None, match_j (N) int32 with -1 = unmatched, match_score (N))."""
