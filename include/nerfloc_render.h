@@ -43,12 +43,13 @@ extern "C" {
 #pragma GCC visibility push(default)
 #endif
 
-#define NL_ABI_VERSION 12  /* 2: nl_render_rays_ex / nl_render_opts (early termination, per-ray query centres); 3: nl_render_opts.flags,
+#define NL_ABI_VERSION 13  /* 2: nl_render_rays_ex / nl_render_opts (early termination, per-ray query centres); 3: nl_render_opts.flags,
                             * reserved fields validated, side stream owned by the nl_frame; 5: NL_PREC_F16MX; 6: nl_frame_diagnostics;
                             * 7: NL_RENDER_PRECISION_GUARD (the precision guard at the boundary), NL_DIAG_GUARD_*; 8: nl_s2d_* (the coarse matcher);
                             * 9: nl_fine_* (the fine matcher); 10: nl_sct_* (the matcher's SelfCrossTransformer);
                             * 11: nl_s2d_*_train (the coarse matcher's training step);
-                            * 12: nl_fine_*_backward, nl_fine_pack_proj_train (the fine matcher's training step) */
+                            * 12: nl_fine_*_backward, nl_fine_pack_proj_train (the fine matcher's training step);
+                            * 13: nl_sct_*_train, nl_sct_backward, nl_sct_layer_backward (the SelfCrossTransformer's training step) */
 #define NL_MAX_VIEWS 16
 #define NL_KNN_MAX_K 8
 
@@ -617,6 +618,46 @@ int nl_sct_layer(const void* packed, int C, int nhead, int F, int layer, int pre
                  const float* mem_pos, int64_t Nk, int64_t B, float* out, void* ws, size_t ws_bytes, void* stream);
 int nl_sct_forward(const void* packed, int C, int nhead, int F, int precision, const float* v0, const float* pos0, int64_t N0, const float* v1, const float* pos1,
                    int64_t N1, int64_t B, float* out0, float* out1, void* ws, size_t ws_bytes, void* stream);
+
+/* ---- SelfCrossTransformer: training step (ABI 13) ---------------------------------------------------------------------------------------
+ * The forward and backward of the four layers above with NO dropout in effect (dropout == 0, or the module in eval mode); dropout inside the kernels is not built.
+ * No Nq x Nk value reaches memory in either direction: the backward rebuilds the probabilities tile by tile from the kept row maximum and sum (the two parts of the
+ * log-sum-exp), in two passes (dQ: a wave per 32 queries over the key tiles; dK / dV: a wave per 32 keys over the query tiles), no float atomics: two calls on the
+ * same inputs give the same bits.  Shapes, precisions, alignment and the order of the checks are nl_sct_forward's; every size query returns 0 for a shape or
+ * configuration the calls refuse.
+ * nl_sct_pack_weights_train: the second image (nl_sct_train_packed_bytes) — the transposes of the three in_proj blocks, out_proj, linear1 and linear2 of every layer
+ * in the fragment planes of the inference image; `tensors` as for nl_sct_pack_weights.
+ * nl_sct_forward_train: nl_sct_forward's arguments plus a caller-owned, 256-byte aligned state buffer of nl_sct_train_state_bytes(B, N0, N1, C, F) bytes (a missing or
+ * short one: NL_ERR_WORKSPACE; `ws` is checked as nl_sct_forward checks it and not written: q, k, v and the attention output go to the state).  out0 / out1 are
+ * bit-identical to nl_sct_forward's in the same mode.  Kept per layer: q, k, v, the attention output before out_proj,
+ * (maximum, sum) per (row, head), the rows after the first LayerNorm, both LayerNorms' normalised rows and 1 / std, and the outputs of layers 0..2 — 8 (rows_q x C) +
+ * 2 (rows_k x C) + 18 rows_q floats per layer; nothing of size F or Nq x Nk.
+ * nl_sct_backward: from both images, the four inputs, the state and the cotangents g_out0 (B,N0,C), g_out1 (B,N1,C) — either may be NULL and then means zero — it
+ * writes g_v0, g_pos0 (B,N0,C), g_v1, g_pos1 (B,N1,C) and the parameter gradients grads[0..51]: a HOST array of DEVICE pointers in state-dict order (shapes of the
+ * parameters), n_grads == 52, or grads == NULL.  Every output pointer may be NULL (a frozen parameter, an input that needs no gradient); the entries of the cross
+ * layers' norm1 pair (indices 32, 33, 46, 47) are ignored and never written: the reference never applies that norm and leaves its .grad None.  A NULL costs no launch
+ * that only it needs and leaves the other outputs' bits unchanged.  All given outputs are overwritten.  With one key (a layer whose Nk == 1) the softmax is constant
+ * and dS is an exact zero, as autograd's.  Workspace: nl_sct_backward_workspace_bytes — about 10 (B max(N0,N1) x C) floats, two (min(rows, 32768) x F) staging
+ * buffers for the linear1 / linear2 weight gradients and the split-K partial tiles of wgrad.  State + workspace at (B 1, N0 1024, N1 4800, C 192, F 512) is
+ * about 0.13 GB, against the 1.08 GB of softmax outputs that an eager autograd which materialises them keeps, and grows linearly with the sequences.
+ * nl_sct_layer_backward: one layer (0..3), mirroring nl_sct_layer: it runs that layer's training forward on (x, x_pos, mem, mem_pos) inside its workspace
+ * (nl_sct_layer_backward_workspace_bytes(B, Nq, Nk, C, F): the backward's plus that layer's state) and then its backward from g_out (B,Nq,C): g_x, g_x_pos (B,Nq,C), g_mem, g_mem_pos (B,Nk,C) and the layer's 12
+ * (self) or 14 (cross) parameter gradients in state-dict order.  For layers 0 / 1 mem / mem_pos are NULL or x / x_pos, g_mem / g_mem_pos must be NULL and the
+ * memory side's gradient is part of g_x / g_x_pos. */
+size_t nl_sct_train_packed_bytes(int C, int nhead, int F);
+int nl_sct_pack_weights_train(int C, int nhead, int F, const float* const* tensors, int n_tensors, void* packed, size_t packed_bytes, void* stream);
+size_t nl_sct_train_state_bytes(int64_t B, int64_t N0, int64_t N1, int C, int F);
+int nl_sct_forward_train(const void* packed, int C, int nhead, int F, int precision, const float* v0, const float* pos0, int64_t N0, const float* v1,
+                         const float* pos1, int64_t N1, int64_t B, float* out0, float* out1, void* state, size_t state_bytes, void* ws, size_t ws_bytes,
+                         void* stream);
+size_t nl_sct_backward_workspace_bytes(int64_t B, int64_t N0, int64_t N1, int C, int F);
+int nl_sct_backward(const void* packed, const void* train_packed, int C, int nhead, int F, int precision, const float* v0, const float* pos0, int64_t N0,
+                    const float* v1, const float* pos1, int64_t N1, int64_t B, const void* state, size_t state_bytes, const float* g_out0, const float* g_out1,
+                    float* g_v0, float* g_pos0, float* g_v1, float* g_pos1, float* const* grads, int n_grads, void* ws, size_t ws_bytes, void* stream);
+size_t nl_sct_layer_backward_workspace_bytes(int64_t B, int64_t Nq, int64_t Nk, int C, int F);
+int nl_sct_layer_backward(const void* packed, const void* train_packed, int C, int nhead, int F, int layer, int precision, const float* x, const float* x_pos,
+                          int64_t Nq, const float* mem, const float* mem_pos, int64_t Nk, int64_t B, const float* g_out, float* g_x, float* g_x_pos, float* g_mem,
+                          float* g_mem_pos, float* const* grads, int n_grads, void* ws, size_t ws_bytes, void* stream);
 
 #if defined(__GNUC__) || defined(__clang__)
 #pragma GCC visibility pop

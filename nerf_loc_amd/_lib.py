@@ -30,7 +30,7 @@ PRECISION_NAMES = {PREC_F32: "fp32", PREC_BF16X3: "bf16x3", PREC_BF16: "bf16", P
 GUARD_DENSITY_LIMIT = {"f16mx": 32.0}  # include/nerfloc_render.h: NL_GUARD_DENSITY_LIMIT_F16MX (the guard's second indicator: the largest density of the frame's guarded batches; bf16x3 has no such limit)
 DIAG_COUNT = 6
 FINE_BACKWARD_MAX_M = 65536  # include/nerfloc_render.h: NL_FINE_BACKWARD_MAX_M (above it the fine matcher's modules train on the eager path)
-ABI_VERSION = 12  # include/nerfloc_render.h: NL_ABI_VERSION
+ABI_VERSION = 13  # include/nerfloc_render.h: NL_ABI_VERSION
 
 
 class NlConfig(C.Structure):
@@ -169,6 +169,14 @@ SYMBOLS = [
     ("nl_sct_workspace_bytes", _Z, [_L, _L, _L, _I, _I]),
     ("nl_sct_layer", _I, [_P, _I, _I, _I, _I, _I, _P, _P, _L, _P, _P, _L, _L, _P, _P, _Z, _P]),
     ("nl_sct_forward", _I, [_P, _I, _I, _I, _I, _P, _P, _L, _P, _P, _L, _L, _P, _P, _P, _Z, _P]),
+    ("nl_sct_train_packed_bytes", _Z, [_I, _I, _I]),
+    ("nl_sct_pack_weights_train", _I, [_I, _I, _I, C.POINTER(_P), _I, _P, _Z, _P]),
+    ("nl_sct_train_state_bytes", _Z, [_L, _L, _L, _I, _I]),
+    ("nl_sct_forward_train", _I, [_P, _I, _I, _I, _I, _P, _P, _L, _P, _P, _L, _L, _P, _P, _P, _Z, _P, _Z, _P]),
+    ("nl_sct_backward_workspace_bytes", _Z, [_L, _L, _L, _I, _I]),
+    ("nl_sct_backward", _I, [_P, _P, _I, _I, _I, _I, _P, _P, _L, _P, _P, _L, _L, _P, _Z, _P, _P, _P, _P, _P, _P, C.POINTER(_P), _I, _P, _Z, _P]),
+    ("nl_sct_layer_backward_workspace_bytes", _Z, [_L, _L, _L, _I, _I]),
+    ("nl_sct_layer_backward", _I, [_P, _P, _I, _I, _I, _I, _I, _P, _P, _L, _P, _P, _L, _L, _P, _P, _P, _P, _P, C.POINTER(_P), _I, _P, _Z, _P]),
     ("nl_backproject_support", _I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _L, _P, _P, _P, _P, C.POINTER(_L), _P, _Z, _P]),
 ]
 

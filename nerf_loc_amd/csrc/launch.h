@@ -188,3 +188,9 @@ int nl_launch_transpose(const float* w, int rows, int cols, float* wt, hipStream
 // ---- fine.hip --------------------------------------------------------------------------------------------
 // out (M * 49, Cout) = rows (M * 49, Cin) . W^T for a proj image of W (Cout x Cin): the window kernels on dense rows, split-bf16 (three terms with x3)
 int nl_launch_fine_rows(const void* img, int Cin, int Cout, bool x3, const float* rows, int64_t M, float* out, hipStream_t st);
+
+// ---- sct.hip ---------------------------------------------------------------------------------------------
+// the projections and the attention of one layer (0..3) of an nl_sct_pack_weights image with the inference kernels, into caller-owned q (B * Nq, C), k, v
+// (B * Nk, C) and attention-output rows (B * Nq, C): the first half of nl_sct_layer, for the training forward (sct_bwd.hip), which keeps them
+int nl_launch_sct_qkv_attn(const void* img, int C, int F, int layer, int precision, const float* x, const float* xpos, int64_t Nq, const float* mem, const float* mpos,
+                           int64_t Nk, int64_t B, float* q, float* k, float* v, float* attn, hipStream_t st);

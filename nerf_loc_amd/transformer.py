@@ -2,8 +2,13 @@
 
 Eval mode on a HIP device is ONE library call (nl_sct_forward, csrc/sct.hip): four post-norm layers, each a projection kernel, a flash-style attention kernel that
 never writes an Nq x Nk tensor, and a row-chain kernel (out_proj, residual, LayerNorm, FFN, residual, LayerNorm) whose hidden rows stay on chip.  Training mode, or
-an input that requires grad while grad is enabled, runs the same four layers in eager PyTorch through the same sub-modules (plumbing so that swapping the class does
-not break a training script; there is no gradient kernel).  Eval mode on CPU tensors is refused: no CPU fallback.
+an input that requires grad while grad is enabled, runs the same four layers in eager PyTorch through the same sub-modules by default.  Eval mode on CPU tensors is
+refused: no CPU fallback.
+
+`hip_training = True` (opt-in, default False) replaces that eager stretch by the library's training step whenever NO dropout is in effect (the constructor's
+dropout == 0, or eval mode): one autograd Function around nl_sct_forward_train / nl_sct_backward (csrc/sct_bwd.hip), which keeps O(rows x C) of state, never a
+heads x Nq x Nk tensor, and gives the same bits on every call.  Dropout inside the kernels is not built: training mode with dropout > 0 stays eager (the reference's
+Matcher constructs both transformers with dropout = 0.1).
 
 The sub-modules carry the reference's names (`self_attn_layer{0,1}.self_attn / linear1 / linear2 / norm1 / norm2`, `cross_attn_layer{0,1}.multihead_attn /
 linear1 / linear2 / norm1 / norm2 / norm3`), so `matcher.coarse_transformer.*` and `matcher.fine_transformer.*` of a NeRF-Loc checkpoint load with strict=True.
@@ -18,7 +23,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _lib
-from ._packing import PackedCache, check_precision, require_device
+from ._packing import PackedCache, check_precision, new_train_cache, require_device
 
 _LIMITS = "nhead == 8, d_model in {64, 128, 192, 256}, dim_feedforward a multiple of 32 in 32..512, activation 'relu'"
 
@@ -54,11 +59,68 @@ class _Layer(nn.Module):
         return norm_b(x + self.dropout_b(f))
 
 
+_UNUSED_PARAMS = (32, 33, 46, 47)   # state-dict indices of the cross layers' norm1 pair: constructed, never applied, no gradient
+
+
+class _TrainStep(torch.autograd.Function):
+    """nl_sct_forward_train / nl_sct_backward around the module's four layers; the 52 parameters are inputs so that autograd routes their gradients."""
+
+    @staticmethod
+    def forward(ctx, mod, v0, pos0, v1, pos1, *params):
+        lib = _lib.load()
+        dev = v0.device
+        C, Fh = mod.d_model, mod.dim_feedforward
+        B, N0, N1 = v0.shape[0], v0.shape[1], v1.shape[1]
+        with torch.cuda.device(dev):
+            packed, tpacked = mod._pack(dev), mod._pack_train(dev)
+            a = [t.detach().to(torch.float32).contiguous() for t in (v0, pos0, v1, pos1)]
+            out0 = torch.empty((B, N0, C), dtype=torch.float32, device=dev)
+            out1 = torch.empty((B, N1, C), dtype=torch.float32, device=dev)
+            sb, wb = lib.nl_sct_train_state_bytes(B, N0, N1, C, Fh), lib.nl_sct_workspace_bytes(B, N0, N1, C, Fh)
+            state = torch.empty(sb, dtype=torch.uint8, device=dev)
+            ws = torch.empty(wb, dtype=torch.uint8, device=dev)
+            st = torch.cuda.current_stream(dev).cuda_stream
+            _lib.check(lib.nl_sct_forward_train(packed.data_ptr(), C, mod.nhead, Fh, _lib.PRECISIONS[mod.precision], a[0].data_ptr(), a[1].data_ptr(), N0,
+                                                a[2].data_ptr(), a[3].data_ptr(), N1, B, out0.data_ptr(), out1.data_ptr(), state.data_ptr(), sb, ws.data_ptr(), wb, st),
+                       "nl_sct_forward_train")
+        ctx.mod, ctx.images, ctx.inputs, ctx.state, ctx.dims = mod, (packed, tpacked), a, state, (B, N0, N1)
+        ctx.in_dtypes = [t.dtype for t in (v0, pos0, v1, pos1)]
+        ctx.param_meta = [(p.shape, p.dtype) for p in params]
+        ctx.set_materialize_grads(False)
+        return out0, out1
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g0, g1):
+        lib = _lib.load()
+        mod, a, (B, N0, N1) = ctx.mod, ctx.inputs, ctx.dims
+        dev = a[0].device
+        C, Fh = mod.d_model, mod.dim_feedforward
+        need = ctx.needs_input_grad
+        with torch.cuda.device(dev):
+            g0, g1 = (None if g is None else g.to(torch.float32).contiguous() for g in (g0, g1))
+            gin = [torch.empty_like(a[i]) if need[1 + i] else None for i in range(4)]
+            gpar = [torch.empty(shape, dtype=torch.float32, device=dev) if need[5 + i] and i not in _UNUSED_PARAMS else None
+                    for i, (shape, _) in enumerate(ctx.param_meta)]
+            ptr = lambda t: None if t is None else t.data_ptr()
+            arr = (ctypes.c_void_p * len(gpar))(*[ptr(t) for t in gpar])
+            wb = lib.nl_sct_backward_workspace_bytes(B, N0, N1, C, Fh)
+            ws = torch.empty(wb, dtype=torch.uint8, device=dev)
+            st = torch.cuda.current_stream(dev).cuda_stream
+            _lib.check(lib.nl_sct_backward(ctx.images[0].data_ptr(), ctx.images[1].data_ptr(), C, mod.nhead, Fh, _lib.PRECISIONS[mod.precision], a[0].data_ptr(),
+                                           a[1].data_ptr(), N0, a[2].data_ptr(), a[3].data_ptr(), N1, B, ctx.state.data_ptr(), ctx.state.numel(), ptr(g0), ptr(g1),
+                                           ptr(gin[0]), ptr(gin[1]), ptr(gin[2]), ptr(gin[3]), arr, len(gpar), ws.data_ptr(), wb, st), "nl_sct_backward")
+        gin = [g if g is None else g.to(dt) for g, dt in zip(gin, ctx.in_dtypes)]
+        gpar = [g if g is None else g.to(dt) for g, (_, dt) in zip(gpar, ctx.param_meta)]
+        return (None, *gin, *gpar)
+
+
 class SelfCrossTransformer(nn.Module, PackedCache):
     """`SelfCrossTransformer(d_model, nhead, ..., dim_feedforward, dropout, activation)` with the reference's signature.
 
     precision: "bf16x3" (default: three-term split products on the matrix pipe, within 1e-4 of the fp32 reference), "fp32" (exact fp32 products) or
     "bf16" (throughput, no bar).
+    hip_training (attribute, default False): take the library's training step instead of eager autograd where it applies (see the module docstring).
     """
 
     def __init__(self, d_model=512, nhead=8, num_encoder_layers=6, num_decoder_layers=6, dim_feedforward=2048, dropout=0.1, activation="relu",
@@ -74,8 +136,11 @@ class SelfCrossTransformer(nn.Module, PackedCache):
             if p.dim() > 1:
                 nn.init.xavier_uniform_(p)
         self.d_model, self.nhead, self.dim_feedforward = int(d_model), int(nhead), int(dim_feedforward)
+        self.dropout = float(dropout)
+        self.hip_training = False
         self.precision = check_precision(precision)
         self._cache_init()
+        self._train_cache = new_train_cache()
 
     # ------------------------------------------------------------------ eager path (training / autograd)
     def _eager(self, v0, pos0, v1, pos1):
@@ -104,6 +169,36 @@ class SelfCrossTransformer(nn.Module, PackedCache):
             _lib.check(lib.nl_sct_pack_weights(self.d_model, self.nhead, self.dim_feedforward, arr, len(ts), packed.data_ptr(), need, st), "nl_sct_pack_weights")
             return packed
         return self._cached(device, ps, pack)
+
+    def _pack_train(self, device):
+        """The training image (the transposed weights nl_sct_backward multiplies by), cached like the inference image."""
+        lib = _lib.load()
+        need = lib.nl_sct_train_packed_bytes(self.d_model, self.nhead, self.dim_feedforward)
+        ps = list(self.parameters())
+
+        def pack(ts):
+            arr = (ctypes.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
+            packed = torch.empty(need, dtype=torch.uint8, device=device)
+            st = torch.cuda.current_stream(device).cuda_stream
+            _lib.check(lib.nl_sct_pack_weights_train(self.d_model, self.nhead, self.dim_feedforward, arr, len(ts), packed.data_ptr(), need, st),
+                       "nl_sct_pack_weights_train")
+            return packed
+        return self._train_cache._cached(device, ps, pack)
+
+    def _library_training_applies(self, ts):
+        """hip_training, HIP tensors, a gradient wanted, no dropout in effect, and a shape inside the library's limits (decided at forward time)."""
+        if not self.hip_training or not all(t.is_cuda for t in ts):
+            return False
+        grad = torch.is_grad_enabled() and (any(t.requires_grad for t in ts) or any(p.requires_grad for p in self.parameters()))
+        if not (self.training or grad) or (self.training and self.dropout > 0):
+            return False
+        v0, pos0, v1, pos1 = ts
+        C = self.d_model
+        if v0.dim() != 3 or v1.dim() != 3 or v0.shape[2] != C or v1.shape[2] != C or v0.shape[0] != v1.shape[0] or pos0.shape != v0.shape or pos1.shape != v1.shape:
+            return False
+        if v0.shape[0] < 1 or v0.shape[1] < 1 or v1.shape[1] < 1 or len(list(self.parameters())) != 52:
+            return False
+        return _lib.load().nl_sct_train_state_bytes(v0.shape[0], v0.shape[1], v1.shape[1], C, self.dim_feedforward) != 0 and self.nhead == 8
 
     def transform(self, v0, pos0, v1, pos1):
         """The library call: (out0 (B, N0, C), out1 (B, N1, C))."""
@@ -135,6 +230,8 @@ class SelfCrossTransformer(nn.Module, PackedCache):
 
     def forward(self, v0, pos_embed0, v1, pos_embed1):
         ts = (v0, pos_embed0, v1, pos_embed1)
+        if self._library_training_applies(ts):
+            return _TrainStep.apply(self, *ts, *self.parameters())
         if self.training or (torch.is_grad_enabled() and any(t.requires_grad for t in ts)):
             return self._eager(*ts)
         return self.transform(*ts)
