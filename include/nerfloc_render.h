@@ -49,7 +49,8 @@ extern "C" {
                             * 9: nl_fine_* (the fine matcher); 10: nl_sct_* (the matcher's SelfCrossTransformer);
                             * 11: nl_s2d_*_train (the coarse matcher's training step);
                             * 12: nl_fine_*_backward, nl_fine_pack_proj_train (the fine matcher's training step);
-                            * 13: nl_sct_*_train, nl_sct_backward, nl_sct_layer_backward (the SelfCrossTransformer's training step) */
+                            * 13: nl_sct_*_train, nl_sct_backward, nl_sct_layer_backward (the SelfCrossTransformer's training step); added within 13, with
+                            * nothing else changed: nl_sct_*_dropout, nl_sct_dropout_mask (that step with dropout inside the kernels) */
 #define NL_MAX_VIEWS 16
 #define NL_KNN_MAX_K 8
 
@@ -620,7 +621,7 @@ int nl_sct_forward(const void* packed, int C, int nhead, int F, int precision, c
                    int64_t N1, int64_t B, float* out0, float* out1, void* ws, size_t ws_bytes, void* stream);
 
 /* ---- SelfCrossTransformer: training step (ABI 13) ---------------------------------------------------------------------------------------
- * The forward and backward of the four layers above with NO dropout in effect (dropout == 0, or the module in eval mode); dropout inside the kernels is not built.
+ * The forward and backward of the four layers above with NO dropout in effect (dropout == 0, or the module in eval mode); with dropout: the next section.
  * No Nq x Nk value reaches memory in either direction: the backward rebuilds the probabilities tile by tile from the kept row maximum and sum (the two parts of the
  * log-sum-exp), in two passes (dQ: a wave per 32 queries over the key tiles; dK / dV: a wave per 32 keys over the query tiles), no float atomics: two calls on the
  * same inputs give the same bits.  Shapes, precisions, alignment and the order of the checks are nl_sct_forward's; every size query returns 0 for a shape or
@@ -658,6 +659,34 @@ size_t nl_sct_layer_backward_workspace_bytes(int64_t B, int64_t Nq, int64_t Nk, 
 int nl_sct_layer_backward(const void* packed, const void* train_packed, int C, int nhead, int F, int layer, int precision, const float* x, const float* x_pos,
                           int64_t Nq, const float* mem, const float* mem_pos, int64_t Nk, int64_t B, const float* g_out, float* g_x, float* g_x_pos, float* g_mem,
                           float* g_mem_pos, float* const* grads, int n_grads, void* ws, size_t ws_bytes, void* stream);
+
+/* ---- SelfCrossTransformer: training step with dropout (an addition within ABI 13: new entry points only, nothing above changes) ---------------
+ * The reference's four dropout sites per layer, inside the kernels: site 0 the attention probabilities after the softmax (B*8, Nq, Nk), site 1 out_proj's output
+ * before the first residual, site 2 the ReLU'd hidden rows before linear2, site 3 linear2's output before the second residual.  No mask is stored: it is a pure
+ * function of (seed, p, layer 0..3, site 0..3, element), recomputed in the backward; state and workspace sizes are those of the calls above, the flash-style
+ * backward keeps no Nq x Nk tensor, and two calls with one seed give the same bits.
+ * The mask: Philox4x32-10 (published constants), key = (seed low word, seed high word), counter = (major >> 2, minor >> 1, group, 4 layer + site); element
+ * (major, minor) is bits [16 (minor & 1), +16) of output word major & 3.  Site 0: major = key, minor = query, group = 8 batch item + head; sites 1..3: major = row
+ * flattened over the batch (b * Nq + q), minor = column, group = 0.  An element is kept when its 16-bit field >= thr = round-half-even(65536 p), capped at 65535:
+ * the keep probability is exactly 1 - thr / 65536 (within 2^-17 of 1 - p) and kept values are scaled by 65536 / (65536 - thr), its inverse, so the expectation is
+ * exact; a p below 2^-17 drops nothing.  tests/sct_dropout_ref.py restates it in numpy.
+ * `p` is a float with 0 <= p < 1; anything else (NaN included) is NL_ERR_BAD_ARG, checked after the checks of the call it extends, in their order.  With p == 0 (a
+ * zero threshold) these calls run the kernels of nl_sct_forward_train / nl_sct_backward / nl_sct_layer_backward and give their bits.  The backward must be given the
+ * forward's (p, seed).  The state's attention output is the DROPPED one.  `seed` is a host value read when the call is made: a call captured in a HIP graph
+ * replays that one seed (and so one mask) on every replay.
+ * nl_sct_dropout_mask: the keep mask (1 = kept, 0 = dropped, one byte per element, DEVICE memory) of one site by the kernels' own device function — site 0:
+ * out (B*8, Nq, n) with n = Nk; sites 1..3: out (B*Nq, n) with n = the row width (C, or F for site 2).  B == 0 is NL_OK. */
+int nl_sct_forward_train_dropout(const void* packed, int C, int nhead, int F, int precision, const float* v0, const float* pos0, int64_t N0, const float* v1,
+                                 const float* pos1, int64_t N1, int64_t B, float* out0, float* out1, void* state, size_t state_bytes, void* ws, size_t ws_bytes,
+                                 float p, uint64_t seed, void* stream);
+int nl_sct_backward_dropout(const void* packed, const void* train_packed, int C, int nhead, int F, int precision, const float* v0, const float* pos0, int64_t N0,
+                            const float* v1, const float* pos1, int64_t N1, int64_t B, const void* state, size_t state_bytes, const float* g_out0,
+                            const float* g_out1, float* g_v0, float* g_pos0, float* g_v1, float* g_pos1, float* const* grads, int n_grads, void* ws, size_t ws_bytes,
+                            float p, uint64_t seed, void* stream);
+int nl_sct_layer_backward_dropout(const void* packed, const void* train_packed, int C, int nhead, int F, int layer, int precision, const float* x, const float* x_pos,
+                                  int64_t Nq, const float* mem, const float* mem_pos, int64_t Nk, int64_t B, const float* g_out, float* g_x, float* g_x_pos,
+                                  float* g_mem, float* g_mem_pos, float* const* grads, int n_grads, void* ws, size_t ws_bytes, float p, uint64_t seed, void* stream);
+int nl_sct_dropout_mask(uint64_t seed, float p, int layer, int site, int64_t B, int64_t Nq, int64_t n, uint8_t* out, void* stream);
 
 #if defined(__GNUC__) || defined(__clang__)
 #pragma GCC visibility pop

@@ -177,6 +177,12 @@ SYMBOLS = [
     ("nl_sct_backward", _I, [_P, _P, _I, _I, _I, _I, _P, _P, _L, _P, _P, _L, _L, _P, _Z, _P, _P, _P, _P, _P, _P, C.POINTER(_P), _I, _P, _Z, _P]),
     ("nl_sct_layer_backward_workspace_bytes", _Z, [_L, _L, _L, _I, _I]),
     ("nl_sct_layer_backward", _I, [_P, _P, _I, _I, _I, _I, _I, _P, _P, _L, _P, _P, _L, _L, _P, _P, _P, _P, _P, C.POINTER(_P), _I, _P, _Z, _P]),
+    ("nl_sct_forward_train_dropout", _I, [_P, _I, _I, _I, _I, _P, _P, _L, _P, _P, _L, _L, _P, _P, _P, _Z, _P, _Z, C.c_float, C.c_uint64, _P]),
+    ("nl_sct_backward_dropout", _I, [_P, _P, _I, _I, _I, _I, _P, _P, _L, _P, _P, _L, _L, _P, _Z, _P, _P, _P, _P, _P, _P, C.POINTER(_P), _I, _P, _Z, C.c_float,
+                                 C.c_uint64, _P]),
+    ("nl_sct_layer_backward_dropout", _I, [_P, _P, _I, _I, _I, _I, _I, _P, _P, _L, _P, _P, _L, _L, _P, _P, _P, _P, _P, C.POINTER(_P), _I, _P, _Z, C.c_float,
+                                       C.c_uint64, _P]),
+    ("nl_sct_dropout_mask", _I, [C.c_uint64, C.c_float, _I, _I, _L, _L, _L, _P, _P]),
     ("nl_backproject_support", _I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _L, _P, _P, _P, _P, C.POINTER(_L), _P, _Z, _P]),
 ]
 

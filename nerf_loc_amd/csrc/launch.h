@@ -191,6 +191,7 @@ int nl_launch_fine_rows(const void* img, int Cin, int Cout, bool x3, const float
 
 // ---- sct.hip ---------------------------------------------------------------------------------------------
 // the projections and the attention of one layer (0..3) of an nl_sct_pack_weights image with the inference kernels, into caller-owned q (B * Nq, C), k, v
-// (B * Nk, C) and attention-output rows (B * Nq, C): the first half of nl_sct_layer, for the training forward (sct_bwd.hip), which keeps them
+// (B * Nk, C) and attention-output rows (B * Nq, C): the first half of nl_sct_layer, for the training forward (sct_bwd.hip), which keeps them.  A drop_p whose
+// 16-bit threshold (sct_drop.h) is not zero takes the dropping attention kernel with the masks of (drop_seed, layer, site 0); 0 is the inference kernel
 int nl_launch_sct_qkv_attn(const void* img, int C, int F, int layer, int precision, const float* x, const float* xpos, int64_t Nq, const float* mem, const float* mpos,
-                           int64_t Nk, int64_t B, float* q, float* k, float* v, float* attn, hipStream_t st);
+                           int64_t Nk, int64_t B, float* q, float* k, float* v, float* attn, float drop_p, unsigned long long drop_seed, hipStream_t st);

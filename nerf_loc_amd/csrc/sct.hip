@@ -1,4 +1,5 @@
-// SelfCrossTransformer (reference: models/COTR/transformer.py:17-64, 171-250) in eval mode: four post-norm layers (self v0, self v1, cross v0 <- v1, cross v1 <- new v0),
+// SelfCrossTransformer (reference: models/COTR/transformer.py:17-64, 171-250) in eval mode (the training forward of sct_bwd.hip launches the projections and the
+// attention from here; with dropout in effect it takes sct_attn_kernel's instantiation with a trailing SctDrop argument, sct_drop.h): four post-norm layers (self v0, self v1, cross v0 <- v1, cross v1 <- new v0),
 // each three kernels on rows flattened over the batch ([B * N][C] fp32, batch first):
 //
 // sct_proj_kernel   q / k / v = (x [+ pos]) . W^T + b.  A workgroup owns 32 rows: x and x + pos are formed once while the tile is loaded into LDS (no x + pos tensor),
@@ -26,6 +27,7 @@
 #include "mfma.h"
 #include "host.h"
 #include "sct.h"
+#include "sct_drop.h"
 
 namespace {
 
@@ -114,8 +116,12 @@ __device__ __forceinline__ void sct_attn_load(const float* kbase, const float* v
   }
 }
 
-template <int MODE, int DH>
-__global__ __launch_bounds__(256) void sct_attn_kernel(const SctAttnArgs a) {
+// DROP (the training forward with dropout in effect, sct_drop.h site 0): the maximum and the sum stay those of the undropped softmax; only the operand of
+// V^T . P^T is keep ? P / (1 - p) : 0.  The registers run along the keys: four generator calls per tile and lane, between the softmax and the second product.
+template <int MODE, int DH, class... DROPARG>
+__global__ __launch_bounds__(256) void sct_attn_kernel(const SctAttnArgs a, const DROPARG... drop) {
+  constexpr bool DROP = sizeof...(DROPARG) != 0;
+  [[maybe_unused]] const auto d = sct_drop_of(drop...);
   if constexpr (MODE == SCT_X3) __builtin_amdgcn_s_setreg(1473, 1);
   __shared__ float part[4][18][64];   // per wave: running maximum, sum, and the 16 accumulator registers, lane-major
   constexpr int C = 8 * DH;
@@ -217,6 +223,11 @@ __global__ __launch_bounds__(256) void sct_attn_kernel(const SctAttnArgs a) {
       m = mnew;
 #pragma unroll
       for (int r = 0; r < 16; ++r) o[r] *= alpha;
+      if constexpr (DROP) {
+        const unsigned keep = sct_drop_bits_major(d, 0, (unsigned)(b * 8 + h), (unsigned)k0, hh, (unsigned)(q0 + col));
+#pragma unroll
+        for (int r = 0; r < 16; ++r) p[r] = sct_drop_apply(d, keep, r, p[r]);
+      }
       // ---- O^T[channel][query] += V^T . P^T; k slot (hh, j) of step s is accumulator register 8 s + j, i.e. key k0 + nl_acc_row(8 s + j, hh)
       if constexpr (MODE == SCT_F32) {
 #pragma unroll
@@ -353,11 +364,13 @@ struct SctRun {
   const float* mem; const float* mpos; int64_t Nk;
   int64_t B; float* out; unsigned char* ws; size_t part;
   float* const* keep = nullptr;   // the training forward (sct_bwd.hip): q, k, v and the attention output go to these caller-owned rows and the row chain is left to it
+  const SctDrop* drop = nullptr;  // ... with dropout in effect (thr > 0): the dropping attention kernel
 };
 
 template <int MODE, int DH>
-void sct_launch_attn(const SctAttnArgs& a, hipStream_t st) {
-  hipLaunchKernelGGL((sct_attn_kernel<MODE, DH>), dim3((unsigned)nl_cdiv(a.items, 4 >> a.lg)), dim3(256), 0, st, a);
+void sct_launch_attn(const SctAttnArgs& a, const SctDrop* d, hipStream_t st) {
+  if (d) hipLaunchKernelGGL((sct_attn_kernel<MODE, DH>), dim3((unsigned)nl_cdiv(a.items, 4 >> a.lg)), dim3(256), 0, st, a, *d);
+  else hipLaunchKernelGGL((sct_attn_kernel<MODE, DH>), dim3((unsigned)nl_cdiv(a.items, 4 >> a.lg)), dim3(256), 0, st, a);
 }
 
 template <int MODE>
@@ -395,10 +408,10 @@ int sct_run_layer(const SctRun& r, hipStream_t st) {
   t.tps = (int)nl_cdiv(t.nkt, 1 << t.lg);
   t.scale = (float)(1.0 / sqrt((double)(C / SCT_HEADS)));
   switch (C) {
-    case 64: sct_launch_attn<MODE, 8>(t, st); break;
-    case 128: sct_launch_attn<MODE, 16>(t, st); break;
-    case 192: sct_launch_attn<MODE, 24>(t, st); break;
-    default: sct_launch_attn<MODE, 32>(t, st); break;
+    case 64: sct_launch_attn<MODE, 8>(t, r.drop, st); break;
+    case 128: sct_launch_attn<MODE, 16>(t, r.drop, st); break;
+    case 192: sct_launch_attn<MODE, 24>(t, r.drop, st); break;
+    default: sct_launch_attn<MODE, 32>(t, r.drop, st); break;
   }
 
   if (r.keep) {
@@ -423,9 +436,10 @@ int sct_run(const SctRun& r, int precision, hipStream_t st) {
 }  // namespace
 
 int nl_launch_sct_qkv_attn(const void* img, int C, int F, int layer, int precision, const float* x, const float* xpos, int64_t Nq, const float* mem, const float* mpos,
-                           int64_t Nk, int64_t B, float* q, float* k, float* v, float* attn, hipStream_t st) {
+                           int64_t Nk, int64_t B, float* q, float* k, float* v, float* attn, float drop_p, unsigned long long drop_seed, hipStream_t st) {
   float* const keep[4] = {q, k, v, attn};
-  const SctRun r{(const unsigned char*)img, C, F, layer, x, xpos, Nq, mem, mpos, Nk, B, nullptr, nullptr, 0, keep};
+  const SctDrop d = sct_drop_make(drop_p, drop_seed, layer);
+  const SctRun r{(const unsigned char*)img, C, F, layer, x, xpos, Nq, mem, mpos, Nk, B, nullptr, nullptr, 0, keep, d.thr ? &d : nullptr};
   return sct_run(r, precision, st);
 }
 

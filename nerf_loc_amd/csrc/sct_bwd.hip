@@ -1,4 +1,5 @@
-// Training step of SelfCrossTransformer with no dropout in effect (sct.hip is the inference forward): nl_sct_forward_train keeps O(rows x C) of state per layer,
+// Training step of SelfCrossTransformer (sct.hip is the inference forward), without dropout and — the *_dropout entry points, the kernels' instantiations with a
+// trailing SctDrop argument, sct_drop.h — with the reference's four dropout sites per layer inside the kernels: nl_sct_forward_train keeps O(rows x C) of state per layer,
 // nl_sct_backward returns the gradients of the four inputs and of the 48 tensors the module applies.  No Nq x Nk value reaches memory in either direction: the
 // probabilities are rebuilt tile by tile from the kept row maximum and sum (the two parts of the log-sum-exp).
 //
@@ -23,12 +24,15 @@
 // The transposed weights come from a second image (nl_sct_pack_weights_train; pack.hip's fragment packer), in sct.h's plane layout so that sct_gemm reads them.
 // Products run in the call's mode (sct.h).  In NL_PREC_BF16X3 the gradient operands are split-FP16 like everything else here: values below 6e-5 in magnitude lose
 // their low term, i.e. gradients are exact to 2^-22 relative to values around one and coarser far below.
+// Dropout: the masks are recomputed from (seed, p, layer, site, element) wherever they are needed — nothing per element is kept and the state and workspace sizes are
+// the same; the kept attention output is the dropped one, so D = sum dO . O holds unchanged.  A zero threshold (p == 0) launches the kernels without the argument.
 // Accumulation across layers (g_x, g_pos, g_mem) is by kernels of one stream that each own their elements: a fixed order, no atomics; two calls give the same bits.
 #include <algorithm>
 #include "common.h"
 #include "mfma.h"
 #include "host.h"
 #include "sct.h"
+#include "sct_drop.h"
 
 namespace {
 
@@ -111,8 +115,12 @@ __device__ __forceinline__ void sct_layernorm_keep(float* y, int ld, int C, cons
   }
 }
 
-template <int MODE>
-__global__ __launch_bounds__(256) void sct_chain_keep_kernel(const SctChainArgs a, float* y1, float* xa, float* xb, float* rstd, float* keep) {
+// DROP: the masks of sites 1 (out_proj's output before the residual), 2 (the ReLU'd hidden rows) and 3 (linear2's output before the residual) on the accumulator
+// registers, which run along the rows: four generator calls per 32 x 32 output block and lane.  The kept state has the same layout; no mask is stored.
+template <int MODE, class... DROPARG>
+__global__ __launch_bounds__(256) void sct_chain_keep_kernel(const SctChainArgs a, float* y1, float* xa, float* xb, float* rstd, float* keep, const DROPARG... drop) {
+  constexpr bool DROP = sizeof...(DROPARG) != 0;
+  [[maybe_unused]] const auto d = sct_drop_of(drop...);
   if constexpr (MODE == SCT_X3) __builtin_amdgcn_s_setreg(1473, 1);
   extern __shared__ __attribute__((aligned(16))) float sct_smem[];
   const int C = a.C, F = a.F, ldc = C + SCT_PAD, ldf = F + SCT_PAD, c4n = C >> 2, nc = C >> 5, nf = F >> 5;
@@ -141,11 +149,14 @@ __global__ __launch_bounds__(256) void sct_chain_keep_kernel(const SctChainArgs 
       if (rb >= nc) break;
       const int n = 32 * rb + col;
       const float bv = bo[n];
+      unsigned kb = 0;
+      if constexpr (DROP) kb = sct_drop_bits_major(d, 1, 0, (unsigned)row0, hh, (unsigned)n);
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const int row = nl_acc_row(r, hh);
         const long long grow = row0 + row < a.rows ? row0 + row : a.rows - 1;
-        y[row * ldc + n] = a.x[(size_t)grow * C + n] + (acc[i][r] + bv);
+        if constexpr (DROP) y[row * ldc + n] = a.x[(size_t)grow * C + n] + sct_drop_apply(d, kb, r, acc[i][r] + bv);
+        else y[row * ldc + n] = a.x[(size_t)grow * C + n] + (acc[i][r] + bv);
       }
     }
   }
@@ -162,8 +173,13 @@ __global__ __launch_bounds__(256) void sct_chain_keep_kernel(const SctChainArgs 
       if (rb >= nf) break;
       const int n = 32 * rb + col;
       const float bv = b1[n];
+      unsigned kb = 0;
+      if constexpr (DROP) kb = sct_drop_bits_major(d, 2, 0, (unsigned)row0, hh, (unsigned)n);
 #pragma unroll
-      for (int r = 0; r < 16; ++r) hb[nl_acc_row(r, hh) * ldf + n] = fmaxf(acc[i][r] + bv, 0.f);
+      for (int r = 0; r < 16; ++r) {
+        if constexpr (DROP) hb[nl_acc_row(r, hh) * ldf + n] = sct_drop_apply(d, kb, r, fmaxf(acc[i][r] + bv, 0.f));
+        else hb[nl_acc_row(r, hh) * ldf + n] = fmaxf(acc[i][r] + bv, 0.f);
+      }
     }
   }
   __syncthreads();
@@ -177,10 +193,13 @@ __global__ __launch_bounds__(256) void sct_chain_keep_kernel(const SctChainArgs 
       if (rb >= nc) break;
       const int n = 32 * rb + col;
       const float bv = b2[n];
+      unsigned kb = 0;
+      if constexpr (DROP) kb = sct_drop_bits_major(d, 3, 0, (unsigned)row0, hh, (unsigned)n);
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const int row = nl_acc_row(r, hh);
-        y[row * ldc + n] = y[row * ldc + n] + (acc[i][r] + bv);
+        if constexpr (DROP) y[row * ldc + n] = y[row * ldc + n] + sct_drop_apply(d, kb, r, acc[i][r] + bv);
+        else y[row * ldc + n] = y[row * ldc + n] + (acc[i][r] + bv);
       }
     }
   }
@@ -330,8 +349,12 @@ struct SctAttnBwdArgs {
   float scale;
 };
 
-template <int MODE, int DH, bool KV>
-__global__ __launch_bounds__(256) void sct_attn_bwd_kernel(const SctAttnBwdArgs a) {
+// DROP (sct_drop.h site 0): P is the undropped softmax rebuilt from (m, l); dP_eff = keep ? dP / (1 - p) : 0, dS = P (dP_eff - D), and dV accumulates
+// keep ? P / (1 - p) : 0.  dQ pass: the registers run along the keys (four generator calls per tile and lane); dK / dV pass: along the queries (eight).
+template <int MODE, int DH, bool KV, class... DROPARG>
+__global__ __launch_bounds__(256) void sct_attn_bwd_kernel(const SctAttnBwdArgs a, const DROPARG... drop) {
+  constexpr bool DROP = sizeof...(DROPARG) != 0;
+  [[maybe_unused]] const auto d = sct_drop_of(drop...);
   if constexpr (MODE == SCT_X3) __builtin_amdgcn_s_setreg(1473, 1);
   constexpr int C = 8 * DH;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, hh = lane >> 5, col = lane & 31;
@@ -370,6 +393,11 @@ __global__ __launch_bounds__(256) void sct_attn_bwd_kernel(const SctAttnBwdArgs 
     const nl_f32x16 s = sct_head_prod<MODE, DH>(a1, b1);    // S^T[key][query] / S[query][key]
     const nl_f32x16 dp = sct_head_prod<MODE, DH>(a2, b2);   // dP in the same orientation
     float p[16], ds[16];
+    unsigned keepb = 0;
+    if constexpr (DROP) {
+      if constexpr (KV) keepb = sct_drop_bits_minor(d, 0, (unsigned)(b * 8 + h), (unsigned)(o0 + col), (unsigned)l0, hh);
+      else keepb = sct_drop_bits_major(d, 0, (unsigned)(b * 8 + h), (unsigned)l0, hh, (unsigned)(o0 + col));
+    }
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       const long long row = l0 + nl_acc_row(r, hh);
@@ -379,7 +407,10 @@ __global__ __launch_bounds__(256) void sct_attn_bwd_kernel(const SctAttnBwdArgs 
         m = a.ml[e * 2]; ri = 1.f / a.ml[e * 2 + 1]; dd = a.dd[e];
       }
       p[r] = row < Nl ? __expf(s[r] - m) * ri : 0.f;
-      ds[r] = a.Nk == 1 ? 0.f : p[r] * (dp[r] - dd);   // one key: the softmax is the constant 1, its derivative an exact zero (dP - D would leave rounding noise)
+      float dpe = dp[r];
+      if constexpr (DROP) dpe = sct_drop_apply(d, keepb, r, dpe);
+      ds[r] = a.Nk == 1 ? 0.f : p[r] * (dpe - dd);   // one key: the softmax is the constant 1, its derivative an exact zero (dP - D would leave rounding noise)
+      if constexpr (DROP && KV) p[r] = sct_drop_apply(d, keepb, r, p[r]);   // dV's operand
     }
     float g[16];
     sct_gather16((KV ? qb : kb) + ch, l0, Nl, hh, C, g);
@@ -450,8 +481,65 @@ __device__ __forceinline__ void sct_layernorm_bwd(float* tile, int ld, int C, co
   }
 }
 
-template <int MODE>
-__global__ __launch_bounds__(256) void sct_chain_bwd_kernel(const SctChainBwdArgs a) {
+// sct_layernorm_bwd where the LayerNorm's input was x + dropout(z) (sct_drop.h `site`): the residual takes the gradient as it is — added to `add`, or stored to `raw`
+// — and z takes it masked and scaled: that goes to the LDS tile (the next product's operand) and to dst (the rows the weight gradient reads).  The lane's columns
+// run along `minor` and its 8 rows along `major`: two generator calls per 64 columns, kept as one bit per (row, column).
+__device__ __forceinline__ void sct_layernorm_bwd_drop(float* tile, int ld, int C, const float* gsrc, const float* xn, const float* rstd, int which, const float* gamma,
+                                                       int lane, int wave, long long row0, long long row_end, float* dst, float* add, float* raw, const SctDrop& d,
+                                                       int site) {
+  const int nci = C >> 6;
+  unsigned kb = 0;
+#pragma unroll
+  for (int g = 0; g < 2; ++g)
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+      if (i < nci) {
+        const uint4 w = sct_drop_words(d, site, 0, (unsigned)((row0 + 8 * wave + 4 * g) >> 2), (unsigned)(lane + 64 * i) >> 1);
+        const unsigned h = lane & 1;
+        kb |= (unsigned)sct_drop_keep(d, w.x, h) << (16 * g + i) | (unsigned)sct_drop_keep(d, w.y, h) << (16 * g + 4 + i) |
+              (unsigned)sct_drop_keep(d, w.z, h) << (16 * g + 8 + i) | (unsigned)sct_drop_keep(d, w.w, h) << (16 * g + 12 + i);
+      }
+  for (int rr = 0; rr < 8; ++rr) {
+    const int row = 8 * wave + rr;
+    const bool live = row0 + row < row_end;
+    const size_t grow = (size_t)(live ? row0 + row : row_end - 1);
+    float t[4] = {0.f, 0.f, 0.f, 0.f}, x[4] = {0.f, 0.f, 0.f, 0.f}, s1 = 0.f, s2 = 0.f;
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+      if (i < nci) {
+        const int c = lane + 64 * i;
+        const float g = gsrc ? gsrc[grow * C + c] : tile[row * ld + c];
+        x[i] = xn[grow * C + c];
+        t[i] = g * gamma[c];
+        s1 += t[i];
+        s2 += t[i] * x[i];
+      }
+    const float m1 = wave_sum(s1) / (float)C, m2 = wave_sum(s2) / (float)C;
+    const float rs = rstd[grow * 2 + which];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+      if (i < nci) {
+        const int c = lane + 64 * i;
+        const float r = rs * ((t[i] - m1) - x[i] * m2);
+        const float rm = sct_drop_apply(d, kb, 4 * rr + i, r);
+        tile[row * ld + c] = rm;
+        if (live) {
+          dst[grow * C + c] = rm;
+          if (add) add[grow * C + c] += r;
+          if (raw) raw[grow * C + c] = r;
+        }
+      }
+  }
+}
+
+// DROP: g_z2 and g_z1 reach the residuals undropped and linear2 / out_proj masked and scaled (sites 3 and 1) — so do the rows gz2 / gz1 that wgrad.hip reads and
+// the operands of g . W2 and g . Wo.  The hidden rows are rebuilt DROPPED (site 2; that is what linear2 multiplied, and what hst stages): a dropped value is positive
+// exactly where the element was kept and the forward's own pre-activation was positive, so one test gives g_pre = both masks, times the scale.  The undropped g_z2
+// waits in the gy1 rows (never null here) between the second LayerNorm's backward and the sum that overwrites them with g_y1.
+template <int MODE, class... DROPARG>
+__global__ __launch_bounds__(256) void sct_chain_bwd_kernel(const SctChainBwdArgs a, const DROPARG... drop) {
+  constexpr bool DROP = sizeof...(DROPARG) != 0;
+  [[maybe_unused]] const auto d = sct_drop_of(drop...);
   if constexpr (MODE == SCT_X3) __builtin_amdgcn_s_setreg(1473, 1);
   extern __shared__ __attribute__((aligned(16))) float sct_smem[];
   const int C = a.C, F = a.F, ldc = C + SCT_PAD, ldf = F + SCT_PAD, c4n = C >> 2, nc = C >> 5, nf = F >> 5;
@@ -478,10 +566,13 @@ __global__ __launch_bounds__(256) void sct_chain_bwd_kernel(const SctChainBwdArg
       if (rb >= nf) break;
       const int n = 32 * rb + col;
       const float bv = b1[n];
+      unsigned kb = 0;
+      if constexpr (DROP) kb = sct_drop_bits_major(d, 2, 0, (unsigned)row0, hh, (unsigned)n);
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const int row = nl_acc_row(r, hh);
-        const float hv = fmaxf(acc[i][r] + bv, 0.f);
+        float hv = fmaxf(acc[i][r] + bv, 0.f);
+        if constexpr (DROP) hv = sct_drop_apply(d, kb, r, hv);
         hb[row * ldf + n] = hv;
         if (a.hst && row0 + row < a.row_end) a.hst[(size_t)(row0 + row - a.row_begin) * F + n] = hv;
       }
@@ -489,7 +580,8 @@ __global__ __launch_bounds__(256) void sct_chain_bwd_kernel(const SctChainBwdArg
   }
   __syncthreads();
   // second LayerNorm backward: g_z2 (the gradient of linear2's output and of the residual beside it)
-  sct_layernorm_bwd(ga, ldc, C, a.g_out, a.xb, a.rstd, 1, lnp + 2 * C, lane, wave, row0, a.row_end, a.gz2, nullptr);
+  if constexpr (DROP) sct_layernorm_bwd_drop(ga, ldc, C, a.g_out, a.xb, a.rstd, 1, lnp + 2 * C, lane, wave, row0, a.row_end, a.gz2, nullptr, a.gy1, d, 3);
+  else sct_layernorm_bwd(ga, ldc, C, a.g_out, a.xb, a.rstd, 1, lnp + 2 * C, lane, wave, row0, a.row_end, a.gz2, nullptr);
   __syncthreads();
   {   // g_h = g_z2 . W2, masked: each hidden value is replaced by its pre-activation's gradient (the same lane reads and writes it)
     nl_f32x16 acc[4];
@@ -503,7 +595,8 @@ __global__ __launch_bounds__(256) void sct_chain_bwd_kernel(const SctChainBwdArg
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const int row = nl_acc_row(r, hh);
-        const float gv = hb[row * ldf + n] > 0.f ? acc[i][r] : 0.f;
+        float gv = hb[row * ldf + n] > 0.f ? acc[i][r] : 0.f;
+        if constexpr (DROP) gv *= d.scale;
         hb[row * ldf + n] = gv;
         if (a.gst && row0 + row < a.row_end) a.gst[(size_t)(row0 + row - a.row_begin) * F + n] = gv;
       }
@@ -522,7 +615,9 @@ __global__ __launch_bounds__(256) void sct_chain_bwd_kernel(const SctChainBwdArg
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const int row = nl_acc_row(r, hh);
-        const float gv = ga[row * ldc + n] + acc[i][r];
+        float gz = ga[row * ldc + n];
+        if constexpr (DROP) gz = a.gy1[(size_t)(row0 + row < a.row_end ? row0 + row : a.row_end - 1) * C + n];
+        const float gv = gz + acc[i][r];
         ga[row * ldc + n] = gv;
         if (a.gy1 && row0 + row < a.row_end) a.gy1[(size_t)(row0 + row) * C + n] = gv;
       }
@@ -530,7 +625,8 @@ __global__ __launch_bounds__(256) void sct_chain_bwd_kernel(const SctChainBwdArg
   }
   __syncthreads();
   // first LayerNorm backward: g_z1 (the gradient of out_proj's output and of the residual x)
-  sct_layernorm_bwd(ga, ldc, C, nullptr, a.xa, a.rstd, 0, lnp, lane, wave, row0, a.row_end, a.gz1, a.gx);
+  if constexpr (DROP) sct_layernorm_bwd_drop(ga, ldc, C, nullptr, a.xa, a.rstd, 0, lnp, lane, wave, row0, a.row_end, a.gz1, a.gx, nullptr, d, 1);
+  else sct_layernorm_bwd(ga, ldc, C, nullptr, a.xa, a.rstd, 0, lnp, lane, wave, row0, a.row_end, a.gz1, a.gx);
   __syncthreads();
   {   // g_attn = g_z1 . Wo
     nl_f32x16 acc[2];
@@ -683,6 +779,7 @@ struct SctLayerFwd {
   const unsigned char* img; int C, F, layer, precision;
   const float *x, *xpos, *mem, *mpos; int64_t Nq, Nk, B;
   float* out; SctKeep keep; bool keep_out;
+  float p; unsigned long long seed;   // dropout (sct_drop.h); p == 0: the kernels without it
 };
 
 template <int MODE, int DH>
@@ -690,8 +787,10 @@ void sct_launch_stats(const SctStatsArgs& a, hipStream_t st) {
   hipLaunchKernelGGL((sct_stats_kernel<MODE, DH>), dim3((unsigned)nl_cdiv(a.items, 4)), dim3(256), 0, st, a);
 }
 template <int MODE, int DH>
-void sct_launch_attn_bwd(const SctAttnBwdArgs& a, bool kv, hipStream_t st) {
-  if (kv) hipLaunchKernelGGL((sct_attn_bwd_kernel<MODE, DH, true>), dim3((unsigned)nl_cdiv(a.items, 4)), dim3(256), 0, st, a);
+void sct_launch_attn_bwd(const SctAttnBwdArgs& a, bool kv, const SctDrop* d, hipStream_t st) {
+  if (d && kv) hipLaunchKernelGGL((sct_attn_bwd_kernel<MODE, DH, true>), dim3((unsigned)nl_cdiv(a.items, 4)), dim3(256), 0, st, a, *d);
+  else if (d) hipLaunchKernelGGL((sct_attn_bwd_kernel<MODE, DH, false>), dim3((unsigned)nl_cdiv(a.items, 4)), dim3(256), 0, st, a, *d);
+  else if (kv) hipLaunchKernelGGL((sct_attn_bwd_kernel<MODE, DH, true>), dim3((unsigned)nl_cdiv(a.items, 4)), dim3(256), 0, st, a);
   else hipLaunchKernelGGL((sct_attn_bwd_kernel<MODE, DH, false>), dim3((unsigned)nl_cdiv(a.items, 4)), dim3(256), 0, st, a);
 }
 #define SCT_BY_C(C, call4)                        \
@@ -708,8 +807,10 @@ int sct_layer_forward_train(const SctLayerFwd& r, hipStream_t st) {
   const SctLayout L = sct_layout(C, F);
   const SctLayerOff& lo = L.l[r.layer];
   const long long rowsq = r.B * r.Nq;
-  if (const int e = nl_launch_sct_qkv_attn(r.img, C, F, r.layer, r.precision, r.x, r.xpos, r.Nq, r.mem, r.mpos, r.Nk, r.B, r.keep.q, r.keep.k, r.keep.v, r.keep.attn, st))
+  if (const int e = nl_launch_sct_qkv_attn(r.img, C, F, r.layer, r.precision, r.x, r.xpos, r.Nq, r.mem, r.mpos, r.Nk, r.B, r.keep.q, r.keep.k, r.keep.v, r.keep.attn,
+                                           r.p, r.seed, st))
     return e;
+  const SctDrop d = sct_drop_make(r.p, r.seed, r.layer);
   SctStatsArgs s;
   s.q = r.keep.q; s.k = r.keep.k; s.ml = r.keep.ml; s.Nq = r.Nq; s.Nk = r.Nk; s.nqt = (int)nl_cdiv(r.Nq, 32); s.items = r.B * SCT_HEADS * s.nqt;
   s.scale = (float)(1.0 / sqrt((double)(C / SCT_HEADS)));
@@ -717,14 +818,20 @@ int sct_layer_forward_train(const SctLayerFwd& r, hipStream_t st) {
   SCT_BY_C(C, SCT_CALL)
 #undef SCT_CALL
   NL_LAUNCH_CHECK();
-  static std::atomic<unsigned long long> chain_set{0};
+  static std::atomic<unsigned long long> chain_set{0}, chain_drop_set{0};
   if (const int e = nl_allow_dynamic_lds((const void*)sct_chain_keep_kernel<MODE>, sct_chain_lds(256, 512), chain_set)) return e;
+  if (d.thr)
+    if (const int e = nl_allow_dynamic_lds((const void*)sct_chain_keep_kernel<MODE, SctDrop>, sct_chain_lds(256, 512), chain_drop_set)) return e;
   SctChainArgs c;
   c.attn = r.keep.attn; c.x = r.x; c.out = r.out;
   c.wo = sct_mat(r.img, lo.m[1], C); c.w1 = sct_mat(r.img, lo.m[2], F); c.w2 = sct_mat(r.img, lo.m[3], C);
   c.vec = (const float*)(r.img + lo.vec); c.rows = rowsq; c.C = C; c.F = F;
-  hipLaunchKernelGGL(sct_chain_keep_kernel<MODE>, dim3((unsigned)nl_cdiv(rowsq, 32)), dim3(256), sct_chain_lds(C, F), st, c, r.keep.y1, r.keep.xa, r.keep.xb,
-                     r.keep.rstd, r.keep_out ? r.keep.out : nullptr);
+  if (d.thr)
+    hipLaunchKernelGGL(sct_chain_keep_kernel<MODE>, dim3((unsigned)nl_cdiv(rowsq, 32)), dim3(256), sct_chain_lds(C, F), st, c, r.keep.y1, r.keep.xa, r.keep.xb,
+                       r.keep.rstd, r.keep_out ? r.keep.out : nullptr, d);
+  else
+    hipLaunchKernelGGL(sct_chain_keep_kernel<MODE>, dim3((unsigned)nl_cdiv(rowsq, 32)), dim3(256), sct_chain_lds(C, F), st, c, r.keep.y1, r.keep.xa, r.keep.xb,
+                       r.keep.rstd, r.keep_out ? r.keep.out : nullptr);
   NL_LAUNCH_CHECK();
   return NL_OK;
 }
@@ -735,6 +842,7 @@ struct SctLayerBwd {
   SctKeep keep; const float* g_out;
   float *g_x, *g_xpos, *g_mem, *g_mpos;   // += targets; any may be null
   float* const* gp;                       // the layer's 12 / 14 parameter gradients in state-dict order; entries may be null
+  float p; unsigned long long seed;       // the forward's dropout (sct_drop.h)
 };
 
 template <int MODE>
@@ -752,8 +860,12 @@ int sct_layer_backward(const SctLayerBwd& r, const SctBwdWs& w, hipStream_t st) 
   const bool in_x = r.g_x || r.g_xpos, in_m = r.g_mem || r.g_mpos;
   if (!(want_in || want_o || want_1 || want_2 || want_lna || want_lnb || in_x || in_m)) return NL_OK;
 
-  static std::atomic<unsigned long long> chain_set{0}, proj_set{0};
+  static std::atomic<unsigned long long> chain_set{0}, chain_drop_set{0}, proj_set{0};
   if (const int e = nl_allow_dynamic_lds((const void*)sct_chain_bwd_kernel<MODE>, sct_chain_lds(256, 512), chain_set)) return e;
+  const SctDrop d = sct_drop_make(r.p, r.seed, l);
+  const SctDrop* dp = d.thr ? &d : nullptr;
+  if (dp)
+    if (const int e = nl_allow_dynamic_lds((const void*)sct_chain_bwd_kernel<MODE, SctDrop>, sct_chain_lds(256, 512), chain_drop_set)) return e;
   if (const int e = nl_allow_dynamic_lds((const void*)sct_proj_bwd_kernel<MODE>, sct_proj_lds(256), proj_set)) return e;
 
   // ---- row chain, in row chunks with the two F-wide weight gradients behind each
@@ -762,14 +874,15 @@ int sct_layer_backward(const SctLayerBwd& r, const SctBwdWs& w, hipStream_t st) 
   c.w1 = sct_mat(r.img, lo.m[2], F);
   c.w2t = sct_mat(r.timg, T.m[l][5], F); c.w1t = sct_mat(r.timg, T.m[l][4], C); c.wot = sct_mat(r.timg, T.m[l][3], C);
   c.vec = (const float*)(r.img + lo.vec);
-  c.gz2 = w.gz2; c.gy1 = want_lna ? w.gy1 : nullptr; c.gz1 = w.gz1; c.gattn = w.gattn;
+  c.gz2 = w.gz2; c.gy1 = want_lna || dp ? w.gy1 : nullptr; c.gz1 = w.gz1; c.gattn = w.gattn;   // dropping: the undropped g_z2 waits in the gy1 rows
   c.gx = r.g_x;
   c.hst = want_2 ? w.hst : nullptr; c.gst = want_1 ? w.gst : nullptr;
   c.C = C; c.F = F;
   for (int64_t b0 = 0; b0 < rq; b0 += w.chunk) {
     const int64_t n = std::min<int64_t>(w.chunk, rq - b0);
     c.row_begin = b0; c.row_end = b0 + n;
-    hipLaunchKernelGGL(sct_chain_bwd_kernel<MODE>, dim3((unsigned)nl_cdiv(n, 32)), dim3(256), sct_chain_lds(C, F), st, c);
+    if (dp) hipLaunchKernelGGL(sct_chain_bwd_kernel<MODE>, dim3((unsigned)nl_cdiv(n, 32)), dim3(256), sct_chain_lds(C, F), st, c, d);
+    else hipLaunchKernelGGL(sct_chain_bwd_kernel<MODE>, dim3((unsigned)nl_cdiv(n, 32)), dim3(256), sct_chain_lds(C, F), st, c);
     NL_LAUNCH_CHECK();
     if (want_1)
       if (const int e = nl_launch_wgrad(w.gst, F, F, r.keep.y1 + (size_t)b0 * C, C, C, n, 0, 0, gp[4] ? gp[4] : w.dummy, C, 1, 0, gp[5], w.wg, w.wg_floats, st)) return e;
@@ -803,13 +916,13 @@ int sct_layer_backward(const SctLayerBwd& r, const SctBwdWs& w, hipStream_t st) 
   const bool need_q = want_in || in_x, need_kv = want_in || in_m || self_tgt;
   if (need_q) {
     t.nto = (int)nl_cdiv(r.Nq, 32); t.items = r.B * SCT_HEADS * t.nto;
-#define SCT_CALL(DH) sct_launch_attn_bwd<MODE, DH>(t, false, st)
+#define SCT_CALL(DH) sct_launch_attn_bwd<MODE, DH>(t, false, dp, st)
     SCT_BY_C(C, SCT_CALL)
 #undef SCT_CALL
   }
   if (need_kv) {
     t.nto = (int)nl_cdiv(r.Nk, 32); t.items = r.B * SCT_HEADS * t.nto;
-#define SCT_CALL(DH) sct_launch_attn_bwd<MODE, DH>(t, true, st)
+#define SCT_CALL(DH) sct_launch_attn_bwd<MODE, DH>(t, true, dp, st)
     SCT_BY_C(C, SCT_CALL)
 #undef SCT_CALL
   }
@@ -880,6 +993,45 @@ bool sct_all16(const void* const* p, int n, bool required) {
   return true;
 }
 
+// ---- the keep mask of one site, one byte per element, by the kernels' own function (nl_sct_dropout_mask).  site 0: out[(b * 8 + h) * Nq + q][k], n = Nk;
+// sites 1 - 3: out[b * Nq + q][column], n = the width
+__global__ __launch_bounds__(256) void sct_drop_mask_kernel(const SctDrop d, int site, long long Nq, long long n, long long total, unsigned char* out) {
+  const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (e >= total) return;
+  const long long row = e / n, c = e - row * n;
+  bool keep;
+  if (site == 0) {
+    const long long g = row / Nq;
+    keep = sct_drop_keep_at(d, 0, (unsigned)g, (unsigned)c, (unsigned)(row - g * Nq));
+  } else {
+    keep = sct_drop_keep_at(d, site, 0, (unsigned)row, (unsigned)c);
+  }
+  out[e] = keep ? 1 : 0;
+}
+
+int sct_forward_train_impl(const void* packed, int C, int nhead, int F, int precision, const float* v0, const float* pos0, int64_t N0, const float* v1,
+                           const float* pos1, int64_t N1, int64_t B, float* out0, float* out1, void* state, size_t state_bytes, void* ws, size_t ws_bytes, float p,
+                           unsigned long long seed, void* stream) {
+  const void* ptrs[6] = {v0, pos0, v1, pos1, out0, out1};
+  bool empty;
+  if (const int s = sct_check(packed, C, nhead, F, precision, B, N0, N1, ptrs, 6, ws, ws_bytes, &empty)) return s;
+  if (empty) return NL_OK;
+  if (out0 == out1) return NL_ERR_BAD_ARG;
+  if (!state || ((uintptr_t)state & 255) != 0 || state_bytes < nl_sct_train_state_bytes(B, N0, N1, C, F)) return NL_ERR_WORKSPACE;
+  if (!sct_drop_p_ok(p)) return NL_ERR_BAD_ARG;
+  const unsigned char* img = (const unsigned char*)packed;
+  hipStream_t st = (hipStream_t)stream;
+  SctKeep k[SCT_LAYERS];
+  sct_state_carve((unsigned char*)state, B, N0, N1, C, k);
+  const SctLayerFwd r[SCT_LAYERS] = {{img, C, F, 0, precision, v0, pos0, v0, pos0, N0, N0, B, out0, k[0], true, p, seed},
+                                     {img, C, F, 1, precision, v1, pos1, v1, pos1, N1, N1, B, out1, k[1], true, p, seed},
+                                     {img, C, F, 2, precision, out0, pos0, out1, pos1, N0, N1, B, out0, k[2], true, p, seed},
+                                     {img, C, F, 3, precision, out1, pos1, out0, pos0, N1, N0, B, out1, k[3], false, p, seed}};
+  for (int l = 0; l < SCT_LAYERS; ++l)
+    if (const int s = sct_fwd_train(r[l], st)) return s;
+  return NL_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -922,23 +1074,12 @@ size_t nl_sct_train_state_bytes(int64_t B, int64_t N0, int64_t N1, int C, int F)
 int nl_sct_forward_train(const void* packed, int C, int nhead, int F, int precision, const float* v0, const float* pos0, int64_t N0, const float* v1,
                          const float* pos1, int64_t N1, int64_t B, float* out0, float* out1, void* state, size_t state_bytes, void* ws, size_t ws_bytes,
                          void* stream) {
-  const void* ptrs[6] = {v0, pos0, v1, pos1, out0, out1};
-  bool empty;
-  if (const int s = sct_check(packed, C, nhead, F, precision, B, N0, N1, ptrs, 6, ws, ws_bytes, &empty)) return s;
-  if (empty) return NL_OK;
-  if (out0 == out1) return NL_ERR_BAD_ARG;
-  if (!state || ((uintptr_t)state & 255) != 0 || state_bytes < nl_sct_train_state_bytes(B, N0, N1, C, F)) return NL_ERR_WORKSPACE;
-  const unsigned char* img = (const unsigned char*)packed;
-  hipStream_t st = (hipStream_t)stream;
-  SctKeep k[SCT_LAYERS];
-  sct_state_carve((unsigned char*)state, B, N0, N1, C, k);
-  const SctLayerFwd r[SCT_LAYERS] = {{img, C, F, 0, precision, v0, pos0, v0, pos0, N0, N0, B, out0, k[0], true},
-                                     {img, C, F, 1, precision, v1, pos1, v1, pos1, N1, N1, B, out1, k[1], true},
-                                     {img, C, F, 2, precision, out0, pos0, out1, pos1, N0, N1, B, out0, k[2], true},
-                                     {img, C, F, 3, precision, out1, pos1, out0, pos0, N1, N0, B, out1, k[3], false}};
-  for (int l = 0; l < SCT_LAYERS; ++l)
-    if (const int s = sct_fwd_train(r[l], st)) return s;
-  return NL_OK;
+  return sct_forward_train_impl(packed, C, nhead, F, precision, v0, pos0, N0, v1, pos1, N1, B, out0, out1, state, state_bytes, ws, ws_bytes, 0.f, 0, stream);
+}
+int nl_sct_forward_train_dropout(const void* packed, int C, int nhead, int F, int precision, const float* v0, const float* pos0, int64_t N0, const float* v1,
+                                 const float* pos1, int64_t N1, int64_t B, float* out0, float* out1, void* state, size_t state_bytes, void* ws, size_t ws_bytes,
+                                 float p, uint64_t seed, void* stream) {
+  return sct_forward_train_impl(packed, C, nhead, F, precision, v0, pos0, N0, v1, pos1, N1, B, out0, out1, state, state_bytes, ws, ws_bytes, p, seed, stream);
 }
 
 size_t nl_sct_backward_workspace_bytes(int64_t B, int64_t N0, int64_t N1, int C, int F) {
@@ -951,9 +1092,10 @@ size_t nl_sct_layer_backward_workspace_bytes(int64_t B, int64_t Nq, int64_t Nk, 
   return sct_bwd_ws(nullptr, B ? B : 1, Nq, Nk, C, F, true).total;
 }
 
-int nl_sct_backward(const void* packed, const void* train_packed, int C, int nhead, int F, int precision, const float* v0, const float* pos0, int64_t N0,
-                    const float* v1, const float* pos1, int64_t N1, int64_t B, const void* state, size_t state_bytes, const float* g_out0, const float* g_out1,
-                    float* g_v0, float* g_pos0, float* g_v1, float* g_pos1, float* const* grads, int n_grads, void* ws, size_t ws_bytes, void* stream) {
+static int sct_backward_impl(const void* packed, const void* train_packed, int C, int nhead, int F, int precision, const float* v0, const float* pos0, int64_t N0,
+                             const float* v1, const float* pos1, int64_t N1, int64_t B, const void* state, size_t state_bytes, const float* g_out0,
+                             const float* g_out1, float* g_v0, float* g_pos0, float* g_v1, float* g_pos1, float* const* grads, int n_grads, void* ws, size_t ws_bytes,
+                             float p, unsigned long long seed, void* stream) {
   bool empty;
   if (const int s = sct_shape_check(C, nhead, F, precision, B, N0, N1, &empty)) return s;
   if (empty) return NL_OK;
@@ -968,6 +1110,7 @@ int nl_sct_backward(const void* packed, const void* train_packed, int C, int nhe
   }
   if (!state || ((uintptr_t)state & 255) != 0 || state_bytes < nl_sct_train_state_bytes(B, N0, N1, C, F)) return NL_ERR_WORKSPACE;
   if (!ws || ((uintptr_t)ws & 255) != 0 || ws_bytes < nl_sct_backward_workspace_bytes(B, N0, N1, C, F)) return NL_ERR_WORKSPACE;
+  if (!sct_drop_p_ok(p)) return NL_ERR_BAD_ARG;
   hipStream_t st = (hipStream_t)stream;
   const unsigned char* img = (const unsigned char*)packed;
   const unsigned char* timg = (const unsigned char*)train_packed;
@@ -1006,28 +1149,43 @@ int nl_sct_backward(const void* packed, const void* train_packed, int C, int nhe
   }
   if (run3) {
     const SctLayerBwd r{img, timg, C, F, 3, k[1].out, pos1, k[2].out, pos0, N1, N0, B, k[3], g_out1, need1 ? w.G[1] : nullptr, g_pos1, need2 ? w.G[2] : nullptr, g_pos0,
-                        gp + 38};
+                        gp + 38, p, seed};
     if (const int s = sct_bwd(r, precision, w, st)) return s;
   }
   if (need2) {
     const SctLayerBwd r{img, timg, C, F, 2, k[0].out, pos0, k[1].out, pos1, N0, N1, B, k[2], w.G[2], need0 ? w.G[0] : nullptr, g_pos0, need1 ? w.G[1] : nullptr, g_pos1,
-                        gp + 24};
+                        gp + 24, p, seed};
     if (const int s = sct_bwd(r, precision, w, st)) return s;
   }
   if (need1) {
-    const SctLayerBwd r{img, timg, C, F, 1, v1, pos1, v1, pos1, N1, N1, B, k[1], w.G[1], g_v1, g_pos1, nullptr, nullptr, gp + 12};
+    const SctLayerBwd r{img, timg, C, F, 1, v1, pos1, v1, pos1, N1, N1, B, k[1], w.G[1], g_v1, g_pos1, nullptr, nullptr, gp + 12, p, seed};
     if (const int s = sct_bwd(r, precision, w, st)) return s;
   }
   if (need0) {
-    const SctLayerBwd r{img, timg, C, F, 0, v0, pos0, v0, pos0, N0, N0, B, k[0], w.G[0], g_v0, g_pos0, nullptr, nullptr, gp};
+    const SctLayerBwd r{img, timg, C, F, 0, v0, pos0, v0, pos0, N0, N0, B, k[0], w.G[0], g_v0, g_pos0, nullptr, nullptr, gp, p, seed};
     if (const int s = sct_bwd(r, precision, w, st)) return s;
   }
   return NL_OK;
 }
 
-int nl_sct_layer_backward(const void* packed, const void* train_packed, int C, int nhead, int F, int layer, int precision, const float* x, const float* x_pos,
-                          int64_t Nq, const float* mem, const float* mem_pos, int64_t Nk, int64_t B, const float* g_out, float* g_x, float* g_x_pos, float* g_mem,
-                          float* g_mem_pos, float* const* grads, int n_grads, void* ws, size_t ws_bytes, void* stream) {
+int nl_sct_backward(const void* packed, const void* train_packed, int C, int nhead, int F, int precision, const float* v0, const float* pos0, int64_t N0,
+                    const float* v1, const float* pos1, int64_t N1, int64_t B, const void* state, size_t state_bytes, const float* g_out0, const float* g_out1,
+                    float* g_v0, float* g_pos0, float* g_v1, float* g_pos1, float* const* grads, int n_grads, void* ws, size_t ws_bytes, void* stream) {
+  return sct_backward_impl(packed, train_packed, C, nhead, F, precision, v0, pos0, N0, v1, pos1, N1, B, state, state_bytes, g_out0, g_out1, g_v0, g_pos0, g_v1, g_pos1,
+                           grads, n_grads, ws, ws_bytes, 0.f, 0, stream);
+}
+int nl_sct_backward_dropout(const void* packed, const void* train_packed, int C, int nhead, int F, int precision, const float* v0, const float* pos0, int64_t N0,
+                            const float* v1, const float* pos1, int64_t N1, int64_t B, const void* state, size_t state_bytes, const float* g_out0,
+                            const float* g_out1, float* g_v0, float* g_pos0, float* g_v1, float* g_pos1, float* const* grads, int n_grads, void* ws, size_t ws_bytes,
+                            float p, uint64_t seed, void* stream) {
+  return sct_backward_impl(packed, train_packed, C, nhead, F, precision, v0, pos0, N0, v1, pos1, N1, B, state, state_bytes, g_out0, g_out1, g_v0, g_pos0, g_v1, g_pos1,
+                           grads, n_grads, ws, ws_bytes, p, seed, stream);
+}
+
+static int sct_layer_backward_impl(const void* packed, const void* train_packed, int C, int nhead, int F, int layer, int precision, const float* x, const float* x_pos,
+                                   int64_t Nq, const float* mem, const float* mem_pos, int64_t Nk, int64_t B, const float* g_out, float* g_x, float* g_x_pos,
+                                   float* g_mem, float* g_mem_pos, float* const* grads, int n_grads, void* ws, size_t ws_bytes, float p, unsigned long long seed,
+                                   void* stream) {
   if (layer < 0 || layer >= SCT_LAYERS) return NL_ERR_BAD_ARG;
   const bool cross = layer >= 2;
   if (!cross) {   // self layers: the memory side is the target side, and its gradient is part of g_x / g_x_pos
@@ -1048,12 +1206,13 @@ int nl_sct_layer_backward(const void* packed, const void* train_packed, int C, i
       if (((uintptr_t)grads[i] & 15) != 0) return NL_ERR_BAD_ARG;
   }
   if (!ws || ((uintptr_t)ws & 255) != 0 || ws_bytes < nl_sct_layer_backward_workspace_bytes(B, Nq, Nk, C, F)) return NL_ERR_WORKSPACE;
+  if (!sct_drop_p_ok(p)) return NL_ERR_BAD_ARG;
   hipStream_t st = (hipStream_t)stream;
   const SctBwdWs w = sct_bwd_ws((unsigned char*)ws, B, Nq, Nk, C, F, true);
   SctKeep k;
   sct_keep_carve((unsigned char*)ws, w.keep_off, B * Nq, B * Nk, C, k, true);
   const unsigned char* img = (const unsigned char*)packed;
-  const SctLayerFwd f{img, C, F, layer, precision, x, x_pos, mem, mem_pos, Nq, Nk, B, w.lout, k, false};
+  const SctLayerFwd f{img, C, F, layer, precision, x, x_pos, mem, mem_pos, Nq, Nk, B, w.lout, k, false, p, seed};
   if (const int s = sct_fwd_train(f, st)) return s;
   float* gp[14];
   const int base[SCT_LAYERS] = {0, 12, 24, 38};
@@ -1067,8 +1226,35 @@ int nl_sct_layer_backward(const void* packed, const void* train_packed, int C, i
   if (g_x_pos) NL_CHECK_HIP(hipMemsetAsync(g_x_pos, 0, bq, st));
   if (g_mem) NL_CHECK_HIP(hipMemsetAsync(g_mem, 0, bk, st));
   if (g_mem_pos) NL_CHECK_HIP(hipMemsetAsync(g_mem_pos, 0, bk, st));
-  const SctLayerBwd r{img, (const unsigned char*)train_packed, C, F, layer, x, x_pos, mem, mem_pos, Nq, Nk, B, k, g_out, g_x, g_x_pos, g_mem, g_mem_pos, gp};
+  const SctLayerBwd r{img, (const unsigned char*)train_packed, C, F, layer, x, x_pos, mem, mem_pos, Nq, Nk, B, k, g_out, g_x, g_x_pos, g_mem, g_mem_pos, gp, p, seed};
   return sct_bwd(r, precision, w, st);
+}
+
+int nl_sct_layer_backward(const void* packed, const void* train_packed, int C, int nhead, int F, int layer, int precision, const float* x, const float* x_pos,
+                          int64_t Nq, const float* mem, const float* mem_pos, int64_t Nk, int64_t B, const float* g_out, float* g_x, float* g_x_pos, float* g_mem,
+                          float* g_mem_pos, float* const* grads, int n_grads, void* ws, size_t ws_bytes, void* stream) {
+  return sct_layer_backward_impl(packed, train_packed, C, nhead, F, layer, precision, x, x_pos, Nq, mem, mem_pos, Nk, B, g_out, g_x, g_x_pos, g_mem, g_mem_pos, grads,
+                                 n_grads, ws, ws_bytes, 0.f, 0, stream);
+}
+int nl_sct_layer_backward_dropout(const void* packed, const void* train_packed, int C, int nhead, int F, int layer, int precision, const float* x, const float* x_pos,
+                                  int64_t Nq, const float* mem, const float* mem_pos, int64_t Nk, int64_t B, const float* g_out, float* g_x, float* g_x_pos,
+                                  float* g_mem, float* g_mem_pos, float* const* grads, int n_grads, void* ws, size_t ws_bytes, float p, uint64_t seed, void* stream) {
+  return sct_layer_backward_impl(packed, train_packed, C, nhead, F, layer, precision, x, x_pos, Nq, mem, mem_pos, Nk, B, g_out, g_x, g_x_pos, g_mem, g_mem_pos, grads,
+                                 n_grads, ws, ws_bytes, p, seed, stream);
+}
+
+int nl_sct_dropout_mask(uint64_t seed, float p, int layer, int site, int64_t B, int64_t Nq, int64_t n, uint8_t* out, void* stream) {
+  if (layer < 0 || layer >= SCT_LAYERS || site < 0 || site > 3 || B < 0 || Nq < 1 || n < 1 || !sct_drop_p_ok(p)) return NL_ERR_BAD_ARG;
+  if (B > SCT_MAX_ROWS || Nq > SCT_MAX_ROWS || n > SCT_MAX_ROWS || B * Nq > SCT_MAX_ROWS) return NL_ERR_UNSUPPORTED;
+  const long long rows = (site == 0 ? 8 : 1) * B * Nq;
+  if ((double)rows * (double)n > 2147483647.0 * 256.0) return NL_ERR_UNSUPPORTED;   // one thread per element, a 32-bit grid
+  if (B == 0) return NL_OK;
+  if (!out) return NL_ERR_BAD_ARG;
+  const SctDrop d = sct_drop_make(p, seed, layer);
+  const long long total = rows * n;
+  hipLaunchKernelGGL(sct_drop_mask_kernel, dim3((unsigned)nl_cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream, d, site, (long long)Nq, (long long)n, total, out);
+  NL_LAUNCH_CHECK();
+  return NL_OK;
 }
 
 }  // extern "C"

@@ -7,8 +7,16 @@ refused: no CPU fallback.
 
 `hip_training = True` (opt-in, default False) replaces that eager stretch by the library's training step whenever NO dropout is in effect (the constructor's
 dropout == 0, or eval mode): one autograd Function around nl_sct_forward_train / nl_sct_backward (csrc/sct_bwd.hip), which keeps O(rows x C) of state, never a
-heads x Nq x Nk tensor, and gives the same bits on every call.  Dropout inside the kernels is not built: training mode with dropout > 0 stays eager (the reference's
-Matcher constructs both transformers with dropout = 0.1).
+heads x Nq x Nk tensor, and gives the same bits on every call.  Training mode with dropout > 0 (the reference's Matcher constructs both transformers with
+dropout = 0.1) stays eager unless `hip_dropout` is set too.
+
+`hip_dropout = True` (opt-in, default False; needs `hip_training`) takes the library's step in training mode with 0 < dropout < 1 as well: nl_sct_forward_train_dropout
+/ nl_sct_backward_dropout drop at the reference's four sites per layer (attention probabilities, out_proj's output, the ReLU'd hidden rows, linear2's output) inside
+the kernels.  The masks are a counter-based function of (seed, p, layer, site, element) — Philox4x32-10, 16-bit thresholds, scale 1 / (actual keep probability);
+csrc/sct_drop.h, restated in tests/sct_dropout_ref.py — recomputed in the backward: nothing per element is kept.  They are NOT torch's masks: same distribution,
+other bits.  One seed per forward: `dropout_seed` if it is an int (tests, reproducible steps: every forward then drops the same elements), else a draw from torch's
+default CPU generator, which follows torch.manual_seed and needs no device synchronisation.  The autograd Function keeps (p, seed) for its backward.  The seed is a
+host value: a forward captured in a HIP graph replays one seed.  dropout >= 1, CPU tensors, shapes outside the limits: eager, as before.  Eval mode is unaffected.
 
 The sub-modules carry the reference's names (`self_attn_layer{0,1}.self_attn / linear1 / linear2 / norm1 / norm2`, `cross_attn_layer{0,1}.multihead_attn /
 linear1 / linear2 / norm1 / norm2 / norm3`), so `matcher.coarse_transformer.*` and `matcher.fine_transformer.*` of a NeRF-Loc checkpoint load with strict=True.
@@ -66,7 +74,7 @@ class _TrainStep(torch.autograd.Function):
     """nl_sct_forward_train / nl_sct_backward around the module's four layers; the 52 parameters are inputs so that autograd routes their gradients."""
 
     @staticmethod
-    def forward(ctx, mod, v0, pos0, v1, pos1, *params):
+    def forward(ctx, mod, p, seed, v0, pos0, v1, pos1, *params):
         lib = _lib.load()
         dev = v0.device
         C, Fh = mod.d_model, mod.dim_feedforward
@@ -80,9 +88,13 @@ class _TrainStep(torch.autograd.Function):
             state = torch.empty(sb, dtype=torch.uint8, device=dev)
             ws = torch.empty(wb, dtype=torch.uint8, device=dev)
             st = torch.cuda.current_stream(dev).cuda_stream
-            _lib.check(lib.nl_sct_forward_train(packed.data_ptr(), C, mod.nhead, Fh, _lib.PRECISIONS[mod.precision], a[0].data_ptr(), a[1].data_ptr(), N0,
-                                                a[2].data_ptr(), a[3].data_ptr(), N1, B, out0.data_ptr(), out1.data_ptr(), state.data_ptr(), sb, ws.data_ptr(), wb, st),
-                       "nl_sct_forward_train")
+            args = (packed.data_ptr(), C, mod.nhead, Fh, _lib.PRECISIONS[mod.precision], a[0].data_ptr(), a[1].data_ptr(), N0, a[2].data_ptr(), a[3].data_ptr(), N1, B,
+                    out0.data_ptr(), out1.data_ptr(), state.data_ptr(), sb, ws.data_ptr(), wb)
+            if p > 0:
+                _lib.check(lib.nl_sct_forward_train_dropout(*args, p, seed, st), "nl_sct_forward_train_dropout")
+            else:
+                _lib.check(lib.nl_sct_forward_train(*args, st), "nl_sct_forward_train")
+        ctx.drop = (p, seed)
         ctx.mod, ctx.images, ctx.inputs, ctx.state, ctx.dims = mod, (packed, tpacked), a, state, (B, N0, N1)
         ctx.in_dtypes = [t.dtype for t in (v0, pos0, v1, pos1)]
         ctx.param_meta = [(p.shape, p.dtype) for p in params]
@@ -99,20 +111,25 @@ class _TrainStep(torch.autograd.Function):
         need = ctx.needs_input_grad
         with torch.cuda.device(dev):
             g0, g1 = (None if g is None else g.to(torch.float32).contiguous() for g in (g0, g1))
-            gin = [torch.empty_like(a[i]) if need[1 + i] else None for i in range(4)]
-            gpar = [torch.empty(shape, dtype=torch.float32, device=dev) if need[5 + i] and i not in _UNUSED_PARAMS else None
+            gin = [torch.empty_like(a[i]) if need[3 + i] else None for i in range(4)]
+            gpar = [torch.empty(shape, dtype=torch.float32, device=dev) if need[7 + i] and i not in _UNUSED_PARAMS else None
                     for i, (shape, _) in enumerate(ctx.param_meta)]
             ptr = lambda t: None if t is None else t.data_ptr()
             arr = (ctypes.c_void_p * len(gpar))(*[ptr(t) for t in gpar])
             wb = lib.nl_sct_backward_workspace_bytes(B, N0, N1, C, Fh)
             ws = torch.empty(wb, dtype=torch.uint8, device=dev)
             st = torch.cuda.current_stream(dev).cuda_stream
-            _lib.check(lib.nl_sct_backward(ctx.images[0].data_ptr(), ctx.images[1].data_ptr(), C, mod.nhead, Fh, _lib.PRECISIONS[mod.precision], a[0].data_ptr(),
-                                           a[1].data_ptr(), N0, a[2].data_ptr(), a[3].data_ptr(), N1, B, ctx.state.data_ptr(), ctx.state.numel(), ptr(g0), ptr(g1),
-                                           ptr(gin[0]), ptr(gin[1]), ptr(gin[2]), ptr(gin[3]), arr, len(gpar), ws.data_ptr(), wb, st), "nl_sct_backward")
+            args = (ctx.images[0].data_ptr(), ctx.images[1].data_ptr(), C, mod.nhead, Fh, _lib.PRECISIONS[mod.precision], a[0].data_ptr(), a[1].data_ptr(), N0,
+                    a[2].data_ptr(), a[3].data_ptr(), N1, B, ctx.state.data_ptr(), ctx.state.numel(), ptr(g0), ptr(g1), ptr(gin[0]), ptr(gin[1]), ptr(gin[2]),
+                    ptr(gin[3]), arr, len(gpar), ws.data_ptr(), wb)
+            p, seed = ctx.drop
+            if p > 0:
+                _lib.check(lib.nl_sct_backward_dropout(*args, p, seed, st), "nl_sct_backward_dropout")
+            else:
+                _lib.check(lib.nl_sct_backward(*args, st), "nl_sct_backward")
         gin = [g if g is None else g.to(dt) for g, dt in zip(gin, ctx.in_dtypes)]
         gpar = [g if g is None else g.to(dt) for g, (_, dt) in zip(gpar, ctx.param_meta)]
-        return (None, *gin, *gpar)
+        return (None, None, None, *gin, *gpar)
 
 
 class SelfCrossTransformer(nn.Module, PackedCache):
@@ -121,6 +138,8 @@ class SelfCrossTransformer(nn.Module, PackedCache):
     precision: "bf16x3" (default: three-term split products on the matrix pipe, within 1e-4 of the fp32 reference), "fp32" (exact fp32 products) or
     "bf16" (throughput, no bar).
     hip_training (attribute, default False): take the library's training step instead of eager autograd where it applies (see the module docstring).
+    hip_dropout (attribute, default False): with hip_training, also in training mode with 0 < dropout < 1 — dropout inside the kernels, with the library's masks.
+    dropout_seed (attribute, default None): an int fixes the mask seed of every forward; None draws one per forward from torch's default CPU generator.
     """
 
     def __init__(self, d_model=512, nhead=8, num_encoder_layers=6, num_decoder_layers=6, dim_feedforward=2048, dropout=0.1, activation="relu",
@@ -138,6 +157,8 @@ class SelfCrossTransformer(nn.Module, PackedCache):
         self.d_model, self.nhead, self.dim_feedforward = int(d_model), int(nhead), int(dim_feedforward)
         self.dropout = float(dropout)
         self.hip_training = False
+        self.hip_dropout = False
+        self.dropout_seed = None
         self.precision = check_precision(precision)
         self._cache_init()
         self._train_cache = new_train_cache()
@@ -186,11 +207,12 @@ class SelfCrossTransformer(nn.Module, PackedCache):
         return self._train_cache._cached(device, ps, pack)
 
     def _library_training_applies(self, ts):
-        """hip_training, HIP tensors, a gradient wanted, no dropout in effect, and a shape inside the library's limits (decided at forward time)."""
+        """hip_training, HIP tensors, a gradient wanted, no dropout in effect (or hip_dropout and dropout < 1), and a shape inside the library's limits (decided at
+        forward time)."""
         if not self.hip_training or not all(t.is_cuda for t in ts):
             return False
         grad = torch.is_grad_enabled() and (any(t.requires_grad for t in ts) or any(p.requires_grad for p in self.parameters()))
-        if not (self.training or grad) or (self.training and self.dropout > 0):
+        if not (self.training or grad) or (self.training and self.dropout > 0 and not (self.hip_dropout and self.dropout < 1)):
             return False
         v0, pos0, v1, pos1 = ts
         C = self.d_model
@@ -231,7 +253,12 @@ class SelfCrossTransformer(nn.Module, PackedCache):
     def forward(self, v0, pos_embed0, v1, pos_embed1):
         ts = (v0, pos_embed0, v1, pos_embed1)
         if self._library_training_applies(ts):
-            return _TrainStep.apply(self, *ts, *self.parameters())
+            p, seed = 0.0, 0
+            if self.training and self.dropout > 0:   # hip_dropout: one seed per forward, a host value
+                p = self.dropout
+                seed = self.dropout_seed if isinstance(self.dropout_seed, int) else int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64).item())
+                seed &= 2 ** 64 - 1
+            return _TrainStep.apply(self, p, seed, *ts, *self.parameters())
         if self.training or (torch.is_grad_enabled() and any(t.requires_grad for t in ts)):
             return self._eager(*ts)
         return self.transform(*ts)
