@@ -1,6 +1,8 @@
-// SelfCrossTransformer (reference: models/COTR/transformer.py:17-64, 171-250) in eval mode (the training forward of sct_bwd.hip launches the projections and the
-// attention from here; with dropout in effect it takes sct_attn_kernel's instantiation with a trailing SctDrop argument, sct_drop.h): four post-norm layers (self v0, self v1, cross v0 <- v1, cross v1 <- new v0),
-// each three kernels on rows flattened over the batch ([B * N][C] fp32, batch first):
+// SelfCrossTransformer (reference: models/COTR/transformer.py:17-64, 171-250): four post-norm layers (self v0, self v1, cross v0 <- v1, cross v1 <- new v0), each
+// three kernels on rows flattened over the batch ([B * N][C] fp32, batch first).  The kernels serve three uses.  Inference (eval mode) is this file's entry points.
+// The training forward (sct_bwd.hip) launches the same projections and attention from here, into rows it keeps (nl_launch_sct_qkv_attn), and the row chain itself,
+// with the stores of what the backward needs.  The training forward with dropout takes the attention's and the chain's instantiations with a trailing SctDrop
+// argument (sct_drop.h); a kernel without that argument is the kernel as it was.
 //
 // sct_proj_kernel   q / k / v = (x [+ pos]) . W^T + b.  A workgroup owns 32 rows: x and x + pos are formed once while the tile is loaded into LDS (no x + pos tensor),
 //   the four waves share the 32-column output blocks of in_proj_weight; [q; k] blocks multiply the x + pos tile, v blocks the x tile.  Cross layers launch it twice
@@ -15,8 +17,8 @@
 //   The same kernel serves every Nq, also Nq == 1 (the fine shape: B x 8 waves with one live column each, four (batch item, head) pairs to a workgroup): a row's bits
 //   must not depend on how many rows or batch items the call holds (tests/test_gpu_sct.py), which rules out a second kernel chosen by Nq or B; the number of key
 //   ranges depends on Nk alone.
-// sct_chain_kernel  out_proj, + residual, LayerNorm, linear1, ReLU, linear2, + residual, LayerNorm for 32 rows that stay in LDS from the attention output to the layer
-//   output; the F-wide hidden rows live in LDS only.  The four waves split the output blocks of each product, so every weight fragment is read by exactly ONE wave
+// sct_chain_kernel  (sct.h) out_proj, + residual, LayerNorm, linear1, ReLU, linear2, + residual, LayerNorm for 32 rows that stay in LDS from the attention output to the
+//   layer output; the F-wide hidden rows live in LDS only.  The four waves split the output blocks of each product, so every weight fragment is read by exactly ONE wave
 //   of the workgroup, straight from L2 in 1-KB coalesced pieces (fragment order): a copy through LDS would add a barrier pair per chunk and no reuse.
 //   Measured: the kernel takes ~90 us per launch whatever the row count — it waits on these loads, which are not requested ahead of use; not yet changed.
 //
@@ -27,7 +29,6 @@
 #include "mfma.h"
 #include "host.h"
 #include "sct.h"
-#include "sct_drop.h"
 
 namespace {
 
@@ -121,7 +122,7 @@ __device__ __forceinline__ void sct_attn_load(const float* kbase, const float* v
 template <int MODE, int DH, class... DROPARG>
 __global__ __launch_bounds__(256) void sct_attn_kernel(const SctAttnArgs a, const DROPARG... drop) {
   constexpr bool DROP = sizeof...(DROPARG) != 0;
-  [[maybe_unused]] const auto d = sct_drop_of(drop...);
+  [[maybe_unused]] const auto d = sct_arg<SctDrop>(drop...);
   if constexpr (MODE == SCT_X3) __builtin_amdgcn_s_setreg(1473, 1);
   __shared__ float part[4][18][64];   // per wave: running maximum, sum, and the 16 accumulator registers, lane-major
   constexpr int C = 8 * DH;
@@ -279,84 +280,6 @@ __global__ __launch_bounds__(256) void sct_attn_kernel(const SctAttnArgs a, cons
   }
 }
 
-// ------------------------------------------------------------------------------------------ post-attention row chain
-template <int MODE>
-__global__ __launch_bounds__(256) void sct_chain_kernel(const SctChainArgs a) {
-  if constexpr (MODE == SCT_X3) __builtin_amdgcn_s_setreg(1473, 1);
-  extern __shared__ __attribute__((aligned(16))) float sct_smem[];
-  const int C = a.C, F = a.F, ldc = C + SCT_PAD, ldf = F + SCT_PAD, c4n = C >> 2, nc = C >> 5, nf = F >> 5;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, hh = lane >> 5, col = lane & 31;
-  const long long row0 = (long long)blockIdx.x * 32;
-  float* y = sct_smem;               // [32][ldc]: the running rows
-  float* hb = sct_smem + 32 * ldc;   // [32][ldc] attention output, then [32][ldf] hidden rows
-  const float* bo = a.vec + 3 * C;
-  const float* b1 = a.vec + 4 * C;
-  const float* b2 = b1 + F;
-  const float* lnp = b2 + C;   // weight A, bias A, weight B, bias B
-
-  for (int i = threadIdx.x; i < 32 * c4n; i += 256) {
-    const int r = i / c4n, c = 4 * (i - r * c4n);
-    const long long row = row0 + r < a.rows ? row0 + r : a.rows - 1;
-    *(float4*)(hb + r * ldc + c) = *(const float4*)(a.attn + (size_t)row * C + c);
-  }
-  __syncthreads();
-  {   // out_proj + bias + residual
-    nl_f32x16 acc[2];
-    nl_acc_zero(acc);
-    sct_gemm<MODE, 2>(acc, hb + col * ldc, C, a.wo, wave, nc, lane);
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const int rb = wave + 4 * i;
-      if (rb >= nc) break;
-      const int n = 32 * rb + col;
-      const float bv = bo[n];
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int row = nl_acc_row(r, hh);
-        const long long grow = row0 + row < a.rows ? row0 + row : a.rows - 1;
-        y[row * ldc + n] = a.x[(size_t)grow * C + n] + (acc[i][r] + bv);
-      }
-    }
-  }
-  __syncthreads();
-  sct_layernorm(y, ldc, C, lnp, lnp + C, lane, wave, nullptr, 0, 0);
-  __syncthreads();
-  {   // linear1 + bias + ReLU -> hidden rows (the attention tile is dead)
-    nl_f32x16 acc[4];
-    nl_acc_zero(acc);
-    sct_gemm<MODE, 4>(acc, y + col * ldc, C, a.w1, wave, nf, lane);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int rb = wave + 4 * i;
-      if (rb >= nf) break;
-      const int n = 32 * rb + col;
-      const float bv = b1[n];
-#pragma unroll
-      for (int r = 0; r < 16; ++r) hb[nl_acc_row(r, hh) * ldf + n] = fmaxf(acc[i][r] + bv, 0.f);
-    }
-  }
-  __syncthreads();
-  {   // linear2 + bias + residual
-    nl_f32x16 acc[2];
-    nl_acc_zero(acc);
-    sct_gemm<MODE, 2>(acc, hb + col * ldf, F, a.w2, wave, nc, lane);
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const int rb = wave + 4 * i;
-      if (rb >= nc) break;
-      const int n = 32 * rb + col;
-      const float bv = b2[n];
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int row = nl_acc_row(r, hh);
-        y[row * ldc + n] = y[row * ldc + n] + (acc[i][r] + bv);
-      }
-    }
-  }
-  __syncthreads();
-  sct_layernorm(y, ldc, C, lnp + 2 * C, lnp + 3 * C, lane, wave, a.out, row0, a.rows);
-}
-
 // ------------------------------------------------------------------------------------------ host side
 struct SctRun {
   const unsigned char* img; int C, F, layer;
@@ -366,12 +289,6 @@ struct SctRun {
   float* const* keep = nullptr;   // the training forward (sct_bwd.hip): q, k, v and the attention output go to these caller-owned rows and the row chain is left to it
   const SctDrop* drop = nullptr;  // ... with dropout in effect (thr > 0): the dropping attention kernel
 };
-
-template <int MODE, int DH>
-void sct_launch_attn(const SctAttnArgs& a, const SctDrop* d, hipStream_t st) {
-  if (d) hipLaunchKernelGGL((sct_attn_kernel<MODE, DH>), dim3((unsigned)nl_cdiv(a.items, 4 >> a.lg)), dim3(256), 0, st, a, *d);
-  else hipLaunchKernelGGL((sct_attn_kernel<MODE, DH>), dim3((unsigned)nl_cdiv(a.items, 4 >> a.lg)), dim3(256), 0, st, a);
-}
 
 template <int MODE>
 int sct_run_layer(const SctRun& r, hipStream_t st) {
@@ -406,23 +323,13 @@ int sct_run_layer(const SctRun& r, hipStream_t st) {
   t.Nq = r.Nq; t.Nk = r.Nk; t.nqt = (int)nl_cdiv(r.Nq, 32); t.nkt = (int)nl_cdiv(r.Nk, 32); t.items = r.B * SCT_HEADS * t.nqt;
   t.lg = t.nkt >= 16 ? 2 : t.nkt >= 4 ? 1 : 0;   // long key sequences are cut into 2 or 4 ranges: enough waves per SIMD to hide the loads; a function of Nk alone
   t.tps = (int)nl_cdiv(t.nkt, 1 << t.lg);
-  t.scale = (float)(1.0 / sqrt((double)(C / SCT_HEADS)));
-  switch (C) {
-    case 64: sct_launch_attn<MODE, 8>(t, r.drop, st); break;
-    case 128: sct_launch_attn<MODE, 16>(t, r.drop, st); break;
-    case 192: sct_launch_attn<MODE, 24>(t, r.drop, st); break;
-    default: sct_launch_attn<MODE, 32>(t, r.drop, st); break;
-  }
-
-  if (r.keep) {
-    NL_LAUNCH_CHECK();
-    return NL_OK;
-  }
-  SctChainArgs c;
-  c.attn = ab; c.x = r.x; c.out = r.out;
-  c.wo = sct_mat(r.img, lo.m[1], C); c.w1 = sct_mat(r.img, lo.m[2], F); c.w2 = sct_mat(r.img, lo.m[3], C);
-  c.vec = vec; c.rows = rowsq; c.C = C; c.F = F;
-  hipLaunchKernelGGL(sct_chain_kernel<MODE>, dim3((unsigned)nl_cdiv(rowsq, 32)), dim3(256), sct_chain_lds(C, F), st, c);
+  t.scale = sct_scale(C);
+  const int e = sct_by_head(C, [&](auto dh) {
+    constexpr int DH = decltype(dh)::value;
+    return sct_launch<sct_attn_kernel<MODE, DH>, sct_attn_kernel<MODE, DH, SctDrop>>(nl_cdiv(t.items, 4 >> t.lg), 0, 0, st, r.drop, t);
+  });
+  if (e || r.keep) return e;
+  hipLaunchKernelGGL(sct_chain_kernel<MODE>, dim3((unsigned)nl_cdiv(rowsq, 32)), dim3(256), sct_chain_lds(C, F), st, sct_chain_args(r.img, lo, C, F, ab, r.x, r.out, rowsq));
   NL_LAUNCH_CHECK();
   return NL_OK;
 }
@@ -456,12 +363,9 @@ int nl_sct_pack_weights(int C, int nhead, int F, const float* const* tensors, in
   const SctLayout L = sct_layout(C, F);
   hipStream_t st = (hipStream_t)stream;
   unsigned char* img = (unsigned char*)packed;
-  // state-dict order: two encoder layers of 12 tensors (in_proj w/b, out_proj w/b, linear1 w/b, linear2 w/b, norm1 w/b, norm2 w/b), two decoder layers of 14
-  // (.., norm1 w/b [constructed, never applied], norm2 w/b, norm3 w/b)
-  const int base[SCT_LAYERS] = {0, 12, 24, 38};
   for (int l = 0; l < SCT_LAYERS; ++l) {
-    const float* const* t = tensors + base[l];
-    const int ln = l < 2 ? 8 : 10;   // first of the four LayerNorm tensors the layer applies
+    const float* const* t = tensors + sct_param_first(l);
+    const int ln = sct_param_norm(l);
     const int N[4] = {3 * C, C, F, C}, K[4] = {C, C, C, F};
     for (int k = 0; k < 4; ++k) {
       const SctMatOff& m = L.l[l].m[k];
@@ -483,7 +387,7 @@ int nl_sct_pack_weights(int C, int nhead, int F, const float* const* tensors, in
 
 size_t nl_sct_workspace_bytes(int64_t B, int64_t N0, int64_t N1, int C, int F) {
   (void)F;   // the hidden rows never leave LDS
-  if (B < 0 || N0 < 1 || N1 < 1 || C < 1 || B > SCT_MAX_ROWS || N0 > SCT_MAX_ROWS || N1 > SCT_MAX_ROWS || B * (N0 > N1 ? N0 : N1) > SCT_MAX_ROWS) return 0;
+  if (!sct_counts_ok(B, N0, N1) || C < 1 || !sct_counts_fit(B, N0, N1, N0 > N1 ? N0 : N1)) return 0;
   return 4 * sct_ws_part(B ? B : 1, N0, N1, C);
 }
 

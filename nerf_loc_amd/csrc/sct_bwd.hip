@@ -1,12 +1,13 @@
-// Training step of SelfCrossTransformer (sct.hip is the inference forward), without dropout and — the *_dropout entry points, the kernels' instantiations with a
-// trailing SctDrop argument, sct_drop.h — with the reference's four dropout sites per layer inside the kernels: nl_sct_forward_train keeps O(rows x C) of state per layer,
-// nl_sct_backward returns the gradients of the four inputs and of the 48 tensors the module applies.  No Nq x Nk value reaches memory in either direction: the
-// probabilities are rebuilt tile by tile from the kept row maximum and sum (the two parts of the log-sum-exp).
+// Training step of SelfCrossTransformer (sct.hip is the inference forward): nl_sct_forward_train keeps O(rows x C) of state per layer, nl_sct_backward returns the
+// gradients of the four inputs and of the 48 tensors the module applies.  No Nq x Nk value reaches memory in either direction: the probabilities are rebuilt tile by
+// tile from the kept row maximum and sum (the two parts of the log-sum-exp).  The *_dropout entry points are the same step with the reference's four dropout sites
+// per layer inside the kernels: the kernels' instantiations with a trailing SctDrop argument (sct_drop.h).
 //
 // Forward (per layer): the INFERENCE projection and attention kernels write q, k, v and the attention output straight into the state (launch.h:
-//   nl_launch_sct_qkv_attn), sct_stats_kernel adds the (maximum, sum) of every (row, head), and sct_chain_keep_kernel is sct_chain_kernel with four more stores —
-//   the rows after the first LayerNorm, both LayerNorms' normalised rows and 1 / std, and the outputs of layers 0..2 that the in-place forward overwrites.  The library
-//   is built without floating-point contraction, so the same expressions give the same bits: out0 / out1 equal nl_sct_forward's (tests/test_gpu_sct_train.py).
+//   nl_launch_sct_qkv_attn), sct_stats_kernel adds the (maximum, sum) of every (row, head), and the row chain is sct_chain_kernel (sct.h) with the SctKeepRows
+//   pointers, i.e. with four more stores: the rows after the first LayerNorm, both LayerNorms' normalised rows and 1 / std, and the outputs of layers 0..2 that the
+//   in-place forward overwrites.  The library is built without floating-point contraction, so the same expressions give the same bits: out0 / out1 equal
+//   nl_sct_forward's (tests/test_gpu_sct_train.py).
 // Backward (layers 3, 2, 1, 0; rows flattened over the batch):
 //   sct_chain_bwd_kernel  32 rows per workgroup in LDS: hidden rows again from the kept y1 with sct_chain_kernel's own product (same fragments, same order: the
 //     ReLU mask is the one the forward applied), second LayerNorm backward, g . W2, mask, g . W1, + the residual's gradient, first LayerNorm backward, g . Wo.
@@ -32,7 +33,6 @@
 #include "mfma.h"
 #include "host.h"
 #include "sct.h"
-#include "sct_drop.h"
 
 namespace {
 
@@ -62,12 +62,18 @@ inline SctTrainLayout sct_train_layout(int C, int F) {
 
 // ------------------------------------------------------------------------------------------ kept state of one layer
 struct SctKeep { float *q, *k, *v, *attn, *ml, *y1, *xa, *xb, *rstd, *out; };
-// carves the layer's buffers at base + o (base may be null: sizes only); returns the offset behind them
+// the next `floats` floats of a carved buffer, at base + o (base may be null: sizes only); o moves behind them, to the next multiple of 256 bytes
+float* sct_take(unsigned char* base, size_t& o, size_t floats) {
+  float* p = base ? (float*)(base + o) : nullptr;
+  o += nl_align_up(floats * 4, 256);
+  return p;
+}
+// carves the layer's buffers at base + o; returns the offset behind them
 size_t sct_keep_carve(unsigned char* base, size_t o, int64_t rq, int64_t rk, int C, SctKeep& k, bool no_out = false) {
-  auto take = [&](size_t floats) { float* p = base ? (float*)(base + o) : nullptr; o += nl_align_up(floats * 4, 256); return p; };
-  k.q = take((size_t)rq * C); k.k = take((size_t)rk * C); k.v = take((size_t)rk * C); k.attn = take((size_t)rq * C);
-  k.ml = take((size_t)rq * 16); k.y1 = take((size_t)rq * C); k.xa = take((size_t)rq * C); k.xb = take((size_t)rq * C);
-  k.rstd = take((size_t)rq * 2); k.out = no_out ? nullptr : take((size_t)rq * C);
+  const size_t q = (size_t)rq * C, m = (size_t)rk * C;
+  k.q = sct_take(base, o, q); k.k = sct_take(base, o, m); k.v = sct_take(base, o, m); k.attn = sct_take(base, o, q);
+  k.ml = sct_take(base, o, (size_t)rq * 16); k.y1 = sct_take(base, o, q); k.xa = sct_take(base, o, q); k.xb = sct_take(base, o, q);
+  k.rstd = sct_take(base, o, (size_t)rq * 2); k.out = no_out ? nullptr : sct_take(base, o, q);
   return o;
 }
 size_t sct_state_carve(unsigned char* base, int64_t B, int64_t N0, int64_t N1, int C, SctKeep (&k)[SCT_LAYERS]) {
@@ -77,134 +83,6 @@ size_t sct_state_carve(unsigned char* base, int64_t B, int64_t N0, int64_t N1, i
     o = sct_keep_carve(base, o, B * nq, B * nk, C, k[l], l == 3);
   }
   return o;
-}
-
-// ------------------------------------------------------------------------------------------ forward: row chain with its state kept
-// sct_layernorm with the normalised rows and 1 / std kept (the same expressions in the same order): in place + y1 (first norm), or to the output rows (+ keep)
-__device__ __forceinline__ void sct_layernorm_keep(float* y, int ld, int C, const float* g, const float* bta, int lane, int wave, float* dst, float* dst2, float* xn,
-                                                   float* rs, int which, long long row0, long long rows) {
-  const int nci = C >> 6;
-  for (int rr = 0; rr < 8; ++rr) {
-    const int row = 8 * wave + rr;
-    const bool live = row0 + row < rows;
-    float v[4] = {0.f, 0.f, 0.f, 0.f}, s = 0.f;
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-      if (i < nci) { v[i] = y[row * ld + lane + 64 * i]; s += v[i]; }
-    const float mean = wave_sum(s) / (float)C;
-    float sq = 0.f;
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-      if (i < nci) { v[i] -= mean; sq += v[i] * v[i]; }
-    const float rstd = 1.f / sqrtf(wave_sum(sq) / (float)C + SCT_EPS);
-    if (live && lane == 0) rs[(size_t)(row0 + row) * 2 + which] = rstd;
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-      if (i < nci) {
-        const int c = lane + 64 * i;
-        const float n = v[i] * rstd;
-        const float r = n * g[c] + bta[c];
-        if (which == 0) y[row * ld + c] = r;
-        if (live) {
-          const size_t e = (size_t)(row0 + row) * C + c;
-          xn[e] = n;
-          if (dst) dst[e] = r;
-          if (dst2) dst2[e] = r;
-        }
-      }
-  }
-}
-
-// DROP: the masks of sites 1 (out_proj's output before the residual), 2 (the ReLU'd hidden rows) and 3 (linear2's output before the residual) on the accumulator
-// registers, which run along the rows: four generator calls per 32 x 32 output block and lane.  The kept state has the same layout; no mask is stored.
-template <int MODE, class... DROPARG>
-__global__ __launch_bounds__(256) void sct_chain_keep_kernel(const SctChainArgs a, float* y1, float* xa, float* xb, float* rstd, float* keep, const DROPARG... drop) {
-  constexpr bool DROP = sizeof...(DROPARG) != 0;
-  [[maybe_unused]] const auto d = sct_drop_of(drop...);
-  if constexpr (MODE == SCT_X3) __builtin_amdgcn_s_setreg(1473, 1);
-  extern __shared__ __attribute__((aligned(16))) float sct_smem[];
-  const int C = a.C, F = a.F, ldc = C + SCT_PAD, ldf = F + SCT_PAD, c4n = C >> 2, nc = C >> 5, nf = F >> 5;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, hh = lane >> 5, col = lane & 31;
-  const long long row0 = (long long)blockIdx.x * 32;
-  float* y = sct_smem;
-  float* hb = sct_smem + 32 * ldc;
-  const float* bo = a.vec + 3 * C;
-  const float* b1 = a.vec + 4 * C;
-  const float* b2 = b1 + F;
-  const float* lnp = b2 + C;
-
-  for (int i = threadIdx.x; i < 32 * c4n; i += 256) {
-    const int r = i / c4n, c = 4 * (i - r * c4n);
-    const long long row = row0 + r < a.rows ? row0 + r : a.rows - 1;
-    *(float4*)(hb + r * ldc + c) = *(const float4*)(a.attn + (size_t)row * C + c);
-  }
-  __syncthreads();
-  {   // out_proj + bias + residual
-    nl_f32x16 acc[2];
-    nl_acc_zero(acc);
-    sct_gemm<MODE, 2>(acc, hb + col * ldc, C, a.wo, wave, nc, lane);
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const int rb = wave + 4 * i;
-      if (rb >= nc) break;
-      const int n = 32 * rb + col;
-      const float bv = bo[n];
-      unsigned kb = 0;
-      if constexpr (DROP) kb = sct_drop_bits_major(d, 1, 0, (unsigned)row0, hh, (unsigned)n);
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int row = nl_acc_row(r, hh);
-        const long long grow = row0 + row < a.rows ? row0 + row : a.rows - 1;
-        if constexpr (DROP) y[row * ldc + n] = a.x[(size_t)grow * C + n] + sct_drop_apply(d, kb, r, acc[i][r] + bv);
-        else y[row * ldc + n] = a.x[(size_t)grow * C + n] + (acc[i][r] + bv);
-      }
-    }
-  }
-  __syncthreads();
-  sct_layernorm_keep(y, ldc, C, lnp, lnp + C, lane, wave, y1, nullptr, xa, rstd, 0, row0, a.rows);
-  __syncthreads();
-  {   // linear1 + bias + ReLU
-    nl_f32x16 acc[4];
-    nl_acc_zero(acc);
-    sct_gemm<MODE, 4>(acc, y + col * ldc, C, a.w1, wave, nf, lane);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int rb = wave + 4 * i;
-      if (rb >= nf) break;
-      const int n = 32 * rb + col;
-      const float bv = b1[n];
-      unsigned kb = 0;
-      if constexpr (DROP) kb = sct_drop_bits_major(d, 2, 0, (unsigned)row0, hh, (unsigned)n);
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        if constexpr (DROP) hb[nl_acc_row(r, hh) * ldf + n] = sct_drop_apply(d, kb, r, fmaxf(acc[i][r] + bv, 0.f));
-        else hb[nl_acc_row(r, hh) * ldf + n] = fmaxf(acc[i][r] + bv, 0.f);
-      }
-    }
-  }
-  __syncthreads();
-  {   // linear2 + bias + residual
-    nl_f32x16 acc[2];
-    nl_acc_zero(acc);
-    sct_gemm<MODE, 2>(acc, hb + col * ldf, F, a.w2, wave, nc, lane);
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const int rb = wave + 4 * i;
-      if (rb >= nc) break;
-      const int n = 32 * rb + col;
-      const float bv = b2[n];
-      unsigned kb = 0;
-      if constexpr (DROP) kb = sct_drop_bits_major(d, 3, 0, (unsigned)row0, hh, (unsigned)n);
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int row = nl_acc_row(r, hh);
-        if constexpr (DROP) y[row * ldc + n] = y[row * ldc + n] + sct_drop_apply(d, kb, r, acc[i][r] + bv);
-        else y[row * ldc + n] = y[row * ldc + n] + (acc[i][r] + bv);
-      }
-    }
-  }
-  __syncthreads();
-  sct_layernorm_keep(y, ldc, C, lnp + 2 * C, lnp + 3 * C, lane, wave, a.out, keep, xb, rstd, 1, row0, a.rows);
 }
 
 // ------------------------------------------------------------------------------------------ attention tiles
@@ -354,7 +232,7 @@ struct SctAttnBwdArgs {
 template <int MODE, int DH, bool KV, class... DROPARG>
 __global__ __launch_bounds__(256) void sct_attn_bwd_kernel(const SctAttnBwdArgs a, const DROPARG... drop) {
   constexpr bool DROP = sizeof...(DROPARG) != 0;
-  [[maybe_unused]] const auto d = sct_drop_of(drop...);
+  [[maybe_unused]] const auto d = sct_arg<SctDrop>(drop...);
   if constexpr (MODE == SCT_X3) __builtin_amdgcn_s_setreg(1473, 1);
   constexpr int C = 8 * DH;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, hh = lane >> 5, col = lane & 31;
@@ -446,59 +324,30 @@ struct SctChainBwdArgs {
 };
 
 // LayerNorm backward of the wave's 8 rows: g_in = rstd (t - mean(t) - xn mean(t xn)), t = g gamma.  g comes from gsrc (global rows) or from the LDS tile, the result
-// goes to the LDS tile and to dst (and is added to add, if given)
-__device__ __forceinline__ void sct_layernorm_bwd(float* tile, int ld, int C, const float* gsrc, const float* xn, const float* rstd, int which, const float* gamma,
-                                                  int lane, int wave, long long row0, long long row_end, float* dst, float* add) {
-  const int nci = C >> 6;
-  for (int rr = 0; rr < 8; ++rr) {
-    const int row = 8 * wave + rr;
-    const bool live = row0 + row < row_end;
-    const size_t grow = (size_t)(live ? row0 + row : row_end - 1);
-    float t[4] = {0.f, 0.f, 0.f, 0.f}, x[4] = {0.f, 0.f, 0.f, 0.f}, s1 = 0.f, s2 = 0.f;
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-      if (i < nci) {
-        const int c = lane + 64 * i;
-        const float g = gsrc ? gsrc[grow * C + c] : tile[row * ld + c];
-        x[i] = xn[grow * C + c];
-        t[i] = g * gamma[c];
-        s1 += t[i];
-        s2 += t[i] * x[i];
-      }
-    const float m1 = wave_sum(s1) / (float)C, m2 = wave_sum(s2) / (float)C;
-    const float rs = rstd[grow * 2 + which];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-      if (i < nci) {
-        const int c = lane + 64 * i;
-        const float r = rs * ((t[i] - m1) - x[i] * m2);
-        tile[row * ld + c] = r;
-        if (live) {
-          dst[grow * C + c] = r;
-          if (add) add[grow * C + c] += r;
-        }
-      }
-  }
-}
-
-// sct_layernorm_bwd where the LayerNorm's input was x + dropout(z) (sct_drop.h `site`): the residual takes the gradient as it is — added to `add`, or stored to `raw`
+// goes to the LDS tile and to dst (and is added to add, if given).
+// With a trailing SctDrop the LayerNorm's input was x + dropout(z) (sct_drop.h `site`): the residual takes the gradient as it is — added to `add`, or stored to `raw`
 // — and z takes it masked and scaled: that goes to the LDS tile (the next product's operand) and to dst (the rows the weight gradient reads).  The lane's columns
 // run along `minor` and its 8 rows along `major`: two generator calls per 64 columns, kept as one bit per (row, column).
-__device__ __forceinline__ void sct_layernorm_bwd_drop(float* tile, int ld, int C, const float* gsrc, const float* xn, const float* rstd, int which, const float* gamma,
-                                                       int lane, int wave, long long row0, long long row_end, float* dst, float* add, float* raw, const SctDrop& d,
-                                                       int site) {
+template <class... DROPARG>
+__device__ __forceinline__ void sct_layernorm_bwd(float* tile, int ld, int C, const float* gsrc, const float* xn, const float* rstd, int which, const float* gamma,
+                                                  int lane, int wave, long long row0, long long row_end, float* dst, float* add, float* raw, int site,
+                                                  const DROPARG&... drop) {
+  constexpr bool DROP = sizeof...(DROPARG) != 0;
+  [[maybe_unused]] const auto d = sct_arg<SctDrop>(drop...);
   const int nci = C >> 6;
-  unsigned kb = 0;
+  [[maybe_unused]] unsigned kb = 0;
+  if constexpr (DROP) {
 #pragma unroll
-  for (int g = 0; g < 2; ++g)
+    for (int g = 0; g < 2; ++g)
 #pragma unroll
-    for (int i = 0; i < 4; ++i)
-      if (i < nci) {
-        const uint4 w = sct_drop_words(d, site, 0, (unsigned)((row0 + 8 * wave + 4 * g) >> 2), (unsigned)(lane + 64 * i) >> 1);
-        const unsigned h = lane & 1;
-        kb |= (unsigned)sct_drop_keep(d, w.x, h) << (16 * g + i) | (unsigned)sct_drop_keep(d, w.y, h) << (16 * g + 4 + i) |
-              (unsigned)sct_drop_keep(d, w.z, h) << (16 * g + 8 + i) | (unsigned)sct_drop_keep(d, w.w, h) << (16 * g + 12 + i);
-      }
+      for (int i = 0; i < 4; ++i)
+        if (i < nci) {
+          const uint4 w = sct_drop_words(d, site, 0, (unsigned)((row0 + 8 * wave + 4 * g) >> 2), (unsigned)(lane + 64 * i) >> 1);
+          const unsigned h = lane & 1;
+          kb |= (unsigned)sct_drop_keep(d, w.x, h) << (16 * g + i) | (unsigned)sct_drop_keep(d, w.y, h) << (16 * g + 4 + i) |
+                (unsigned)sct_drop_keep(d, w.z, h) << (16 * g + 8 + i) | (unsigned)sct_drop_keep(d, w.w, h) << (16 * g + 12 + i);
+        }
+  }
   for (int rr = 0; rr < 8; ++rr) {
     const int row = 8 * wave + rr;
     const bool live = row0 + row < row_end;
@@ -521,7 +370,8 @@ __device__ __forceinline__ void sct_layernorm_bwd_drop(float* tile, int ld, int 
       if (i < nci) {
         const int c = lane + 64 * i;
         const float r = rs * ((t[i] - m1) - x[i] * m2);
-        const float rm = sct_drop_apply(d, kb, 4 * rr + i, r);
+        float rm = r;
+        if constexpr (DROP) rm = sct_drop_apply(d, kb, 4 * rr + i, r);
         tile[row * ld + c] = rm;
         if (live) {
           dst[grow * C + c] = rm;
@@ -539,7 +389,7 @@ __device__ __forceinline__ void sct_layernorm_bwd_drop(float* tile, int ld, int 
 template <int MODE, class... DROPARG>
 __global__ __launch_bounds__(256) void sct_chain_bwd_kernel(const SctChainBwdArgs a, const DROPARG... drop) {
   constexpr bool DROP = sizeof...(DROPARG) != 0;
-  [[maybe_unused]] const auto d = sct_drop_of(drop...);
+  [[maybe_unused]] const auto d = sct_arg<SctDrop>(drop...);
   if constexpr (MODE == SCT_X3) __builtin_amdgcn_s_setreg(1473, 1);
   extern __shared__ __attribute__((aligned(16))) float sct_smem[];
   const int C = a.C, F = a.F, ldc = C + SCT_PAD, ldf = F + SCT_PAD, c4n = C >> 2, nc = C >> 5, nf = F >> 5;
@@ -580,8 +430,7 @@ __global__ __launch_bounds__(256) void sct_chain_bwd_kernel(const SctChainBwdArg
   }
   __syncthreads();
   // second LayerNorm backward: g_z2 (the gradient of linear2's output and of the residual beside it)
-  if constexpr (DROP) sct_layernorm_bwd_drop(ga, ldc, C, a.g_out, a.xb, a.rstd, 1, lnp + 2 * C, lane, wave, row0, a.row_end, a.gz2, nullptr, a.gy1, d, 3);
-  else sct_layernorm_bwd(ga, ldc, C, a.g_out, a.xb, a.rstd, 1, lnp + 2 * C, lane, wave, row0, a.row_end, a.gz2, nullptr);
+  sct_layernorm_bwd(ga, ldc, C, a.g_out, a.xb, a.rstd, 1, lnp + 2 * C, lane, wave, row0, a.row_end, a.gz2, nullptr, DROP ? a.gy1 : nullptr, 3, drop...);
   __syncthreads();
   {   // g_h = g_z2 . W2, masked: each hidden value is replaced by its pre-activation's gradient (the same lane reads and writes it)
     nl_f32x16 acc[4];
@@ -625,8 +474,7 @@ __global__ __launch_bounds__(256) void sct_chain_bwd_kernel(const SctChainBwdArg
   }
   __syncthreads();
   // first LayerNorm backward: g_z1 (the gradient of out_proj's output and of the residual x)
-  if constexpr (DROP) sct_layernorm_bwd_drop(ga, ldc, C, nullptr, a.xa, a.rstd, 0, lnp, lane, wave, row0, a.row_end, a.gz1, a.gx, nullptr, d, 1);
-  else sct_layernorm_bwd(ga, ldc, C, nullptr, a.xa, a.rstd, 0, lnp, lane, wave, row0, a.row_end, a.gz1, a.gx);
+  sct_layernorm_bwd(ga, ldc, C, nullptr, a.xa, a.rstd, 0, lnp, lane, wave, row0, a.row_end, a.gz1, a.gx, nullptr, 1, drop...);
   __syncthreads();
   {   // g_attn = g_z1 . Wo
     nl_f32x16 acc[2];
@@ -730,14 +578,6 @@ __global__ __launch_bounds__(256) void sct_add_kernel(const float* x, const floa
 }
 
 // ------------------------------------------------------------------------------------------ host side
-// floats of tensor i (state-dict order) of the module
-size_t sct_tensor_floats(int i, int C, int F) {
-  const int l = i < 12 ? 0 : i < 24 ? 1 : i < 38 ? 2 : 3;
-  const int base[SCT_LAYERS] = {0, 12, 24, 38};
-  const int k = i - base[l];
-  const size_t n[8] = {(size_t)3 * C * C, (size_t)3 * C, (size_t)C * C, (size_t)C, (size_t)F * C, (size_t)F, (size_t)C * F, (size_t)C};
-  return k < 8 ? n[k] : (size_t)C;
-}
 int sct_wg_splits(int64_t rows) { return (int)std::min<int64_t>(256, std::max<int64_t>(1, nl_cdiv(rows, 256))); }
 
 // workspace of the backward: the gradients at the three inner layer outputs and one layer's temporaries (sized by the longer side); x + pos and mem + pos of the
@@ -750,23 +590,23 @@ struct SctBwdWs {
 SctBwdWs sct_bwd_ws(unsigned char* base, int64_t B, int64_t N0, int64_t N1, int C, int F, bool layer) {
   SctBwdWs w;
   size_t o = 0;
-  auto take = [&](size_t floats) { float* p = base ? (float*)(base + o) : nullptr; o += nl_align_up(floats * 4, 256); return p; };
   const int64_t r0 = B * N0, r1 = B * N1, rm = std::max(r0, r1);
   const size_t rc = (size_t)rm * C;
-  w.G[0] = take((size_t)r0 * C); w.G[1] = take((size_t)r1 * C); w.G[2] = take((size_t)r0 * C);
-  w.gz2 = take(rc); w.gy1 = take(rc); w.gz1 = take(rc); w.gattn = take(rc); w.dd = take((size_t)rm * 8);
-  w.dq = take(rc); w.dk = take(rc); w.dv = take(rc); w.xp = w.gz2; w.mp = w.gy1;
+  w.G[0] = sct_take(base, o, (size_t)r0 * C); w.G[1] = sct_take(base, o, (size_t)r1 * C); w.G[2] = sct_take(base, o, (size_t)r0 * C);
+  w.gz2 = sct_take(base, o, rc); w.gy1 = sct_take(base, o, rc); w.gz1 = sct_take(base, o, rc); w.gattn = sct_take(base, o, rc);
+  w.dd = sct_take(base, o, (size_t)rm * 8);
+  w.dq = sct_take(base, o, rc); w.dk = sct_take(base, o, rc); w.dv = sct_take(base, o, rc); w.xp = w.gz2; w.mp = w.gy1;
   w.chunk = std::min<int64_t>(rm, SCT_BWD_CHUNK);
-  w.hst = take((size_t)w.chunk * F); w.gst = take((size_t)w.chunk * F);
+  w.hst = sct_take(base, o, (size_t)w.chunk * F); w.gst = sct_take(base, o, (size_t)w.chunk * F);
   const size_t mn = (size_t)C * std::max(C, F);
   w.wg_floats = (size_t)sct_wg_splits(rm) * (mn + std::max(C, F));
-  w.wg = take(w.wg_floats);
-  w.lnp = take((size_t)nl_cdiv(rm, SCT_LN_ROWS) * 2 * C);
-  w.dummy = take(mn);
+  w.wg = sct_take(base, o, w.wg_floats);
+  w.lnp = sct_take(base, o, (size_t)nl_cdiv(rm, SCT_LN_ROWS) * 2 * C);
+  w.dummy = sct_take(base, o, mn);
   w.lout = nullptr;
   w.keep_off = o;
   if (layer) {
-    w.lout = take((size_t)r0 * C);
+    w.lout = sct_take(base, o, (size_t)r0 * C);
     w.keep_off = o;
     SctKeep k;
     o = sct_keep_carve(nullptr, o, r0, r1, C, k, true);
@@ -782,30 +622,10 @@ struct SctLayerFwd {
   float p; unsigned long long seed;   // dropout (sct_drop.h); p == 0: the kernels without it
 };
 
-template <int MODE, int DH>
-void sct_launch_stats(const SctStatsArgs& a, hipStream_t st) {
-  hipLaunchKernelGGL((sct_stats_kernel<MODE, DH>), dim3((unsigned)nl_cdiv(a.items, 4)), dim3(256), 0, st, a);
-}
-template <int MODE, int DH>
-void sct_launch_attn_bwd(const SctAttnBwdArgs& a, bool kv, const SctDrop* d, hipStream_t st) {
-  if (d && kv) hipLaunchKernelGGL((sct_attn_bwd_kernel<MODE, DH, true>), dim3((unsigned)nl_cdiv(a.items, 4)), dim3(256), 0, st, a, *d);
-  else if (d) hipLaunchKernelGGL((sct_attn_bwd_kernel<MODE, DH, false>), dim3((unsigned)nl_cdiv(a.items, 4)), dim3(256), 0, st, a, *d);
-  else if (kv) hipLaunchKernelGGL((sct_attn_bwd_kernel<MODE, DH, true>), dim3((unsigned)nl_cdiv(a.items, 4)), dim3(256), 0, st, a);
-  else hipLaunchKernelGGL((sct_attn_bwd_kernel<MODE, DH, false>), dim3((unsigned)nl_cdiv(a.items, 4)), dim3(256), 0, st, a);
-}
-#define SCT_BY_C(C, call4)                        \
-  switch (C) {                                    \
-    case 64: call4(8); break;                     \
-    case 128: call4(16); break;                   \
-    case 192: call4(24); break;                   \
-    default: call4(32); break;                    \
-  }
-
 template <int MODE>
 int sct_layer_forward_train(const SctLayerFwd& r, hipStream_t st) {
   const int C = r.C, F = r.F;
   const SctLayout L = sct_layout(C, F);
-  const SctLayerOff& lo = L.l[r.layer];
   const long long rowsq = r.B * r.Nq;
   if (const int e = nl_launch_sct_qkv_attn(r.img, C, F, r.layer, r.precision, r.x, r.xpos, r.Nq, r.mem, r.mpos, r.Nk, r.B, r.keep.q, r.keep.k, r.keep.v, r.keep.attn,
                                            r.p, r.seed, st))
@@ -813,27 +633,13 @@ int sct_layer_forward_train(const SctLayerFwd& r, hipStream_t st) {
   const SctDrop d = sct_drop_make(r.p, r.seed, r.layer);
   SctStatsArgs s;
   s.q = r.keep.q; s.k = r.keep.k; s.ml = r.keep.ml; s.Nq = r.Nq; s.Nk = r.Nk; s.nqt = (int)nl_cdiv(r.Nq, 32); s.items = r.B * SCT_HEADS * s.nqt;
-  s.scale = (float)(1.0 / sqrt((double)(C / SCT_HEADS)));
-#define SCT_CALL(DH) sct_launch_stats<MODE, DH>(s, st)
-  SCT_BY_C(C, SCT_CALL)
-#undef SCT_CALL
+  s.scale = sct_scale(C);
+  sct_by_head(C, [&](auto dh) { hipLaunchKernelGGL((sct_stats_kernel<MODE, decltype(dh)::value>), dim3((unsigned)nl_cdiv(s.items, 4)), dim3(256), 0, st, s); });
   NL_LAUNCH_CHECK();
-  static std::atomic<unsigned long long> chain_set{0}, chain_drop_set{0};
-  if (const int e = nl_allow_dynamic_lds((const void*)sct_chain_keep_kernel<MODE>, sct_chain_lds(256, 512), chain_set)) return e;
-  if (d.thr)
-    if (const int e = nl_allow_dynamic_lds((const void*)sct_chain_keep_kernel<MODE, SctDrop>, sct_chain_lds(256, 512), chain_drop_set)) return e;
-  SctChainArgs c;
-  c.attn = r.keep.attn; c.x = r.x; c.out = r.out;
-  c.wo = sct_mat(r.img, lo.m[1], C); c.w1 = sct_mat(r.img, lo.m[2], F); c.w2 = sct_mat(r.img, lo.m[3], C);
-  c.vec = (const float*)(r.img + lo.vec); c.rows = rowsq; c.C = C; c.F = F;
-  if (d.thr)
-    hipLaunchKernelGGL(sct_chain_keep_kernel<MODE>, dim3((unsigned)nl_cdiv(rowsq, 32)), dim3(256), sct_chain_lds(C, F), st, c, r.keep.y1, r.keep.xa, r.keep.xb,
-                       r.keep.rstd, r.keep_out ? r.keep.out : nullptr, d);
-  else
-    hipLaunchKernelGGL(sct_chain_keep_kernel<MODE>, dim3((unsigned)nl_cdiv(rowsq, 32)), dim3(256), sct_chain_lds(C, F), st, c, r.keep.y1, r.keep.xa, r.keep.xb,
-                       r.keep.rstd, r.keep_out ? r.keep.out : nullptr);
-  NL_LAUNCH_CHECK();
-  return NL_OK;
+  return sct_launch<sct_chain_keep<MODE>, sct_chain_keep<MODE, SctDrop>>(
+      nl_cdiv(rowsq, 32), sct_chain_lds(C, F), sct_chain_lds(256, 512), st, d.thr ? &d : nullptr,
+      sct_chain_args(r.img, L.l[r.layer], C, F, r.keep.attn, r.x, r.out, rowsq),
+      r.keep.y1, r.keep.xa, r.keep.xb, r.keep.rstd, r.keep_out ? r.keep.out : nullptr);
 }
 
 struct SctLayerBwd {
@@ -854,19 +660,16 @@ int sct_layer_backward(const SctLayerBwd& r, const SctBwdWs& w, hipStream_t st) 
   const SctLayerOff& lo = L.l[l];
   const int64_t rq = r.B * r.Nq, rk = r.B * r.Nk;
   float* const* gp = r.gp;
-  const int ln = cross ? 10 : 8;
+  const int ln = sct_param_norm(l);
   const bool want_in = gp[0] || gp[1], want_o = gp[2] || gp[3], want_1 = gp[4] || gp[5], want_2 = gp[6] || gp[7];
   const bool want_lna = gp[ln] || gp[ln + 1], want_lnb = gp[ln + 2] || gp[ln + 3];
   const bool in_x = r.g_x || r.g_xpos, in_m = r.g_mem || r.g_mpos;
   if (!(want_in || want_o || want_1 || want_2 || want_lna || want_lnb || in_x || in_m)) return NL_OK;
 
-  static std::atomic<unsigned long long> chain_set{0}, chain_drop_set{0}, proj_set{0};
-  if (const int e = nl_allow_dynamic_lds((const void*)sct_chain_bwd_kernel<MODE>, sct_chain_lds(256, 512), chain_set)) return e;
+  static std::atomic<unsigned long long> proj_set{0};
+  if (const int e = nl_allow_dynamic_lds((const void*)sct_proj_bwd_kernel<MODE>, sct_proj_lds(256), proj_set)) return e;
   const SctDrop d = sct_drop_make(r.p, r.seed, l);
   const SctDrop* dp = d.thr ? &d : nullptr;
-  if (dp)
-    if (const int e = nl_allow_dynamic_lds((const void*)sct_chain_bwd_kernel<MODE, SctDrop>, sct_chain_lds(256, 512), chain_drop_set)) return e;
-  if (const int e = nl_allow_dynamic_lds((const void*)sct_proj_bwd_kernel<MODE>, sct_proj_lds(256), proj_set)) return e;
 
   // ---- row chain, in row chunks with the two F-wide weight gradients behind each
   SctChainBwdArgs c;
@@ -881,9 +684,8 @@ int sct_layer_backward(const SctLayerBwd& r, const SctBwdWs& w, hipStream_t st) 
   for (int64_t b0 = 0; b0 < rq; b0 += w.chunk) {
     const int64_t n = std::min<int64_t>(w.chunk, rq - b0);
     c.row_begin = b0; c.row_end = b0 + n;
-    if (dp) hipLaunchKernelGGL(sct_chain_bwd_kernel<MODE>, dim3((unsigned)nl_cdiv(n, 32)), dim3(256), sct_chain_lds(C, F), st, c, d);
-    else hipLaunchKernelGGL(sct_chain_bwd_kernel<MODE>, dim3((unsigned)nl_cdiv(n, 32)), dim3(256), sct_chain_lds(C, F), st, c);
-    NL_LAUNCH_CHECK();
+    if (const int e = sct_launch<sct_chain_bwd_kernel<MODE>, sct_chain_bwd_kernel<MODE, SctDrop>>(nl_cdiv(n, 32), sct_chain_lds(C, F), sct_chain_lds(256, 512), st, dp, c))
+      return e;
     if (want_1)
       if (const int e = nl_launch_wgrad(w.gst, F, F, r.keep.y1 + (size_t)b0 * C, C, C, n, 0, 0, gp[4] ? gp[4] : w.dummy, C, 1, 0, gp[5], w.wg, w.wg_floats, st)) return e;
     if (want_2)
@@ -911,22 +713,21 @@ int sct_layer_backward(const SctLayerBwd& r, const SctBwdWs& w, hipStream_t st) 
   t.q = r.keep.q; t.k = r.keep.k; t.v = r.keep.v; t.dO = w.gattn; t.ml = r.keep.ml; t.dd = w.dd;
   t.dq = w.dq; t.dk = w.dk; t.dv = w.dv;
   t.Nq = r.Nq; t.Nk = r.Nk;
-  t.scale = (float)(1.0 / sqrt((double)(C / SCT_HEADS)));
+  t.scale = sct_scale(C);
   const bool self_tgt = !cross && in_x;   // a self layer's memory side is its own x
   const bool need_q = want_in || in_x, need_kv = want_in || in_m || self_tgt;
-  if (need_q) {
-    t.nto = (int)nl_cdiv(r.Nq, 32); t.items = r.B * SCT_HEADS * t.nto;
-#define SCT_CALL(DH) sct_launch_attn_bwd<MODE, DH>(t, false, dp, st)
-    SCT_BY_C(C, SCT_CALL)
-#undef SCT_CALL
-  }
-  if (need_kv) {
-    t.nto = (int)nl_cdiv(r.Nk, 32); t.items = r.B * SCT_HEADS * t.nto;
-#define SCT_CALL(DH) sct_launch_attn_bwd<MODE, DH>(t, true, dp, st)
-    SCT_BY_C(C, SCT_CALL)
-#undef SCT_CALL
-  }
-  NL_LAUNCH_CHECK();
+  auto pass = [&](auto kv, int64_t n_owned) {   // kv: std::bool_constant — the dK / dV pass, or the dQ pass
+    t.nto = (int)nl_cdiv(n_owned, 32); t.items = r.B * SCT_HEADS * t.nto;
+    return sct_by_head(C, [&](auto dh) {
+      constexpr int DH = decltype(dh)::value;
+      constexpr bool KV = decltype(kv)::value;
+      return sct_launch<sct_attn_bwd_kernel<MODE, DH, KV>, sct_attn_bwd_kernel<MODE, DH, KV, SctDrop>>(nl_cdiv(t.items, 4), 0, 0, st, dp, t);
+    });
+  };
+  if (need_q)
+    if (const int e = pass(std::false_type{}, r.Nq)) return e;
+  if (need_kv)
+    if (const int e = pass(std::true_type{}, r.Nk)) return e;
 
   // ---- in_proj: weight and bias from (x + pos, mem + pos, mem)
   if (want_in) {
@@ -973,24 +774,43 @@ int sct_bwd(const SctLayerBwd& r, int precision, const SctBwdWs& w, hipStream_t 
   return sct_layer_backward<SCT_BF>(r, w, st);
 }
 
-// the shape checks of sct_check (sct.h) for the calls whose pointers may be null: NL_OK + *empty for B == 0
-int sct_shape_check(int C, int nhead, int F, int precision, int64_t B, int64_t N0, int64_t N1, bool* empty) {
-  *empty = false;
-  if (B < 0 || N0 < 1 || N1 < 1) return NL_ERR_BAD_ARG;
-  if (!sct_cfg_ok(C, nhead, F)) return NL_ERR_UNSUPPORTED;
-  if (const int ps = nl_prec_status_no_mx(precision)) return ps;
-  if (N0 > SCT_MAX_ROWS || N1 > SCT_MAX_ROWS || B > SCT_MAX_ROWS || B * (N0 > N1 ? N0 : N1) > SCT_MAX_ROWS) return NL_ERR_UNSUPPORTED;
-  if (B == 0) *empty = true;
-  return NL_OK;
-}
+// the size queries' answer to a shape a call would refuse: 0
 bool sct_shape_ok(int64_t B, int64_t N0, int64_t N1, int C, int F) {
-  return B >= 0 && N0 >= 1 && N1 >= 1 && sct_cfg_ok(C, SCT_HEADS, F) && B <= SCT_MAX_ROWS && N0 <= SCT_MAX_ROWS && N1 <= SCT_MAX_ROWS &&
-         B * (N0 > N1 ? N0 : N1) <= SCT_MAX_ROWS;
+  bool empty;
+  return sct_shape_status(C, SCT_HEADS, F, NL_PREC_F32, B, N0, N1, &empty) == NL_OK;
 }
 bool sct_all16(const void* const* p, int n, bool required) {
   for (int i = 0; i < n; ++i)
     if ((required && !p[i]) || ((uintptr_t)p[i] & 15) != 0) return false;
   return true;
+}
+// What the two backward entry points check alike before anything is dereferenced: both images, the rows a call needs (req) and may leave out (opt), and the grads
+// array, which may be null and else holds n_want pointers, each null or aligned
+int sct_bwd_args_status(const void* packed, const void* train_packed, const void* const* req, int nreq, const void* const* opt, int nopt, float* const* grads,
+                        int n_grads, int n_want) {
+  if (!packed || !train_packed || (((uintptr_t)packed | (uintptr_t)train_packed) & 15) != 0) return NL_ERR_BAD_ARG;
+  if (!sct_all16(req, nreq, true) || !sct_all16(opt, nopt, false)) return NL_ERR_BAD_ARG;
+  if (grads && (n_grads != n_want || !sct_all16((const void* const*)grads, n_want, false))) return NL_ERR_BAD_ARG;
+  return NL_OK;
+}
+// ... and clear alike.  gp[i]: the requested gradient of tensor i of layers [l0, l1), counted from the first of them — null where it is not asked for and for a
+// decoder layer's norm1, which is never applied; any[l]: layer l has one.  Those and the four input-gradient targets (tgt[0], tgt[1]: b0 bytes; tgt[2], tgt[3]:
+// b1 bytes) are zeroed.
+int sct_bwd_zero(float* const* grads, int l0, int l1, int C, int F, float** gp, bool* any, float* const (&tgt)[4], size_t b0, size_t b1, hipStream_t st) {
+  for (int l = l0; l < l1; ++l) {
+    any[l] = false;
+    for (int k = 0; k < sct_param_count(l); ++k) {
+      const int i = sct_param_first(l) - sct_param_first(l0) + k;
+      gp[i] = grads && sct_param_applied(l, k) ? grads[i] : nullptr;
+      if (gp[i]) {
+        any[l] = true;
+        NL_CHECK_HIP(hipMemsetAsync(gp[i], 0, sct_param_floats(k, C, F) * 4, st));
+      }
+    }
+  }
+  for (int i = 0; i < 4; ++i)
+    if (tgt[i]) NL_CHECK_HIP(hipMemsetAsync(tgt[i], 0, i < 2 ? b0 : b1, st));
+  return NL_OK;
 }
 
 // ---- the keep mask of one site, one byte per element, by the kernels' own function (nl_sct_dropout_mask).  site 0: out[(b * 8 + h) * Nq + q][k], n = Nk;
@@ -1048,9 +868,8 @@ int nl_sct_pack_weights_train(int C, int nhead, int F, const float* const* tenso
   hipStream_t st = (hipStream_t)stream;
   unsigned char* img = (unsigned char*)packed;
   float* stage = (float*)(img + L.stage);
-  const int base[SCT_LAYERS] = {0, 12, 24, 38};
   for (int l = 0; l < SCT_LAYERS; ++l) {
-    const float* const* t = tensors + base[l];
+    const float* const* t = tensors + sct_param_first(l);
     // source (rows x cols, torch layout) of the six transposes: the three blocks of in_proj_weight, out_proj, linear1, linear2
     const float* src[6] = {t[0], t[0] + (size_t)C * C, t[0] + (size_t)2 * C * C, t[2], t[4], t[6]};
     const int rows[6] = {C, C, C, C, F, C}, cols[6] = {C, C, C, C, C, F};
@@ -1097,17 +916,11 @@ static int sct_backward_impl(const void* packed, const void* train_packed, int C
                              const float* g_out1, float* g_v0, float* g_pos0, float* g_v1, float* g_pos1, float* const* grads, int n_grads, void* ws, size_t ws_bytes,
                              float p, unsigned long long seed, void* stream) {
   bool empty;
-  if (const int s = sct_shape_check(C, nhead, F, precision, B, N0, N1, &empty)) return s;
+  if (const int s = sct_shape_status(C, nhead, F, precision, B, N0, N1, &empty)) return s;
   if (empty) return NL_OK;
-  if (!packed || !train_packed || (((uintptr_t)packed | (uintptr_t)train_packed) & 15) != 0) return NL_ERR_BAD_ARG;
   const void* in[4] = {v0, pos0, v1, pos1};
   const void* opt[6] = {g_out0, g_out1, g_v0, g_pos0, g_v1, g_pos1};
-  if (!sct_all16(in, 4, true) || !sct_all16(opt, 6, false)) return NL_ERR_BAD_ARG;
-  if (grads) {
-    if (n_grads != SCT_TENSORS) return NL_ERR_BAD_ARG;
-    for (int i = 0; i < SCT_TENSORS; ++i)
-      if (((uintptr_t)grads[i] & 15) != 0) return NL_ERR_BAD_ARG;
-  }
+  if (const int s = sct_bwd_args_status(packed, train_packed, in, 4, opt, 6, grads, n_grads, SCT_TENSORS)) return s;
   if (!state || ((uintptr_t)state & 255) != 0 || state_bytes < nl_sct_train_state_bytes(B, N0, N1, C, F)) return NL_ERR_WORKSPACE;
   if (!ws || ((uintptr_t)ws & 255) != 0 || ws_bytes < nl_sct_backward_workspace_bytes(B, N0, N1, C, F)) return NL_ERR_WORKSPACE;
   if (!sct_drop_p_ok(p)) return NL_ERR_BAD_ARG;
@@ -1120,21 +933,8 @@ static int sct_backward_impl(const void* packed, const void* train_packed, int C
   const size_t b0 = (size_t)B * N0 * C * 4, b1 = (size_t)B * N1 * C * 4;
 
   float* gp[SCT_TENSORS];
-  bool anyp[SCT_LAYERS] = {false, false, false, false};
-  const int base[SCT_LAYERS + 1] = {0, 12, 24, 38, 52};
-  for (int l = 0; l < SCT_LAYERS; ++l)
-    for (int i = base[l]; i < base[l + 1]; ++i) {
-      gp[i] = grads ? grads[i] : nullptr;
-      if (l >= 2 && (i - base[l] == 8 || i - base[l] == 9)) gp[i] = nullptr;   // the cross layers' norm1 is never applied
-      if (gp[i]) {
-        anyp[l] = true;
-        NL_CHECK_HIP(hipMemsetAsync(gp[i], 0, sct_tensor_floats(i, C, F) * 4, st));
-      }
-    }
-  if (g_v0) NL_CHECK_HIP(hipMemsetAsync(g_v0, 0, b0, st));
-  if (g_pos0) NL_CHECK_HIP(hipMemsetAsync(g_pos0, 0, b0, st));
-  if (g_v1) NL_CHECK_HIP(hipMemsetAsync(g_v1, 0, b1, st));
-  if (g_pos1) NL_CHECK_HIP(hipMemsetAsync(g_pos1, 0, b1, st));
+  bool anyp[SCT_LAYERS];
+  if (const int s = sct_bwd_zero(grads, 0, SCT_LAYERS, C, F, gp, anyp, {g_v0, g_pos0, g_v1, g_pos1}, b0, b1, st)) return s;
   if (!g_out0 && !g_out1) return NL_OK;   // zero cotangents: every gradient is zero
 
   // which layers anything asked for depends on; a layer's gradient towards a side nobody needs is not formed
@@ -1149,16 +949,16 @@ static int sct_backward_impl(const void* packed, const void* train_packed, int C
   }
   if (run3) {
     const SctLayerBwd r{img, timg, C, F, 3, k[1].out, pos1, k[2].out, pos0, N1, N0, B, k[3], g_out1, need1 ? w.G[1] : nullptr, g_pos1, need2 ? w.G[2] : nullptr, g_pos0,
-                        gp + 38, p, seed};
+                        gp + sct_param_first(3), p, seed};
     if (const int s = sct_bwd(r, precision, w, st)) return s;
   }
   if (need2) {
     const SctLayerBwd r{img, timg, C, F, 2, k[0].out, pos0, k[1].out, pos1, N0, N1, B, k[2], w.G[2], need0 ? w.G[0] : nullptr, g_pos0, need1 ? w.G[1] : nullptr, g_pos1,
-                        gp + 24, p, seed};
+                        gp + sct_param_first(2), p, seed};
     if (const int s = sct_bwd(r, precision, w, st)) return s;
   }
   if (need1) {
-    const SctLayerBwd r{img, timg, C, F, 1, v1, pos1, v1, pos1, N1, N1, B, k[1], w.G[1], g_v1, g_pos1, nullptr, nullptr, gp + 12, p, seed};
+    const SctLayerBwd r{img, timg, C, F, 1, v1, pos1, v1, pos1, N1, N1, B, k[1], w.G[1], g_v1, g_pos1, nullptr, nullptr, gp + sct_param_first(1), p, seed};
     if (const int s = sct_bwd(r, precision, w, st)) return s;
   }
   if (need0) {
@@ -1193,18 +993,11 @@ static int sct_layer_backward_impl(const void* packed, const void* train_packed,
     mem = x; mem_pos = x_pos;
   }
   bool empty;
-  if (const int s = sct_shape_check(C, nhead, F, precision, B, Nq, Nk, &empty)) return s;
+  if (const int s = sct_shape_status(C, nhead, F, precision, B, Nq, Nk, &empty)) return s;
   if (empty) return NL_OK;
-  if (!packed || !train_packed || (((uintptr_t)packed | (uintptr_t)train_packed) & 15) != 0) return NL_ERR_BAD_ARG;
   const void* in[5] = {x, x_pos, mem, mem_pos, g_out};
   const void* opt[4] = {g_x, g_x_pos, g_mem, g_mem_pos};
-  if (!sct_all16(in, 5, true) || !sct_all16(opt, 4, false)) return NL_ERR_BAD_ARG;
-  const int np = cross ? 14 : 12;
-  if (grads) {
-    if (n_grads != np) return NL_ERR_BAD_ARG;
-    for (int i = 0; i < np; ++i)
-      if (((uintptr_t)grads[i] & 15) != 0) return NL_ERR_BAD_ARG;
-  }
+  if (const int s = sct_bwd_args_status(packed, train_packed, in, 5, opt, 4, grads, n_grads, sct_param_count(layer))) return s;
   if (!ws || ((uintptr_t)ws & 255) != 0 || ws_bytes < nl_sct_layer_backward_workspace_bytes(B, Nq, Nk, C, F)) return NL_ERR_WORKSPACE;
   if (!sct_drop_p_ok(p)) return NL_ERR_BAD_ARG;
   hipStream_t st = (hipStream_t)stream;
@@ -1215,17 +1008,8 @@ static int sct_layer_backward_impl(const void* packed, const void* train_packed,
   const SctLayerFwd f{img, C, F, layer, precision, x, x_pos, mem, mem_pos, Nq, Nk, B, w.lout, k, false, p, seed};
   if (const int s = sct_fwd_train(f, st)) return s;
   float* gp[14];
-  const int base[SCT_LAYERS] = {0, 12, 24, 38};
-  for (int i = 0; i < np; ++i) {
-    gp[i] = grads ? grads[i] : nullptr;
-    if (cross && (i == 8 || i == 9)) gp[i] = nullptr;
-    if (gp[i]) NL_CHECK_HIP(hipMemsetAsync(gp[i], 0, sct_tensor_floats(base[layer] + i, C, F) * 4, st));
-  }
-  const size_t bq = (size_t)B * Nq * C * 4, bk = (size_t)B * Nk * C * 4;
-  if (g_x) NL_CHECK_HIP(hipMemsetAsync(g_x, 0, bq, st));
-  if (g_x_pos) NL_CHECK_HIP(hipMemsetAsync(g_x_pos, 0, bq, st));
-  if (g_mem) NL_CHECK_HIP(hipMemsetAsync(g_mem, 0, bk, st));
-  if (g_mem_pos) NL_CHECK_HIP(hipMemsetAsync(g_mem_pos, 0, bk, st));
+  bool anyp[SCT_LAYERS];
+  if (const int s = sct_bwd_zero(grads, layer, layer + 1, C, F, gp, anyp, {g_x, g_x_pos, g_mem, g_mem_pos}, (size_t)B * Nq * C * 4, (size_t)B * Nk * C * 4, st)) return s;
   const SctLayerBwd r{img, (const unsigned char*)train_packed, C, F, layer, x, x_pos, mem, mem_pos, Nq, Nk, B, k, g_out, g_x, g_x_pos, g_mem, g_mem_pos, gp, p, seed};
   return sct_bwd(r, precision, w, st);
 }
@@ -1244,8 +1028,8 @@ int nl_sct_layer_backward_dropout(const void* packed, const void* train_packed, 
 }
 
 int nl_sct_dropout_mask(uint64_t seed, float p, int layer, int site, int64_t B, int64_t Nq, int64_t n, uint8_t* out, void* stream) {
-  if (layer < 0 || layer >= SCT_LAYERS || site < 0 || site > 3 || B < 0 || Nq < 1 || n < 1 || !sct_drop_p_ok(p)) return NL_ERR_BAD_ARG;
-  if (B > SCT_MAX_ROWS || Nq > SCT_MAX_ROWS || n > SCT_MAX_ROWS || B * Nq > SCT_MAX_ROWS) return NL_ERR_UNSUPPORTED;
+  if (layer < 0 || layer >= SCT_LAYERS || site < 0 || site > 3 || !sct_counts_ok(B, Nq, n) || !sct_drop_p_ok(p)) return NL_ERR_BAD_ARG;
+  if (!sct_counts_fit(B, Nq, n, Nq)) return NL_ERR_UNSUPPORTED;
   const long long rows = (site == 0 ? 8 : 1) * B * Nq;
   if ((double)rows * (double)n > 2147483647.0 * 256.0) return NL_ERR_UNSUPPORTED;   // one thread per element, a 32-bit grid
   if (B == 0) return NL_OK;

@@ -1,5 +1,5 @@
 // The dropout masks of the SelfCrossTransformer training step (sct.hip's dropping attention, sct_bwd.hip): ONE definition, used by every kernel that drops and by
-// nl_sct_dropout_mask; tests/sct_dropout_ref.py restates it in numpy bit for bit.  Include after sct.h.
+// nl_sct_dropout_mask; tests/sct_dropout_ref.py restates it in numpy bit for bit.  Needs common.h alone; sct.h includes it.
 //
 // Generator: Philox4x32-10 (Salmon, Moraes, Dror, Shaw: "Parallel random numbers: as easy as 1, 2, 3", SC'11) with its published constants; key = the 64-bit seed
 // (low word, high word).  One call gives four 32-bit words = eight 16-bit fields = a block of 4 x 2 elements:
@@ -15,7 +15,8 @@
 // per 32 x 32 tile and wave in both orientations = two per lane.
 #pragma once
 #include <cmath>
-#include "sct.h"
+#include <type_traits>
+#include "common.h"
 
 namespace {
 
@@ -99,10 +100,16 @@ __device__ __forceinline__ unsigned sct_drop_bits_minor(const SctDrop& d, int si
   auto take = [q](unsigned v) { return ((v >> (2 * q)) & 3u) | ((v >> (8 + 2 * q)) & 3u) << 2; };
   return take(s0) | take(s1) << 4 | take(s2) << 8 | take(s3) << 12;
 }
-// A kernel that has a dropping variant takes a trailing parameter pack: empty (the kernel as it was, with the same signature and device code) or one SctDrop
-struct SctNoDrop {};
-__device__ __forceinline__ SctNoDrop sct_drop_of() { return SctNoDrop{}; }
-__device__ __forceinline__ const SctDrop& sct_drop_of(const SctDrop& d) { return d; }
+// A kernel that has variants takes a trailing parameter pack: empty (the kernel as it was, with the same signature and device code), or the variants' argument
+// structs — one SctDrop where it drops.  sct_arg<T>(pack...) is the pack's T, or an SctNone where it holds none.
+struct SctNone {};
+template <class T>
+__device__ __forceinline__ SctNone sct_arg() { return SctNone{}; }
+template <class T, class A, class... R>
+__device__ __forceinline__ auto sct_arg(const A& a, const R&... r) {
+  if constexpr (std::is_same_v<T, A>) return a;
+  else return sct_arg<T>(r...);
+}
 __device__ __forceinline__ float sct_drop_apply(const SctDrop& d, unsigned bits, int r, float v) { return (bits >> r) & 1u ? v * d.scale : 0.f; }
 
 }  // namespace
