@@ -8,24 +8,29 @@
 //
 // Structure (per frame): points are counting-sorted by the 18-bit Morton code of their cell in a fixed 64^3 grid
 // over the cloud's bounding box, so an octree node of ANY level l (side 2^l fine cells, Morton prefix m) is the
-// contiguous range [starts[m << 3l], starts[(m+1) << 3l]) of the sorted array — no explicit tree is stored.
+// contiguous range [starts[m << 3l], starts[(m+1) << 3l]) of the sorted array.  Every node of every level has a 32-byte record
+// (knn_nodes.h) with that range and the exact bounding box of the points in it, built bottom-up with the grid: the search tests a
+// node with one record fetch and prunes by the box of its points, not by its cell (the cloud is surface-like: a sparse node's
+// points fill a small part of its cell, and most queries lie in empty space).
 // Search (one wave64 per query, wave-uniform control flow):
 //   phase 1  greedy descent: at every level the 8 children are tested by 8 lanes and the nearest child that still
 //            holds >= K points is entered; the node where this stops (<= 8(K-1) points unless a fine cell is
 //            dense) is scanned, giving an upper bound U on the K-th neighbour's dist2.
 //   phase 2  breadth-first descent from the root, 8 nodes x 8 children per step, keeping children with points and
-//            mindist2(q, child box) <= U (boxes widened by a rounding slack); nodes with <= 16 points become leaves
-//            and are scanned four at a time (one per 16-lane slot); the K best keys are wave-uniform (SGPRs) and are
+//            mindist2(q, box of the child's points) <= U; nodes with <= 8 points become leaves
+//            and are scanned eight at a time (one per 8-lane slot); the K best keys are wave-uniform (SGPRs) and are
 //            updated by a selection loop built on DPP wave-min reductions; U tightens as soon as K real candidates
 //            are known.
 // The kernel is VALU-issue bound (not memory bound): the design goal is few vector instructions per query.
 #include "common.h"
+#include "knn_nodes.h"
 
 namespace {
 
 constexpr int GRID_BITS = 6;
 constexpr int GRID_N = 1 << GRID_BITS;              // 64 cells per axis
 constexpr int GRID_CELLS = GRID_N * GRID_N * GRID_N;  // 262144
+static_assert(NL_KNN_DEPTH == GRID_BITS, "knn_nodes.h: the fine cells are the deepest nodes");
 
 __device__ __forceinline__ unsigned part1by2(unsigned x) {
   x &= 0x3ffu;
@@ -129,6 +134,21 @@ __global__ void knn_scatter_kernel(const float* __restrict__ xyz, int M, const i
   sorted[pos] = make_float4(xyz[3 * (size_t)i], xyz[3 * (size_t)i + 1], xyz[3 * (size_t)i + 2], __int_as_float(i));
 }
 
+// per-node records (knn_nodes.h), bottom-up: the fine cells from the sorted points ...
+__global__ void knn_nodes_leaf_kernel(const int* __restrict__ starts, const float4* __restrict__ sorted, NlKnnNode* __restrict__ nodes) {
+  const int cell = blockIdx.x * blockDim.x + threadIdx.x;
+  if (cell < GRID_CELLS) nl_knn_node_from_points(nodes, starts, (const float*)sorted, cell);
+}
+// ... then the depths d_hi down to d_lo from their children.  Several depths in one launch only with ONE workgroup (the barrier orders its own stores and loads):
+// the 585 nodes of depths 3 .. 0
+__global__ void knn_nodes_up_kernel(NlKnnNode* nodes, int d_hi, int d_lo) {
+  for (int d = d_hi; d >= d_lo; --d) {
+    const int n = 1 << (3 * d);
+    for (int m = blockIdx.x * blockDim.x + threadIdx.x; m < n; m += gridDim.x * blockDim.x) nl_knn_node_from_children(nodes, nl_knn_node_base(d) + m);
+    if (d > d_lo) __syncthreads();
+  }
+}
+
 typedef unsigned long long u64;
 
 // ---- wave-uniform primitives -------------------------------------------------------------------------------------
@@ -217,18 +237,18 @@ __device__ __forceinline__ void select_into(BestK<K>& best, unsigned kd, unsigne
 }
 
 struct QueryCtx {
-  float qx, qy, qz, org0, org1, org2, cell, slack;
+  float qx, qy, qz, org0, org1, org2, slack;
 };
 
-// squared distance from the query to the (slack-widened) box of the level-L node with integer cell coordinates (cx, cy, cz);
-// the search carries node coordinates next to the Morton code, so no code is ever decoded
-__device__ __forceinline__ float node_mindist2(const QueryCtx& c, unsigned cx, unsigned cy, unsigned cz, int L) {
-  const float cl = c.cell * (float)(1 << L);
-  const float x0 = c.org0 + (float)cx * cl, y0 = c.org1 + (float)cy * cl, z0 = c.org2 + (float)cz * cl;
-  const float dx = fmaxf(fmaxf(x0 - c.qx, c.qx - (x0 + cl)) - c.slack, 0.f);
-  const float dy = fmaxf(fmaxf(y0 - c.qy, c.qy - (y0 + cl)) - c.slack, 0.f);
-  const float dz = fmaxf(fmaxf(z0 - c.qz, c.qz - (z0 + cl)) - c.slack, 0.f);
-  return dx * dx + dy * dy + dz * dz;
+// squared distance from the query to the bounding box of a node's points (knn_nodes.h), a lower bound of the dist2 of every point of the node AS COMPUTED by
+// candidate(): the same three differences, squares and sums in the same order without contraction, and every one of these roundings is monotone — for a point p
+// of the node |fl(q - p)| >= fl(distance to the box) per axis, so the bound holds term by term.  (Boxes of real points need no cell slack; the callers keep the
+// multiplicative margin on U all the same.)  An empty node's box (+-3.4e38) gives +inf.
+__device__ __forceinline__ float node_mindist2(const QueryCtx& c, const NlKnnNode& r) {
+  const float dx = fmaxf(fmaxf(r.mnx - c.qx, c.qx - r.mxx), 0.f);
+  const float dy = fmaxf(fmaxf(r.mny - c.qy, c.qy - r.mxy), 0.f);
+  const float dz = fmaxf(fmaxf(r.mnz - c.qz, c.qz - r.mxz), 0.f);
+  return __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
 }
 
 // candidate key of sorted[pos] for this lane (valid lanes only), with phase-1 survivors filtered out (DEDUPE: phase 2
@@ -270,16 +290,18 @@ __device__ __forceinline__ void scan_range(const QueryCtx& c, const float4* __re
 }
 
 // frontier entries per wave (nodes kept as leaves beyond that).  256 -> 128 in round 5: 15 KB of LDS per workgroup instead of 23.5 = 8 waves per SIMD
-// instead of 6: 0.80 -> 0.70 ms at config 2; a fuller frontier spills into coarse leaves, exact either way
+// instead of 6: 0.80 -> 0.70 ms at config 2; a fuller frontier spills into coarse leaves, exact either way.  (11 KB since the frontier holds node indices only.)
+// Re-measured with the node records (half the leaves per query): LEAF_COUNT_MAX 16 / 4 and a flush threshold of 16 / 64 / 120 are flat or slower
+// (profiles/knn_nodes_tuning.txt).
 constexpr int FRONT_CAP = 128;
 constexpr int LEAF_CAP = 128;
 constexpr int LEAF_COUNT_MAX = 8;   // nodes with <= this many points are scanned instead of expanded; also the slot width
 
 template <int K, int SPW>
 __global__ __launch_bounds__(256) void knn_wave_kernel(const float* __restrict__ q, int N, const NlGridParams* __restrict__ gpp,
-                                                       const int* __restrict__ starts, const float4* __restrict__ sorted,
+                                                       const NlKnnNode* __restrict__ nodes, const float4* __restrict__ sorted,
                                                        int Kout, int* __restrict__ idx_out, float* __restrict__ d2_out) {
-  __shared__ unsigned s_front[4][2][FRONT_CAP], s_fxyz[4][2][FRONT_CAP];   // Morton prefix; cell coordinates x | y << 10 | z << 20
+  __shared__ unsigned s_front[4][2][FRONT_CAP];   // node indices (knn_nodes.h: a child's index follows from its parent's)
   __shared__ int s_leaf_s[4][LEAF_CAP], s_leaf_l[4][LEAF_CAP];
   __shared__ u64 s_ckey[4][64];        // deferred selection: the keys within the bound, in arrival order ...
   __shared__ unsigned s_cpos[4][64];   // ... and their positions in the sorted array
@@ -287,7 +309,7 @@ __global__ __launch_bounds__(256) void knn_wave_kernel(const float* __restrict__
   const int n0 = __builtin_amdgcn_readfirstlane((nl_xcd_block() * 4 + wv) * SPW);
   QueryCtx c;
   c.org0 = gpp->origin[0]; c.org1 = gpp->origin[1]; c.org2 = gpp->origin[2];
-  c.cell = gpp->cell; c.slack = 1e-3f * c.cell;
+  c.slack = 1e-3f * gpp->cell;
   const float inv_cell = gpp->inv_cell;
   bool prev_full = false;   // the previous query of this wave found K neighbours, whose sorted-array positions are
   unsigned ppos = 0;        // in ppos of the lanes with pkeep set (lane k < K after a selection-loop query; the lanes that held them after a deferred one)
@@ -343,26 +365,18 @@ __global__ __launch_bounds__(256) void knn_wave_kernel(const float* __restrict__
   };
   if (!prev_full) {
     // -------------------------------------------------------------- phase 1: greedy descent -> upper bound U
-    unsigned m = 0, mx = 0, my = 0, mz = 0;   // Morton prefix and cell coordinates of the node being descended (wave-uniform)
-    int L = GRID_BITS;
-    while (L > 0) {
+    unsigned node = 0;   // the node being descended (wave-uniform)
+    for (int L = GRID_BITS; L > 0; --L) {
       unsigned key = 0xffffffffu;
       if (lane < 8) {
-        const unsigned mc = (m << 3) | (unsigned)lane;
-        const int sh = 3 * (L - 1);
-        const int cnt = starts[(mc + 1) << sh] - starts[mc << sh];
-        if (cnt >= K)
-          key = (__float_as_uint(node_mindist2(c, 2 * mx + (lane & 1), 2 * my + ((lane >> 1) & 1), 2 * mz + ((lane >> 2) & 1), L - 1)) & ~7u) | (unsigned)lane;
+        const NlKnnNode r = nodes[8u * node + 1u + (unsigned)lane];
+        if (r.count >= K) key = (__float_as_uint(node_mindist2(c, r)) & ~7u) | (unsigned)lane;
       }
       key = wave_umin(key);
       if (key == 0xffffffffu) break;
-      const unsigned ch = key & 7u;
-      m = (m << 3) | ch;
-      mx = 2 * mx + (ch & 1); my = 2 * my + ((ch >> 1) & 1); mz = 2 * mz + ((ch >> 2) & 1);
-      --L;
+      node = 8u * node + 1u + (key & 7u);
     }
-    const int rs0 = starts[m << (3 * L)], len0 = starts[(m + 1) << (3 * L)] - rs0;
-    scan_range<K, false>(c, sorted, rs0, len0, lane, best, sink);
+    scan_range<K, false>(c, sorted, nodes[node].start, nodes[node].count, lane, best, sink);
     U = best.full() ? __uint_as_float(best.td) : 3.4e38f;
   } else {
     // upper bound from the previous query's neighbours (lane k < K re-measures its k-th one): the largest of their K
@@ -379,8 +393,6 @@ __global__ __launch_bounds__(256) void knn_wave_kernel(const float* __restrict__
   // ---------------------------------------------------------------- phase 2: pruned breadth-first descent
   unsigned* front = s_front[wv][0];
   unsigned* nextf = s_front[wv][1];
-  unsigned* fxyz = s_fxyz[wv][0];
-  unsigned* nextx = s_fxyz[wv][1];
   int* leaf_s = s_leaf_s[wv];
   int* leaf_l = s_leaf_l[wv];
   int nfront = 1, nleaf = 0;
@@ -401,14 +413,14 @@ __global__ __launch_bounds__(256) void knn_wave_kernel(const float* __restrict__
       const unsigned nx = (unsigned)(lo0 >> Ls) + (lane & 1), ny = (unsigned)(lo1 >> Ls) + ((lane >> 1) & 1), nz = (unsigned)(lo2 >> Ls) + ((lane >> 2) & 1);
       const bool ok = lane < 8 && nx <= (unsigned)(hi0 >> Ls) && ny <= (unsigned)(hi1 >> Ls) && nz <= (unsigned)(hi2 >> Ls);
       const u64 mk = __ballot(ok);
-      if (ok) { const int pos = __popcll(mk & lt_mask); front[pos] = morton3(nx, ny, nz); fxyz[pos] = nx | (ny << 10) | (nz << 20); }
+      if (ok) front[__popcll(mk & lt_mask)] = (unsigned)nl_knn_node_base(GRID_BITS - Ls) + morton3(nx, ny, nz);
       nfront = __popcll(mk);
     }
   }
-  if (Lstart == GRID_BITS && lane == 0) { front[0] = 0u; fxyz[0] = 0u; }
+  if (Lstart == GRID_BITS && lane == 0) front[0] = 0u;
   KNN_CNT(4, Lstart); KNN_CNT(5, prev_full ? 0 : 1); KNN_CNT(6 + Lstart, 1);
 
-  // leaves hold <= 16 points each: four leaves per 64-lane batch, one per 16-lane slot (no prefix sums, no index search)
+  // leaves hold <= LEAF_COUNT_MAX points each: eight leaves per 64-lane batch, one per 8-lane slot (no prefix sums, no index search)
   auto flush_leaves = [&]() {
     constexpr int SL = LEAF_COUNT_MAX;   // lanes per slot
     for (int b = 0; b < nleaf; b += 64 / SL) {
@@ -426,21 +438,18 @@ __global__ __launch_bounds__(256) void knn_wave_kernel(const float* __restrict__
 
   for (int L = Lstart; L > 0; --L) {
     int nnext = 0;
-    const int sh = 3 * (L - 1);
     for (int base = 0; base < nfront; base += 8) {
       KNN_CNT(0, 1);
       const int ni = base + (lane >> 3);
       bool keep = false, leaf = false;
-      unsigned mc = 0, cxyz = 0;
+      unsigned mc = 0;
       int rs = 0, cnt = 0;
       if (ni < nfront) {
-        mc = (front[ni] << 3) | (unsigned)(lane & 7);
-        const unsigned pxyz = fxyz[ni];
-        const unsigned cx = 2 * (pxyz & 1023u) + (lane & 1), cy = 2 * ((pxyz >> 10) & 1023u) + ((lane >> 1) & 1), cz = 2 * (pxyz >> 20) + ((lane >> 2) & 1);
-        cxyz = cx | (cy << 10) | (cz << 20);
-        rs = starts[mc << sh];
-        cnt = starts[(mc + 1) << sh] - rs;
-        keep = cnt > 0 && node_mindist2(c, cx, cy, cz, L - 1) <= U * 1.000001f;   // '<=' keeps exact ties; margin covers fp32 rounding
+        mc = 8u * front[ni] + 1u + (unsigned)(lane & 7);
+        const NlKnnNode r = nodes[mc];   // one record: the range and the box of the child's points
+        rs = r.start;
+        cnt = r.count;
+        keep = cnt > 0 && node_mindist2(c, r) <= U * 1.000001f;   // '<=' keeps exact ties; margin covers fp32 rounding
         leaf = keep && (L - 1 == 0 || cnt <= LEAF_COUNT_MAX);
       }
       const bool inner = keep && !leaf;
@@ -450,7 +459,7 @@ __global__ __launch_bounds__(256) void knn_wave_kernel(const float* __restrict__
       const int room = FRONT_CAP - nnext;
       const int pi = __popcll(mi & lt_mask);
       const bool spill = inner && pi >= room;
-      if (inner && !spill) { nextf[nnext + pi] = mc; nextx[nnext + pi] = cxyz; }
+      if (inner && !spill) nextf[nnext + pi] = mc;
       nnext += ci < room ? ci : room;
       // ranges wider than a slot (dense fine cells, spilled inner nodes) are rare: scanned right away, one by one
       const bool lf = leaf || spill;
@@ -464,13 +473,13 @@ __global__ __launch_bounds__(256) void knn_wave_kernel(const float* __restrict__
       const bool small = lf && cnt <= LEAF_COUNT_MAX;
       const u64 ml = __ballot(small);
       const int cl_ = __popcll(ml);
+      KNN_CNT(13, cl_);
       if (nleaf + cl_ > LEAF_CAP) flush_leaves();
       if (small) { const int p = nleaf + __popcll(ml & lt_mask); leaf_s[p] = rs; leaf_l[p] = cnt; }
       nleaf += cl_;
       if (nleaf >= 32) flush_leaves();
     }
     unsigned* t = front; front = nextf; nextf = t;
-    t = fxyz; fxyz = nextx; nextx = t;
     nfront = nnext;
     if (nfront == 0) break;
   }
@@ -518,6 +527,7 @@ size_t nl_knn_grid_bytes(int64_t M) {
   b += 2 * nl_align_up(sizeof(int) * GRID_CELLS, 256);
   b += nl_align_up(sizeof(int) * (size_t)(M > 0 ? M : 1), 256);
   b += nl_align_up(sizeof(float4) * (size_t)(M > 0 ? M : 1), 256);
+  b += nl_align_up(sizeof(NlKnnNode) * (size_t)NL_KNN_NODES, 256);
   return b;
 }
 
@@ -528,7 +538,8 @@ int nl_knn_grid_build(NlKnnGrid* g, void* mem, const float* xyz, int64_t M, hipS
   g->counts = (int*)p; p += nl_align_up(sizeof(int) * GRID_CELLS, 256);
   g->cursor = (int*)p; p += nl_align_up(sizeof(int) * GRID_CELLS, 256);
   g->cell_of = (int*)p; p += nl_align_up(sizeof(int) * (size_t)(M > 0 ? M : 1), 256);
-  g->sorted = (float4*)p;
+  g->sorted = (float4*)p; p += nl_align_up(sizeof(float4) * (size_t)(M > 0 ? M : 1), 256);
+  g->nodes = (NlKnnNode*)p;
   g->M = (int)M;
   if (M <= 0) return NL_OK;
   NL_CHECK_HIP(hipMemsetAsync(g->counts, 0, sizeof(int) * GRID_CELLS, st));
@@ -537,6 +548,11 @@ int nl_knn_grid_build(NlKnnGrid* g, void* mem, const float* xyz, int64_t M, hipS
   hipLaunchKernelGGL(knn_count_kernel, dim3(nb), dim3(256), 0, st, xyz, (int)M, g->params, g->counts, g->cell_of);
   hipLaunchKernelGGL(knn_scan_kernel, dim3(1), dim3(1024), 0, st, g->counts, g->starts, g->cursor);
   hipLaunchKernelGGL(knn_scatter_kernel, dim3(nb), dim3(256), 0, st, xyz, (int)M, g->cell_of, g->cursor, g->sorted);
+  // node records, bottom-up: 64^3 fine cells, 32^3 and 16^3 nodes as grids, the 585 nodes above in one workgroup
+  hipLaunchKernelGGL(knn_nodes_leaf_kernel, dim3(GRID_CELLS / 256), dim3(256), 0, st, g->starts, g->sorted, g->nodes);
+  hipLaunchKernelGGL(knn_nodes_up_kernel, dim3((1 << 15) / 256), dim3(256), 0, st, g->nodes, 5, 5);
+  hipLaunchKernelGGL(knn_nodes_up_kernel, dim3((1 << 12) / 256), dim3(256), 0, st, g->nodes, 4, 4);
+  hipLaunchKernelGGL(knn_nodes_up_kernel, dim3(1), dim3(512), 0, st, g->nodes, 3, 0);
   NL_LAUNCH_CHECK();
   return NL_OK;
 }
@@ -555,7 +571,7 @@ int nl_knn_search(const NlKnnGrid* g, const float* xyz, int64_t N, int K, int* i
   const bool big = N >= (1 << 18);
   const int spw = big ? 16 : spw_small;
   dim3 grid(nl_xcd_grid(nl_cdiv(N, 4 * spw)));
-#define NL_KNN(KK, SPW) hipLaunchKernelGGL((knn_wave_kernel<KK, SPW>), grid, dim3(256), 0, st, xyz, (int)N, g->params, g->starts, g->sorted, K, idx, d2)
+#define NL_KNN(KK, SPW) hipLaunchKernelGGL((knn_wave_kernel<KK, SPW>), grid, dim3(256), 0, st, xyz, (int)N, g->params, g->nodes, g->sorted, K, idx, d2)
   if (K == 1) { if (big) NL_KNN(1, 16); else NL_KNN(1, spw_small); }
   else { if (big) NL_KNN(8, 16); else NL_KNN(8, spw_small); }
 #undef NL_KNN
@@ -565,8 +581,8 @@ int nl_knn_search(const NlKnnGrid* g, const float* xyz, int64_t N, int K, int* i
     unsigned long long h[16];
     hipStreamSynchronize(st);
     hipMemcpyFromSymbol(h, HIP_SYMBOL(knn_stats), sizeof(h));
-    fprintf(stderr, "knn stats per query (N = %lld): frontier batches %.2f, leaf batches %.2f, selection iterations %.2f, range batches %.2f, start level %.2f, phase-1 %.3f; start-level histogram",
-            (long long)N, (double)h[0] / N, (double)h[1] / N, (double)h[2] / N, (double)h[3] / N, (double)h[4] / N, (double)h[5] / N);
+    fprintf(stderr, "knn stats per query (N = %lld): frontier batches %.2f, leaf batches %.2f, selection iterations %.2f, range batches %.2f, start level %.2f, phase-1 %.3f, leaves %.2f; start-level histogram",
+            (long long)N, (double)h[0] / N, (double)h[1] / N, (double)h[2] / N, (double)h[3] / N, (double)h[4] / N, (double)h[5] / N, (double)h[13] / N);
     for (int l = 0; l <= GRID_BITS; ++l) fprintf(stderr, " %d:%.3f", l, (double)h[6 + l] / N);
     fprintf(stderr, "\n");
     hipMemset(nullptr, 0, 0);

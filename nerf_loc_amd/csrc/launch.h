@@ -47,6 +47,7 @@ struct NlKnnGrid {
   int* cursor;           // device [GRID_CELLS]
   int* cell_of;          // device [M]
   float4* sorted;        // device [M]
+  struct NlKnnNode* nodes;   // device [NL_KNN_NODES]: per-node range and bounding box of its points (knn_nodes.h)
   int M;
 };
 size_t nl_knn_grid_bytes(int64_t M);
