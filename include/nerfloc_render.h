@@ -50,7 +50,8 @@ extern "C" {
                             * 11: nl_s2d_*_train (the coarse matcher's training step);
                             * 12: nl_fine_*_backward, nl_fine_pack_proj_train (the fine matcher's training step);
                             * 13: nl_sct_*_train, nl_sct_backward, nl_sct_layer_backward (the SelfCrossTransformer's training step); added within 13, with
-                            * nothing else changed: nl_sct_*_dropout, nl_sct_dropout_mask (that step with dropout inside the kernels) */
+                            * nothing else changed: nl_sct_*_dropout, nl_sct_dropout_mask (that step with dropout inside the kernels); nl_pnp_* (the absolute
+                            * pose from the matches: P3P RANSAC + refinement) */
 #define NL_MAX_VIEWS 16
 #define NL_KNN_MAX_K 8
 
@@ -687,6 +688,51 @@ int nl_sct_layer_backward_dropout(const void* packed, const void* train_packed, 
                                   int64_t Nq, const float* mem, const float* mem_pos, int64_t Nk, int64_t B, const float* g_out, float* g_x, float* g_x_pos,
                                   float* g_mem, float* g_mem_pos, float* const* grads, int n_grads, void* ws, size_t ws_bytes, float p, uint64_t seed, void* stream);
 int nl_sct_dropout_mask(uint64_t seed, float p, int layer, int site, int64_t B, int64_t Nq, int64_t n, uint8_t* out, void* stream);
+
+/* ---- Absolute camera pose from 2D-3D matches: P3P RANSAC + refinement (an addition within ABI 13: new entry points only, nothing above changes) ----------
+ * Replaces the external CPU solver the reference hands `mkps2d` / `mkps3d` to (pycolmap.absolute_pose_estimation, nerf_pose_estimator.py:528-540, 557-583) by
+ * calls on the stream the matches were produced on: no copy to the host, no synchronisation, no allocation, and two calls give the same bits.
+ * A PROBLEM is M matches — pixels pts2d (M, 2) and world points pts3d (M, 3), fp32, DEVICE — with pinhole intrinsics (fx, fy, cx, cy), a threshold thr in pixels,
+ * H hypotheses and a 64-bit seed.  A CALL holds B problems with their matches concatenated; `offsets` (B + 1 int32, offsets[0] = 0, non-decreasing), `intrinsics`
+ * (B x 4 doubles) and `thr` (B doubles) are HOST arrays, read when the call is made (a call captured in a HIP graph replays those values; the captured graph is a
+ * plain chain of kernels).  Poses are 12 doubles, world to camera, row-major [R | t].  All arithmetic after loading the fp32 inputs is fp64.
+ * The inlier rule, everywhere: a match is an inlier of (R, t) when Z > 0 and (fx X/Z + cx - x)^2 + (fy Y/Z + cy - y)^2 <= thr^2, (X, Y, Z) = R p + t.
+ *  1. Samples.  Sample h of problem b is three distinct indices from ONE Philox4x32-10 call (the generator of the dropout masks above): counter (h, 0, b, 0x504E50),
+ *     key = seed; i0 = (w0 M) >> 32, j1 = (w1 (M - 1)) >> 32, j2 = (w2 (M - 2)) >> 32 as 64-bit products; i1 = j1 + (j1 >= i0); i2 = j2, incremented once if
+ *     >= min(i0, i1), then once more if >= max(i0, i1).  A pure function of (seed, b, h, M).  (M < 3: the three indices are -1.)
+ *  2. Minimal solver.  P3P on the three unit bearings and world points: Grunert's quartic in the ratio of two depths, solved in closed form (Ferrari; the resolvent
+ *     cubic's real root takes one Newton step), every real root with positive depths polished by ONE Newton step on the three law-of-cosines equations, the pose from
+ *     the two congruent triangles.  Up to four solutions per sample in slots [h][0 .. nsol[h]), the other slots zero; the slot order is unspecified.  nsol = 0 for a
+ *     degenerate sample (world triangle of zero area, coincident bearings), both checked; a non-finite solution is never kept.
+ *  3. Score.  A candidate's score is its integer inlier count over all M matches; an invalid slot (and a pose with a non-finite entry) scores -1.
+ *  4. Selection.  The highest count; among equals the LOWEST candidate index 4 h + slot.
+ *  5. Local optimisation.  NL_PNP_LO_ROUNDS rounds: take the inliers of the current pose, stop if there are fewer than 4, run NL_PNP_GN_ITERS Gauss-Newton
+ *     iterations on them — residuals in pixels, left perturbation R <- exp(w) R, t <- t + d, the 6 x 6 normal equations J^T J + 1e-12 I solved by Cholesky.  A failed
+ *     factorisation or a non-finite step ends the optimisation and keeps the last finite pose.
+ *  6. Result.  mask = the inlier set of the FINAL pose (one byte per match), num_inliers its size, success = num_inliers >= min_inliers (>= 4) with a finite pose.
+ *     A problem with M < 4, or without any valid candidate, is not an error: success = 0, the identity pose, an empty mask.
+ * There is no adaptive stopping: H is fixed per call (counting trials would need a synchronisation).  tests/pnp_ref.py restates all six steps in fp64 numpy.
+ * info (B x 4 int32, DEVICE): success, num_inliers, best_candidate, best_count (nl_pnp_refine: the last two are -1).
+ * Checks, before anything is dereferenced: a negative count, min_inliers < 4, a null pointer with work to do, offsets that do not start at 0 or decrease, fx / fy /
+ * thr not finite and positive (cx, cy not finite): NL_ERR_BAD_ARG; H not a multiple of 64 in 64..65536, a problem above 2^20 matches, B above 2^20, P above 2^30:
+ * NL_ERR_UNSUPPORTED; a missing, short or not 256-byte aligned workspace: NL_ERR_WORKSPACE; B == 0 (nl_pnp_score: P == 0): NL_OK, nothing launched.
+ * nl_pnp_workspace_bytes: 0 for arguments the calls refuse; linear in B; nothing is kept per match, so M_total does not enter today.
+ * nl_pnp_samples: step 1 alone, samples (B, H, 3) int32.  nl_pnp_hypotheses: steps 1 + 2, poses (B, H, 4, 12) doubles, nsol (B, H) int32, samples optional (NULL).
+ * nl_pnp_score: step 3 for ANY P poses (P, 12) against one problem; nsol (NULL, or (P / 4) int32 with P a multiple of 4) marks slot i & 3 of sample i >> 2 invalid
+ * when it is not below nsol.  nl_pnp_refine: steps 5 + 6 of one problem from pose_in.  nl_pnp_ransac: the whole; poses (B, 12), mask (offsets[B] bytes), info, and
+ * optionally the (B, 4 H) counts (NULL: not wanted). */
+#define NL_PNP_LO_ROUNDS 3
+#define NL_PNP_GN_ITERS 5
+size_t nl_pnp_workspace_bytes(int64_t M_total, int64_t B, int H);
+int nl_pnp_samples(uint64_t seed, const int32_t* offsets, int64_t B, int H, int32_t* samples, void* stream);
+int nl_pnp_hypotheses(const float* pts2d, const float* pts3d, const int32_t* offsets, const double* intrinsics, int64_t B, int H, uint64_t seed, int32_t* samples,
+                      double* poses, int32_t* nsol, void* stream);
+int nl_pnp_score(const float* pts2d, const float* pts3d, int64_t M, const double* intrinsics, double thr, const double* poses, const int32_t* nsol, int64_t P,
+                 int32_t* counts, void* stream);
+int nl_pnp_refine(const float* pts2d, const float* pts3d, int64_t M, const double* intrinsics, double thr, int min_inliers, const double* pose_in, double* pose_out,
+                  uint8_t* mask, int32_t* info, void* stream);
+int nl_pnp_ransac(const float* pts2d, const float* pts3d, const int32_t* offsets, const double* intrinsics, const double* thr, int64_t B, int H, uint64_t seed,
+                  int min_inliers, double* poses, uint8_t* mask, int32_t* info, int32_t* counts, void* ws, size_t ws_bytes, void* stream);
 
 #if defined(__GNUC__) || defined(__clang__)
 #pragma GCC visibility pop

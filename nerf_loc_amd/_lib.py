@@ -183,6 +183,12 @@ SYMBOLS = [
     ("nl_sct_layer_backward_dropout", _I, [_P, _P, _I, _I, _I, _I, _I, _P, _P, _L, _P, _P, _L, _L, _P, _P, _P, _P, _P, C.POINTER(_P), _I, _P, _Z, C.c_float,
                                        C.c_uint64, _P]),
     ("nl_sct_dropout_mask", _I, [C.c_uint64, C.c_float, _I, _I, _L, _L, _L, _P, _P]),
+    ("nl_pnp_workspace_bytes", _Z, [_L, _L, _I]),
+    ("nl_pnp_samples", _I, [C.c_uint64, _P, _L, _I, _P, _P]),
+    ("nl_pnp_hypotheses", _I, [_P, _P, _P, _P, _L, _I, C.c_uint64, _P, _P, _P, _P]),
+    ("nl_pnp_score", _I, [_P, _P, _L, _P, C.c_double, _P, _P, _L, _P, _P]),
+    ("nl_pnp_refine", _I, [_P, _P, _L, _P, C.c_double, _I, _P, _P, _P, _P, _P]),
+    ("nl_pnp_ransac", _I, [_P, _P, _P, _P, _P, _L, _I, C.c_uint64, _I, _P, _P, _P, _P, _P, _Z, _P]),
     ("nl_backproject_support", _I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _L, _P, _P, _P, _P, C.POINTER(_L), _P, _Z, _P]),
 ]
 
