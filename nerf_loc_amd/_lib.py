@@ -231,6 +231,18 @@ def check(status: int, what: str = "") -> None:
         raise RuntimeError(f"libnerfloc_render {what}: {msg} ({status})")
 
 
+def ptr(t):
+    """A tensor's device address for an optional pointer argument: None (NULL) for None."""
+    return None if t is None else t.data_ptr()
+
+
+def workspace(nbytes: int, device, what: str, error=RuntimeError) -> torch.Tensor:
+    """The byte tensor for a `*_workspace_bytes` answer; 0 is the library's refusal of the shape or option: error(what)."""
+    if nbytes == 0:
+        raise error(what)
+    return torch.empty(nbytes, dtype=torch.uint8, device=device)
+
+
 def weight_names():
     lib = load()
     return [lib.nl_weight_name(i).decode() for i in range(lib.nl_num_weights())]

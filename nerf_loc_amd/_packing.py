@@ -56,6 +56,18 @@ def pack_matcher_mlp_train(who, module, device):
     return module._train_cache._cached(device, [module.mlps[0].weight, module.mlps[2].weight], pack)
 
 
+def matcher_mlp_grad_buffers(module, needs, device):
+    """(the six parameters of module.mlps, an fp32 gradient buffer for each one whose entry of `needs` is set and None for the others: a NULL pointer in the
+    backward call)."""
+    params = [module.get_parameter(n) for n in MATCHER_MLP_PARAMS]
+    return params, [torch.empty(p.shape, dtype=torch.float32, device=device) if need else None for p, need in zip(params, needs)]
+
+
+def matcher_mlp_grads_out(params, grads):
+    """The buffers of matcher_mlp_grad_buffers in their parameters' dtypes, as an autograd backward returns them."""
+    return [None if g is None else g.to(p.dtype) for g, p in zip(grads, params)]
+
+
 def new_train_cache():
     cache = PackedCache()
     cache._cache_init()

@@ -239,7 +239,7 @@ class ConditionalNeRF(nn.Module):
         self._frame_token: Dict[str, object] = {}
         self._weights_version = -1
         # training steps (compute_render_loss): the stages whose weight gradients the library computes run as HIP autograd nodes
-        # (diff_render.*TrainFn); False = the all-eager fp32 graph
+        # (diff_render's stage nodes, given their parameter tensors); False = the all-eager fp32 graph
         self.hip_training = True
 
     # ------------------------------------------------------------------ HIP plumbing
@@ -479,8 +479,8 @@ class ConditionalNeRF(nn.Module):
             # confidences; the two raw multi-view entries are returned without one.
             xyz = xyz.detach().float().contiguous()
             dirs = None if direction is None else direction[:, :3].detach().float().contiguous()
-            G, _ = diff_render.MvAggTrainFn.apply(xyz, fr["feat_fine_src"], fr["vis_featmaps"], r, *[p[n] for n in diff_render.MV_PARAMS])
-            fa = diff_render.PointBranchTrainFn.apply(xyz, dirs, G, sp["feature"], r, int(K), *[p[n] for n in diff_render.POINT_PARAMS])
+            G, _ = diff_render.MvAggFn.apply(xyz, r, fr["feat_fine_src"], fr["vis_featmaps"], *[p[n] for n in diff_render.MV_PARAMS])
+            fa = diff_render.PointBranchFn.apply(xyz, dirs, G, r, int(K), sp["feature"], *[p[n] for n in diff_render.POINT_PARAMS])
             with torch.no_grad():
                 _, rgb_feat, vis_ang, _ = r.mv_aggregate(xyz, data["pose"][:3, 3] if "pose" in data else torch.zeros(3))
                 d2, idx = r.knn(xyz, K)

@@ -26,6 +26,7 @@
 #include "s2d_bwd.h"
 #include "fine.h"
 #include "host.h"
+#include "s2d_bwd_host.h"
 
 namespace {
 
@@ -265,23 +266,8 @@ __global__ __launch_bounds__(256) void fine_map_gather_kernel(const FineMapArgs 
 }
 
 // ------------------------------------------------------------------------------------------ workspaces
-struct MatchBwdWs { size_t x, h1, ga2, ga1, w3part, wg, dummy, total; size_t wg_floats; };
-MatchBwdWs match_bwd_ws(int64_t M, int C) {
-  MatchBwdWs w;
-  const size_t P = (size_t)M * FINE_WW;
-  size_t o = 0;
-  auto take = [&](size_t bytes) { const size_t at = o; o += nl_align_up(bytes, 256); return at; };
-  w.x = take(P * C * 4);
-  w.h1 = take(P * S2D_H * 4);
-  w.ga2 = take(P * S2D_H * 4);
-  w.ga1 = take(P * S2D_H * 4);
-  w.w3part = take((size_t)M * S2D_W3P_LD * 4);
-  w.wg_floats = std::max(nl_wgrad_scratch_floats((int64_t)P, S2D_H, C), nl_wgrad_scratch_floats((int64_t)P, S2D_H, S2D_H));
-  w.wg = take(w.wg_floats * 4);
-  w.dummy = take((size_t)S2D_H * 256 * 4);
-  w.total = o;
-  return w;
-}
+// the shared operand block (s2d_bwd_host.h): 49 operand rows and one partial row of gW3 per match
+S2dMlpBwdWs match_bwd_ws(int64_t M, int C) { return S2dMlpBwdWs((size_t)M * FINE_WW, (size_t)M, C); }
 struct WinBwdWs { size_t X, rows, wg, dummy, key, start, list, total; size_t wg_floats; };
 WinBwdWs win_bwd_ws(int Cf, int Cout, int64_t K, int64_t M) {
   WinBwdWs w;
@@ -341,29 +327,20 @@ int nl_fine_match_backward(const void* packed_mlp, const void* train_packed, int
   if (!packed_mlp || !train_packed || !feat_f0 || !feat_f1 || !heatmap || !g_expec) return NL_ERR_BAD_ARG;
   if ((((uintptr_t)packed_mlp | (uintptr_t)train_packed | (uintptr_t)feat_f0 | (uintptr_t)feat_f1 | (uintptr_t)g_feat_f0 | (uintptr_t)g_feat_f1) & 15) != 0)
     return NL_ERR_BAD_ARG;   // read / written as 16-byte pieces
-  if ((((uintptr_t)heatmap | (uintptr_t)g_expec | (uintptr_t)g_w1 | (uintptr_t)g_b1 | (uintptr_t)g_w2 | (uintptr_t)g_b2 | (uintptr_t)g_w3 | (uintptr_t)g_b3) & 3) != 0)
-    return NL_ERR_BAD_ARG;
-  const MatchBwdWs w = match_bwd_ws(M, C);
+  const S2dMlpGrads g{g_w1, g_b1, g_w2, g_b2, g_w3, g_b3};
+  if ((((uintptr_t)heatmap | (uintptr_t)g_expec | g.addr_bits()) & 3) != 0) return NL_ERR_BAD_ARG;
+  const S2dMlpBwdWs w = match_bwd_ws(M, C);
   if (!workspace || workspace_bytes < w.total || ((uintptr_t)workspace & 15) != 0) return NL_ERR_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
   unsigned char* ws = (unsigned char*)workspace;
-  const bool want1 = g_w1 || g_b1, want2 = g_w2 || g_b2;
   const int64_t P = M * FINE_WW;
 
-  if (g_w1) NL_CHECK_HIP(hipMemsetAsync(g_w1, 0, (size_t)S2D_H * C * 4, st));
-  if (g_b1) NL_CHECK_HIP(hipMemsetAsync(g_b1, 0, S2D_H * 4, st));
-  if (g_w2) NL_CHECK_HIP(hipMemsetAsync(g_w2, 0, (size_t)S2D_H * S2D_H * 4, st));
-  if (g_b2) NL_CHECK_HIP(hipMemsetAsync(g_b2, 0, S2D_H * 4, st));
-  if (g_w3) NL_CHECK_HIP(hipMemsetAsync(g_w3, 0, S2D_H * 4, st));
-  if (g_b3) NL_CHECK_HIP(hipMemsetAsync(g_b3, 0, 4, st));
+  if (const int e = s2d_mlp_grads_zero(g, C, st)) return e;
 
   FineMatchBwdArgs a;
   a.img = (const unsigned char*)packed_mlp; a.timg = (const unsigned char*)train_packed;
   a.f0 = feat_f0; a.f1 = feat_f1; a.heat = heatmap; a.g_expec = g_expec;
-  a.x = want1 ? (float*)(ws + w.x) : nullptr;
-  a.ga1 = want1 ? (float*)(ws + w.ga1) : nullptr;
-  a.h1 = want2 ? (float*)(ws + w.h1) : nullptr;
-  a.ga2 = want2 ? (float*)(ws + w.ga2) : nullptr;
+  w.operands(ws, g, a.x, a.ga1, a.h1, a.ga2);
   a.w3part = g_w3 ? (float*)(ws + w.w3part) : nullptr;
   a.g_f0 = g_feat_f0; a.g_f1 = g_feat_f1;
   a.M = (int)M; a.C = C;
@@ -371,19 +348,11 @@ int nl_fine_match_backward(const void* packed_mlp, const void* train_packed, int
   float* wg = (float*)(ws + w.wg);
   float* dummy = (float*)(ws + w.dummy);
 
-  const dim3 grid((unsigned)nl_cdiv(M, 4));
-  if (precision == NL_PREC_BF16) {
-    hipLaunchKernelGGL(fine_match_bwd_kernel<false>, grid, dim3(256), 0, st, a);
-  } else {
-    static std::atomic<unsigned long long> lds_set{0};   // the exact kernel's dynamic LDS is beyond the 64 KB a kernel gets unasked
-    if (const int e = nl_allow_dynamic_lds((const void*)fine_match_bwd_kernel<true>, S2D_F32_LDS, lds_set)) return e;
-    hipLaunchKernelGGL(fine_match_bwd_kernel<true>, grid, dim3(256), S2D_F32_LDS, st, a);
-  }
-  NL_LAUNCH_CHECK();
-  if (want2)
-    if (const int e = nl_launch_wgrad(a.ga2, S2D_H, S2D_H, a.h1, S2D_H, S2D_H, P, 0, 0, g_w2 ? g_w2 : dummy, S2D_H, 1, 0, g_b2, wg, w.wg_floats, st)) return e;
-  if (want1)
-    if (const int e = nl_launch_wgrad(a.ga1, S2D_H, S2D_H, a.x, C, C, P, 0, 0, g_w1 ? g_w1 : dummy, C, 1, 0, g_b1, wg, w.wg_floats, st)) return e;
+  static std::atomic<unsigned long long> lds_set{0};
+  // (named ahead of <true>: the two kernels lie in the code object in the order of their first use, and tools/kernel_identity.py holds the device code fixed)
+  const auto bf16_kernel = fine_match_bwd_kernel<false>;
+  if (const int e = s2d_mlp_bwd_launch(fine_match_bwd_kernel<true>, bf16_kernel, dim3((unsigned)nl_cdiv(M, 4)), a, precision, lds_set, st)) return e;
+  if (const int e = s2d_mlp_wgrad(a.x, a.ga1, a.h1, a.ga2, C, P, g, dummy, wg, w.wg_floats, st)) return e;
   // gb3 stays the zero written above: the softmax ignores a common shift of a match's 49 logits, so expec_f does not depend on b3 at all (the sum of the
   // logit gradients that autograd forms there is rounding noise around zero)
   if (g_w3)

@@ -22,6 +22,7 @@
 #include "s2d.h"
 #include "s2d_bwd.h"
 #include "host.h"
+#include "s2d_bwd_host.h"
 
 namespace {
 
@@ -217,26 +218,16 @@ int64_t bwd_chunk_rows(int64_t N, int64_t M) {
   const int64_t r = std::max<int64_t>(2, (pairs / M) & ~(int64_t)1);
   return std::min<int64_t>(r, (N + 1) & ~(int64_t)1);
 }
-struct BwdWs { size_t x, h1, ga2, ga1, gx, w3part, gd0part, wg, dummy, total; size_t wg_floats; int64_t rows; int nseg; };
+// the shared operand block (s2d_bwd_host.h) for one chunk, then the chunk's g_x and the segment sums of g_desc0
+struct BwdWs : S2dMlpBwdWs { size_t gx, gd0part; int64_t rows; int nseg; using S2dMlpBwdWs::S2dMlpBwdWs; };
 BwdWs bwd_ws(int64_t N, int64_t M, int C) {
-  BwdWs w;
-  w.rows = bwd_chunk_rows(N, M);
+  const int64_t rows = bwd_chunk_rows(N, M);
+  const size_t P = (size_t)rows * (size_t)M;
+  BwdWs w(P, (size_t)nl_cdiv(M, 32) * (size_t)(rows / 2), C);
+  w.rows = rows;
   w.nseg = (int)nl_cdiv(M, 256);
-  const size_t P = (size_t)w.rows * (size_t)M;
-  const size_t items = (size_t)nl_cdiv(M, 32) * (size_t)(w.rows / 2);
-  size_t o = 0;
-  auto take = [&](size_t bytes) { const size_t at = o; o += nl_align_up(bytes, 256); return at; };
-  w.x = take(P * C * 4);
-  w.h1 = take(P * S2D_H * 4);
-  w.ga2 = take(P * S2D_H * 4);
-  w.ga1 = take(P * S2D_H * 4);
-  w.gx = take(P * C * 4);
-  w.w3part = take(items * S2D_W3P_LD * 4);
-  w.gd0part = take((size_t)w.rows * w.nseg * C * 4);
-  w.wg_floats = std::max(nl_wgrad_scratch_floats((int64_t)P, S2D_H, C), nl_wgrad_scratch_floats((int64_t)P, S2D_H, S2D_H));
-  w.wg = take(w.wg_floats * 4);
-  w.dummy = take((size_t)S2D_H * 256 * 4);
-  w.total = o;
+  w.gx = w.take(P * C * 4);
+  w.gd0part = w.take((size_t)w.rows * w.nseg * C * 4);
   return w;
 }
 
@@ -267,10 +258,8 @@ int nl_s2d_pack_train_weights(int C, const float* w1, const float* w2, void* pac
   hipStream_t st = (hipStream_t)stream;
   float* w2t = (float*)(img + T.f32w2t);
   float* w1t = (float*)(img + T.f32w1t);
-  hipLaunchKernelGGL(s2d_transpose_kernel, dim3((unsigned)nl_cdiv(S2D_H * S2D_H, 256)), dim3(256), 0, st, w2, S2D_H, S2D_H, w2t);
-  NL_LAUNCH_CHECK();
-  hipLaunchKernelGGL(s2d_transpose_kernel, dim3((unsigned)nl_cdiv(S2D_H * C, 256)), dim3(256), 0, st, w1, S2D_H, C, w1t);
-  NL_LAUNCH_CHECK();
+  if (const int e = nl_launch_transpose(w2, S2D_H, S2D_H, w2t, st)) return e;
+  if (const int e = nl_launch_transpose(w1, S2D_H, C, w1t, st)) return e;
   auto u16 = [&](size_t off) { return (unsigned short*)(img + off); };
   if (const int e = nl_launch_frag_pack(w2t, S2D_H, S2D_H, u16(T.w2t_hi), u16(T.w2t_lo), nullptr, nullptr, nullptr, true, st)) return e;
   if (const int e = nl_launch_frag_pack(w1t, C, S2D_H, u16(T.w1t_hi), u16(T.w1t_lo), nullptr, nullptr, nullptr, true, st)) return e;
@@ -291,43 +280,30 @@ int nl_s2d_backward_train(const void* packed, const void* train_packed, int C, i
   if (!packed || !train_packed || !desc0 || !desc1 || !logits || !g_desc0 || !g_desc1) return NL_ERR_BAD_ARG;
   if ((target != nullptr) != (g_loss != nullptr)) return NL_ERR_BAD_ARG;
   if ((((uintptr_t)packed | (uintptr_t)train_packed | (uintptr_t)desc0 | (uintptr_t)desc1 | (uintptr_t)g_desc0 | (uintptr_t)g_desc1) & 15) != 0) return NL_ERR_BAD_ARG;
-  if ((((uintptr_t)logits | (uintptr_t)target | (uintptr_t)g_loss | (uintptr_t)g_score | (uintptr_t)g_w1 | (uintptr_t)g_b1 | (uintptr_t)g_w2 | (uintptr_t)g_b2 |
-        (uintptr_t)g_w3 | (uintptr_t)g_b3) & 3) != 0)
-    return NL_ERR_BAD_ARG;
+  const S2dMlpGrads g{g_w1, g_b1, g_w2, g_b2, g_w3, g_b3};
+  if ((((uintptr_t)logits | (uintptr_t)target | (uintptr_t)g_loss | (uintptr_t)g_score | g.addr_bits()) & 3) != 0) return NL_ERR_BAD_ARG;
   const BwdWs w = bwd_ws(N, M, C);
   if (!workspace || workspace_bytes < w.total || ((uintptr_t)workspace & 15) != 0) return NL_ERR_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
   unsigned char* ws = (unsigned char*)workspace;
-  const bool want1 = g_w1 || g_b1, want2 = g_w2 || g_b2, want3 = g_w3 || g_b3;
 
   NL_CHECK_HIP(hipMemsetAsync(g_desc1, 0, (size_t)M * C * 4, st));
-  if (g_w1) NL_CHECK_HIP(hipMemsetAsync(g_w1, 0, (size_t)S2D_H * C * 4, st));
-  if (g_b1) NL_CHECK_HIP(hipMemsetAsync(g_b1, 0, S2D_H * 4, st));
-  if (g_w2) NL_CHECK_HIP(hipMemsetAsync(g_w2, 0, (size_t)S2D_H * S2D_H * 4, st));
-  if (g_b2) NL_CHECK_HIP(hipMemsetAsync(g_b2, 0, S2D_H * 4, st));
-  if (g_w3) NL_CHECK_HIP(hipMemsetAsync(g_w3, 0, S2D_H * 4, st));
-  if (g_b3) NL_CHECK_HIP(hipMemsetAsync(g_b3, 0, 4, st));
+  if (const int e = s2d_mlp_grads_zero(g, C, st)) return e;
 
   BwdArgs a;
   a.img = (const unsigned char*)packed; a.timg = (const unsigned char*)train_packed;
   a.desc0 = desc0; a.desc1 = desc1;
   a.logits = logits; a.target = target; a.g_loss = g_loss; a.g_score = g_score;
-  a.x = want1 ? (float*)(ws + w.x) : nullptr;
-  a.ga1 = want1 ? (float*)(ws + w.ga1) : nullptr;
-  a.h1 = want2 ? (float*)(ws + w.h1) : nullptr;
-  a.ga2 = want2 ? (float*)(ws + w.ga2) : nullptr;
+  w.operands(ws, g, a.x, a.ga1, a.h1, a.ga2);
   a.gx = (float*)(ws + w.gx);
-  a.w3part = want3 ? (float*)(ws + w.w3part) : nullptr;
+  a.w3part = g.want3() ? (float*)(ws + w.w3part) : nullptr;
   a.N = (int)N; a.M = (int)M; a.C = C;
   a.inv_total = (float)(1.0 / ((double)N * (double)M));
   float* wg = (float*)(ws + w.wg);
   float* dummy = (float*)(ws + w.dummy);
   float* gd0part = (float*)(ws + w.gd0part);
   const int MT = (int)nl_cdiv(M, 32);
-
-  static std::atomic<unsigned long long> lds_set{0};   // the exact kernel's dynamic LDS is beyond the 64 KB a kernel gets unasked
-  if (precision != NL_PREC_BF16)
-    if (const int e = nl_allow_dynamic_lds((const void*)s2d_bwd_kernel<true>, S2D_F32_LDS, lds_set)) return e;
+  static std::atomic<unsigned long long> lds_set{0};
 
   for (int64_t r0 = 0; r0 < N; r0 += w.rows) {
     const int64_t r1 = std::min(N, r0 + w.rows);
@@ -336,14 +312,9 @@ int nl_s2d_backward_train(const void* packed, const void* train_packed, int C, i
     a.r0 = (int)r0; a.r1 = (int)r1;
     const int items = MT * ((rows + 1) / 2);
     const dim3 grid((unsigned)nl_cdiv(items, 4));
-    if (precision == NL_PREC_BF16) hipLaunchKernelGGL(s2d_bwd_kernel<false>, grid, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL(s2d_bwd_kernel<true>, grid, dim3(256), S2D_F32_LDS, st, a);
-    NL_LAUNCH_CHECK();
-    if (want2)
-      if (const int e = nl_launch_wgrad(a.ga2, S2D_H, S2D_H, a.h1, S2D_H, S2D_H, P, 0, 0, g_w2 ? g_w2 : dummy, S2D_H, 1, 0, g_b2, wg, w.wg_floats, st)) return e;
-    if (want1)
-      if (const int e = nl_launch_wgrad(a.ga1, S2D_H, S2D_H, a.x, C, C, P, 0, 0, g_w1 ? g_w1 : dummy, C, 1, 0, g_b1, wg, w.wg_floats, st)) return e;
-    if (want3) {
+    if (const int e = s2d_mlp_bwd_launch(s2d_bwd_kernel<true>, s2d_bwd_kernel<false>, grid, a, precision, lds_set, st)) return e;
+    if (const int e = s2d_mlp_wgrad(a.x, a.ga1, a.h1, a.ga2, C, P, g, dummy, wg, w.wg_floats, st)) return e;
+    if (g.want3()) {
       hipLaunchKernelGGL(s2d_w3_reduce_kernel, dim3(129), dim3(256), 0, st, a.w3part, items, g_w3, g_b3);
       NL_LAUNCH_CHECK();
     }

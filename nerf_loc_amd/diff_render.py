@@ -99,17 +99,48 @@ class KnnDist2Fn(torch.autograd.Function):
         return gx, gsp, None
 
 
+def _same_state(ctx):
+    """The library nodes keep no activations: their backward recomputes from the renderer's CURRENT weights and frame tables, which therefore must be
+    the forward call's (one training / refinement step = forward and backward against one frame)."""
+    if ctx.r.state_gen != ctx.gen:
+        raise RuntimeError("the HipRenderer's weights or frame were replaced between the forward and the backward pass of this autograd node")
+
+
+# ----------------------------------------------------------------------------- the per-stage nodes (PointBranchFn, MvAggFn, UnetFn, BlendFn)
+# Each is one node for both uses.  Frozen (pose refinement, pose_optimizer.py:131-168: weights and per-frame tables are constants): the call ends at the
+# renderer and the backward is the stage's `nl_*_backward`.  A training step (compute_render_loss, model.py:641-685) appends the frame tensors and the
+# stage's *_PARAMS tensors, so that autograd knows where their gradients go — the renderer must hold their CURRENT values — and the backward is
+# `nl_*_backward_train`, which delivers those gradients in the same pass as the input gradients (§5.14).  A node takes the training entry point iff it was
+# GIVEN parameter tensors, whether or not any of them requires grad (as RenderFn): that entry point's workspace sizer and kernels differ from the frozen one's.
+def _stage_train_grads(ctx, params, first, **frame):
+    """The TrainGrads of a stage node's backward (None: a frozen call).  params: the stage's *_PARAMS, whose tensors are the inputs from position `first` on;
+    frame: TrainGrads keyword -> position of that frame tensor among the inputs."""
+    if not ctx.train:
+        return None
+    need = ctx.needs_input_grad
+    return ctx.r.train_grads([n for n, nd in zip(params, need[first:]) if nd], **{k: need[i] for k, i in frame.items()})
+
+
+def _stage_grads(ctx, fixed, tg, params, *frame):
+    """A stage node's backward result: `fixed` (the inputs up to the renderer / K), then the gradients of the frame tensors (attributes `frame` of tg) and of
+    `params`, cut to the inputs the call was given."""
+    tail = (None,) * (len(frame) + len(params)) if tg is None else tuple(getattr(tg, f) for f in frame) + tuple(tg.weights.get(n) for n in params)
+    return (fixed + tail)[:len(ctx.needs_input_grad)]
+
+
 class PointBranchFn(torch.autograd.Function):
-    """The neural-point branch (model.py:372-427) with FROZEN weights as one autograd node on the HIP library: forward = the fused kernels
-    of `nl_point_mlp`, backward = `nl_point_mlp_backward` (staged recompute + transposed-weight GEMMs; nothing is saved but the inputs).
-    Used by the pose-refinement gradient path (eval mode: the weights and the support table are constants, pose_optimizer.py:131-168);
-    training keeps the eager graph, which also reaches the weights.  `renderer`: a HipRenderer holding the same weights and frame."""
+    """The neural-point branch (model.py:372-427) as one autograd node on the HIP library: (xyz, dirs, G, renderer, K[, support features, *POINT_PARAMS
+    tensors]) -> feature_agg; forward = the fused kernels of `nl_point_mlp`, backward = `nl_point_mlp_backward` (staged recompute + transposed-weight GEMMs;
+    nothing is saved but the inputs).  `renderer`: a HipRenderer holding the same weights and frame.  A training step: `nl_point_mlp_backward_train` also
+    delivers the gradients of the branch's 16 parameter tensors and of the support table's features (weight gradients as split-K products over the recomputed
+    activations).  base_mlp_agg_weight and the neighbours' confidences get no gradient: it is identically zero (the softmax / the normalisation run over K
+    identical rows, model.py:415-427)."""
 
     @staticmethod
-    def forward(ctx, xyz, dirs, G, renderer, K):
+    def forward(ctx, xyz, dirs, G, renderer, K, sp_feature=None, *params):
         xyz, G = xyz.contiguous(), G.contiguous()
         dirs = None if dirs is None else dirs.contiguous()
-        ctx.r, ctx.K, ctx.has_dir, ctx.gen = renderer, int(K), dirs is not None, renderer.state_gen
+        ctx.r, ctx.K, ctx.has_dir, ctx.gen, ctx.train = renderer, int(K), dirs is not None, renderer.state_gen, len(params) > 0
         fa, d2, idx = renderer.point_mlp(xyz, dirs, G, K=int(K))
         ctx.save_for_backward(xyz, G, d2, idx, *([dirs] if dirs is not None else []))
         return fa
@@ -119,15 +150,9 @@ class PointBranchFn(torch.autograd.Function):
         _same_state(ctx)
         xyz, G, d2, idx = ctx.saved_tensors[:4]
         dirs = ctx.saved_tensors[4] if ctx.has_dir else None
-        gx, gd, gg = ctx.r.point_mlp_backward(xyz, dirs, G, g_fa.contiguous(), K=ctx.K, knn=(d2, idx))
-        return gx, gd, gg, None, None
-
-
-def _same_state(ctx):
-    """The library nodes keep no activations: their backward recomputes from the renderer's CURRENT weights and frame tables, which therefore must be
-    the forward call's (one training / refinement step = forward and backward against one frame)."""
-    if ctx.r.state_gen != ctx.gen:
-        raise RuntimeError("the HipRenderer's weights or frame were replaced between the forward and the backward pass of this autograd node")
+        tg = _stage_train_grads(ctx, POINT_PARAMS, 6, support_feature=5)
+        gx, gd, gg = ctx.r.point_mlp_backward(xyz, dirs, G, g_fa.contiguous(), K=ctx.K, knn=(d2, idx), train=tg)
+        return _stage_grads(ctx, (gx, gd, gg, None, None), tg, POINT_PARAMS, "support_feature")
 
 
 # RenderFn keeps the staged forward's activations for the backward call when they fit this many bytes (one chunk: ~90 KB per sample at W = 256, i.e. a
@@ -243,34 +268,6 @@ POINT_PARAMS = ("ray_diff_fc.0.weight", "ray_diff_fc.0.bias", "ray_diff_fc.2.wei
                 "base_mlp_attn.layer_norm.weight", "base_mlp_attn.layer_norm.bias")
 
 
-class PointBranchTrainFn(torch.autograd.Function):
-    """PointBranchFn for a TRAINING step (compute_render_loss, model.py:641-685): the same HIP forward, and a backward that also delivers the
-    gradients of the branch's 16 parameter tensors and of the support table's features (nl_point_mlp_backward_train: weight gradients as
-    split-K products over the recomputed activations, in the same pass as the input gradients).  `renderer` holds the CURRENT values of
-    `params` (POINT_PARAMS order) and of the support table; the tensors are passed so that autograd knows where the gradients go.
-    base_mlp_agg_weight and the neighbours' confidences get no gradient: it is identically zero (the softmax / the normalisation run over K
-    identical rows, model.py:415-427)."""
-
-    @staticmethod
-    def forward(ctx, xyz, dirs, G, sp_feature, renderer, K, *params):
-        xyz, G = xyz.contiguous(), G.contiguous()
-        dirs = None if dirs is None else dirs.contiguous()
-        ctx.r, ctx.K, ctx.has_dir, ctx.gen = renderer, int(K), dirs is not None, renderer.state_gen
-        fa, d2, idx = renderer.point_mlp(xyz, dirs, G, K=int(K))
-        ctx.save_for_backward(xyz, G, d2, idx, *([dirs] if dirs is not None else []))
-        return fa
-
-    @staticmethod
-    def backward(ctx, g_fa):
-        _same_state(ctx)
-        xyz, G, d2, idx = ctx.saved_tensors[:4]
-        dirs = ctx.saved_tensors[4] if ctx.has_dir else None
-        names = [n for n, need in zip(POINT_PARAMS, ctx.needs_input_grad[6:]) if need]
-        tg = ctx.r.train_grads(names, support_feature=ctx.needs_input_grad[3])
-        gx, gd, gg = ctx.r.point_mlp_backward(xyz, dirs, G, g_fa.contiguous(), K=ctx.K, knn=(d2, idx), train=tg)
-        return (gx, gd, gg, tg.support_feature, None, None) + tuple(tg.weights.get(n) for n in POINT_PARAMS)
-
-
 _DEC = [f"multiview_aggregator.dist_decoder.{d}_decoder.{i}.{t}" for d in ("mean", "var", "aw", "vis") for i in (0, 2, 4) for t in ("weight", "bias")]
 MV_PARAMS = tuple(f"multiview_aggregator.out_fc.{i}.{t}" for i in (0, 2) for t in ("weight", "bias")) + tuple(_DEC)
 BLEND_PARAMS = tuple(f"rgb_blending_mlp.{i}.{t}" for i in (0, 2, 4) for t in ("weight", "bias")) + tuple(_DEC)
@@ -281,84 +278,18 @@ UNET_PARAMS = tuple(f"ray_unet.{blk}.{i}.{t}" for blk in ("conv1", "conv2", "con
                     for i in (0, 1) for t in ("weight", "bias"))
 
 
-class UnetTrainFn(torch.autograd.Function):
-    """UnetFn for a training step: (x (R*S, W), renderer, *UNET_PARAMS) -> geo; backward = nl_ray_unet_backward_train: also the gradients of the seven
-    blocks' convolutions (one split-K product per tap) and LayerNorm([C, L]) tables (sums over the rays)."""
-
-    @staticmethod
-    def forward(ctx, x, renderer, *params):
-        x = x.contiguous()
-        ctx.r, ctx.gen = renderer, renderer.state_gen
-        ctx.save_for_backward(x)
-        return renderer.ray_unet(x)
-
-    @staticmethod
-    def backward(ctx, g_geo):
-        _same_state(ctx)
-        x, = ctx.saved_tensors
-        names = [n for n, need in zip(UNET_PARAMS, ctx.needs_input_grad[2:]) if need]
-        tg = ctx.r.train_grads(names)
-        gx = ctx.r.ray_unet_backward(x, g_geo.contiguous(), train=tg)
-        return (gx, None) + tuple(tg.weights.get(n) for n in UNET_PARAMS)
-
-
-class MvAggTrainFn(torch.autograd.Function):
-    """MvAggFn for a training step: (xyz, feature maps (V,h,w,C), DepthFusionNet maps (V,32,vh,vw), renderer, *MV_PARAMS tensors) -> (G, valid_s);
-    backward = nl_mv_aggregate_backward_train: also d/d out_fc, d/d the four decoders, d/d both maps."""
-
-    @staticmethod
-    def forward(ctx, xyz, feat_maps, vis_maps, renderer, *params):
-        xyz = xyz.contiguous()
-        ctx.r, ctx.gen = renderer, renderer.state_gen
-        ctx.save_for_backward(xyz)
-        mv, _, _, valid = renderer.mv_aggregate(xyz, torch.zeros(3), want_raw=False)
-        ctx.mark_non_differentiable(valid)
-        return mv, valid
-
-    @staticmethod
-    def backward(ctx, g_mv, _g_valid):
-        _same_state(ctx)
-        xyz, = ctx.saved_tensors
-        names = [n for n, need in zip(MV_PARAMS, ctx.needs_input_grad[4:]) if need]
-        tg = ctx.r.train_grads(names, feat_maps=ctx.needs_input_grad[1], vis_featmaps=ctx.needs_input_grad[2])
-        gx = ctx.r.mv_aggregate_backward(xyz, g_mv.contiguous(), train=tg)
-        return (gx if ctx.needs_input_grad[0] else None, tg.feat_maps, tg.vis_featmaps, None) + tuple(tg.weights.get(n) for n in MV_PARAMS)
-
-
-class BlendTrainFn(torch.autograd.Function):
-    """BlendFn for a training step: (xyz, feature_agg, query centre, blend-projected maps P (V,h,w,32) = feature maps . the feature columns of
-    rgb_blending_mlp.0 [its graph carries those columns' and the maps' gradient], DepthFusionNet maps, renderer, *BLEND_PARAMS) -> rgb_s (N,3);
-    backward = nl_blend_backward_train."""
-
-    @staticmethod
-    def forward(ctx, xyz, fa, qc, pmaps, vis_maps, renderer, *params):
-        xyz, fa = xyz.contiguous(), fa.contiguous()
-        ctx.r, ctx.gen = renderer, renderer.state_gen
-        ctx.save_for_backward(xyz, fa, qc)
-        return renderer.blend(xyz, qc, fa)
-
-    @staticmethod
-    def backward(ctx, g_rgb_s):
-        _same_state(ctx)
-        xyz, fa, qc = ctx.saved_tensors
-        names = [n for n, need in zip(BLEND_PARAMS, ctx.needs_input_grad[6:]) if need]
-        tg = ctx.r.train_grads(names, vis_featmaps=ctx.needs_input_grad[4], blend_feat_maps=ctx.needs_input_grad[3])
-        gx, gfa, gq = ctx.r.blend_backward(xyz, qc, fa, g_rgb_s.contiguous(), want_g_query_center=ctx.needs_input_grad[2], train=tg)
-        return (gx if ctx.needs_input_grad[0] else None, gfa, None if gq is None else gq.to(qc.dtype), tg.blend_feat_maps, tg.vis_featmaps, None) + \
-            tuple(tg.weights.get(n) for n in BLEND_PARAMS)
-
-
 RENDER_PARAMS = POINT_PARAMS + MV_PARAMS + BLEND_PARAMS[:6] + UNET_PARAMS + HEAD_PARAMS   # the 84 tensors of the ray path
 
 
 class MvAggFn(torch.autograd.Function):
-    """Multi-view aggregation (multiview_aggregator.py:156-222) with frozen weights / support maps as one autograd node on the HIP library:
-    xyz (N,3) -> (G (N,W), valid_s (N) int32 [non-differentiable: #views that see the sample > 1]); backward = nl_mv_aggregate_backward."""
+    """Multi-view aggregation (multiview_aggregator.py:156-222) as one autograd node on the HIP library: (xyz (N,3), renderer[, feature maps (V,h,w,C),
+    DepthFusionNet maps (V,32,vh,vw), *MV_PARAMS tensors]) -> (G (N,W), valid_s (N) int32 [non-differentiable: #views that see the sample > 1]);
+    backward = nl_mv_aggregate_backward; a training step: nl_mv_aggregate_backward_train, also d/d out_fc, d/d the four decoders, d/d both maps."""
 
     @staticmethod
-    def forward(ctx, xyz, renderer):
+    def forward(ctx, xyz, renderer, feat_maps=None, vis_maps=None, *params):
         xyz = xyz.contiguous()
-        ctx.r, ctx.gen = renderer, renderer.state_gen
+        ctx.r, ctx.gen, ctx.train = renderer, renderer.state_gen, len(params) > 0
         ctx.save_for_backward(xyz)
         mv, _, _, valid = renderer.mv_aggregate(xyz, torch.zeros(3), want_raw=False)
         ctx.mark_non_differentiable(valid)
@@ -368,16 +299,20 @@ class MvAggFn(torch.autograd.Function):
     def backward(ctx, g_mv, _g_valid):
         _same_state(ctx)
         xyz, = ctx.saved_tensors
-        return ctx.r.mv_aggregate_backward(xyz, g_mv.contiguous()), None
+        tg = _stage_train_grads(ctx, MV_PARAMS, 4, feat_maps=2, vis_featmaps=3)
+        gx = ctx.r.mv_aggregate_backward(xyz, g_mv.contiguous(), train=tg)
+        return _stage_grads(ctx, (gx if ctx.needs_input_grad[0] else None, None), tg, MV_PARAMS, "feat_maps", "vis_featmaps")
 
 
 class UnetFn(torch.autograd.Function):
-    """The ray U-Net (ray_unet.py:55-69) with frozen weights on the HIP library: x (R*S, W) sample-major -> geo (R*S, W); backward = nl_ray_unet_backward."""
+    """The ray U-Net (ray_unet.py:55-69) on the HIP library: (x (R*S, W) sample-major, renderer[, *UNET_PARAMS tensors]) -> geo (R*S, W); backward =
+    nl_ray_unet_backward; a training step: nl_ray_unet_backward_train, also the gradients of the seven blocks' convolutions (one split-K product per tap)
+    and LayerNorm([C, L]) tables (sums over the rays)."""
 
     @staticmethod
-    def forward(ctx, x, renderer):
+    def forward(ctx, x, renderer, *params):
         x = x.contiguous()
-        ctx.r, ctx.gen = renderer, renderer.state_gen
+        ctx.r, ctx.gen, ctx.train = renderer, renderer.state_gen, len(params) > 0
         ctx.save_for_backward(x)
         return renderer.ray_unet(x)
 
@@ -385,17 +320,19 @@ class UnetFn(torch.autograd.Function):
     def backward(ctx, g_geo):
         _same_state(ctx)
         x, = ctx.saved_tensors
-        return ctx.r.ray_unet_backward(x, g_geo.contiguous()), None
+        tg = _stage_train_grads(ctx, UNET_PARAMS, 2)
+        return _stage_grads(ctx, (ctx.r.ray_unet_backward(x, g_geo.contiguous(), train=tg), None), tg, UNET_PARAMS)
 
 
 class BlendFn(torch.autograd.Function):
-    """Per-sample colours (model.py:528-538) with frozen weights / maps: (xyz (N,3), feature_agg (N,W), query camera centre (3,)) -> rgb_s (N,3);
-    forward = nl_blend, backward = nl_blend_backward."""
+    """Per-sample colours (model.py:528-538): (xyz (N,3), feature_agg (N,W), query camera centre (3,), renderer[, blend-projected maps P (V,h,w,32) = feature
+    maps . the feature columns of rgb_blending_mlp.0 [its graph carries those columns' and the maps' gradient], DepthFusionNet maps, *BLEND_PARAMS tensors])
+    -> rgb_s (N,3); forward = nl_blend, backward = nl_blend_backward; a training step: nl_blend_backward_train."""
 
     @staticmethod
-    def forward(ctx, xyz, fa, qc, renderer):
+    def forward(ctx, xyz, fa, qc, renderer, pmaps=None, vis_maps=None, *params):
         xyz, fa = xyz.contiguous(), fa.contiguous()
-        ctx.r, ctx.gen = renderer, renderer.state_gen
+        ctx.r, ctx.gen, ctx.train = renderer, renderer.state_gen, len(params) > 0
         ctx.save_for_backward(xyz, fa, qc)
         return renderer.blend(xyz, qc, fa)
 
@@ -403,8 +340,10 @@ class BlendFn(torch.autograd.Function):
     def backward(ctx, g_rgb_s):
         _same_state(ctx)
         xyz, fa, qc = ctx.saved_tensors
-        gx, gfa, gq = ctx.r.blend_backward(xyz, qc, fa, g_rgb_s.contiguous(), want_g_query_center=ctx.needs_input_grad[2])
-        return gx, gfa, (None if gq is None else gq.to(qc.dtype)), None
+        need = ctx.needs_input_grad
+        tg = _stage_train_grads(ctx, BLEND_PARAMS, 6, blend_feat_maps=4, vis_featmaps=5)
+        gx, gfa, gq = ctx.r.blend_backward(xyz, qc, fa, g_rgb_s.contiguous(), want_g_query_center=need[2], train=tg)
+        return _stage_grads(ctx, (gx if need[0] else None, gfa, None if gq is None else gq.to(qc.dtype), None), tg, BLEND_PARAMS, "blend_feat_maps", "vis_featmaps")
 
 
 def rays_from_pose(uv: Tensor, K: Tensor, pose: Tensor):
@@ -614,7 +553,7 @@ def render_rays_diff(p: Dict[str, Tensor], fr: Dict, rays_o: Tensor, rays_d: Ten
     parameters `p` and the frame tensors.  frozen_renderer: a HipRenderer holding exactly `p` and `fr['support']` — states that both are
     constants of this call, so the neural-point branch may run as PointBranchFn (HIP forward + HIP backward) instead of eager ops.
     train_renderer: a HipRenderer holding the CURRENT VALUES of `p` and of the frame tensors (a training step): the stages whose weight
-    gradients the library computes (`*TrainFn`) run as HIP nodes that also return d/d parameters and d/d frame tensors; the others stay eager.
+    gradients the library computes run as HIP nodes given their parameter tensors, which also return d/d parameters and d/d frame tensors; the others stay eager.
     whole_path (with either renderer; no `beta`): the whole function is ONE node (`RenderFn`: fused forward, `nl_render_rays_backward`) instead of one
     node per stage.
     fr: topk_Ks, topk_poses, topk_images, feat_fine_src, vis_featmaps, near, far (python floats), support {xyz, feature, confidence, direction}."""
@@ -645,8 +584,8 @@ def render_rays_diff(p: Dict[str, Tensor], fr: Dict, rays_o: Tensor, rays_d: Ten
         agg = PointBranchFn.apply(xyz, dirs.contiguous(), G, r, 8)
     elif hip_train:
         # a training step: the same three nodes, whose backward also returns the gradients of their parameters and of the per-frame tensors
-        G, valid_s = MvAggTrainFn.apply(xyz, fr["feat_fine_src"], fr["vis_featmaps"], r, *[p[n] for n in MV_PARAMS])
-        agg = PointBranchTrainFn.apply(xyz, dirs.contiguous(), G, fr["support"]["feature"], r, 8, *[p[n] for n in POINT_PARAMS])
+        G, valid_s = MvAggFn.apply(xyz, r, fr["feat_fine_src"], fr["vis_featmaps"], *[p[n] for n in MV_PARAMS])
+        agg = PointBranchFn.apply(xyz, dirs.contiguous(), G, r, 8, fr["support"]["feature"], *[p[n] for n in POINT_PARAMS])
     else:
         G, mvf, mvv, mask1 = _mv_aggregate(p, fr, xyz)
         with torch.no_grad():
@@ -656,7 +595,7 @@ def render_rays_diff(p: Dict[str, Tensor], fr: Dict, rays_o: Tensor, rays_d: Ten
     if frozen and S == r.S:
         geo = UnetFn.apply(agg, r)
     elif hip_train and S == r.S:
-        geo = UnetTrainFn.apply(agg, r, *[p[n] for n in UNET_PARAMS])
+        geo = UnetFn.apply(agg, r, *[p[n] for n in UNET_PARAMS])
     else:
         geo = _ray_unet(p, agg.view(R, S, W).permute(0, 2, 1)).permute(0, 2, 1).reshape(R * S, W)
     sigma = F.softplus(_lin(p, "sigma_mlp.0", geo)).view(R, S)
@@ -667,7 +606,7 @@ def render_rays_diff(p: Dict[str, Tensor], fr: Dict, rays_o: Tensor, rays_d: Ten
         # projection is one small product per frame here, its graph carries those columns' and the maps' share of the gradient
         Cf = fr["feat_fine_src"].shape[-1]
         pmaps = F.linear(fr["feat_fine_src"], p["rgb_blending_mlp.0.weight"][:, W + 3:W + 3 + Cf])
-        rgb_s = BlendTrainFn.apply(xyz, agg, query_pose[:3, 3], pmaps, fr["vis_featmaps"], r, *[p[n] for n in BLEND_PARAMS]).view(R, S, 3)
+        rgb_s = BlendFn.apply(xyz, agg, query_pose[:3, 3], r, pmaps, fr["vis_featmaps"], *[p[n] for n in BLEND_PARAMS]).view(R, S, 3)
     else:
         V = mvf.shape[1]
         ang = _view_angles(xyz, query_pose[:3, 3], fr["topk_poses"][:, :3, 3])

@@ -17,8 +17,8 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _lib
-from ._packing import (MATCHER_HIDDEN, MATCHER_MLP_PARAMS, PackedCache, check_precision, new_train_cache, pack_matcher_mlp, pack_matcher_mlp_train,
-                       require_device)
+from ._packing import (MATCHER_HIDDEN, MATCHER_MLP_PARAMS, PackedCache, check_precision, matcher_mlp_grad_buffers, matcher_mlp_grads_out, new_train_cache,
+                       pack_matcher_mlp, pack_matcher_mlp_train, require_device)
 
 
 def gather_windows(feat_f1, b_ids, j_ids, stride, window=7):
@@ -183,22 +183,18 @@ class _FineMatchFn(torch.autograd.Function):
         M, Cf = f0.shape[0], mod.feat_dim
         need = ctx.needs_input_grad
         with torch.cuda.device(dev):
-            ws_bytes = lib.nl_fine_match_backward_workspace_bytes(M, Cf)
-            if ws_bytes == 0:
-                raise RuntimeError("FineMatching: shape not supported by the training kernels")
-            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+            ws = _lib.workspace(lib.nl_fine_match_backward_workspace_bytes(M, Cf), dev, "FineMatching: shape not supported by the training kernels")
             ge = g_expec.detach().to(torch.float32).contiguous()
             g_f0 = torch.empty_like(f0) if need[2] else None
             g_f1 = torch.empty_like(f1) if need[3] else None
-            params = [mod.get_parameter(n) for n in MATCHER_MLP_PARAMS]
-            g_params = [torch.empty(p.shape, dtype=torch.float32, device=dev) if need[4 + i] else None for i, p in enumerate(params)]
+            params, g_params = matcher_mlp_grad_buffers(mod, need[4:], dev)
             st = torch.cuda.current_stream(dev).cuda_stream
-            ptr = lambda t: None if t is None else t.data_ptr()
+            ptr = _lib.ptr
             _lib.check(lib.nl_fine_match_backward(ctx.packed.data_ptr(), ctx.tpacked.data_ptr(), Cf, _lib.PRECISIONS[mod.precision], f0.data_ptr(), f1.data_ptr(), M,
-                                                  heat.data_ptr(), ge.data_ptr(), ptr(g_f0), ptr(g_f1), *[ptr(g) for g in g_params], ws.data_ptr(), ws_bytes, st),
+                                                  heat.data_ptr(), ge.data_ptr(), ptr(g_f0), ptr(g_f1), *[ptr(g) for g in g_params], ws.data_ptr(), ws.numel(), st),
                        "nl_fine_match_backward")
-        out_params = [None if g is None else g.to(p.dtype) for g, p in zip(g_params, params)]
-        return (None, None, None if g_f0 is None else g_f0.to(ctx.in_dtypes[0]), None if g_f1 is None else g_f1.to(ctx.in_dtypes[1]), *out_params)
+        return (None, None, None if g_f0 is None else g_f0.to(ctx.in_dtypes[0]), None if g_f1 is None else g_f1.to(ctx.in_dtypes[1]),
+                *matcher_mlp_grads_out(params, g_params))
 
 
 class _FineWindowsFn(torch.autograd.Function):
@@ -224,18 +220,16 @@ class _FineWindowsFn(torch.autograd.Function):
         Cout, M = mod.out_channels, j.shape[0]
         need = ctx.needs_input_grad
         with torch.cuda.device(dev):
-            ws_bytes = lib.nl_fine_windows_backward_workspace_bytes(Cf, Cout, B, Hf, Wf, ctx.stride, M)
-            if ws_bytes == 0:
-                raise RuntimeError("FinePreprocess: shape not supported by the training kernels")
-            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+            ws = _lib.workspace(lib.nl_fine_windows_backward_workspace_bytes(Cf, Cout, B, Hf, Wf, ctx.stride, M), dev,
+                                "FinePreprocess: shape not supported by the training kernels")
             go = g_out.detach().to(torch.float32).contiguous()
             g_map = torch.empty_like(nhwc) if need[4] else None
             g_w = torch.empty((Cout, Cf), dtype=torch.float32, device=dev) if need[5] else None
             g_b = torch.empty((Cout,), dtype=torch.float32, device=dev) if need[6] else None
             st = torch.cuda.current_stream(dev).cuda_stream
-            ptr = lambda t: None if t is None else t.data_ptr()
+            ptr = _lib.ptr
             _lib.check(lib.nl_fine_windows_backward(ctx.packed.data_ptr(), ctx.tpacked.data_ptr(), Cf, Cout, _lib.PRECISIONS[mod.precision], nhwc.data_ptr(), B, Hf, Wf,
-                                                    b.data_ptr(), j.data_ptr(), M, ctx.stride, go.data_ptr(), ptr(g_w), ptr(g_b), ptr(g_map), ws.data_ptr(), ws_bytes,
+                                                    b.data_ptr(), j.data_ptr(), M, ctx.stride, go.data_ptr(), ptr(g_w), ptr(g_b), ptr(g_map), ws.data_ptr(), ws.numel(),
                                                     st), "nl_fine_windows_backward")
         return (None, None, None, None, None if g_map is None else g_map.permute(0, 3, 1, 2).to(ctx.in_dtype),
                 None if g_w is None else g_w.to(mod.proj.weight.dtype), None if g_b is None else g_b.to(mod.proj.bias.dtype))
@@ -281,7 +275,7 @@ class FineMatching(nn.Module, PackedCache):
             heat = torch.empty((M, 49), dtype=torch.float32, device=dev) if want_heatmap else None
             st = torch.cuda.current_stream(dev).cuda_stream
             _lib.check(lib.nl_fine_match(packed.data_ptr(), self.feat_dim, _lib.PRECISIONS[self.precision], f0.data_ptr(), f1.data_ptr(), M, kc.data_ptr(),
-                                         expec.data_ptr(), kf.data_ptr(), heat.data_ptr() if want_heatmap else None, st), "nl_fine_match")
+                                         expec.data_ptr(), kf.data_ptr(), _lib.ptr(heat), st), "nl_fine_match")
         return expec, kf, heat, f0, f1, packed
 
     def match(self, feat_f0, feat_f1, mkps2d_c, want_heatmap=False):

@@ -13,7 +13,8 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from ._packing import MATCHER_HIDDEN, MATCHER_MLP_PARAMS, PackedCache, check_precision, pack_matcher_mlp, pack_matcher_mlp_train, require_device
+from ._packing import (MATCHER_HIDDEN, MATCHER_MLP_PARAMS, PackedCache, check_precision, matcher_mlp_grad_buffers, matcher_mlp_grads_out,
+                       pack_matcher_mlp, pack_matcher_mlp_train, require_device)
 
 
 def sigmoid_focal_loss(logits: torch.Tensor, target: torch.Tensor, alpha: float = 0.25, gamma: float = 2.0) -> torch.Tensor:
@@ -49,10 +50,7 @@ class _S2DTrainFn(torch.autograd.Function):
         N, M, Cf = d0.shape[0], d1.shape[0], mod.feat_dim
         with torch.cuda.device(dev):
             packed = mod._packed_weights(dev)
-            ws_bytes = lib.nl_s2d_forward_train_workspace_bytes(N, M, Cf)
-            if ws_bytes == 0:
-                raise RuntimeError("S2DMatching: unsupported shape")
-            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+            ws = _lib.workspace(lib.nl_s2d_forward_train_workspace_bytes(N, M, Cf), dev, "S2DMatching: unsupported shape")
             scores = torch.empty((N, M), dtype=torch.float32, device=dev)
             logits = torch.empty((N, M), dtype=torch.float32, device=dev)
             loss = torch.zeros((), dtype=torch.float32, device=dev)
@@ -63,9 +61,8 @@ class _S2DTrainFn(torch.autograd.Function):
                 raise ValueError(f"S2DMatching: conf_matrix_gt must be ({N}, {M})")
             st = torch.cuda.current_stream(dev).cuda_stream
             _lib.check(lib.nl_s2d_forward_train(packed.data_ptr(), Cf, _lib.PRECISIONS[mod.precision], d0.data_ptr(), N, d1.data_ptr(), M, C.c_float(float(mod.thr)),
-                                                None if tgt is None else tgt.data_ptr(), scores.data_ptr(), logits.data_ptr(),
-                                                None if tgt is None else loss.data_ptr(), match_j.data_ptr(), match_s.data_ptr(), ws.data_ptr(), ws_bytes, st),
-                       "nl_s2d_forward_train")
+                                                _lib.ptr(tgt), scores.data_ptr(), logits.data_ptr(), None if tgt is None else loss.data_ptr(), match_j.data_ptr(),
+                                                match_s.data_ptr(), ws.data_ptr(), ws.numel(), st), "nl_s2d_forward_train")
         ctx.mod, ctx.has_target = mod, tgt is not None
         # the images of the weights this forward ran on: a parameter changed in place before backward() must not meet the saved logits
         ctx.packed, ctx.tpacked = packed, mod._packed_train_weights(dev) if any(ctx.needs_input_grad) else None
@@ -86,25 +83,21 @@ class _S2DTrainFn(torch.autograd.Function):
         N, M, Cf = d0.shape[0], d1.shape[0], mod.feat_dim
         with torch.cuda.device(dev):
             packed, tpacked = ctx.packed, ctx.tpacked
-            ws_bytes = lib.nl_s2d_backward_train_workspace_bytes(N, M, Cf)
-            if ws_bytes == 0:
-                raise RuntimeError("S2DMatching: shape not supported by the training kernels")
-            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+            ws = _lib.workspace(lib.nl_s2d_backward_train_workspace_bytes(N, M, Cf), dev, "S2DMatching: shape not supported by the training kernels")
             g_d0 = torch.empty_like(d0)
             g_d1 = torch.empty_like(d1)
-            params = [mod.get_parameter(n) for n in MATCHER_MLP_PARAMS]
-            g_params = [torch.empty(p.shape, dtype=torch.float32, device=dev) if ctx.needs_input_grad[4 + i] else None for i, p in enumerate(params)]
+            params, g_params = matcher_mlp_grad_buffers(mod, ctx.needs_input_grad[4:], dev)
             gl = None
             if tgt is not None:
                 gl = (torch.zeros((), dtype=torch.float32, device=dev) if g_loss is None else g_loss.detach().to(torch.float32)).reshape(1).contiguous()
             gs = None if g_score is None else g_score.detach().to(torch.float32).contiguous()
             st = torch.cuda.current_stream(dev).cuda_stream
-            ptr = lambda t: None if t is None else t.data_ptr()
+            ptr = _lib.ptr
             _lib.check(lib.nl_s2d_backward_train(packed.data_ptr(), tpacked.data_ptr(), Cf, _lib.PRECISIONS[mod.precision], d0.data_ptr(), N, d1.data_ptr(), M,
                                                  logits.data_ptr(), ptr(tgt), ptr(gl), ptr(gs), g_d0.data_ptr(), g_d1.data_ptr(), *[ptr(g) for g in g_params],
-                                                 ws.data_ptr(), ws_bytes, st), "nl_s2d_backward_train")
-        out_params = [None if g is None else g.to(p.dtype) for g, p in zip(g_params, params)]
-        return (None, None, g_d0.to(ctx.in_dtypes[0]) if ctx.needs_input_grad[2] else None, g_d1.to(ctx.in_dtypes[1]) if ctx.needs_input_grad[3] else None, *out_params)
+                                                 ws.data_ptr(), ws.numel(), st), "nl_s2d_backward_train")
+        return (None, None, g_d0.to(ctx.in_dtypes[0]) if ctx.needs_input_grad[2] else None, g_d1.to(ctx.in_dtypes[1]) if ctx.needs_input_grad[3] else None,
+                *matcher_mlp_grads_out(params, g_params))
 
 
 class S2DMatching(nn.Module, PackedCache):
@@ -163,17 +156,14 @@ class S2DMatching(nn.Module, PackedCache):
         N, M = d0.shape[0], d1.shape[0]
         with torch.cuda.device(dev):
             packed = self._packed_weights(dev)
-            ws_bytes = lib.nl_s2d_min_workspace_bytes(N, M, self.feat_dim, int(want))
-            if ws_bytes == 0:
-                raise RuntimeError("S2DMatching: unsupported shape")
-            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+            ws = _lib.workspace(lib.nl_s2d_min_workspace_bytes(N, M, self.feat_dim, int(want)), dev, "S2DMatching: unsupported shape")
             scores = torch.empty((N, M), dtype=torch.float32, device=dev) if want else None
             match_j = torch.empty(N, dtype=torch.int32, device=dev)
             match_s = torch.empty(N, dtype=torch.float32, device=dev)
             st = torch.cuda.current_stream(dev).cuda_stream
             _lib.check(lib.nl_s2d_match(packed.data_ptr(), self.feat_dim, _lib.PRECISIONS[self.precision], d0.data_ptr(), N, d1.data_ptr(), M,
-                                        C.c_float(float(self.thr)), scores.data_ptr() if want else None, match_j.data_ptr(), match_s.data_ptr(),
-                                        ws.data_ptr(), ws_bytes, st), "nl_s2d_match")
+                                        C.c_float(float(self.thr)), _lib.ptr(scores), match_j.data_ptr(), match_s.data_ptr(), ws.data_ptr(), ws.numel(), st),
+                       "nl_s2d_match")
         return scores, match_j, match_s
 
     def forward(self, desc0, desc1, data):

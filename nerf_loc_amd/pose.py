@@ -83,17 +83,14 @@ def absolute_pose_batch(problems, hypotheses: int = DEFAULT_HYPOTHESES, seed: in
     intr = (C.c_double * (4 * B))(*[v for p in problems for v in _intrinsics(p["K"])])
     thr = (C.c_double * B)(*[float(p["thr"]) for p in problems])
     H = int(hypotheses)
-    need = lib.nl_pnp_workspace_bytes(offsets[B], B, H)
-    if need == 0:
-        raise ValueError(f"absolute_pose: hypotheses must be a multiple of 64 in 64..65536, got {H}")
     with torch.cuda.device(dev):
-        ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        ws = _lib.workspace(lib.nl_pnp_workspace_bytes(offsets[B], B, H), dev, f"absolute_pose: hypotheses must be a multiple of 64 in 64..65536, got {H}", ValueError)
         pose = torch.empty(B, 12, dtype=torch.float64, device=dev)
         mask = torch.empty(max(int(offsets[B]), 1), dtype=torch.uint8, device=dev)
         info = torch.empty(B, 4, dtype=torch.int32, device=dev)
         st = torch.cuda.current_stream(dev).cuda_stream
         _lib.check(lib.nl_pnp_ransac(p2.data_ptr(), p3.data_ptr(), offsets, intr, thr, B, H, int(seed) & 0xFFFFFFFFFFFFFFFF, int(min_inliers), pose.data_ptr(),
-                                     mask.data_ptr(), info.data_ptr(), None, ws.data_ptr(), need, st), "nl_pnp_ransac")
+                                     mask.data_ptr(), info.data_ptr(), None, ws.data_ptr(), ws.numel(), st), "nl_pnp_ransac")
         T, Ti = _transforms(pose)
         inl = mask.bool()
     return [{"T_w2c": T[b], "T_c2w": Ti[b], "inliers": inl[offsets[b]:offsets[b + 1]], "num_inliers": info[b, 1], "success": info[b, 0],

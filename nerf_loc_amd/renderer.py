@@ -15,10 +15,6 @@ import torch
 from . import _lib as L
 
 
-def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
-    return None if t is None else t.data_ptr()
-
-
 def _dev_f32(t, device) -> torch.Tensor:
     t = torch.as_tensor(t)
     return t.to(device=device, dtype=torch.float32).contiguous()
@@ -132,7 +128,7 @@ class GraphedRender:
 
     def _call(self):
         r = self.r
-        L.check(r.lib.nl_render_rays_ex(ct.byref(r.cfg), r.packed.data_ptr(), r._frame, None, self.o.data_ptr(), self.d.data_ptr(), _ptr(self.z), self.R,
+        L.check(r.lib.nl_render_rays_ex(ct.byref(r.cfg), r.packed.data_ptr(), r._frame, None, self.o.data_ptr(), self.d.data_ptr(), L.ptr(self.z), self.R,
                                         1 if self.white else 0, ct.byref(self.ro), self.ws.data_ptr(), self.ws.numel(), r._stream(), ct.byref(self.opts)), "nl_render_rays")
 
     def run(self, o, d, q_rows, z, clone: bool = True):
@@ -196,8 +192,8 @@ class TrainGrads:
         self._scratch = torch.empty(nb, dtype=torch.uint8, device=dev)
         self.c = L.NlTrainGrads()
         self.c.weights = ct.cast(self._arr, ct.POINTER(ct.c_void_p))
-        self.c.support_feature = _ptr(self.support_feature)
-        self.c.feat_maps, self.c.vis_featmaps, self.c.blend_feat_maps = _ptr(self.feat_maps), _ptr(self._vis_hwc), _ptr(self.blend_feat_maps)
+        self.c.support_feature = L.ptr(self.support_feature)
+        self.c.feat_maps, self.c.vis_featmaps, self.c.blend_feat_maps = L.ptr(self.feat_maps), L.ptr(self._vis_hwc), L.ptr(self.blend_feat_maps)
         self.c.scratch = self._scratch.data_ptr()
         self.c.scratch_bytes = nb
 
@@ -509,7 +505,7 @@ class HipRenderer:
         if precision_guard:
             opts.flags |= L.RENDER_PRECISION_GUARD
         L.check(self.lib.nl_render_rays_ex(ct.byref(self.cfg), self.packed.data_ptr(), self._frame, None if per_ray else qc.data_ptr(), o.data_ptr(),
-                                           d.data_ptr(), _ptr(z), R, int(bool(white_bkgd)), ct.byref(ro), ws.data_ptr(), ws.numel(), self._stream(),
+                                           d.data_ptr(), L.ptr(z), R, int(bool(white_bkgd)), ct.byref(ro), ws.data_ptr(), ws.numel(), self._stream(),
                                            ct.byref(opts) if (early_term_eps > 0 or per_ray or not side_stream or precision_guard) else None), "nl_render_rays")
         out["mask"] = out["mask"].view(torch.bool)   # 0 / 1 bytes reinterpreted: no conversion kernel
         if "sigma" in out:
@@ -532,7 +528,7 @@ class HipRenderer:
         z = None if z_vals is None else _dev_f32(z_vals, self.device)
         zo = torch.empty(R, self.S, device=self.device)
         xyz = torch.empty(R * self.S, 3, device=self.device)
-        L.check(self.lib.nl_sample_points(o.data_ptr(), d.data_ptr(), R, self.S, self.near, self.far, _ptr(z), zo.data_ptr(), xyz.data_ptr(), self._stream()), "nl_sample_points")
+        L.check(self.lib.nl_sample_points(o.data_ptr(), d.data_ptr(), R, self.S, self.near, self.far, L.ptr(z), zo.data_ptr(), xyz.data_ptr(), self._stream()), "nl_sample_points")
         return zo, xyz
 
     def mv_aggregate(self, xyz, query_center, want_raw: bool = True, want_blend: bool = False):
@@ -573,7 +569,7 @@ class HipRenderer:
         idx = torch.empty(N, K, dtype=torch.int32, device=self.device)
         d2 = torch.empty(N, K, device=self.device)
         ws = self._workspace(self.lib.nl_point_mlp_workspace_bytes(ct.byref(self.cfg), N))
-        L.check(self.lib.nl_point_mlp(ct.byref(self.cfg), self.packed.data_ptr(), self._frame, x.data_ptr(), _ptr(dr), 0 if dr is None else dr.shape[1],
+        L.check(self.lib.nl_point_mlp(ct.byref(self.cfg), self.packed.data_ptr(), self._frame, x.data_ptr(), L.ptr(dr), 0 if dr is None else dr.shape[1],
                                       g.data_ptr(), N, K, fa.data_ptr(), idx.data_ptr(), d2.data_ptr(), ws.data_ptr(), ws.numel(), self._stream()), "nl_point_mlp")
         return fa, d2, idx
 
@@ -592,7 +588,7 @@ class HipRenderer:
         qc, qrows = self._centres(query_center, R)
         cots = [None if t is None else _dev_f32(t, dev) for t in (g_rgb, g_depth, g_depth_uncertainty, g_feat, g_weights)]
         c = L.NlRenderCotangents()
-        c.g_rgb, c.g_depth, c.g_depth_uncertainty, c.g_feat, c.g_weights = [_ptr(t) for t in cots]
+        c.g_rgb, c.g_depth, c.g_depth_uncertainty, c.g_feat, c.g_weights = [L.ptr(t) for t in cots]
         if knn is not None:   # (d2, idx) of the forward call: saves the second neighbour search
             kd2, kidx = knn[0].contiguous(), knn[1].to(torch.int32).contiguous()
             c.knn_d2, c.knn_idx = kd2.data_ptr(), kidx.data_ptr()
@@ -602,8 +598,8 @@ class HipRenderer:
             workspace_rays = getattr(self, "backward_rays_per_chunk", None)   # None: the library's default (~64 k samples per chunk, ~90 KB each at W = 256)
         ws = self._workspace(self.lib.nl_render_rays_backward_workspace_bytes(ct.byref(self.cfg), self.V, R if workspace_rays is None else int(workspace_rays),
                                                                               0 if train is None else 1))
-        L.check(self.lib.nl_render_rays_backward(ct.byref(self.cfg), self.packed.data_ptr(), self._frame, _ptr(qc), _ptr(qrows), o.data_ptr(), d.data_ptr(), z.data_ptr(), R,
-                                                 1 if white_bkgd else 0, ct.byref(c), go.data_ptr(), gd.data_ptr(), _ptr(gq),
+        L.check(self.lib.nl_render_rays_backward(ct.byref(self.cfg), self.packed.data_ptr(), self._frame, L.ptr(qc), L.ptr(qrows), o.data_ptr(), d.data_ptr(), z.data_ptr(), R,
+                                                 1 if white_bkgd else 0, ct.byref(c), go.data_ptr(), gd.data_ptr(), L.ptr(gq),
                                                  None if train is None else ct.byref(train.c), ws.data_ptr(), ws.numel(), self._stream()),
                 "nl_render_rays_backward")
         return go, gd, (None if gq is None else gq.sum(0))
@@ -649,7 +645,7 @@ class HipRenderer:
             bh = L.NlBetaHead()
             bh.weight, bh.bias, bh.beta_min, bh.beta = bw.data_ptr(), bb.data_ptr(), float(beta_min), out["beta"].data_ptr()
             bkeep = (bw, bb, float(beta_min))
-        L.check(self.lib.nl_render_rays_forward_keep(ct.byref(self.cfg), self.packed.data_ptr(), self._frame, _ptr(qc), _ptr(qrows), o.data_ptr(), d.data_ptr(), z.data_ptr(), R,
+        L.check(self.lib.nl_render_rays_forward_keep(ct.byref(self.cfg), self.packed.data_ptr(), self._frame, L.ptr(qc), L.ptr(qrows), o.data_ptr(), d.data_ptr(), z.data_ptr(), R,
                                                      1 if white_bkgd else 0, ct.byref(ro), None if bh is None else ct.byref(bh), 1 if train else 0, ws.data_ptr(),
                                                      ws.numel(), self._stream()), "nl_render_rays_forward_keep")
         out["mask"] = out["mask"].view(torch.bool)
@@ -665,7 +661,7 @@ class HipRenderer:
         dev = self.device
         cots = [None if t is None else _dev_f32(t, dev) for t in (g_rgb, g_depth, g_depth_uncertainty, g_feat, g_weights)]
         c = L.NlRenderCotangents()
-        c.g_rgb, c.g_depth, c.g_depth_uncertainty, c.g_feat, c.g_weights = [_ptr(t) for t in cots]
+        c.g_rgb, c.g_depth, c.g_depth_uncertainty, c.g_feat, c.g_weights = [L.ptr(t) for t in cots]
         go, gd = torch.empty(R, 3, device=dev), torch.empty(R, 3, device=dev)
         gq = torch.empty(R, 3, device=dev) if want_g_query_center else None
         bh, gbw, gbb = None, None, None
@@ -676,8 +672,8 @@ class HipRenderer:
             if want_beta_grads and train is not None:
                 gbw, gbb = torch.zeros(1, self.W, device=dev), torch.zeros(1, device=dev)
                 bh.g_weight, bh.g_bias = gbw.data_ptr(), gbb.data_ptr()
-        L.check(self.lib.nl_render_rays_backward_kept(ct.byref(self.cfg), self.packed.data_ptr(), self._frame, _ptr(qc), _ptr(qrows), d.data_ptr(), R, 1 if white else 0,
-                                                      ct.byref(c), None if bh is None else ct.byref(bh), go.data_ptr(), gd.data_ptr(), _ptr(gq),
+        L.check(self.lib.nl_render_rays_backward_kept(ct.byref(self.cfg), self.packed.data_ptr(), self._frame, L.ptr(qc), L.ptr(qrows), d.data_ptr(), R, 1 if white else 0,
+                                                      ct.byref(c), None if bh is None else ct.byref(bh), go.data_ptr(), gd.data_ptr(), L.ptr(gq),
                                                       None if train is None else ct.byref(train.c), ws.data_ptr(), ws.numel(), self._stream()),
                 "nl_render_rays_backward_kept")
         res = (go, gd, (None if gq is None else gq.sum(0)))
@@ -708,6 +704,20 @@ class HipRenderer:
             ent = reg[key] = GraphedKeep(self, R, white_bkgd)
         return ent
 
+    def _stage_backward(self, stage: str, frozen_sizer: str, size_args, chunk_args, args, train: "TrainGrads"):
+        """The library call of one stage's backward wrapper: `nl_<stage>_backward`, or with `train` its `_train` twin, which takes the same arguments with the
+        nl_train_grads pointer in front of the workspace (in the library the frozen entry point is the `_train` one with a null pointer; both are called by name
+        here, so an error names the entry point the caller asked for).  The workspace comes from the entry point's own sizer — `frozen_sizer`, or
+        `nl_<stage>_backward_train_workspace_bytes`: their chunk caps differ — and is cut to that sizer's answer for `chunk_args` when those are given
+        (tests: a workspace for fewer rows than the call's makes the entry point walk them in chunks)."""
+        name = f"nl_{stage}_backward" + ("" if train is None else "_train")
+        sizer = getattr(self.lib, frozen_sizer if train is None else name + "_workspace_bytes")
+        ws = self._workspace(sizer(ct.byref(self.cfg), *size_args))
+        if chunk_args is not None:
+            ws = ws[: sizer(ct.byref(self.cfg), *chunk_args)]
+        grads = () if train is None else (ct.byref(train.c),)
+        L.check(getattr(self.lib, name)(ct.byref(self.cfg), self.packed.data_ptr(), *args, *grads, ws.data_ptr(), ws.numel(), self._stream()), name)
+
     def ray_unet_backward(self, x, g_geo, workspace_rays: Optional[int] = None, train: "TrainGrads" = None):
         """Input gradient of `ray_unet` (nl_ray_unet_backward): x, g_geo (R*S, W) -> g_x (R*S, W).  train: also ADD the gradients of the 28 U-Net tensors
         into that TrainGrads (nl_ray_unet_backward_train)."""
@@ -716,16 +726,8 @@ class HipRenderer:
         xin, g = _dev_f32(x, self.device), _dev_f32(g_geo, self.device)
         R = xin.shape[0] // self.S
         gx = torch.empty_like(xin)
-        wsb = self.lib.nl_ray_unet_backward_workspace_bytes if train is None else self.lib.nl_ray_unet_backward_train_workspace_bytes
-        ws = self._workspace(wsb(ct.byref(self.cfg), R))
-        if workspace_rays is not None:
-            ws = ws[: wsb(ct.byref(self.cfg), int(workspace_rays))]
-        if train is not None:
-            L.check(self.lib.nl_ray_unet_backward_train(ct.byref(self.cfg), self.packed.data_ptr(), xin.data_ptr(), R, g.data_ptr(), gx.data_ptr(), ct.byref(train.c),
-                                                        ws.data_ptr(), ws.numel(), self._stream()), "nl_ray_unet_backward_train")
-            return gx
-        L.check(self.lib.nl_ray_unet_backward(ct.byref(self.cfg), self.packed.data_ptr(), xin.data_ptr(), R, g.data_ptr(), gx.data_ptr(), ws.data_ptr(), ws.numel(),
-                                              self._stream()), "nl_ray_unet_backward")
+        self._stage_backward("ray_unet", "nl_ray_unet_backward_workspace_bytes", (R,), None if workspace_rays is None else (int(workspace_rays),),
+                             (xin.data_ptr(), R, g.data_ptr(), gx.data_ptr()), train)
         return gx
 
     def mv_aggregate_backward(self, xyz, g_mv_feat, workspace_samples: Optional[int] = None, train: "TrainGrads" = None):
@@ -735,16 +737,9 @@ class HipRenderer:
         x, g = _dev_f32(xyz, self.device), _dev_f32(g_mv_feat, self.device)
         N = x.shape[0]
         gx = torch.empty(N, 3, device=self.device)
-        wsb = self.lib.nl_mv_aggregate_backward_workspace_bytes if train is None else self.lib.nl_mv_aggregate_backward_train_workspace_bytes
-        ws = self._workspace(wsb(ct.byref(self.cfg), self.V, N))
-        if workspace_samples is not None:
-            ws = ws[: wsb(ct.byref(self.cfg), self.V, int(workspace_samples))]
-        if train is not None:
-            L.check(self.lib.nl_mv_aggregate_backward_train(ct.byref(self.cfg), self.packed.data_ptr(), self._frame, x.data_ptr(), N, g.data_ptr(), gx.data_ptr(),
-                                                            ct.byref(train.c), ws.data_ptr(), ws.numel(), self._stream()), "nl_mv_aggregate_backward_train")
-            return gx
-        L.check(self.lib.nl_mv_aggregate_backward(ct.byref(self.cfg), self.packed.data_ptr(), self._frame, x.data_ptr(), N, g.data_ptr(), gx.data_ptr(),
-                                                  ws.data_ptr(), ws.numel(), self._stream()), "nl_mv_aggregate_backward")
+        self._stage_backward("mv_aggregate", "nl_mv_aggregate_backward_workspace_bytes", (self.V, N),
+                             None if workspace_samples is None else (self.V, int(workspace_samples)),
+                             (self._frame, x.data_ptr(), N, g.data_ptr(), gx.data_ptr()), train)
         return gx
 
     def blend(self, xyz, query_center, feature_agg):
@@ -770,17 +765,9 @@ class HipRenderer:
         gx = torch.empty(N, 3, device=self.device)
         gfa = torch.empty(N, self.W, device=self.device)
         gq = torch.empty(N, 3, device=self.device) if want_g_query_center else None
-        wsb = self.lib.nl_blend_workspace_bytes if train is None else self.lib.nl_blend_backward_train_workspace_bytes
-        ws = self._workspace(wsb(ct.byref(self.cfg), self.V, N))
-        if workspace_samples is not None:
-            ws = ws[: wsb(ct.byref(self.cfg), self.V, int(workspace_samples))]
-        if train is not None:
-            L.check(self.lib.nl_blend_backward_train(ct.byref(self.cfg), self.packed.data_ptr(), self._frame, qc.data_ptr(), x.data_ptr(), fa.data_ptr(), N,
-                                                     g.data_ptr(), gx.data_ptr(), gfa.data_ptr(), _ptr(gq), ct.byref(train.c), ws.data_ptr(), ws.numel(),
-                                                     self._stream()), "nl_blend_backward_train")
-            return gx, gfa, (None if gq is None else gq.sum(0))
-        L.check(self.lib.nl_blend_backward(ct.byref(self.cfg), self.packed.data_ptr(), self._frame, qc.data_ptr(), x.data_ptr(), fa.data_ptr(), N, g.data_ptr(),
-                                           gx.data_ptr(), gfa.data_ptr(), _ptr(gq), ws.data_ptr(), ws.numel(), self._stream()), "nl_blend_backward")
+        # (the frozen entry point shares the forward stage's sizer)
+        self._stage_backward("blend", "nl_blend_workspace_bytes", (self.V, N), None if workspace_samples is None else (self.V, int(workspace_samples)),
+                             (self._frame, qc.data_ptr(), x.data_ptr(), fa.data_ptr(), N, g.data_ptr(), gx.data_ptr(), gfa.data_ptr(), L.ptr(gq)), train)
         return gx, gfa, (None if gq is None else gq.sum(0))
 
     # ------------------------------------------------------------------ training: weight gradients
@@ -807,19 +794,10 @@ class HipRenderer:
         gx = torch.empty(N, 3, device=dev)
         gd = None if dr is None else torch.empty(N, 3, device=dev)
         gg = torch.empty(N, self.W, device=dev)
-        wsb = self.lib.nl_point_mlp_backward_workspace_bytes if train is None else self.lib.nl_point_mlp_backward_train_workspace_bytes
-        ws = self._workspace(wsb(ct.byref(self.cfg), N))
-        if workspace_samples is not None:   # (tests: a workspace for fewer samples than N makes the entry point walk N in chunks)
-            ws = ws[: wsb(ct.byref(self.cfg), int(workspace_samples))]
         d2, idx = (None, None) if knn is None else (knn[0].contiguous(), knn[1].to(torch.int32).contiguous())
-        if train is not None:
-            L.check(self.lib.nl_point_mlp_backward_train(ct.byref(self.cfg), self.packed.data_ptr(), self._frame, x.data_ptr(), _ptr(dr), 0 if dr is None else dr.shape[1],
-                                                         g.data_ptr(), N, K, _ptr(idx), _ptr(d2), gy.data_ptr(), gx.data_ptr(), _ptr(gd), gg.data_ptr(),
-                                                         ct.byref(train.c), ws.data_ptr(), ws.numel(), self._stream()), "nl_point_mlp_backward_train")
-            return gx, gd, gg
-        L.check(self.lib.nl_point_mlp_backward(ct.byref(self.cfg), self.packed.data_ptr(), self._frame, x.data_ptr(), _ptr(dr), 0 if dr is None else dr.shape[1],
-                                               g.data_ptr(), N, K, _ptr(idx), _ptr(d2), gy.data_ptr(), gx.data_ptr(), _ptr(gd), gg.data_ptr(), ws.data_ptr(),
-                                               ws.numel(), self._stream()), "nl_point_mlp_backward")
+        self._stage_backward("point_mlp", "nl_point_mlp_backward_workspace_bytes", (N,), None if workspace_samples is None else (int(workspace_samples),),
+                             (self._frame, x.data_ptr(), L.ptr(dr), 0 if dr is None else dr.shape[1], g.data_ptr(), N, K, L.ptr(idx), L.ptr(d2), gy.data_ptr(),
+                              gx.data_ptr(), L.ptr(gd), gg.data_ptr()), train)
         return gx, gd, gg
 
     def hierarchical_depths(self, pixel_coordinates, K, pose, z_base, u, n_coarse: int = 64, near=None, far=None, lindisp: bool = False):
@@ -908,7 +886,7 @@ class HipRenderer:
             setattr(ro, k, t.data_ptr())
         ws = self._workspace(self.lib.nl_heads_composite_workspace_bytes(ct.byref(self.cfg), V, R))
         L.check(self.lib.nl_heads_composite(ct.byref(self.cfg), self.packed.data_ptr(), V, z.data_ptr(), fa.data_ptr(), g.data_ptr(), b1.data_ptr(), rv.data_ptr(),
-                                            _ptr(vs), R, int(bool(white_bkgd)), ct.byref(ro), ws.data_ptr(), ws.numel(), self._stream()), "nl_heads_composite")
+                                            L.ptr(vs), R, int(bool(white_bkgd)), ct.byref(ro), ws.data_ptr(), ws.numel(), self._stream()), "nl_heads_composite")
         out["mask"] = out["mask"].view(torch.bool)
         return out
 
@@ -963,7 +941,7 @@ def render_rays_multi(jobs):
             opts.ray_centers = qc_t.data_ptr()
         a = arr[i]
         a.frame, a.query_center = r._frame, (None if per_ray else qc_t.data_ptr())
-        a.rays_o, a.rays_d, a.z_vals, a.R = o.data_ptr(), d.data_ptr(), _ptr(z), R
+        a.rays_o, a.rays_d, a.z_vals, a.R = o.data_ptr(), d.data_ptr(), L.ptr(z), R
         a.out, a.ws, a.ws_bytes, a.opts = ct.pointer(ro), ws.data_ptr(), ws.numel(), ct.pointer(opts)
         keep.append((o, d, z, qc_t, ro, opts, ws))
         outs.append(out)

@@ -114,7 +114,7 @@ class _TrainStep(torch.autograd.Function):
             gin = [torch.empty_like(a[i]) if need[3 + i] else None for i in range(4)]
             gpar = [torch.empty(shape, dtype=torch.float32, device=dev) if need[7 + i] and i not in _UNUSED_PARAMS else None
                     for i, (shape, _) in enumerate(ctx.param_meta)]
-            ptr = lambda t: None if t is None else t.data_ptr()
+            ptr = _lib.ptr
             arr = (ctypes.c_void_p * len(gpar))(*[ptr(t) for t in gpar])
             wb = lib.nl_sct_backward_workspace_bytes(B, N0, N1, C, Fh)
             ws = torch.empty(wb, dtype=torch.uint8, device=dev)
@@ -241,13 +241,11 @@ class SelfCrossTransformer(nn.Module, PackedCache):
             if N0 < 1 or N1 < 1:
                 raise ValueError("SelfCrossTransformer: both sequences need at least one element")
             a = [t.detach().to(torch.float32).contiguous() for t in ts]   # the one copy of a non-contiguous input
-            need = lib.nl_sct_workspace_bytes(B, N0, N1, C, self.dim_feedforward)
-            if need == 0:
-                raise RuntimeError(f"SelfCrossTransformer: B * max(N0, N1) = {B * max(N0, N1)} exceeds the kernels' limit of 2^24 rows")
-            ws = torch.empty(need, dtype=torch.uint8, device=dev)
+            ws = _lib.workspace(lib.nl_sct_workspace_bytes(B, N0, N1, C, self.dim_feedforward), dev,
+                                f"SelfCrossTransformer: B * max(N0, N1) = {B * max(N0, N1)} exceeds the kernels' limit of 2^24 rows")
             st = torch.cuda.current_stream(dev).cuda_stream
             _lib.check(lib.nl_sct_forward(packed.data_ptr(), C, self.nhead, self.dim_feedforward, _lib.PRECISIONS[self.precision], a[0].data_ptr(), a[1].data_ptr(),
-                                          N0, a[2].data_ptr(), a[3].data_ptr(), N1, B, out0.data_ptr(), out1.data_ptr(), ws.data_ptr(), need, st), "nl_sct_forward")
+                                          N0, a[2].data_ptr(), a[3].data_ptr(), N1, B, out0.data_ptr(), out1.data_ptr(), ws.data_ptr(), ws.numel(), st), "nl_sct_forward")
         return out0, out1
 
     def forward(self, v0, pos_embed0, v1, pos_embed1):

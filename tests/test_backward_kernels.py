@@ -429,7 +429,7 @@ def test_blend_weight_gradients_match_autograd(case, precision, chunk):
     pp = {k: v.detach().clone().requires_grad_(k in names) for k, v in p.items()}
     feat, vis = fr["feat_fine_src"].detach().clone().requires_grad_(True), fr["vis_featmaps"].detach().clone().requires_grad_(True)
     pmaps = F.linear(feat, pp["rgb_blending_mlp.0.weight"][:, W + 3:W + 3 + C])
-    out = dr.BlendTrainFn.apply(xyz, fa, qc, pmaps, vis, r, *[pp[n] for n in names])
+    out = dr.BlendFn.apply(xyz, fa, qc, r, pmaps, vis, *[pp[n] for n in names])
     gs = torch.autograd.grad((out * cot).sum(), [pp[n] for n in names] + [feat, vis])
     got = dict(zip(names + ["feat_fine_src", "vis_featmaps"], gs))
     _assert_param_grads(got, ref32, ref64, 3e-4, f"{case}/{precision}", exact_forward=True)
@@ -463,6 +463,44 @@ def test_ray_unet_weight_gradients_match_autograd(case, precision, chunk):
     gx = r.ray_unet_backward(x, cot, train=tg, workspace_rays=chunk)
     assert torch.equal(gx, r.ray_unet_backward(x, cot, workspace_rays=chunk))
     _assert_param_grads({k: v.clone() for k, v in tg.weights.items()}, ref32, ref64, 3e-4, f"{case}/{precision}", exact_forward=True)
+
+
+@pytest.mark.gpu
+def test_stage_nodes_given_frozen_parameters_take_the_training_entry_point():
+    """A stage node takes the library's training entry point iff it was GIVEN parameter tensors, not iff one of them requires grad: with every parameter, map
+    and support tensor frozen, the input gradients are bit for bit those of the same call with parameters that require grad (the frozen entry point's differ in
+    the last bits for the aggregation and the neural-point branch: other kernels, see the two tests above), and no parameter receives a gradient.  The smallest
+    scene; the nodes have no chunk argument, their calls hold the whole batch."""
+    import torch.nn.functional as F
+    from tests.golden_cases import build_case
+    cfg, r, p, fr, xyz, pose = _mv_setup("tiny_full", "fp32")
+    dev, N, W = xyz.device, xyz.shape[0], cfg.W
+    g = torch.Generator().manual_seed(23)
+    rnd = lambda *shape: torch.randn(*shape, generator=g).to(dev)
+    G, fa, dirs, x = rnd(N, W), rnd(N, W), F.normalize(rnd(N, 3), dim=1), rnd(4 * cfg.S_total, W)
+    sp_feat = torch.from_numpy(np.ascontiguousarray(build_case("tiny_full")["frame"]["support_fine"]["feature"])).to(dev)
+    feat, vis = fr["feat_fine_src"], fr["vis_featmaps"]
+    pmaps = F.linear(feat, p["rgb_blending_mlp.0.weight"][:, W + 3:W + 3 + cfg.C])
+    nodes = [("point", dr.POINT_PARAMS, [xyz, dirs, G], lambda i, ps: dr.PointBranchFn.apply(*i, r, 8, sp_feat, *ps)),
+             ("mv", dr.MV_PARAMS, [xyz], lambda i, ps: dr.MvAggFn.apply(*i, r, feat, vis, *ps)[0]),
+             ("unet", dr.UNET_PARAMS, [x], lambda i, ps: dr.UnetFn.apply(*i, r, *ps)),
+             ("blend", dr.BLEND_PARAMS, [xyz, fa, pose[:3, 3]], lambda i, ps: dr.BlendFn.apply(*i, r, pmaps, vis, *ps))]
+
+    def run(fn, inputs, names, train):
+        ins = [t.detach().clone().requires_grad_(True) for t in inputs]
+        ps = [p[n].detach().clone().requires_grad_(train) for n in names]
+        out = fn(ins, ps)
+        cot = torch.randn(out.shape, generator=torch.Generator().manual_seed(7)).to(dev)
+        (out * cot).sum().backward()
+        return [t.grad for t in ins], [t.grad for t in ps]
+    for what, names, inputs, fn in nodes:
+        gi_frozen, gp_frozen = run(fn, inputs, names, False)
+        gi_train, gp_train = run(fn, inputs, names, True)
+        assert all(gp is None for gp in gp_frozen), what
+        assert all(gp is not None for gp in gp_train), what
+        for a, b in zip(gi_frozen, gi_train):
+            assert a is not None and torch.equal(a, b), what
+    assert all(t.grad is None for t in (sp_feat, feat, vis, pmaps))
 
 
 def _view_count_case(name):

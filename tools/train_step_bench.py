@@ -1,6 +1,6 @@
 """Time the render part of one training step (compute_render_loss, model.py:641-685: N_rand = 1024 rays x 64 samples, forward + backward to
 every parameter of the ray path, the feature maps, the DepthFusionNet maps and the support table) on the gradient path of the drop-in, with the
-library's training nodes (diff_render.*TrainFn) against the all-eager fp32 graph.  python tools/train_step_bench.py [rays] [samples] [W] [steps]"""
+library's training nodes (diff_render's stage nodes, given their parameter tensors) against the all-eager fp32 graph.  python tools/train_step_bench.py [rays] [samples] [W] [steps]"""
 import gc, os, sys, time
 import numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
