@@ -111,8 +111,10 @@ class FinePreprocess(nn.Module, PackedCache):
         parity mode computes them in exact fp32 (119 us instead of 79 us at the shipped size); the backward products stay three-term split-bf16."""
         return "fp32" if self.precision == "bf16x3" else self.precision
 
-    def _windows_call(self, feat_f1, b_ids, j_ids, stride, precision=None):
-        """nl_fine_windows: (out (M, 49, out_channels), the NHWC map it read, b, j as int64 device tensors, the packed image)."""
+    def _windows_call(self, feat_f1, b_ids, j_ids, stride, precision=None, check_ids=True):
+        """nl_fine_windows: (out (M, 49, out_channels), the NHWC map it read, b, j as int64 device tensors, the packed image).
+        check_ids=False (internal: Matcher.forward_padded, whose ids come from the library's own selection over this map's grid, checked there against the number
+        of coarse cells) skips the host range check and with it the read-back."""
         require_device("FinePreprocess", feat_f1)
         if self.W != 7:
             raise RuntimeError("FinePreprocess: the HIP kernel is built for fine_window_size 7")
@@ -130,7 +132,7 @@ class FinePreprocess(nn.Module, PackedCache):
             _lib.check(_lib.NL_ERR_BAD_ARG, "nl_fine_windows (stride / id shapes)")
         L = ((Hf - 1) // stride + 1) * ((Wf - 1) // stride + 1)
         # entry points validate from the host (the kernel only keeps a bad id from reading foreign memory)
-        if M and bool(((j < 0) | (j >= L) | (b < 0) | (b >= B)).any()):   # one reduction, one read-back
+        if check_ids and M and bool(((j < 0) | (j >= L) | (b < 0) | (b >= B)).any()):   # one reduction, one read-back
             _lib.check(_lib.NL_ERR_BAD_ARG, f"nl_fine_windows (j_ids outside [0, {L}) or b_ids outside [0, {B}))")
         lib = _lib.load()
         with torch.cuda.device(dev):
