@@ -258,12 +258,19 @@ int nl_heads_composite(const nl_config* cfg, const void* packed, int V, const fl
                        int64_t R, int white_bkgd, const nl_render_out* out, void* ws, size_t ws_bytes, void* stream);
 
 /* a20 (hierarchical): coarse NeuRay weights (R,Sc) for z_coarse (R,Sc) along un-normalised K^-1[u,v,1] rays, Sc <= 64.
- * query_w2c_kinv HOST 12+9 floats: inv(pose)[:3] (3x4 row-major) then inv(K) (3x3). */
+ * query_w2c_kinv HOST 12+9 floats: inv(pose)[:3] (3x4 row-major) then inv(K) (3x3).  z_coarse holds one row PER RAY (rows may differ), each strictly
+ * increasing.  depth_coarse (R) = sum(weights * z_coarse) may be NULL; weights are the same bits either way.  A sample that no view sees takes the ground
+ * state alpha = sigmoid(-15).  Contract, checked before the workspace is looked at: 3 <= Sc <= 64 — Sc < 3: NL_ERR_BAD_ARG, Sc > 64: NL_ERR_UNSUPPORTED;
+ * R == 0: NL_OK, nothing is read; precision NL_PREC_F32 runs per-lane fp32 decoders, every other one the split-fp16 MFMA decoders. */
 size_t nl_coarse_weights_workspace_bytes(int V, int64_t R, int Sc);
 int nl_coarse_weights(const nl_config* cfg, const void* packed, const nl_frame* frame, const float* query_w2c_kinv,
                       const float* pixel_coordinates, const float* z_coarse, int64_t R, int Sc, float* weights,
                       float* depth_coarse, void* ws, size_t ws_bytes, void* stream);
-/* inverse-CDF sampling with caller-provided uniforms u (R,Ni), merged with z_base (R,Sb) and sorted -> z_out (R,Sb+Ni). */
+/* inverse-CDF sampling with caller-provided uniforms u (R,Ni) in [0, 1), merged with z_base (R,Sb) and sorted -> z_out (R,Sb+Ni).  The pdf is
+ * weights_coarse[:, 1:-1] + 1e-5 over the Sc - 1 mid-points of z_coarse; a bin whose cdf step is below 1e-5 returns its lower mid-point (utils.py:73-112).
+ * z_base needs no order; the merge is exact (the output holds the bits of z_base and of the samples, ascending); every pointer must be non-NULL, z_base too
+ * when Sb == 0.  Contract, checked before any launch: Sb >= 0, Ni >= 1, Sb + Ni >= 1, Sc >= 3, else NL_ERR_BAD_ARG; Sb + Ni <= 256 and Sc <= 64, else
+ * NL_ERR_UNSUPPORTED (one wave sorts a ray's keys in a 256-entry network; one coarse sample per lane).  R == 0: NL_OK, nothing is read. */
 int nl_sample_pdf(const float* z_coarse, const float* weights_coarse, int Sc, const float* u, int Ni,
                   const float* z_base, int Sb, int64_t R, float* z_out, void* stream);
 

@@ -640,6 +640,8 @@ int nl_coarse_weights(const nl_config* cfg, const void* packed, const nl_frame* 
   NL_EFF_CFG(cfg);
   if (R == 0) return NL_OK;   // empty batch: nothing to do, data pointers may be null
   if (!cfg_ok(cfg) || !packed || !f || !w2c_kinv || !pix || !zc || !weights || !ws || R < 0) return NL_ERR_BAD_ARG;
+  if (Sc < 3) return NL_ERR_BAD_ARG;           // the resampling drops both ends of a row: fewer than 3 samples leave no bin
+  if (Sc > 64) return NL_ERR_UNSUPPORTED;      // coarse_ray_kernel: one sample per lane
   if (ws_bytes < nl_coarse_weights_workspace_bytes(f->views.V, R, Sc)) return NL_ERR_WORKSPACE;
   const size_t part = nl_align_up((size_t)f->views.V * R * Sc * 4, 256);
   float* wa = (float*)ws; float* wv = (float*)((char*)ws + part); float* wm = (float*)((char*)ws + 2 * part);
@@ -652,6 +654,9 @@ int nl_sample_pdf(const float* zc, const float* wc, int Sc, const float* u, int 
                   void* stream) {
   if (R == 0) return NL_OK;   // empty batch: nothing to do, data pointers may be null
   if (!zc || !wc || !u || !zb || !z_out || R < 0) return NL_ERR_BAD_ARG;
+  // before any launch: sample_pdf_kernel writes s_sort[Sb + i], a negative Sb would land below the array
+  if (Sb < 0 || Ni < 1 || (int64_t)Sb + Ni < 1 || Sc < 3) return NL_ERR_BAD_ARG;
+  if ((int64_t)Sb + Ni > 256 || Sc > 64) return NL_ERR_UNSUPPORTED;   // one wave sorts a ray's 256 keys in LDS; one coarse sample per lane
   return nl_launch_sample_pdf(zc, wc, Sc, u, Ni, zb, Sb, R, z_out, (hipStream_t)stream);
 }
 
