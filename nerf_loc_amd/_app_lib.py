@@ -1,35 +1,26 @@
 """ctypes binding of libnerfloc_app.so (C-ABI in include/nerfloc_app.h): appearance adaptation — channel statistics, the adaptation MLP, FiLM and its gradients.
 
-Built by the same `make` as libnerfloc_render.so (`_lib.build()`), loaded after torch for the same reason, and it speaks `_lib`'s conventions: `_lib.check` for
-the NL_* status codes, `_lib.workspace` for `*_workspace_bytes` answers.  No fallback: a missing library or symbol raises.
+Built by the same `make` as libnerfloc_render.so (`_lib.build()`), bound from its header by the same layer (`_cabi.bind`), and it speaks `_lib`'s conventions:
+`_lib.check` for the NL_* status codes, `_lib.workspace` for `*_workspace_bytes` answers.  No fallback: a missing library or symbol raises.
 """
 from __future__ import annotations
 
 import ctypes as C
 import os
 
-import torch  # noqa: F401  -- must precede CDLL (see _lib.py: one HIP runtime per process, torch's)
+import torch
 
-from . import _lib
+from . import _cabi, _lib
+from ._cabi import dense_f32, stream
 
 LIB_PATH = os.environ.get("NERFLOC_APP_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc", "libnerfloc_app.so")
-ABI_VERSION = 1  # include/nerfloc_app.h: NLA_ABI_VERSION
-LAYOUT_NCHW, LAYOUT_NHWC = 0, 1   # NLA_LAYOUT_*
-FILM_CLIP01 = 1                   # NLA_FILM_CLIP01
-HIDDEN = 64                       # NLA_ADAPT_HIDDEN
-
-_P, _I, _L, _Z, _U = C.c_void_p, C.c_int, C.c_int64, C.c_size_t, C.c_uint
-# every symbol include/nerfloc_app.h declares: (name, restype, argtypes)
-SYMBOLS = [
-    ("nla_abi_version", _I, []),
-    ("nla_channel_stats_workspace_bytes", _Z, [_L, _I, _L, _I]),
-    ("nla_channel_stats", _I, [_P, _L, _I, _L, _I, _P, _P, _Z, _P]),
-    ("nla_adapt_code", _I, [_P, _P, C.POINTER(_P), _L, _I, _I, _P, _P]),
-    ("nla_film", _I, [_P, _P, _L, _L, _I, _U, _P, _P]),
-    ("nla_film_backward_block_pixels", _L, [_I]),
-    ("nla_film_backward_workspace_bytes", _Z, [_L, _L, _I]),
-    ("nla_film_backward", _I, [_P, _P, _P, _L, _L, _I, _U, _P, _P, _P, _Z, _P]),
-]
+HEADER = "nerfloc_app.h"
+ABI_VERSION = 1  # the NLA_ABI_VERSION these wrappers were written against (load() holds it against the header's and the library's)
+_D = _cabi.defines(HEADER)
+LAYOUT_NCHW, LAYOUT_NHWC = _D["NLA_LAYOUT_NCHW"], _D["NLA_LAYOUT_NHWC"]
+FILM_CLIP01 = _D["NLA_FILM_CLIP01"]
+HIDDEN = _D["NLA_ADAPT_HIDDEN"]
+SYMBOLS = _cabi.prototypes(HEADER, "nla_")   # every symbol the header declares: (name, restype, argtypes)
 
 _app = None
 
@@ -37,29 +28,9 @@ _app = None
 def load() -> C.CDLL:
     """Load the library and bind every declared symbol; raises if anything is missing."""
     global _app
-    if _app is not None:
-        return _app
-    if not os.path.exists(LIB_PATH):
-        raise RuntimeError(f"{LIB_PATH} not found: run `python -c 'import __graft_entry__ as g; g.build()'` (the library path has no CPU fallback)")
-    lib = C.CDLL(LIB_PATH)
-    for name, res, args in SYMBOLS:
-        fn = getattr(lib, name)  # AttributeError if the symbol is not exported
-        fn.restype = res
-        fn.argtypes = args
-    if lib.nla_abi_version() != ABI_VERSION:
-        raise RuntimeError("libnerfloc_app.so ABI version mismatch")
-    _app = lib
-    return lib
-
-
-def _stream(dev):
-    return torch.cuda.current_stream(dev).cuda_stream
-
-
-def _dense(t, what):
-    if t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous():
-        raise ValueError(f"{what}: expected a contiguous fp32 tensor on a HIP device")
-    return t
+    if _app is None:
+        _app = _cabi.bind(LIB_PATH, HEADER, "nla_", "nla_abi_version", "NLA_ABI_VERSION", ABI_VERSION, what="the library path has no CPU fallback")
+    return _app
 
 
 def channel_stats(x, layout=None):
@@ -79,7 +50,7 @@ def channel_stats(x, layout=None):
         if B == 0:
             return out
         ws = _lib.workspace(lib.nla_channel_stats_workspace_bytes(B, Cc, HW, layout), dev, f"channel_stats: C = {Cc} or H W = {HW} is outside the limits", ValueError)
-        _lib.check(lib.nla_channel_stats(x.data_ptr(), B, Cc, HW, layout, out.data_ptr(), ws.data_ptr(), ws.numel(), _stream(dev)), "nla_channel_stats")
+        _lib.check(lib.nla_channel_stats(x.data_ptr(), B, Cc, HW, layout, out.data_ptr(), ws.data_ptr(), ws.numel(), stream(dev)), "nla_channel_stats")
     return out
 
 
@@ -93,14 +64,14 @@ def adapt_code(emb, target, weights):
     for w, shape in zip(weights, shapes):
         if tuple(w.shape) != shape or w.device != dev:
             raise ValueError(f"adapt_code: expected a weight of shape {shape} on {dev}")
-        _dense(w, "adapt_code")
+        dense_f32(w, "adapt_code")
     if target.numel() != E or C2 % 2:
         raise ValueError("adapt_code: target must hold E values and the last layer 2 C rows")
-    _dense(emb, "adapt_code"), _dense(target, "adapt_code")
+    dense_f32(emb, "adapt_code"), dense_f32(target, "adapt_code")
     with torch.cuda.device(dev):
         code = torch.empty((V, C2), dtype=torch.float32, device=dev)
-        ptrs = (_P * 6)(*[w.data_ptr() for w in weights])
-        _lib.check(lib.nla_adapt_code(emb.data_ptr(), target.data_ptr(), ptrs, V, E, C2 // 2, code.data_ptr(), _stream(dev)), "nla_adapt_code")
+        ptrs = (C.c_void_p * 6)(*[w.data_ptr() for w in weights])
+        _lib.check(lib.nla_adapt_code(emb.data_ptr(), target.data_ptr(), ptrs, V, E, C2 // 2, code.data_ptr(), stream(dev)), "nla_adapt_code")
     return code
 
 
@@ -109,14 +80,14 @@ def film(x, code, clip=False, out=None):
     lib = load()
     dev = x.device
     V, Cc = int(x.shape[0]), int(x.shape[-1])
-    _dense(x, "film"), _dense(code, "film")
+    dense_f32(x, "film"), dense_f32(code, "film")
     if tuple(code.shape) != (V, 2 * Cc):
         raise ValueError("film: code must be (V, 2 C)")
     HW = x.numel() // max(V * Cc, 1)
     with torch.cuda.device(dev):
-        y = torch.empty_like(x) if out is None else _dense(out, "film")
+        y = torch.empty_like(x) if out is None else dense_f32(out, "film")
         if x.numel():
-            _lib.check(lib.nla_film(x.data_ptr(), code.data_ptr(), V, HW, Cc, FILM_CLIP01 if clip else 0, y.data_ptr(), _stream(dev)), "nla_film")
+            _lib.check(lib.nla_film(x.data_ptr(), code.data_ptr(), V, HW, Cc, FILM_CLIP01 if clip else 0, y.data_ptr(), stream(dev)), "nla_film")
     return y
 
 
@@ -125,16 +96,16 @@ def film_backward(x, code, g_y, clip=False, want_x=True, want_code=True, g_x_out
     lib = load()
     dev = x.device
     V, Cc = int(x.shape[0]), int(x.shape[-1])
-    _dense(x, "film_backward"), _dense(code, "film_backward"), _dense(g_y, "film_backward")
+    dense_f32(x, "film_backward"), dense_f32(code, "film_backward"), dense_f32(g_y, "film_backward")
     if g_y.shape != x.shape or tuple(code.shape) != (V, 2 * Cc):
         raise ValueError("film_backward: g_y must have x's shape and code must be (V, 2 C)")
     HW = x.numel() // max(V * Cc, 1)
     with torch.cuda.device(dev):
-        g_x = (torch.empty_like(x) if g_x_out is None else _dense(g_x_out, "film_backward")) if want_x else None
+        g_x = (torch.empty_like(x) if g_x_out is None else dense_f32(g_x_out, "film_backward")) if want_x else None
         g_code = torch.empty((V, 2 * Cc), dtype=torch.float32, device=dev) if want_code else None
         if not x.numel():
             return g_x, (g_code.zero_() if want_code else None)
         ws = _lib.workspace(lib.nla_film_backward_workspace_bytes(V, HW, Cc), dev, "film_backward: the shape is outside the limits", ValueError) if want_code else None
         _lib.check(lib.nla_film_backward(x.data_ptr(), code.data_ptr(), g_y.data_ptr(), V, HW, Cc, FILM_CLIP01 if clip else 0, _lib.ptr(g_x), _lib.ptr(g_code),
-                                         _lib.ptr(ws), ws.numel() if want_code else 0, _stream(dev)), "nla_film_backward")
+                                         _lib.ptr(ws), ws.numel() if want_code else 0, stream(dev)), "nla_film_backward")
     return g_x, g_code

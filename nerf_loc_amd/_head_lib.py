@@ -1,33 +1,24 @@
 """ctypes binding of libnerfloc_head.so (C-ABI in include/nerfloc_head.h): the head's device-side glue — match selection with a device count, the two position
 encodings, the pose solver with device counts.
 
-Built by the same `make` as libnerfloc_render.so (`_lib.build()`), loaded after torch for the same reason, and it speaks `_lib`'s conventions: `_lib.check` for
-the NL_* status codes, `_lib.workspace` for `*_workspace_bytes` answers.  No fallback: a missing library or symbol raises.
+Built by the same `make` as libnerfloc_render.so (`_lib.build()`), bound from its header by the same layer (`_cabi.bind`), and it speaks `_lib`'s conventions:
+`_lib.check` for the NL_* status codes, `_lib.workspace` for `*_workspace_bytes` answers.  No fallback: a missing library or symbol raises.
 """
 from __future__ import annotations
 
 import ctypes as C
 import os
 
-import torch  # noqa: F401  -- must precede CDLL (see _lib.py: one HIP runtime per process, torch's)
+import torch
 
-from . import _lib
+from . import _cabi, _lib
+from ._cabi import stream
 
 LIB_PATH = os.environ.get("NERFLOC_HEAD_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc", "libnerfloc_head.so")
-ABI_VERSION = 1  # include/nerfloc_head.h: NLH_ABI_VERSION
+HEADER = "nerfloc_head.h"
+ABI_VERSION = 1  # the NLH_ABI_VERSION these wrappers were written against (load() holds it against the header's and the library's)
 INFO_COUNT, INFO_TOTAL, INFO_OVERFLOW = 0, 1, 2   # nlh_select_matches: the words of `info`
-
-_P, _I, _L, _Z = C.c_void_p, C.c_int, C.c_int64, C.c_size_t
-# every symbol include/nerfloc_head.h declares: (name, restype, argtypes)
-SYMBOLS = [
-    ("nlh_abi_version", _I, []),
-    ("nlh_select_workspace_bytes", _Z, [_L]),
-    ("nlh_select_matches", _I, [_P, _L, _L, _L, _I] + [_P] * 13 + [_Z, _P]),
-    ("nlh_pos_sine_grid", _I, [_I, _I, _I, _P, _P]),
-    ("nlh_embed_points", _I, [_P, _L, _I, _I, _P, _P]),
-    ("nlh_pnp_workspace_bytes", _Z, [_L, _L, _I]),
-    ("nlh_pnp_ransac_counted", _I, [_P, _P, _P, _P, _P, _P, _L, _I, C.c_uint64, _I, _P, _P, _P, _P, _P, _Z, _P]),
-]
+SYMBOLS = _cabi.prototypes(HEADER, "nlh_")   # every symbol the header declares: (name, restype, argtypes)
 
 _head = None
 
@@ -35,23 +26,9 @@ _head = None
 def load() -> C.CDLL:
     """Load the library and bind every declared symbol; raises if anything is missing."""
     global _head
-    if _head is not None:
-        return _head
-    if not os.path.exists(LIB_PATH):
-        raise RuntimeError(f"{LIB_PATH} not found: run `python -c 'import __graft_entry__ as g; g.build()'` (the head has no CPU fallback)")
-    lib = C.CDLL(LIB_PATH)
-    for name, res, args in SYMBOLS:
-        fn = getattr(lib, name)  # AttributeError if the symbol is not exported
-        fn.restype = res
-        fn.argtypes = args
-    if lib.nlh_abi_version() != ABI_VERSION:
-        raise RuntimeError("libnerfloc_head.so ABI version mismatch")
-    _head = lib
-    return lib
-
-
-def _stream(dev):
-    return torch.cuda.current_stream(dev).cuda_stream
+    if _head is None:
+        _head = _cabi.bind(LIB_PATH, HEADER, "nlh_", "nlh_abi_version", "NLH_ABI_VERSION", ABI_VERSION, what="the head has no CPU fallback")
+    return _head
 
 
 def select_matches(match_j, cap, kps3d, kps2d, rows_a=None, rows_b=None):
@@ -78,7 +55,7 @@ def select_matches(match_j, cap, kps3d, kps2d, rows_a=None, rows_b=None):
         ptr = _lib.ptr
         _lib.check(lib.nlh_select_matches(match_j.data_ptr(), N, cap, Mc, Cc, kps3d.data_ptr(), ptr(kps2d) if Mc else None, ptr(rows_a), ptr(rows_b), ids[0].data_ptr(),
                                           ids[1].data_ptr(), ids[2].data_ptr(), mk3.data_ptr(), mk2.data_ptr(), ptr(oa), ptr(ob), info.data_ptr(), ws.data_ptr(),
-                                          ws.numel(), _stream(dev)), "nlh_select_matches")
+                                          ws.numel(), stream(dev)), "nlh_select_matches")
     return {"i_ids": ids[0], "j_ids": ids[1], "b_ids": ids[2], "mkps3d": mk3, "mkps2d_c": mk2, "out_a": oa, "out_b": ob, "info": info}
 
 
@@ -87,7 +64,7 @@ def pos_sine_grid(H, W, Cc, device):
     lib = load()
     with torch.cuda.device(device):
         out = torch.empty((int(H), int(W), int(Cc)), dtype=torch.float32, device=device)
-        _lib.check(lib.nlh_pos_sine_grid(int(H), int(W), int(Cc), out.data_ptr(), _stream(device)), "nlh_pos_sine_grid")
+        _lib.check(lib.nlh_pos_sine_grid(int(H), int(W), int(Cc), out.data_ptr(), stream(device)), "nlh_pos_sine_grid")
     return out
 
 
@@ -99,5 +76,5 @@ def embed_points(x, L):
     flat = x.detach().to(torch.float32).reshape(-1, D).contiguous()
     with torch.cuda.device(dev):
         out = torch.empty((flat.shape[0], 2 * D * int(L)), dtype=torch.float32, device=dev)
-        _lib.check(lib.nlh_embed_points(flat.data_ptr(), flat.shape[0], D, int(L), out.data_ptr(), _stream(dev)), "nlh_embed_points")
+        _lib.check(lib.nlh_embed_points(flat.data_ptr(), flat.shape[0], D, int(L), out.data_ptr(), stream(dev)), "nlh_embed_points")
     return out.reshape(*x.shape[:-1], 2 * D * int(L))

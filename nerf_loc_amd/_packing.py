@@ -50,7 +50,7 @@ def pack_matcher_mlp_train(who, module, device):
         if need == 0:
             raise RuntimeError(f"{who}: feat_dim {module.feat_dim} is not supported by the HIP kernel (a multiple of 32, 32..256)")
         packed = torch.empty(need, dtype=torch.uint8, device=device)
-        st = torch.cuda.current_stream(device).cuda_stream
+        st = _lib.stream(device)
         _lib.check(lib.nl_s2d_pack_train_weights(module.feat_dim, ts[0].data_ptr(), ts[1].data_ptr(), packed.data_ptr(), need, st), "nl_s2d_pack_train_weights")
         return packed
     return module._train_cache._cached(device, [module.mlps[0].weight, module.mlps[2].weight], pack)
@@ -82,7 +82,7 @@ def pack_matcher_mlp(who, module, device):
         if need == 0:
             raise RuntimeError(f"{who}: feat_dim {module.feat_dim} is not supported by the HIP kernel (a multiple of 32, 32..256)")
         packed = torch.empty(need, dtype=torch.uint8, device=device)
-        st = torch.cuda.current_stream(device).cuda_stream
+        st = _lib.stream(device)
         _lib.check(lib.nl_s2d_pack_weights(module.feat_dim, *[t.data_ptr() for t in ts], packed.data_ptr(), need, st), "nl_s2d_pack_weights")
         return packed
     return module._cached(device, [module.get_parameter(n) for n in MATCHER_MLP_PARAMS], pack)

@@ -64,7 +64,7 @@ class CompositeFn(torch.autograd.Function):
         gs, grs, gft = torch.empty_like(sigma), torch.empty_like(rgb_s), torch.empty_like(ft)
         ptr = lambda t: None if t is None else t.contiguous().data_ptr()   # noqa: E731
         keep = [None if g is None else g.contiguous() for g in (g_rgb, g_depth, g_unc, g_feat, g_wts)]
-        st = torch.cuda.current_stream(sigma.device).cuda_stream
+        st = L.stream(sigma.device)
         with torch.cuda.device(sigma.device):
             L.check(L.load().nl_composite_backward(z.data_ptr(), sigma.data_ptr(), rgb_s.data_ptr(), ft.data_ptr(), R, S, C, int(ctx.white),
                                                    *[ptr(g) for g in keep], gs.data_ptr(), grs.data_ptr(), gft.data_ptr(), st), "nl_composite_backward")
@@ -92,7 +92,7 @@ class KnnDist2Fn(torch.autograd.Function):
         g = g_d2.contiguous()
         gx = torch.empty_like(xyz)
         gsp = torch.zeros_like(sp) if ctx.needs_input_grad[1] else None
-        st = torch.cuda.current_stream(xyz.device).cuda_stream
+        st = L.stream(xyz.device)
         with torch.cuda.device(xyz.device):
             L.check(L.load().nl_knn_backward(xyz.data_ptr(), sp.data_ptr(), idx32.data_ptr(), g.data_ptr(), N, K, M, gx.data_ptr(),
                                              None if gsp is None else gsp.data_ptr(), st), "nl_knn_backward")

@@ -87,7 +87,7 @@ class FinePreprocess(nn.Module, PackedCache):
 
         def pack(ts):
             packed = torch.empty(need, dtype=torch.uint8, device=device)
-            st = torch.cuda.current_stream(device).cuda_stream
+            st = _lib.stream(device)
             _lib.check(lib.nl_fine_pack_proj(self.in_channels_fine, self.out_channels, ts[0].data_ptr(), ts[1].data_ptr(), packed.data_ptr(), need, st),
                        "nl_fine_pack_proj")
             return packed
@@ -100,7 +100,7 @@ class FinePreprocess(nn.Module, PackedCache):
 
         def pack(ts):
             packed = torch.empty(need, dtype=torch.uint8, device=device)
-            st = torch.cuda.current_stream(device).cuda_stream
+            st = _lib.stream(device)
             _lib.check(lib.nl_fine_pack_proj_train(self.in_channels_fine, self.out_channels, ts[0].data_ptr(), packed.data_ptr(), need, st), "nl_fine_pack_proj_train")
             return packed
         return self._train_cache._cached(device, [self.proj.weight], pack)
@@ -138,7 +138,7 @@ class FinePreprocess(nn.Module, PackedCache):
         with torch.cuda.device(dev):
             packed = self._pack(dev)
             out = torch.empty((M, 49, self.out_channels), dtype=torch.float32, device=dev)
-            st = torch.cuda.current_stream(dev).cuda_stream
+            st = _lib.stream(dev)
             _lib.check(lib.nl_fine_windows(packed.data_ptr(), self.in_channels_fine, self.out_channels, _lib.PRECISIONS[precision or self.precision],
                                            nhwc.data_ptr(), B, Hf, Wf, b.data_ptr(), j.data_ptr(), M, stride, out.data_ptr(), st), "nl_fine_windows")
         return out, nhwc, b, j, packed
@@ -190,7 +190,7 @@ class _FineMatchFn(torch.autograd.Function):
             g_f0 = torch.empty_like(f0) if need[2] else None
             g_f1 = torch.empty_like(f1) if need[3] else None
             params, g_params = matcher_mlp_grad_buffers(mod, need[4:], dev)
-            st = torch.cuda.current_stream(dev).cuda_stream
+            st = _lib.stream(dev)
             ptr = _lib.ptr
             _lib.check(lib.nl_fine_match_backward(ctx.packed.data_ptr(), ctx.tpacked.data_ptr(), Cf, _lib.PRECISIONS[mod.precision], f0.data_ptr(), f1.data_ptr(), M,
                                                   heat.data_ptr(), ge.data_ptr(), ptr(g_f0), ptr(g_f1), *[ptr(g) for g in g_params], ws.data_ptr(), ws.numel(), st),
@@ -228,7 +228,7 @@ class _FineWindowsFn(torch.autograd.Function):
             g_map = torch.empty_like(nhwc) if need[4] else None
             g_w = torch.empty((Cout, Cf), dtype=torch.float32, device=dev) if need[5] else None
             g_b = torch.empty((Cout,), dtype=torch.float32, device=dev) if need[6] else None
-            st = torch.cuda.current_stream(dev).cuda_stream
+            st = _lib.stream(dev)
             ptr = _lib.ptr
             _lib.check(lib.nl_fine_windows_backward(ctx.packed.data_ptr(), ctx.tpacked.data_ptr(), Cf, Cout, _lib.PRECISIONS[mod.precision], nhwc.data_ptr(), B, Hf, Wf,
                                                     b.data_ptr(), j.data_ptr(), M, ctx.stride, go.data_ptr(), ptr(g_w), ptr(g_b), ptr(g_map), ws.data_ptr(), ws.numel(),
@@ -275,7 +275,7 @@ class FineMatching(nn.Module, PackedCache):
             expec = torch.empty((M, 3), dtype=torch.float32, device=dev)
             kf = torch.empty((M, 2), dtype=torch.float32, device=dev)
             heat = torch.empty((M, 49), dtype=torch.float32, device=dev) if want_heatmap else None
-            st = torch.cuda.current_stream(dev).cuda_stream
+            st = _lib.stream(dev)
             _lib.check(lib.nl_fine_match(packed.data_ptr(), self.feat_dim, _lib.PRECISIONS[self.precision], f0.data_ptr(), f1.data_ptr(), M, kc.data_ptr(),
                                          expec.data_ptr(), kf.data_ptr(), _lib.ptr(heat), st), "nl_fine_match")
         return expec, kf, heat, f0, f1, packed

@@ -31,7 +31,7 @@ def cross_view_features(imgs: torch.Tensor, depths: torch.Tensor, Ks: torch.Tens
     V, _, H, W = imgs.shape
     out = torch.empty(V, 12, H, W, dtype=torch.float32, device=imgs.device)
     ws = _workspace(lib, V, H, W, 1, imgs.device)
-    st = torch.cuda.current_stream(imgs.device).cuda_stream
+    st = L.stream(imgs.device)
     L.check(lib.nl_cross_view_features(imgs.data_ptr(), depths.data_ptr(), Ks.data_ptr(), c2w.data_ptr(), V, H, W, float(near), float(far),
                                        out.data_ptr(), ws.data_ptr(), ws.numel(), st), "nl_cross_view_features")
     ws.record_stream(torch.cuda.current_stream(imgs.device))
@@ -53,7 +53,7 @@ def backproject_support(imgs: torch.Tensor, feats: torch.Tensor, depths: torch.T
     direction = torch.empty(cap, 4, dtype=torch.float32, device=dev)
     ws = _workspace(lib, V, H, W, stride, dev)
     m = ct.c_int64(0)
-    st = torch.cuda.current_stream(dev).cuda_stream
+    st = L.stream(dev)
     L.check(lib.nl_backproject_support(imgs.data_ptr(), feats.data_ptr(), depths.data_ptr(), Ks.data_ptr(), c2w.data_ptr(), V, H, W, fh, fw, C,
                                        int(stride), cap, feature.data_ptr(), xyz.data_ptr(), ref.data_ptr(), direction.data_ptr(), ct.byref(m),
                                        ws.data_ptr(), ws.numel(), st), "nl_backproject_support")
@@ -70,7 +70,7 @@ def get_rays(H: int, W: int, K: torch.Tensor, c2w: torch.Tensor, uv: torch.Tenso
     o = torch.empty(R, 3, dtype=torch.float32, device=K.device)
     d = torch.empty(R, 3, dtype=torch.float32, device=K.device)
     uvp = None if uv is None else _f32(uv, "pts2d")
-    st = torch.cuda.current_stream(K.device).cuda_stream
+    st = L.stream(K.device)
     L.check(lib.nl_get_rays(K.data_ptr(), c2w.data_ptr(), None if uvp is None else uvp.data_ptr(), int(H), int(W), R, o.data_ptr(), d.data_ptr(), st),
             "nl_get_rays")
     return (o.view(H, W, 3), d.view(H, W, 3)) if uv is None else (o, d)

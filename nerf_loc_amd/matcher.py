@@ -145,7 +145,7 @@ class Matcher(nn.Module):
             offsets = (C.c_int32 * 2)(0, cap)
             intr = (C.c_double * 4)(fx, fy, cx, cy)
             thr_h = (C.c_double * 1)(float(thr))
-            st = torch.cuda.current_stream(dev).cuda_stream
+            st = _lib.stream(dev)
             _lib.check(lib.nlh_pnp_ransac_counted(p2.data_ptr(), p3.data_ptr(), offsets, out["match_info"].data_ptr(), intr, thr_h, 1, H, int(seed) & 0xFFFFFFFFFFFFFFFF,
                                                   int(min_inliers), pose.data_ptr(), mask.data_ptr(), info.data_ptr(), None, ws.data_ptr(), ws.numel(), st),
                        "nlh_pnp_ransac_counted")

@@ -59,7 +59,7 @@ class _S2DTrainFn(torch.autograd.Function):
             tgt = None if target is None else target.detach().to(device=dev, dtype=torch.float32).contiguous()
             if tgt is not None and tuple(tgt.shape) != (N, M):
                 raise ValueError(f"S2DMatching: conf_matrix_gt must be ({N}, {M})")
-            st = torch.cuda.current_stream(dev).cuda_stream
+            st = _lib.stream(dev)
             _lib.check(lib.nl_s2d_forward_train(packed.data_ptr(), Cf, _lib.PRECISIONS[mod.precision], d0.data_ptr(), N, d1.data_ptr(), M, C.c_float(float(mod.thr)),
                                                 _lib.ptr(tgt), scores.data_ptr(), logits.data_ptr(), None if tgt is None else loss.data_ptr(), match_j.data_ptr(),
                                                 match_s.data_ptr(), ws.data_ptr(), ws.numel(), st), "nl_s2d_forward_train")
@@ -91,7 +91,7 @@ class _S2DTrainFn(torch.autograd.Function):
             if tgt is not None:
                 gl = (torch.zeros((), dtype=torch.float32, device=dev) if g_loss is None else g_loss.detach().to(torch.float32)).reshape(1).contiguous()
             gs = None if g_score is None else g_score.detach().to(torch.float32).contiguous()
-            st = torch.cuda.current_stream(dev).cuda_stream
+            st = _lib.stream(dev)
             ptr = _lib.ptr
             _lib.check(lib.nl_s2d_backward_train(packed.data_ptr(), tpacked.data_ptr(), Cf, _lib.PRECISIONS[mod.precision], d0.data_ptr(), N, d1.data_ptr(), M,
                                                  logits.data_ptr(), ptr(tgt), ptr(gl), ptr(gs), g_d0.data_ptr(), g_d1.data_ptr(), *[ptr(g) for g in g_params],
@@ -160,7 +160,7 @@ class S2DMatching(nn.Module, PackedCache):
             scores = torch.empty((N, M), dtype=torch.float32, device=dev) if want else None
             match_j = torch.empty(N, dtype=torch.int32, device=dev)
             match_s = torch.empty(N, dtype=torch.float32, device=dev)
-            st = torch.cuda.current_stream(dev).cuda_stream
+            st = _lib.stream(dev)
             _lib.check(lib.nl_s2d_match(packed.data_ptr(), self.feat_dim, _lib.PRECISIONS[self.precision], d0.data_ptr(), N, d1.data_ptr(), M,
                                         C.c_float(float(self.thr)), _lib.ptr(scores), match_j.data_ptr(), match_s.data_ptr(), ws.data_ptr(), ws.numel(), st),
                        "nl_s2d_match")

@@ -88,7 +88,7 @@ def absolute_pose_batch(problems, hypotheses: int = DEFAULT_HYPOTHESES, seed: in
         pose = torch.empty(B, 12, dtype=torch.float64, device=dev)
         mask = torch.empty(max(int(offsets[B]), 1), dtype=torch.uint8, device=dev)
         info = torch.empty(B, 4, dtype=torch.int32, device=dev)
-        st = torch.cuda.current_stream(dev).cuda_stream
+        st = _lib.stream(dev)
         _lib.check(lib.nl_pnp_ransac(p2.data_ptr(), p3.data_ptr(), offsets, intr, thr, B, H, int(seed) & 0xFFFFFFFFFFFFFFFF, int(min_inliers), pose.data_ptr(),
                                      mask.data_ptr(), info.data_ptr(), None, ws.data_ptr(), ws.numel(), st), "nl_pnp_ransac")
         T, Ti = _transforms(pose)

@@ -241,7 +241,7 @@ class HipRenderer:
         self._weight_shapes = {n: tuple(t.shape) for n, t in zip(names, keep)}
         self._weight_tensors = dict(zip(names, keep))   # fp32 device copies as packed (a few MB): the training nodes read some of them back
         self.state_gen = getattr(self, "state_gen", 0) + 1   # autograd nodes check that weights / frame did not change between their forward and backward
-        st = torch.cuda.current_stream(self.device).cuda_stream
+        st = L.stream(self.device)
         L.check(self.lib.nl_pack_weights(ct.byref(self.cfg), arr, len(names), self.packed.data_ptr(), self.packed.numel(), st), "nl_pack_weights")
         torch.cuda.current_stream(self.device).synchronize()  # sources may be freed after this
         self._weights_loaded = True
@@ -311,7 +311,7 @@ class HipRenderer:
         if nbytes == 0:
             raise ValueError("nl_frame_bytes rejected the frame description")
         mem = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        st = torch.cuda.current_stream(dev).cuda_stream
+        st = L.stream(dev)
         fr = ct.c_void_p(None)
         L.check(self.lib.nl_frame_create(ct.byref(self.cfg), ct.byref(d), mem.data_ptr(), nbytes, st, ct.byref(fr)), "nl_frame_create")
         self._frame = fr
@@ -344,7 +344,7 @@ class HipRenderer:
 
     # ------------------------------------------------------------------ helpers
     def _stream(self) -> int:
-        return torch.cuda.current_stream(self.device).cuda_stream
+        return L.stream(self.device)
 
     def _workspace(self, nbytes: int) -> torch.Tensor:
         if getattr(self, "guard_bytes", 0):

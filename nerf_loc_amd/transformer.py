@@ -87,7 +87,7 @@ class _TrainStep(torch.autograd.Function):
             sb, wb = lib.nl_sct_train_state_bytes(B, N0, N1, C, Fh), lib.nl_sct_workspace_bytes(B, N0, N1, C, Fh)
             state = torch.empty(sb, dtype=torch.uint8, device=dev)
             ws = torch.empty(wb, dtype=torch.uint8, device=dev)
-            st = torch.cuda.current_stream(dev).cuda_stream
+            st = _lib.stream(dev)
             args = (packed.data_ptr(), C, mod.nhead, Fh, _lib.PRECISIONS[mod.precision], a[0].data_ptr(), a[1].data_ptr(), N0, a[2].data_ptr(), a[3].data_ptr(), N1, B,
                     out0.data_ptr(), out1.data_ptr(), state.data_ptr(), sb, ws.data_ptr(), wb)
             if p > 0:
@@ -118,7 +118,7 @@ class _TrainStep(torch.autograd.Function):
             arr = (ctypes.c_void_p * len(gpar))(*[ptr(t) for t in gpar])
             wb = lib.nl_sct_backward_workspace_bytes(B, N0, N1, C, Fh)
             ws = torch.empty(wb, dtype=torch.uint8, device=dev)
-            st = torch.cuda.current_stream(dev).cuda_stream
+            st = _lib.stream(dev)
             args = (ctx.images[0].data_ptr(), ctx.images[1].data_ptr(), C, mod.nhead, Fh, _lib.PRECISIONS[mod.precision], a[0].data_ptr(), a[1].data_ptr(), N0,
                     a[2].data_ptr(), a[3].data_ptr(), N1, B, ctx.state.data_ptr(), ctx.state.numel(), ptr(g0), ptr(g1), ptr(gin[0]), ptr(gin[1]), ptr(gin[2]),
                     ptr(gin[3]), arr, len(gpar), ws.data_ptr(), wb)
@@ -186,7 +186,7 @@ class SelfCrossTransformer(nn.Module, PackedCache):
         def pack(ts):
             arr = (ctypes.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
             packed = torch.empty(need, dtype=torch.uint8, device=device)
-            st = torch.cuda.current_stream(device).cuda_stream
+            st = _lib.stream(device)
             _lib.check(lib.nl_sct_pack_weights(self.d_model, self.nhead, self.dim_feedforward, arr, len(ts), packed.data_ptr(), need, st), "nl_sct_pack_weights")
             return packed
         return self._cached(device, ps, pack)
@@ -200,7 +200,7 @@ class SelfCrossTransformer(nn.Module, PackedCache):
         def pack(ts):
             arr = (ctypes.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
             packed = torch.empty(need, dtype=torch.uint8, device=device)
-            st = torch.cuda.current_stream(device).cuda_stream
+            st = _lib.stream(device)
             _lib.check(lib.nl_sct_pack_weights_train(self.d_model, self.nhead, self.dim_feedforward, arr, len(ts), packed.data_ptr(), need, st),
                        "nl_sct_pack_weights_train")
             return packed
@@ -243,7 +243,7 @@ class SelfCrossTransformer(nn.Module, PackedCache):
             a = [t.detach().to(torch.float32).contiguous() for t in ts]   # the one copy of a non-contiguous input
             ws = _lib.workspace(lib.nl_sct_workspace_bytes(B, N0, N1, C, self.dim_feedforward), dev,
                                 f"SelfCrossTransformer: B * max(N0, N1) = {B * max(N0, N1)} exceeds the kernels' limit of 2^24 rows")
-            st = torch.cuda.current_stream(dev).cuda_stream
+            st = _lib.stream(dev)
             _lib.check(lib.nl_sct_forward(packed.data_ptr(), C, self.nhead, self.dim_feedforward, _lib.PRECISIONS[self.precision], a[0].data_ptr(), a[1].data_ptr(),
                                           N0, a[2].data_ptr(), a[3].data_ptr(), N1, B, out0.data_ptr(), out1.data_ptr(), ws.data_ptr(), ws.numel(), st), "nl_sct_forward")
         return out0, out1
