@@ -21,6 +21,7 @@
 // Every sum has an order that depends on the shapes and the ids alone and no float atomic touches a result: two calls give the same bits.
 #include <algorithm>
 #include "common.h"
+#include "compact.h"
 #include "mfma.h"
 #include "s2d.h"
 #include "s2d_bwd.h"
@@ -187,24 +188,11 @@ __global__ __launch_bounds__(256) void fine_key_count_kernel(const FineMapArgs a
   a.key[m] = key;
   if (ok) atomicAdd(a.start + key, 1);   // an integer count: its value does not depend on the order
 }
-// start[0 .. K] = exclusive scan of the counts in place (start[K] = the number of placed matches); one workgroup, each thread a contiguous range
+// start[0 .. K] = exclusive scan of the counts in place (start[K] = the number of placed matches); one workgroup (compact.h)
 __global__ __launch_bounds__(1024) void fine_scan_kernel(int* start, int K) {
   __shared__ int part[1024];
-  const int tid = threadIdx.x;
-  const int per = (K + 1023) / 1024, k0 = min(K, tid * per), k1 = min(K, k0 + per);
-  int s = 0;
-  for (int k = k0; k < k1; ++k) s += start[k];
-  part[tid] = s;
-  __syncthreads();
-  for (int o = 1; o < 1024; o <<= 1) {
-    const int v = tid >= o ? part[tid - o] : 0;
-    __syncthreads();
-    part[tid] += v;
-    __syncthreads();
-  }
-  int run = part[tid] - s;   // exclusive
-  for (int k = k0; k < k1; ++k) { const int c = start[k]; start[k] = run; run += c; }
-  if (tid == 1023) start[K] = part[1023];
+  const int total = nl_scan_exclusive<1024>(start, K, part);
+  if (threadIdx.x == 1023) start[K] = total;
 }
 // match m goes to its window's list at its rank among the earlier matches of that window
 __global__ __launch_bounds__(256) void fine_place_kernel(const FineMapArgs a) {

@@ -5,10 +5,11 @@
 //   nlg_build_pairs      pair_project_kernel / scan_kernel<2> / pair_emit_kernel: the same chain with two counted sets (valid, pos) and the fallback decided in the scan
 //   nlg_conf_target      one launch, every value written once, 16-byte stores over the aligned part
 //   nlg_cell_grid        one launch
-// The order of a compaction comes from the scheme of nlh_select_matches (csrc/head.hip): ballot / popcount per wave, the four wave totals added in wave order, the
-// chunk's scanned offset.  No atomics, no kernel that waits on another workgroup; fp64 from the loaded inputs to every decision (-ffp-contract=off: no fused
-// multiply-add, so tests/geom_ref.py's numpy sees the same roundings).
+// The order of a compaction comes from compact.h: ballot / popcount per wave, the CHUNK / 64 wave totals added in wave order, the chunk's scanned offset.
+// No atomics, no kernel that waits on another workgroup; fp64 from the loaded inputs to every decision (-ffp-contract=off: no fused multiply-add, so
+// tests/geom_ref.py's numpy sees the same roundings).
 #include "common.h"
+#include "compact.h"
 #include "../../include/nerfloc_geom.h"
 
 namespace {
@@ -65,13 +66,6 @@ __device__ __forceinline__ bool project(const double* __restrict__ P, double p0,
   return (u >= 0.0) && (v >= 0.0) && (u < Wd) && (v < Hd) && (z > 0.0);
 }
 
-// flags below this lane of the wave; the workgroup's wave totals go through LDS (wtot: CHUNK / 64 ints per counted set)
-__device__ __forceinline__ int wave_rank(bool f, int* __restrict__ wtot) {
-  const unsigned long long bal = __ballot(f);
-  if ((threadIdx.x & 63) == 0) wtot[threadIdx.x >> 6] = __popcll(bal);
-  return __builtin_amdgcn_mbcnt_hi((unsigned)(bal >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)bal, 0u));
-}
-
 __global__ __launch_bounds__(CHUNK) void vis_mask_kernel(const float* __restrict__ pts, int N, const void* __restrict__ poses, int V, int f64,
                                                          const float* __restrict__ K, int H, int W, unsigned char* __restrict__ mask, int* __restrict__ chunk_cnt) {
   __shared__ double P[NLG_MAX_VIEWS * 12];
@@ -87,44 +81,20 @@ __global__ __launch_bounds__(CHUNK) void vis_mask_kernel(const float* __restrict
     }
     mask[i] = vis ? 1 : 0;
   }
-  wave_rank(vis, wtot);
+  nl_wave_rank(vis, wtot);
   __syncthreads();
-  if (threadIdx.x == 0) chunk_cnt[blockIdx.x] = wtot[0] + wtot[1] + wtot[2] + wtot[3];
+  if (threadIdx.x == 0) chunk_cnt[blockIdx.x] = nl_group_total<CHUNK / 64>(wtot);
 }
 
-// SETS arrays of nchunks counts, one after the other in `cnt`, each turned into its exclusive scan in place (thread t owns the chunks [t per, (t + 1) per), as
-// sel_scan_kernel of head.hip).  SETS == 2 (valid, then pos): the positive set is pos unless fewer than NLG_MIN_POSITIVES rows are pos.
+// SETS arrays of nchunks counts, one after the other in `cnt`, each turned into its exclusive scan in place (compact.h).
+// SETS == 2 (valid, then pos): the positive set is pos unless fewer than NLG_MIN_POSITIVES rows are pos.
 template <int SETS>
 __global__ __launch_bounds__(SCAN_THREADS) void scan_kernel(int* __restrict__ cnt, int nchunks, int cap, int* __restrict__ info) {
   __shared__ int part[SCAN_THREADS];
-  const int tid = threadIdx.x;
-  const int per = (nchunks + SCAN_THREADS - 1) / SCAN_THREADS;
   int total[SETS];
 #pragma unroll
-  for (int s = 0; s < SETS; ++s) {
-    int* a = cnt + (size_t)s * nchunks;
-    int own = 0;
-    for (int k = 0; k < per; ++k) {
-      const int c = tid * per + k;
-      if (c < nchunks) own += a[c];
-    }
-    part[tid] = own;
-    __syncthreads();
-    for (int d = 1; d < SCAN_THREADS; d <<= 1) {
-      const int v = tid >= d ? part[tid - d] : 0;
-      __syncthreads();
-      part[tid] += v;
-      __syncthreads();
-    }
-    int run = part[tid] - own;
-    for (int k = 0; k < per; ++k) {
-      const int c = tid * per + k;
-      if (c < nchunks) { const int v = a[c]; a[c] = run; run += v; }
-    }
-    total[s] = part[SCAN_THREADS - 1];
-    __syncthreads();   // part is reused by the next set
-  }
-  if (tid == 0) {
+  for (int s = 0; s < SETS; ++s) total[s] = nl_scan_exclusive<SCAN_THREADS>(cnt + (size_t)s * nchunks, nchunks, part);
+  if (threadIdx.x == 0) {
     const int fallback = SETS == 2 && total[SETS - 1] < NLG_MIN_POSITIVES ? 1 : 0;
     const int tot = fallback ? total[0] : total[SETS - 1];
     info[0] = min(tot, cap); info[1] = tot; info[2] = tot > cap ? 1 : 0; info[3] = fallback;
@@ -136,11 +106,10 @@ __global__ __launch_bounds__(CHUNK) void vis_emit_kernel(const unsigned char* __
   __shared__ int wtot[CHUNK / 64];
   const int i = blockIdx.x * CHUNK + threadIdx.x;   // i < max(N, cap) rounded up to a chunk: at most 2^24 + 255
   const bool f = i < N && mask[i] != 0;
-  const int rank = wave_rank(f, wtot);
+  const int rank = nl_wave_rank(f, wtot);
   __syncthreads();
   if (f) {
-    int k = chunk_off[blockIdx.x] + rank;           // f implies blockIdx.x < nchunks
-    for (int w = 0; w < (int)(threadIdx.x >> 6); ++w) k += wtot[w];
+    const int k = chunk_off[blockIdx.x] + nl_group_rank(rank, wtot);   // f implies blockIdx.x < nchunks
     if (k < cap) idx[k] = i;
   }
   if (i < cap && i >= info[0]) idx[i] = 0;           // k < count for every emitted row: the two stores never meet
@@ -171,12 +140,12 @@ __global__ __launch_bounds__(CHUNK) void pair_project_kernel(const float* __rest
     valid[i] = ok ? 1 : 0; pos[i] = good ? 1 : 0;
     cell[i] = j;   // of every valid row for now: pair_emit_kernel knows the positive set
   }
-  wave_rank(ok, wv);
-  wave_rank(good, wp);
+  nl_wave_rank(ok, wv);
+  nl_wave_rank(good, wp);
   __syncthreads();
   if (threadIdx.x == 0) {
-    cnt[blockIdx.x] = wv[0] + wv[1] + wv[2] + wv[3];
-    cnt[nchunks + blockIdx.x] = wp[0] + wp[1] + wp[2] + wp[3];
+    cnt[blockIdx.x] = nl_group_total<CHUNK / 64>(wv);
+    cnt[nchunks + blockIdx.x] = nl_group_total<CHUNK / 64>(wp);
   }
 }
 
@@ -187,14 +156,13 @@ __global__ __launch_bounds__(CHUNK) void pair_emit_kernel(const unsigned char* _
   const int i = blockIdx.x * CHUNK + threadIdx.x;
   const bool fallback = info[3] != 0;
   const bool f = i < N && (fallback ? valid[i] : pos[i]) != 0;
-  const int rank = wave_rank(f, wtot);
+  const int rank = nl_wave_rank(f, wtot);
   __syncthreads();
   if (i < N) {
     const int j = f ? gt_j[i] : -1;
     if (!f) gt_j[i] = -1;
     if (f) {
-      int k = off[(fallback ? 0 : nchunks) + blockIdx.x] + rank;
-      for (int w = 0; w < (int)(threadIdx.x >> 6); ++w) k += wtot[w];
+      const int k = off[(fallback ? 0 : nchunks) + blockIdx.x] + nl_group_rank(rank, wtot);
       if (k < cap) { pairs[k] = i; pairs[(size_t)cap + k] = j; }
     }
   }

@@ -1,6 +1,6 @@
 // libnerfloc_head.so, part 1 (include/nerfloc_head.h states the contracts; tests/head_ref.py restates them in numpy): the glue of the localisation head that has to
 // stay on the device for "descriptors in, pose out" to be queued without a host round trip.
-//   nlh_select_matches   the ordered, fixed-capacity match lists of the coarse stage with a DEVICE-side count.  Three launches, a plain chain:
+//   nlh_select_matches   the ordered, fixed-capacity match lists of the coarse stage with a DEVICE-side count.  Three launches, a plain chain (compact.h):
 //     sel_scan_kernel    one workgroup: matched rows per chunk of 256 (ballot + popcount per wave), then the exclusive scan of the chunk counts and `info`
 //     sel_write_kernel   one workgroup per chunk: rank inside the wave from the ballot, the four wave totals added in wave order, + the chunk's offset = k;
 //                        ids and points of the rows with k < cap
@@ -10,6 +10,7 @@
 // Integers only where order could matter (no atomics at all): two calls give the same bits.  The sines are ocml's full-range sinf / cosf (Payne-Hanek reduction
 // for large arguments), never the hardware v_sin_f32: the embedder's arguments reach 2^31 |x|.
 #include "common.h"
+#include "compact.h"
 #include "../../include/nerfloc_head.h"
 
 namespace {
@@ -36,31 +37,9 @@ __global__ __launch_bounds__(SEL_SCAN_THREADS) void sel_scan_kernel(const int* _
     for (int q = 0; q < SEL_CHUNK / 64; ++q) cnt += __popcll(__ballot(sel_matched(match_j, c * SEL_CHUNK + q * 64 + lane, N, Mc)));
     if (lane == 0) chunk_off[c] = cnt;
   }
-  __syncthreads();
-  // thread t owns the chunks [t per, (t + 1) per): its sum, an inclusive scan of the 1024 sums through LDS, then its chunks' exclusive offsets in ascending order
-  const int per = (nchunks + SEL_SCAN_THREADS - 1) / SEL_SCAN_THREADS;
-  int own = 0;
-  for (int k = 0; k < per; ++k) {
-    const int c = tid * per + k;
-    if (c < nchunks) own += chunk_off[c];
-  }
-  part[tid] = own;
-  __syncthreads();
-  for (int d = 1; d < SEL_SCAN_THREADS; d <<= 1) {
-    const int v = tid >= d ? part[tid - d] : 0;
-    __syncthreads();
-    part[tid] += v;
-    __syncthreads();
-  }
-  int run = part[tid] - own;
-  for (int k = 0; k < per; ++k) {
-    const int c = tid * per + k;
-    if (c < nchunks) { const int v = chunk_off[c]; chunk_off[c] = run; run += v; }
-  }
-  if (tid == SEL_SCAN_THREADS - 1) {
-    const int total = part[tid];
-    info[0] = min(total, cap); info[1] = total; info[2] = total > cap ? 1 : 0; info[3] = 0;
-  }
+  __syncthreads();   // the counts, written by other waves, are what the scan reads
+  const int total = nl_scan_exclusive<SEL_SCAN_THREADS>(chunk_off, nchunks, part);
+  if (tid == SEL_SCAN_THREADS - 1) { info[0] = min(total, cap); info[1] = total; info[2] = total > cap ? 1 : 0; info[3] = 0; }
 }
 
 __global__ __launch_bounds__(SEL_CHUNK) void sel_write_kernel(const int* __restrict__ match_j, int N, int Mc, int cap, const int* __restrict__ chunk_off,
@@ -68,15 +47,11 @@ __global__ __launch_bounds__(SEL_CHUNK) void sel_write_kernel(const int* __restr
                                                               long long* __restrict__ j_ids, long long* __restrict__ b_ids, float* __restrict__ mkps3d,
                                                               float* __restrict__ mkps2d_c) {
   __shared__ int wtot[SEL_CHUNK / 64];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int i = blockIdx.x * SEL_CHUNK + tid;
+  const int i = blockIdx.x * SEL_CHUNK + threadIdx.x;
   const bool f = sel_matched(match_j, i, N, Mc);
-  const unsigned long long bal = __ballot(f);
-  const int rank = __builtin_amdgcn_mbcnt_hi((unsigned)(bal >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)bal, 0u));   // matched lanes below this one
-  if (lane == 0) wtot[wave] = __popcll(bal);
+  const int rank = nl_wave_rank(f, wtot);   // matched lanes below this one
   __syncthreads();
-  int k = chunk_off[blockIdx.x] + rank;
-  for (int w = 0; w < wave; ++w) k += wtot[w];
+  const int k = chunk_off[blockIdx.x] + nl_group_rank(rank, wtot);
   if (f && k < cap) {
     const int j = match_j[i];
     i_ids[k] = i; j_ids[k] = j; b_ids[k] = 0;

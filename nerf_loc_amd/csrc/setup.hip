@@ -13,6 +13,7 @@
 //
 // Both are HBM/latency-trivial (a few MB, tens of microseconds); what they remove is ~700 framework launches and 2V syncs.
 #include "common.h"
+#include "compact.h"
 #include "mvdec.h"
 
 namespace {
@@ -204,22 +205,11 @@ __global__ void bp_count_kernel(const float* __restrict__ depths, int H, int W, 
   if (threadIdx.x == 0) rowcnt[row] = c;
 }
 
-// exclusive scan of the row counts, in place; rowcnt[rows] = total
-__global__ void bp_scan_kernel(int* __restrict__ rowcnt, int rows) {
+// exclusive scan of the row counts, in place (compact.h); rowcnt[rows] = total
+__global__ __launch_bounds__(256) void bp_scan_kernel(int* __restrict__ rowcnt, int rows) {
   __shared__ int part[256];
-  const int t = threadIdx.x, per = (rows + 255) / 256, b = t * per, e = min(b + per, rows);
-  int s = 0;
-  for (int i = b; i < e; ++i) s += rowcnt[i];
-  part[t] = s;
-  __syncthreads();
-  if (t == 0) {
-    int a = 0;
-    for (int i = 0; i < 256; ++i) { const int c = part[i]; part[i] = a; a += c; }
-    rowcnt[rows] = a;
-  }
-  __syncthreads();
-  int a = part[t];
-  for (int i = b; i < e; ++i) { const int c = rowcnt[i]; rowcnt[i] = a; a += c; }
+  const int total = nl_scan_exclusive<256>(rowcnt, rows, part);
+  if (threadIdx.x == 0) rowcnt[rows] = total;
 }
 
 constexpr int BP_MAX_W = 4096;
@@ -239,7 +229,7 @@ __global__ __launch_bounds__(256) void bp_fill_kernel(const float* __restrict__ 
       const int xx = x0 + (int)threadIdx.x;
       const bool ok = xx < Ws && dp[nearest_src(xx < Ws ? xx : 0, sx, W)] > 0.f;
       const unsigned long long b = __ballot(ok);
-      if (ok) cols[base + __popcll(b & ((1ull << threadIdx.x) - 1ull))] = (unsigned short)xx;
+      if (ok) cols[base + nl_lane_rank(b)] = (unsigned short)xx;
       base += __popcll(b);
     }
     if (threadIdx.x == 0) s_cnt = base;
