@@ -4,7 +4,8 @@ Own PyTorch restatement of the reference's per-frame CNN so that reference check
 `DepthFusionNet` (conditional_nerf/depth_fusion.py:239-282) = cross-view depth/colour consistency features
 (:163-207; on the HIP library, `nl_cross_view_features`) -> `ResEncoder` (conditional_nerf/neuray_ops.py:164-239) + a 2-layer depth skip -> 32-channel map at 1/4
 resolution.  It runs once per query frame (not per ray); its output is what `nl_frame_create` receives as
-`vis_featmaps`.  Module/parameter names mirror the reference's state_dict (72 tensors under
+`vis_featmaps`.  With `hip_encode` set, `encode` runs the whole CNN as one call of the fifth HIP library (`nlc_dfnet_forward`, include/nerfloc_cnn.h) wherever no
+gradient is wanted; the default is the eager path.  Module/parameter names mirror the reference's state_dict (72 tensors under
 `multiview_aggregator.depth_fusion.*`).
 """
 from __future__ import annotations
@@ -12,6 +13,8 @@ from __future__ import annotations
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
+
+from . import _packing
 
 
 def _conv3x3(i, o, stride=1):
@@ -105,8 +108,10 @@ class ResEncoder(nn.Module):
         return self.out_conv(x)
 
 
-class DepthFusionNet(nn.Module):
+class DepthFusionNet(nn.Module, _packing.PackedCache):
     """depth_fusion.py:239-282 — (imgs, depths, Ks, c2w poses, depth_range) -> (V,32,H/4,W/4)."""
+
+    hip_encode = False   # opt-in, settable per instance: encode() through libnerfloc_cnn.so where it applies (see encode)
 
     def __init__(self, cfg=None, in_channels=None):
         super().__init__()
@@ -114,15 +119,34 @@ class DepthFusionNet(nn.Module):
         self.depth_skip = nn.Sequential(nn.Conv2d(1, 8, 2, 2), nn.ReLU(True), nn.Conv2d(8, 16, 2, 2))
         self.conv_out = nn.Conv2d(16 + 32, 32, 1, 1)
         self.out_channels = 32
+        self._cache_init()
 
     def forward(self, imgs, feats, depths, Ks, poses, depth_range):
         """The hand-made input channels (normalised inverse depth + cross-view consistency statistics, reference :150-227) come
-        from the HIP library in one pass; the CNN is PyTorch-ROCm (MIOpen)."""
+        from the HIP library in one pass; the CNN is PyTorch-ROCm (MIOpen), or with `hip_encode` the library's encoder: then nothing eager lies between the two calls."""
         from .frame_setup import cross_view_features
         near, far = [float(x) for x in depth_range.reshape(-1)[:2]]
         return self.encode(cross_view_features(imgs, depths, Ks, poses, near, far))
 
+    def _use_hip(self, cnn_in):
+        """The library call is taken only for an fp32 (V, 12, H, W) tensor on a HIP device, inside the library's limits, where no gradient is wanted.  The module's
+        train / eval mode does not enter: InstanceNorm without running statistics is the same function in both."""
+        if not self.hip_encode or not cnn_in.is_cuda or cnn_in.dtype != torch.float32 or cnn_in.dim() != 4 or cnn_in.shape[1] != 12:
+            return False
+        if torch.is_grad_enabled() and (cnn_in.requires_grad or any(p.requires_grad for p in self.parameters())):
+            return False
+        from . import _cnn_lib
+        return _cnn_lib.supported(int(cnn_in.shape[0]), int(cnn_in.shape[2]), int(cnn_in.shape[3]))
+
+    def _encode_hip(self, cnn_in):
+        from . import _cnn_lib
+        sd = dict(self.named_parameters())
+        packed = self._cached(cnn_in.device, [sd[n] for n in _cnn_lib.weight_names()], _cnn_lib.pack_weights)
+        return _cnn_lib.dfnet_forward(packed, cnn_in.contiguous())
+
     def encode(self, cnn_in):
-        """(V,12,H,W) = [rgb | normalised inverse depth | 8 consistency channels] -> (V,32,H/4,W/4) (reference :279-282)."""
+        """(V,12,H,W) = [rgb | normalised inverse depth | 8 consistency channels] -> (V,32,H/4,W/4) (reference :279-282).  The path is chosen per call."""
+        if self._use_hip(cnn_in):
+            return self._encode_hip(cnn_in)
         x = self.fuse_net(cnn_in)
         return self.conv_out(torch.cat([self.depth_skip(cnn_in[:, 3:4]), x], 1))
