@@ -151,6 +151,12 @@ __global__ void knn_nodes_up_kernel(NlKnnNode* nodes, int d_hi, int d_lo) {
 
 typedef unsigned long long u64;
 
+// The lane mask of a predicate straight from the compare (v_cmp into an SGPR pair): __ballot() takes an int, and the predicate's round trip through 0 / 1
+// (v_cndmask + v_cmp_ne) is two vector instructions per ballot that the compiler does not fold away.
+__device__ __forceinline__ u64 ballot64(bool p) { return __builtin_amdgcn_ballot_w64(p); }
+// set bits of m below this lane: v_mbcnt_lo + v_mbcnt_hi (the mask-and-popcount form is four instructions)
+__device__ __forceinline__ int prefix_count(u64 m) { return (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u)); }
+
 // ---- wave-uniform primitives -------------------------------------------------------------------------------------
 // Wave-wide unsigned min as 6 DPP-modified v_min_u32 (row_shr 1/2/4/8 scan inside each row of 16, then row_bcast:15 and
 // row_bcast:31 carry the row totals up) + one v_readlane: the result is wave-uniform (an SGPR).  The __shfl-based
@@ -210,7 +216,10 @@ struct BestK {
 
 // Merge one candidate per lane (kd = bits(dist2), ki = idx; 0xffffffff/0xffffffff = none) into the best list.
 #ifdef KNN_STATS   // debug build: step counts over one search, printed by nl_knn_search (tools/build_variant.sh stats knn.hip -DKNN_STATS)
-__device__ unsigned long long knn_stats[16];
+// [0..15] step counts; histograms (profiles/knn_halfwave_stats.txt): [16 + n] frontier batches with n nodes (1..8), [25 + n] leaf batches with n leaves (1..8),
+// [34 + n] queries ranked with n deferred candidates (0..64), [99 + n] levels entered with a frontier of n nodes (17 = more than 16)
+constexpr int KNN_NSTATS = 128;
+__device__ unsigned long long knn_stats[KNN_NSTATS];
 #define KNN_CNT(i, v) do { if (__lane_id() == 0) atomicAdd(&knn_stats[i], (unsigned long long)(v)); } while (0)
 #else
 #define KNN_CNT(i, v)
@@ -218,18 +227,18 @@ __device__ unsigned long long knn_stats[16];
 template <int K>
 __device__ __forceinline__ void select_into(BestK<K>& best, unsigned kd, unsigned ki, unsigned kp) {
   while (true) {
-    const bool cont = kd < best.td || (kd == best.td && ki < best.ti);
-    if (__ballot(cont) == 0ull) break;
+    const bool cont = (((u64)kd << 32) | (u64)ki) < (((u64)best.td << 32) | (u64)best.ti);   // the tuple order as ONE 64-bit compare, which the ballot takes as it is
+    if (ballot64(cont) == 0ull) break;
     KNN_CNT(2, 1);
     const unsigned dmin = wave_umin(cont ? kd : 0xffffffffu);
     const bool tie = cont && kd == dmin;
-    const u64 tm = __ballot(tie);
+    const u64 tm = ballot64(tie);
     unsigned imin;
     int src = __builtin_ctzll(tm);
     if (__popcll(tm) == 1) imin = (unsigned)__builtin_amdgcn_readlane((int)ki, src);
     else {
       imin = wave_umin(tie ? ki : 0xffffffffu);
-      src = __builtin_ctzll(__ballot(tie && ki == imin));
+      src = __builtin_ctzll(ballot64(tie && ki == imin));
     }
     best.insert(dmin, imin, (unsigned)__builtin_amdgcn_readlane((int)kp, src));
     if (tie && ki == imin) { kd = 0xffffffffu; ki = 0xffffffffu; }
@@ -316,6 +325,12 @@ __global__ __launch_bounds__(256) void knn_wave_kernel(const float* __restrict__
   bool pkeep = false;
   u64* const ckey = s_ckey[wv];
   unsigned* const cpos = s_cpos[wv];
+  // the six bounds of the start-level box, one per lane: lane 2 a + b holds axis a's lower (b = 0) or upper (b = 1) bound (lanes past 5 repeat axis 2, unused)
+  const int box_ax = min(lane >> 1, 2);
+  const float box_org = box_ax == 0 ? c.org0 : (box_ax == 1 ? c.org1 : c.org2);
+  const int box_step = (lane & 1) ? 1 : -1;
+  // ds_bpermute addresses (4 x lane) of the three of those lanes whose coordinates make up the start node of lane l < 8: bit a of l picks lower or upper
+  const int seed_ax = 4 * (lane & 1), seed_ay = 4 * (2 + ((lane >> 1) & 1)), seed_az = 4 * (4 + ((lane >> 2) & 1));
 
   // A wave answers SPW consecutive queries (neighbouring samples of a ray).  Only the first one pays for phase 1: the K
   // neighbours of the previous query, re-measured from this one, give the bound instead.
@@ -331,7 +346,7 @@ __global__ __launch_bounds__(256) void knn_wave_kernel(const float* __restrict__
   // DEFERRED SELECTION (round 5).  With the bound of the previous query's neighbours (within a few percent of the K-th distance) only ~10 candidates per query pass
   // `dist2 <= U`, and at least K do (those neighbours themselves).  Feeding them to the selection loop one by one (a wave-min, two ballots and an insert each: ~40 vector
   // instructions x 10.4 per query = a third of the kernel's instructions, KNN_STATS build) is replaced by: append each batch's survivors to a list in LDS (one ballot +
-  // prefix count per batch), and at the end give every entry its RANK among them (one 64-bit compare per pair: 2 v_readlane + v_cmp_lt_u64 + v_addc per entry) — the
+  // prefix count per batch), and at the end give every entry its RANK among them (one 64-bit compare per pair: v_cmp_lt_u64 + v_addc per entry, the entry read back from LDS) — the
   // entries of rank < K ARE the answer, already in their output slots.  Same keys, same order: the (dist2 bits, idx) tuples are unique.  U does not tighten during such
   // a query (it is tight already).  A list that would pass 64 entries is poured into the selection loop's list and the query continues there (exact either way).
   bool deferred = prev_full;
@@ -352,15 +367,14 @@ __global__ __launch_bounds__(256) void knn_wave_kernel(const float* __restrict__
     ncand = 0;
     deferred = false;
   };
-  const u64 lt_mask = (1ull << lane) - 1ull;
   auto sink = [&](unsigned kd, unsigned ki, unsigned kp) __attribute__((always_inline)) {
     if (!deferred) { select_into<K>(best, kd, ki, kp); return; }
     const bool v = ki != 0xffffffffu;
-    const u64 mv = __ballot(v);
+    const u64 mv = ballot64(v);
     if (mv == 0ull) return;
     const int cn = __popcll(mv);
     if (ncand + cn > 64) { pour(); select_into<K>(best, kd, ki, kp); return; }
-    if (v) { const int pos = ncand + __popcll(mv & lt_mask); ckey[pos] = ((u64)kd << 32) | (u64)ki; cpos[pos] = kp; }
+    if (v) { const int pos = ncand + prefix_count(mv); ckey[pos] = ((u64)kd << 32) | (u64)ki; cpos[pos] = kp; }
     ncand += cn;
   };
   if (!prev_full) {
@@ -401,10 +415,14 @@ __global__ __launch_bounds__(256) void knn_wave_kernel(const float* __restrict__
   // (Wave-uniform arithmetic; the box is widened by the rounding slack and one cell, and every child still passes the exact box test below.)
   int Lstart = GRID_BITS;
   if (U < 3.0e38f) {
-    const float r = sqrtf(U * 1.000001f) + c.slack;
-    const int lo0 = min(max((int)floorf((c.qx - r - c.org0) * inv_cell) - 1, 0), GRID_N - 1), hi0 = min(max((int)floorf((c.qx + r - c.org0) * inv_cell) + 1, 0), GRID_N - 1);
-    const int lo1 = min(max((int)floorf((c.qy - r - c.org1) * inv_cell) - 1, 0), GRID_N - 1), hi1 = min(max((int)floorf((c.qy + r - c.org1) * inv_cell) + 1, 0), GRID_N - 1);
-    const int lo2 = min(max((int)floorf((c.qz - r - c.org2) * inv_cell) - 1, 0), GRID_N - 1), hi2 = min(max((int)floorf((c.qz + r - c.org2) * inv_cell) + 1, 0), GRID_N - 1);
+    // The hardware square root (1 ulp) in place of sqrtf's refined one (~20 instructions): the factor 1.000001 on U is 5e-7 of r, eight times that error, and the
+    // box only has to CONTAIN the ball.  The six bounds are one lane each (lo = floor((q - r - org) / cell) - 1, hi = floor((q + r - org) / cell) + 1, clamped to the
+    // grid: the same operations in the same order as when every lane computed all six), read back as scalars.
+    const float r = __builtin_amdgcn_sqrtf(U * 1.000001f) + c.slack;
+    const int bound = min(max((int)floorf((q[3 * (size_t)n + box_ax] + ((lane & 1) ? r : -r) - box_org) * inv_cell) + box_step, 0), GRID_N - 1);
+    const int lo0 = __builtin_amdgcn_readlane(bound, 0), hi0 = __builtin_amdgcn_readlane(bound, 1);
+    const int lo1 = __builtin_amdgcn_readlane(bound, 2), hi1 = __builtin_amdgcn_readlane(bound, 3);
+    const int lo2 = __builtin_amdgcn_readlane(bound, 4), hi2 = __builtin_amdgcn_readlane(bound, 5);
     int Ls = 1;
     while (Ls < GRID_BITS && (((hi0 >> Ls) - (lo0 >> Ls)) > 1 || ((hi1 >> Ls) - (lo1 >> Ls)) > 1 || ((hi2 >> Ls) - (lo2 >> Ls)) > 1)) ++Ls;
     Ls = __builtin_amdgcn_readfirstlane(Ls);
@@ -412,8 +430,13 @@ __global__ __launch_bounds__(256) void knn_wave_kernel(const float* __restrict__
       Lstart = Ls;
       const unsigned nx = (unsigned)(lo0 >> Ls) + (lane & 1), ny = (unsigned)(lo1 >> Ls) + ((lane >> 1) & 1), nz = (unsigned)(lo2 >> Ls) + ((lane >> 2) & 1);
       const bool ok = lane < 8 && nx <= (unsigned)(hi0 >> Ls) && ny <= (unsigned)(hi1 >> Ls) && nz <= (unsigned)(hi2 >> Ls);
-      const u64 mk = __ballot(ok);
-      if (ok) front[__popcll(mk & lt_mask)] = (unsigned)nl_knn_node_base(GRID_BITS - Ls) + morton3(nx, ny, nz);
+      const u64 mk = ballot64(ok);
+      // Morton code of (nx, ny, nz): the bits of the six coordinates involved are spread ONCE, by the lanes that hold the bounds (lane 2 a + b: axis a's
+      // (lo_a >> Ls) + b, shifted into place; quad_perm [0, 0, 2, 2] brings lo_a to both lanes of the pair), and every lane gathers its three
+      const int lo_l = __builtin_amdgcn_update_dpp(0, bound, 0xA0, 0xf, 0xf, false);
+      const int spread = (int)(part1by2((unsigned)(lo_l >> Ls) + (unsigned)(lane & 1)) << box_ax);
+      const unsigned code = (unsigned)(__builtin_amdgcn_ds_bpermute(seed_ax, spread) | __builtin_amdgcn_ds_bpermute(seed_ay, spread) | __builtin_amdgcn_ds_bpermute(seed_az, spread));
+      if (ok) front[prefix_count(mk)] = (unsigned)nl_knn_node_base(GRID_BITS - Ls) + code;
       nfront = __popcll(mk);
     }
   }
@@ -424,7 +447,7 @@ __global__ __launch_bounds__(256) void knn_wave_kernel(const float* __restrict__
   auto flush_leaves = [&]() {
     constexpr int SL = LEAF_COUNT_MAX;   // lanes per slot
     for (int b = 0; b < nleaf; b += 64 / SL) {
-      KNN_CNT(1, 1);
+      KNN_CNT(1, 1); KNN_CNT(25 + min(nleaf - b, 64 / SL), 1);
       const int e = b + lane / SL;
       const bool ok = e < nleaf;
       const int rs = ok ? leaf_s[e] : 0, ln = ok ? leaf_l[e] : 0;
@@ -438,44 +461,47 @@ __global__ __launch_bounds__(256) void knn_wave_kernel(const float* __restrict__
 
   for (int L = Lstart; L > 0; --L) {
     int nnext = 0;
+    KNN_CNT(99 + min(nfront, 17), 1);
     for (int base = 0; base < nfront; base += 8) {
-      KNN_CNT(0, 1);
+      KNN_CNT(0, 1); KNN_CNT(16 + min(nfront - base, 8), 1);
       const int ni = base + (lane >> 3);
-      bool keep = false, leaf = false;
       unsigned mc = 0;
-      int rs = 0, cnt = 0;
+      int rs = 0;
+      // the child's point count if the child is kept, else 0.  Every list's mask below is ONE compare of this register, combined as scalars: a mask built from
+      // predicates that leave the branch costs a v_cndmask + v_cmp_ne to rebuild (the ballot of anything but a compare), three times per batch
+      int ck = 0;
       if (ni < nfront) {
         mc = 8u * front[ni] + 1u + (unsigned)(lane & 7);
         const NlKnnNode r = nodes[mc];   // one record: the range and the box of the child's points
         rs = r.start;
-        cnt = r.count;
-        keep = cnt > 0 && node_mindist2(c, r) <= U * 1.000001f;   // '<=' keeps exact ties; margin covers fp32 rounding
-        leaf = keep && (L - 1 == 0 || cnt <= LEAF_COUNT_MAX);
+        // '<=' keeps exact ties; margin covers fp32 rounding.  '&', not '&&': the box is tested whether or not the node has points (an empty node's gives +inf), so the
+        // record is ONE fetch — with '&&' the compiler fetched {start, count} first and the box in a branch behind it: two dependent round trips per batch
+        ck = ((r.count > 0) & (node_mindist2(c, r) <= U * 1.000001f)) ? r.count : 0;
       }
-      const bool inner = keep && !leaf;
-      const u64 mi = __ballot(inner);
+      const bool wide = ck > LEAF_COUNT_MAX;         // kept and wider than a leaf slot: an inner node, or a dense fine cell
+      const u64 mwide = ballot64(wide);
+      const u64 mi = L - 1 == 0 ? 0ull : mwide;      // inner nodes
       const int ci = __popcll(mi);
       // inner nodes that do not fit the frontier are scanned as (coarse) leaves instead: still exact
       const int room = FRONT_CAP - nnext;
-      const int pi = __popcll(mi & lt_mask);
-      const bool spill = inner && pi >= room;
-      if (inner && !spill) nextf[nnext + pi] = mc;
+      const int pi = prefix_count(mi);
+      if (wide && L - 1 != 0 && pi < room) nextf[nnext + pi] = mc;
       nnext += ci < room ? ci : room;
       // ranges wider than a slot (dense fine cells, spilled inner nodes) are rare: scanned right away, one by one
-      const bool lf = leaf || spill;
-      u64 mbig = __ballot(lf && cnt > LEAF_COUNT_MAX);
+      u64 mbig = L - 1 == 0 ? mwide : 0ull;
+      if (ci > room) mbig |= mi & ballot64(pi >= room);
       while (mbig) {
         const int src = __builtin_ctzll(mbig);
         mbig &= mbig - 1;
-        scan_range<K, true>(c, sorted, __builtin_amdgcn_readlane(rs, src), __builtin_amdgcn_readlane(cnt, src), lane, best, sink, dedupe_now, __float_as_uint(U));
+        scan_range<K, true>(c, sorted, __builtin_amdgcn_readlane(rs, src), __builtin_amdgcn_readlane(ck, src), lane, best, sink, dedupe_now, __float_as_uint(U));
         if (best.full()) U = fminf(U, __uint_as_float(best.td));
       }
-      const bool small = lf && cnt <= LEAF_COUNT_MAX;
-      const u64 ml = __ballot(small);
+      const bool kept = ck > 0;
+      const u64 ml = ballot64(kept) & ~mwide;        // kept, at most a slot wide: leaves
       const int cl_ = __popcll(ml);
       KNN_CNT(13, cl_);
       if (nleaf + cl_ > LEAF_CAP) flush_leaves();
-      if (small) { const int p = nleaf + __popcll(ml & lt_mask); leaf_s[p] = rs; leaf_l[p] = cnt; }
+      if (kept && !wide) { const int p = nleaf + prefix_count(ml); leaf_s[p] = rs; leaf_l[p] = ck; }
       nleaf += cl_;
       if (nleaf >= 32) flush_leaves();
     }
@@ -487,14 +513,14 @@ __global__ __launch_bounds__(256) void knn_wave_kernel(const float* __restrict__
 
   if (deferred && ncand < K) pour();   // (cannot happen: the previous neighbours lie within the bound; kept so that the slots past the list are written below)
   if (deferred) {
+    KNN_CNT(34 + ncand, 1);
     lds_list_handover();
     const u64 mine = lane < ncand ? ckey[lane] : ~0ull;
     const unsigned mlo = (unsigned)mine, mhi = (unsigned)(mine >> 32);
     int rank = 0;
-    for (int jj = 0; jj < ncand; ++jj) {   // wave-uniform trip count; entry jj as a scalar pair against every lane's own key
-      const u64 kj = ((u64)(unsigned)__builtin_amdgcn_readlane((int)mhi, jj) << 32) | (u64)(unsigned)__builtin_amdgcn_readlane((int)mlo, jj);
-      rank += kj < mine ? 1 : 0;
-    }
+    // wave-uniform trip count; entry jj comes back from the list in LDS, one address for the whole wave (a broadcast, several entries per read once unrolled):
+    // a compare and an add per entry — as a scalar pair out of the lanes' own copies it was two v_readlane more
+    for (int jj = 0; jj < ncand; ++jj) rank += ckey[jj] < mine ? 1 : 0;
     const bool win = lane < ncand && rank < K;
     if (win && rank < Kout) {
       idx_out[(size_t)n * Kout + rank] = (int)mlo;
@@ -578,15 +604,26 @@ int nl_knn_search(const NlKnnGrid* g, const float* xyz, int64_t N, int K, int* i
   NL_LAUNCH_CHECK();
 #ifdef KNN_STATS
   {
-    unsigned long long h[16];
+    unsigned long long h[KNN_NSTATS];
     hipStreamSynchronize(st);
     hipMemcpyFromSymbol(h, HIP_SYMBOL(knn_stats), sizeof(h));
     fprintf(stderr, "knn stats per query (N = %lld): frontier batches %.2f, leaf batches %.2f, selection iterations %.2f, range batches %.2f, start level %.2f, phase-1 %.3f, leaves %.2f; start-level histogram",
             (long long)N, (double)h[0] / N, (double)h[1] / N, (double)h[2] / N, (double)h[3] / N, (double)h[4] / N, (double)h[5] / N, (double)h[13] / N);
     for (int l = 0; l <= GRID_BITS; ++l) fprintf(stderr, " %d:%.3f", l, (double)h[6 + l] / N);
     fprintf(stderr, "\n");
+    auto hist = [&](const char* what, int base, int lo, int hi) {
+      unsigned long long tot = 0;
+      for (int n = lo; n <= hi; ++n) tot += h[base + n];
+      fprintf(stderr, "  %s (total %llu):", what, tot);
+      for (int n = lo; n <= hi; ++n) if (h[base + n]) fprintf(stderr, " %d:%.4f", n, (double)h[base + n] / (double)(tot ? tot : 1));
+      fprintf(stderr, "\n");
+    };
+    hist("nodes per frontier batch", 16, 1, 8);
+    hist("leaves per leaf batch", 25, 1, 8);
+    hist("deferred candidates at ranking", 34, 0, 64);
+    hist("frontier nodes per level entered (17 = more)", 99, 0, 17);
     hipMemset(nullptr, 0, 0);
-    unsigned long long z[16] = {0};
+    unsigned long long z[KNN_NSTATS] = {0};
     hipMemcpyToSymbol(HIP_SYMBOL(knn_stats), z, sizeof(z));
   }
 #endif
