@@ -99,6 +99,17 @@ class GraphedKeep:
         self._run("bwd")
         return self.go.clone(), self.gd.clone(), self.gq.sum(0)
 
+    # -- in place, for a caller that fills and reads the static buffers itself and captures its own graph around the pair (pose_optimizer.PoseOptimizer.refine):
+    # rays in self.o / self.d / self.q (per-ray centres) / self.z, results in self.out, cotangents in self.cot, ray gradients in self.go / self.gd / self.gq
+    def forward_inplace(self):
+        """nl_render_rays_forward_keep on the static buffers, enqueued on the current stream (no copy-in, no clone-out, no graph of its own)."""
+        self._fwd_call()
+        self.fwd_count += 1
+
+    def backward_inplace(self):
+        """nl_render_rays_backward_kept on the static buffers, enqueued on the current stream: once per forward_inplace (it consumes the kept activations)."""
+        self._bwd_call()
+
 
 class GraphedRender:
     """The fused inference path (`nl_render_rays_ex`) of ONE batch shape against ONE frame / weight set / precision as a HIP graph (round 5).
@@ -158,6 +169,10 @@ class _Lease:
         self._pool = pool
 
     def __del__(self):
+        self._pool["busy"] = False
+
+    def release(self):
+        """Frees the pool now, for a holder that knows it is done (dropping the lease does the same whenever the last reference goes)."""
         self._pool["busy"] = False
 
 
@@ -703,6 +718,27 @@ class HipRenderer:
                 reg[k] = "seen"
             ent = reg[key] = GraphedKeep(self, R, white_bkgd)
         return ent
+
+    def keep_buffers(self, R: int, white_bkgd: bool = False, max_bytes: Optional[int] = None):
+        """The GraphedKeep of this batch shape for the CURRENT frame / weights, made on the first request (a caller that drives the pair in place holds its
+        static buffers from its first step on; `graphed_keep` hands them out only from the second request).  None when the pair does not fit `max_bytes` as one
+        chunk, or under a guard."""
+        self._ready()
+        if getattr(self, "guard_bytes", 0):
+            return None
+        need = self.lib.nl_render_rays_keep_workspace_bytes(ct.byref(self.cfg), self.V, int(R), 0)
+        if need == 0 or (max_bytes is not None and need > max_bytes):
+            return None
+        reg = self.__dict__.setdefault("_graphs", {})
+        if reg.get("gen") != self.state_gen:
+            reg.clear()
+            reg["gen"] = self.state_gen
+        key = (int(R), bool(white_bkgd))
+        if not isinstance(reg.get(key), GraphedKeep):
+            for k in [k for k, v in reg.items() if isinstance(v, GraphedKeep)][:-1]:   # (at most two shapes own a static workspace, as in graphed_keep)
+                reg[k] = "seen"
+            reg[key] = GraphedKeep(self, R, white_bkgd)
+        return reg[key]
 
     def _stage_backward(self, stage: str, frozen_sizer: str, size_args, chunk_args, args, train: "TrainGrads"):
         """The library call of one stage's backward wrapper: `nl_<stage>_backward`, or with `train` its `_train` twin, which takes the same arguments with the
