@@ -1,4 +1,4 @@
-"""The one ctypes binding layer of the seven shared libraries: every signature is read from the C header that declares it.
+"""The one ctypes binding layer of the eight shared libraries: every signature is read from the C header that declares it.
 
 The compiler ties header and implementation (each .hip unit includes its header); `prototypes` ties the binding to the same text, so no entry point is described
 by hand a second time.  The type rule, applied to a parameter after dropping `const` and its name:

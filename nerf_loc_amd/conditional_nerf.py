@@ -197,7 +197,7 @@ class ConditionalNeRF(nn.Module):
     _SAFER = {"f16mx": "bf16x3", "bf16x3": "fp32", "bf16": "bf16x3"}
 
     def __init__(self, args, activation_func=None, precision: str = "f16mx", device: Optional[str] = None, precision_guard: bool = True,
-                 hip_frame_cnn: bool = False):
+                 hip_frame_cnn: bool = False, hip_frame_cnn_training: bool = False):
         super().__init__()
         self.args = copy.deepcopy(args)
         C, W = args.backbone2d_fpn_dim, args.model_3d_hidden_dim
@@ -212,6 +212,8 @@ class ConditionalNeRF(nn.Module):
         self.multiview_aggregator = MultiviewFeatureAggregator(args, in_channels=C, out_channels=W)
         if hip_frame_cnn:   # the per-frame CNN through libnerfloc_cnn.so where no gradient is wanted (DepthFusionNet.encode); off by default
             self.multiview_aggregator.depth_fusion.hip_encode = True
+        if hip_frame_cnn_training:   # its forward + backward through libnerfloc_cnn_train.so where the parameters want gradients; off by default
+            self.multiview_aggregator.depth_fusion.hip_training = True
         self.confidence_mlp = nn.Sequential(nn.Linear(W, 64), act(), nn.Linear(64, 1), nn.Sigmoid())
         self.keypoint_head = nn.Sequential(nn.Linear(C, 1), nn.Sigmoid())
         self.base_mlp = nn.Sequential(nn.Linear(F_ + xyz_dim + view_dim, W), act(), nn.Linear(W, W), act(), nn.Linear(W, W), act())

@@ -5,7 +5,8 @@ Own PyTorch restatement of the reference's per-frame CNN so that reference check
 (:163-207; on the HIP library, `nl_cross_view_features`) -> `ResEncoder` (conditional_nerf/neuray_ops.py:164-239) + a 2-layer depth skip -> 32-channel map at 1/4
 resolution.  It runs once per query frame (not per ray); its output is what `nl_frame_create` receives as
 `vis_featmaps`.  With `hip_encode` set, `encode` runs the whole CNN as one call of the fifth HIP library (`nlc_dfnet_forward`, include/nerfloc_cnn.h) wherever no
-gradient is wanted; the default is the eager path.  Module/parameter names mirror the reference's state_dict (72 tensors under
+gradient is wanted; with `hip_training` set, a call whose parameters want gradients runs forward and backward as one autograd node on the eighth library
+(`nlct_dfnet_forward_train` / `nlct_dfnet_backward`, include/nerfloc_cnn_train.h).  The default of both is the eager path.  Module/parameter names mirror the reference's state_dict (72 tensors under
 `multiview_aggregator.depth_fusion.*`).
 """
 from __future__ import annotations
@@ -13,6 +14,8 @@ from __future__ import annotations
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
+
+from torch.autograd.function import once_differentiable
 
 from . import _packing
 
@@ -108,10 +111,32 @@ class ResEncoder(nn.Module):
         return self.out_conv(x)
 
 
+class _EncodeTrain(torch.autograd.Function):
+    """encode as one node: nlct_dfnet_forward_train keeps the state, nlct_dfnet_backward writes the gradients of the parameters that want one (the others pass NULL).
+    cnn_in gets no gradient (the call is taken only where it wants none).  The backward uses the image its forward ran on."""
+
+    @staticmethod
+    def forward(ctx, module, cnn_in, *params):
+        from . import _cnn_train_lib
+        x = cnn_in.detach().contiguous()
+        ctx.packed = module._packed_training(x.device, params)
+        out, ctx.state = _cnn_train_lib.dfnet_forward_train(ctx.packed, x)
+        ctx.x, ctx.shapes, ctx.dtypes = x, [tuple(p.shape) for p in params], [p.dtype for p in params]
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_out):
+        from . import _cnn_train_lib
+        grads = _cnn_train_lib.dfnet_backward(ctx.packed, ctx.x, ctx.state, g_out.to(torch.float32).contiguous(), ctx.shapes, ctx.needs_input_grad[2:])
+        return (None, None) + tuple(None if g is None else g.to(d) for g, d in zip(grads, ctx.dtypes))
+
+
 class DepthFusionNet(nn.Module, _packing.PackedCache):
     """depth_fusion.py:239-282 — (imgs, depths, Ks, c2w poses, depth_range) -> (V,32,H/4,W/4)."""
 
     hip_encode = False   # opt-in, settable per instance: encode() through libnerfloc_cnn.so where it applies (see encode)
+    hip_training = False   # opt-in, settable per instance: encode() + its backward through libnerfloc_cnn_train.so where the parameters want gradients
 
     def __init__(self, cfg=None, in_channels=None):
         super().__init__()
@@ -120,6 +145,7 @@ class DepthFusionNet(nn.Module, _packing.PackedCache):
         self.conv_out = nn.Conv2d(16 + 32, 32, 1, 1)
         self.out_channels = 32
         self._cache_init()
+        self._train_cache = _packing.new_train_cache()   # the training image (nlct_dfnet_pack_weights); pack_count counts both images
 
     def forward(self, imgs, feats, depths, Ks, poses, depth_range):
         """The hand-made input channels (normalised inverse depth + cross-view consistency statistics, reference :150-227) come
@@ -144,9 +170,34 @@ class DepthFusionNet(nn.Module, _packing.PackedCache):
         packed = self._cached(cnn_in.device, [sd[n] for n in _cnn_lib.weight_names()], _cnn_lib.pack_weights)
         return _cnn_lib.dfnet_forward(packed, cnn_in.contiguous())
 
+    def _use_hip_training(self, cnn_in):
+        """The training pair is taken only for an fp32 (V, 12, H, W) tensor on a HIP device, inside the library's limits, with grad enabled, where cnn_in itself
+        wants no gradient and at least one parameter does."""
+        if not self.hip_training or not torch.is_grad_enabled() or not cnn_in.is_cuda or cnn_in.dtype != torch.float32 or cnn_in.dim() != 4 or cnn_in.shape[1] != 12:
+            return False
+        if cnn_in.requires_grad or not any(p.requires_grad for p in self.parameters()):
+            return False
+        from . import _cnn_lib
+        return _cnn_lib.supported(int(cnn_in.shape[0]), int(cnn_in.shape[2]), int(cnn_in.shape[3]))
+
+    def _packed_training(self, device, params):
+        from . import _cnn_train_lib
+
+        def pack(ts):
+            self.pack_count += 1
+            return _cnn_train_lib.pack_weights(ts)
+        return self._train_cache._cached(device, list(params), pack)
+
+    def _encode_hip_training(self, cnn_in):
+        from . import _cnn_lib
+        sd = dict(self.named_parameters())
+        return _EncodeTrain.apply(self, cnn_in, *[sd[n] for n in _cnn_lib.weight_names()])
+
     def encode(self, cnn_in):
         """(V,12,H,W) = [rgb | normalised inverse depth | 8 consistency channels] -> (V,32,H/4,W/4) (reference :279-282).  The path is chosen per call."""
         if self._use_hip(cnn_in):
             return self._encode_hip(cnn_in)
+        if self._use_hip_training(cnn_in):
+            return self._encode_hip_training(cnn_in)
         x = self.fuse_net(cnn_in)
         return self.conv_out(torch.cat([self.depth_skip(cnn_in[:, 3:4]), x], 1))
