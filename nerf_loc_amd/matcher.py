@@ -18,7 +18,7 @@ import ctypes as C
 import torch
 import torch.nn as nn
 
-from . import _head_lib, _lib
+from . import _counted_lib, _head_lib, _lib
 from ._packing import check_precision, require_device
 from .fine_matching import FineMatching, FinePreprocess
 from .matching import S2DMatching
@@ -89,11 +89,16 @@ class Matcher(nn.Module):
         return t
 
     @torch.no_grad()
-    def forward_padded(self, data, capacity=None):
+    def forward_padded(self, data, capacity=None, num_points=None):
         """`forward` in eval mode with fixed shapes: i_ids, j_ids, b_ids, mkps3d, mkps2d_c, expec_f, mkps2d_f (and `pairs`) hold `capacity` rows, of which the first
         `num_matches` (a 0-d int32 DEVICE tensor) are forward's rows, in forward's order; `overflow` (0-d int32) is 1 when more rows matched than `capacity`, which
         then holds the first `capacity` of them.  capacity defaults to N: a 3-D point has at most one partner, so N cannot overflow.  Rows at and beyond
-        num_matches are computed from zero descriptors and are finite; nothing may depend on them.  No host read-back; returns a new dict on top of `data`."""
+        num_matches are computed from zero descriptors and are finite; nothing may depend on them.  No host read-back; returns a new dict on top of `data`.
+        num_points (default None: all N) is a 0-d int32 DEVICE tensor n: only the first n rows of the 3-D inputs (desc_3d, pos_emd_3d, desc_3d_fine, kps3d) exist
+        (libnerfloc_counted.so).  The first num_matches rows are then forward's rows on those inputs cut to n rows, bit for bit; input rows at and beyond n must be
+        finite and no valid row depends on them.  A host integer or a CPU tensor raises: it would hide a read-back or defeat graph replay."""
+        if num_points is not None:
+            _counted_lib.device_count(num_points, "Matcher.forward_padded")
         t = self._padded_inputs("forward_padded", data)
         N, Mc = t["desc_3d"].shape[0], t["desc_2d_coarse"].shape[0]
         cap = N if capacity is None else int(capacity)
@@ -106,8 +111,12 @@ class Matcher(nn.Module):
         if tuple(t["kps2d"].shape) != (Mc, 2) or tuple(t["kps3d"].shape) != (N, 3) or Bf < 1 or stride < 1 or Mc > cells:
             # the selection's j_ids lie in [0, Mc): with Mc <= cells they are valid window ids, which is why the windows call needs no read-back here
             raise ValueError(f"Matcher.forward_padded: kps3d (N, 3), kps2d (Mc, 2) and at most one 2-D key point per coarse cell ({cells}) of feat_fine are required")
-        d3, d2 = self.coarse_transformer.transform(t["desc_3d"][None], t["pos_emd_3d"][None], t["desc_2d_coarse"][None], t["pos_emd_2d"][None])
-        scores, match_j, _ = self.coarse_matcher.match(d3[0], d2[0])
+        if num_points is None:
+            d3, d2 = self.coarse_transformer.transform(t["desc_3d"][None], t["pos_emd_3d"][None], t["desc_2d_coarse"][None], t["pos_emd_2d"][None])
+            scores, match_j, _ = self.coarse_matcher.match(d3[0], d2[0])
+        else:   # rows behind the count are no keys of the transformer and take no part in the selection's maxima; match_j is -1 there
+            d3, d2 = self.coarse_transformer.transform(t["desc_3d"][None], t["pos_emd_3d"][None], t["desc_2d_coarse"][None], t["pos_emd_2d"][None], n0=num_points)
+            scores, match_j, _ = self.coarse_matcher.match(d3[0], d2[0], n=num_points)
         sel = _head_lib.select_matches(match_j, cap, t["kps3d"], t["kps2d"], t["desc_3d_fine"], t["pos_emd_3d"])
         win = self.fine_preprocess._windows_call(feat_fine, sel["b_ids"], sel["j_ids"], stride, check_ids=False)[0]
         W = self.fine_window_size
@@ -121,16 +130,18 @@ class Matcher(nn.Module):
         return out
 
     @torch.no_grad()
-    def localize(self, data, K, thr, hypotheses: int = DEFAULT_HYPOTHESES, seed: int = 0, min_inliers: int = 4, capacity=None):
+    def localize(self, data, K, thr, hypotheses: int = DEFAULT_HYPOTHESES, seed: int = 0, min_inliers: int = 4, capacity=None, num_points=None):
         """Descriptors in, pose out, without a host synchronisation: forward_padded, mkps2d_f * stride_fine, nlh_pnp_ransac_counted on the device count.
         K: (fx, fy, cx, cy) or a 3 x 3 matrix as numbers or a CPU tensor (a device tensor would cost a read-back), thr in pixels.  Returns DEVICE tensors: T_w2c,
         T_c2w (4 x 4 float64), inliers (capacity) bool — False at and beyond num_matches —, num_inliers, success, num_matches, overflow (0-d int32) and the padded
         match tensors of forward_padded.  The pose, mask and counts equal pose.absolute_pose on forward's matches with the same seed, bit for bit.  Fewer than
-        four matches: the identity, success 0.  One linear chain on the current stream: capturable with torch.cuda.graph after one warm call."""
+        four matches: the identity, success 0.  One linear chain on the current stream: capturable with torch.cuda.graph after one warm call.
+        num_points: forward_padded's — with a 0-d int32 DEVICE tensor n the first num_matches rows, the pose, the mask and the counts equal `forward` followed by
+        absolute_pose on the first n rows of the 3-D inputs, bit for bit (the second stage of cascade.localize_cascade); n == 0: the identity, success 0."""
         if torch.is_tensor(K) and K.is_cuda:
             raise ValueError("Matcher.localize: K must be numbers or a CPU tensor (a device tensor would synchronise)")
         fx, fy, cx, cy = _intrinsics(K)
-        out = self.forward_padded(data, capacity)
+        out = self.forward_padded(data, capacity, num_points)
         lib = _head_lib.load()
         p3 = out["mkps3d"]
         dev = p3.device

@@ -12,7 +12,7 @@ import ctypes as C
 import torch
 import torch.nn as nn
 
-from . import _lib
+from . import _counted_lib, _lib
 from ._packing import (MATCHER_HIDDEN, MATCHER_MLP_PARAMS, PackedCache, check_precision, matcher_mlp_grad_buffers, matcher_mlp_grads_out,
                        pack_matcher_mlp, pack_matcher_mlp_train, require_device)
 
@@ -143,13 +143,18 @@ class S2DMatching(nn.Module, PackedCache):
         """The training image (the transposed weights of nl_s2d_pack_train_weights), cached like the inference image."""
         return pack_matcher_mlp_train("S2DMatching", self, device)
 
-    def match(self, desc0, desc1, want_scores=None):
-        """The library call: (score_matrix or None, match_j (N) int32 with -1 = unmatched, match_score (N))."""
+    def match(self, desc0, desc1, want_scores=None, n=None):
+        """The library call: (score_matrix or None, match_j (N) int32 with -1 = unmatched, match_score (N)).  n (default None: every row exists) is a 0-d int32
+        DEVICE tensor: only the first n rows of desc0 exist.  nl_s2d_match still scores all N rows (a pair's score has its own bits whatever the other rows are);
+        nlk_s2d_select_counted (libnerfloc_counted.so) then replaces the selection: maxima over rows < n, match_j = -1 and match_score = 0 behind n."""
         require_device("S2DMatching", desc0, desc1)
         if desc0.dim() != 2 or desc1.dim() != 2 or desc0.shape[1] != self.feat_dim or desc1.shape[1] != self.feat_dim:
             raise ValueError(f"S2DMatching: descriptors must be (N, {self.feat_dim}) and (M, {self.feat_dim})")
         want = self.want_score_matrix if want_scores is None else bool(want_scores)
         dev = desc0.device
+        if n is not None:
+            _counted_lib.device_count(n, "S2DMatching.match", dev)
+            keep, want = want, True   # the counted selection reads the matrix
         lib = _lib.load()
         d0 = desc0.detach().to(torch.float32).contiguous()
         d1 = desc1.detach().to(torch.float32).contiguous()
@@ -164,6 +169,9 @@ class S2DMatching(nn.Module, PackedCache):
             _lib.check(lib.nl_s2d_match(packed.data_ptr(), self.feat_dim, _lib.PRECISIONS[self.precision], d0.data_ptr(), N, d1.data_ptr(), M,
                                         C.c_float(float(self.thr)), _lib.ptr(scores), match_j.data_ptr(), match_s.data_ptr(), ws.data_ptr(), ws.numel(), st),
                        "nl_s2d_match")
+            if n is not None:
+                match_j, match_s = _counted_lib.s2d_select_counted(scores, n, self.thr)
+                scores = scores if keep else None
         return scores, match_j, match_s
 
     def forward(self, desc0, desc1, data):

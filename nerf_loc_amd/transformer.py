@@ -30,7 +30,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import _lib
+from . import _counted_lib, _lib
 from ._packing import PackedCache, check_precision, new_train_cache, require_device
 
 _LIMITS = "nhead == 8, d_model in {64, 128, 192, 256}, dim_feedforward a multiple of 32 in 32..512, activation 'relu'"
@@ -222,8 +222,10 @@ class SelfCrossTransformer(nn.Module, PackedCache):
             return False
         return _lib.load().nl_sct_train_state_bytes(v0.shape[0], v0.shape[1], v1.shape[1], C, self.dim_feedforward) != 0 and self.nhead == 8
 
-    def transform(self, v0, pos0, v1, pos1):
-        """The library call: (out0 (B, N0, C), out1 (B, N1, C))."""
+    def transform(self, v0, pos0, v1, pos1, n0=None):
+        """The library call: (out0 (B, N0, C), out1 (B, N1, C)).  n0 (default None: every row exists) is a 0-d int32 DEVICE tensor: only the first n0 rows of
+        sequence 0 exist — nlk_sct_forward_counted (libnerfloc_counted.so); out0[:, :n0] and out1 then carry the bits of the call on v0[:, :n0].  The rows behind
+        n0 must be finite.  A host integer or a CPU tensor raises."""
         ts = (v0, pos0, v1, pos1)
         require_device("SelfCrossTransformer", *ts)
         C = self.d_model
@@ -232,6 +234,13 @@ class SelfCrossTransformer(nn.Module, PackedCache):
         dev = v0.device
         B, N0, N1 = v0.shape[0], v0.shape[1], v1.shape[1]
         lib = _lib.load()
+        if n0 is not None:
+            _counted_lib.device_count(n0, "SelfCrossTransformer.transform", dev)
+            if N0 < 1 or N1 < 1:
+                raise ValueError("SelfCrossTransformer: both sequences need at least one element")
+            with torch.cuda.device(dev):
+                a = [t.detach().to(torch.float32).contiguous() for t in ts]
+                return _counted_lib.sct_forward_counted(self._pack(dev), C, self.nhead, self.dim_feedforward, _lib.PRECISIONS[self.precision], *a, n0)
         with torch.cuda.device(dev):
             packed = self._pack(dev)   # raises for an unsupported configuration
             out0 = torch.empty((B, N0, C), dtype=torch.float32, device=dev)
